@@ -24,10 +24,16 @@ REAL shard gathered onto every rank through sharding.all_gather_rows — on its 
      fhe_shard_range share of 630 when N > 1)                         -> products/s
 
 `roofline` describes the WHOLE step against the HBM roofline (algorithmic bytes of SURVEY.md §8d
-per unit / measured time per unit); `roofline.kernels` holds every kernel's own average launch
-time (HIP events on the launch stream) and, for the dominant one, its own algorithmic rate;
-`roofline.valu` prices the same step against the measured integer ceiling of the chip
-(butterflies per second of tools/ubench_bfly.hip), which is what binds every configuration here.
+per unit / measured time per unit); `roofline.valu` prices the same step against the measured integer
+ceiling of the chip (butterflies per second of tools/ubench_bfly.hip), which is what binds every
+configuration here.
+
+A plain run sets up, pre-warms, warms up, times the K steps and prints the line: nothing else.
+`--full` adds what takes runs or checks of its own: `roofline.kernels` (every kernel's own average
+launch time, HIP events on the launch stream, over extra steps after the timed ones) and, for the
+dominant one, its own algorithmic rate; `parity` against the CPU oracle (`--no-parity` drops it);
+`cpu_baseline` (`--no-cpu-baseline` drops it).
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed (see dump_outputs).
 PyTorch is used for device memory, streams and torch.distributed only.
 """
 import argparse
@@ -77,11 +83,17 @@ def parse():
     ap.add_argument("--batch-tile", type=int, default=0, help="polynomials per launch (0 = library default)")
     ap.add_argument("--prewarm", type=float, default=0.15,
                     help="seconds of untimed steps BEFORE the --warmup steps, so that the chip is at its sustained clocks (0: none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure per-kernel times, check parity against the CPU oracle and time the CPU baseline "
+                         "(a plain run does only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64; "
+                         "a fixed, seeded sample of rows where the output exceeds 48 MiB; rank 0's shard)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: no parity check")
     ap.add_argument("--parity-all-ranks", action="store_true",
-                    help="every rank checks its own shard against the oracle (default: rank 0 only)")
+                    help="with --full: every rank checks its own shard against the oracle (default: rank 0 only)")
     ap.add_argument("--gather-check", action="store_true",
                     help="config 5, N > 1: all-gather the shards (sharding.ShardedNTT driven by Plan.forward_dev) "
                          "and compare with the single-rank transform of the whole batch on rank 0")
@@ -232,6 +244,8 @@ def workload_ntt(args, pkg, torch, dev, st, rank, world, inverse_too):
                    "arithmetic": pkg.Plan.ARITH_NAMES[arith],
                    "parallelism": f"batch-sharded x{world}, no collective"},
         "global_units_per_step": transforms * total, "scaling": "strong" if strong else "weak",
+        "outputs": dict(ntt_forward=y.view(batch, n), **({"ntt_inverse": z.view(batch, n)} if inverse_too else {})),
+        "output_bits": q.bit_length(),
         "plan": plan, "x": x, "y": y, "n": n, "q": q, "batch": batch, "seed": seed, "total": total, "b0": b0,
     }
 
@@ -289,6 +303,7 @@ def workload_bfv(args, pkg, torch, dev, st, rank, world):
                                "per GPU (BASELINE.json configs[2]), device-resident",
                    "n": n, "q": q, "batch_per_gpu": batch, "global_batch": world * batch,
                    "parallelism": f"batch-sharded x{world}, no collective"},
+        "outputs": {"ct_mul_c0": out[0], "ct_mul_c1": out[1]}, "output_bits": q.bit_length(),
     }
 
 
@@ -344,6 +359,7 @@ def workload_extprod(args, pkg, torch, dev, st, rank, world):
                    "n": n, "k": k, "l": l, "batch_per_gpu": batch, "global_batch": total,
                    "parallelism": f"product-sharded x{world}, no collective"},
         "global_units_per_step": total, "scaling": "strong" if args.global_batch else "weak",
+        "outputs": {"ext_product": out.view(batch, (k + 1) * n)}, "output_bits": 64,     # torus words: all 64 bits
     }
 
 
@@ -353,6 +369,33 @@ def workload_extprod(args, pkg, torch, dev, st, rank, world):
 # (same box, same process order; profiles/r05_warmup_effect.txt).  Their defaults therefore warm up for >= 0.1 s and time
 # >= 0.2 s; the driver's own --steps / --warmup always win.
 CONFIG_STEPS = {5: (10, 2), 2: (2000, 1000), 3: (100, 50), 4: (1000, 500)}
+
+DUMP_BYTES = 48 << 20      # all files of --dump-outputs together (the headline's output alone is 32 GiB)
+
+
+def dump_outputs(W, torch, out_dir):
+    """Write each output of the workload (a device tensor of 64-bit words, one row per unit) as float64 .npy files.
+    Words below 2^53 are exact in float64 and go to <name>.npy; wider words are split into <name>_hi32.npy and
+    <name>_lo32.npy (the upper and lower 32 bits of the unsigned word, both exact).  An output larger than its share of
+    DUMP_BYTES is sampled: the same seeded choice of rows for every output of a run, sorted, so two builds run with
+    the same arguments write the same rows."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    wide = W["output_bits"] > 53
+    files = len(W["outputs"]) * (2 if wide else 1)
+    for name, t in W["outputs"].items():
+        rows, cols = t.shape
+        keep = max(1, DUMP_BYTES // files // (8 * cols))
+        if rows > keep:
+            idx = np.sort(np.random.default_rng(0xD0).choice(rows, keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        words = t.cpu().numpy().view(np.uint64)
+        if wide:
+            np.save(os.path.join(out_dir, name + "_hi32.npy"), (words >> np.uint64(32)).astype(np.float64))
+            np.save(os.path.join(out_dir, name + "_lo32.npy"), (words & np.uint64(0xFFFFFFFF)).astype(np.float64))
+        else:
+            np.save(os.path.join(out_dir, name + ".npy"), words.astype(np.float64))
 
 
 def self_launch(args):
@@ -469,16 +512,21 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- per-kernel durations, measured with HIP events on the launch stream ----------
-    B.kernel_timing_reset()
-    B.kernel_timing_enable(True)
-    prof_steps = max(1, min(3, args.steps))
-    for _ in range(prof_steps):
-        step()
-    torch.cuda.synchronize()
-    timing = B.kernel_timing_read()
-    B.kernel_timing_enable(False)
-    B.kernel_timing_reset()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(W, torch, args.dump_outputs)
+
+    # ---- --full: per-kernel durations, measured with HIP events on the launch stream ----------
+    timing = {}
+    if args.full:
+        B.kernel_timing_reset()
+        B.kernel_timing_enable(True)
+        prof_steps = max(1, min(3, args.steps))
+        for _ in range(prof_steps):
+            step()
+        torch.cuda.synchronize()
+        timing = B.kernel_timing_read()
+        B.kernel_timing_enable(False)
+        B.kernel_timing_reset()
 
     out = None
     if rank == 0:
@@ -501,7 +549,7 @@ def main():
             "algorithmic_bytes_per_unit": W["alg_bytes_per_unit"],
             # the whole step against the HBM roofline — for the transforms this is the number the 40 % target is about
             "step_achieved": step_achieved, "step_frac": step_achieved / HBM_PEAK_GBS,
-            "dominant_kernel": dom, "kernels": kernels,
+            **({"dominant_kernel": dom, "kernels": kernels} if args.full else {}),
             "valu": {"bound": "integer butterflies (no MFMA on this path)", "achieved": per_gpu * W["bfly_per_unit"] / 1e9,
                      "peak": valu_peak, "unit": "Gbutterfly/s",
                      "frac": per_gpu * W["bfly_per_unit"] / 1e9 / valu_peak,
@@ -553,24 +601,25 @@ def main():
             "dtype": W.get("dtype", "u64"), "data": "synthetic", "config": W["config"], "roofline": roofline,
         }
 
-    # ---- parity against the CPU oracle (checker only; never inside the timed region) ----------
-    if not args.no_parity and (rank == 0 or args.parity_all_ranks):
-        import numpy as np
-        from oracle import load_oracle
+    # ---- --full: parity against the CPU oracle (checker only; never inside the timed region) ----------
+    if args.full and not args.no_parity:
+        if rank == 0 or args.parity_all_ranks:
+            import numpy as np
+            from oracle import load_oracle
 
-        rows, bad = W["parity"](load_oracle(), np)
-        mine = torch.tensor([rows, bad, 1], dtype=torch.int64, device=cdev)
-    else:
-        mine = torch.tensor([0, 0, 0], dtype=torch.int64, device=cdev)
-    if dist is not None and args.parity_all_ranks:
-        dist.all_reduce(mine, op=dist.ReduceOp.SUM)
-    if rank == 0 and not args.no_parity:
-        rows, bad, ranks = (int(v) for v in mine.tolist())
-        out["parity"] = {"rows_checked": rows, "mismatching_rows": bad, "ranks_checked": ranks,
-                         "oracle": "oracle/ (CPU restatement of the reference)"}
-        if bad:
-            print(json.dumps(out))
-            raise SystemExit(f"PARITY FAILURE: {bad} of {rows} checked units differ from the oracle")
+            rows, bad = W["parity"](load_oracle(), np)
+            mine = torch.tensor([rows, bad, 1], dtype=torch.int64, device=cdev)
+        else:
+            mine = torch.tensor([0, 0, 0], dtype=torch.int64, device=cdev)
+        if dist is not None and args.parity_all_ranks:
+            dist.all_reduce(mine, op=dist.ReduceOp.SUM)
+        if rank == 0:
+            rows, bad, ranks = (int(v) for v in mine.tolist())
+            out["parity"] = {"rows_checked": rows, "mismatching_rows": bad, "ranks_checked": ranks,
+                             "oracle": "oracle/ (CPU restatement of the reference)"}
+            if bad:
+                print(json.dumps(out))
+                raise SystemExit(f"PARITY FAILURE: {bad} of {rows} checked units differ from the oracle")
 
     # ---- N > 1: shards gathered through sharding.ShardedNTT == the single-rank transform ----------
     if args.gather_check and dist is not None and args.config == 5:
@@ -633,7 +682,7 @@ def main():
                                 "note": "timed on its own after the transform; not part of `value` (SURVEY.md §8e)"}
         del gathered
 
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         import numpy as np
         from oracle import load_oracle
 

@@ -229,7 +229,7 @@ def test_bench_two_ranks_on_one_gpu(pkg, oracle, tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--share-gpu", "--backend", "gloo", "--batch-per-gpu", "256", "--no-cpu-baseline",
+           "--share-gpu", "--backend", "gloo", "--batch-per-gpu", "256", "--full", "--no-cpu-baseline",
            "--parity-all-ranks", "--gather-check"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -271,7 +271,7 @@ def test_bench_through_rccl_at_world_size_one(pkg, need_gpu):
     barriers, the MAX all-reduce of the elapsed time on a DEVICE tensor and all_gather_into_tensor of the rank's real
     shard all execute in librccl — nothing of the N > 1 line is first run on the day an 8-GPU node appears."""
     out = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--backend", "nccl", "--force-dist", "--allgather",
-                      "--batch-per-gpu", "256", "--no-cpu-baseline", "--parity-all-ranks"], 1)
+                      "--batch-per-gpu", "256", "--full", "--no-cpu-baseline", "--parity-all-ranks"], 1)
     assert out["n_gpus"] == 1 and out["distributed"]["backend"].startswith("rccl") and out["distributed"]["forced_at_world_1"]
     assert out["parity"]["mismatching_rows"] == 0 and out["parity"]["ranks_checked"] == 1
     ag = out["allgather"]
@@ -290,7 +290,7 @@ def test_bench_strong_scaling_two_ranks_on_one_gpu(pkg, need_gpu):
     polynomials by fhe_shard_range (257 + 256), both shards against the oracle, shards gathered == single-rank
     transform, and the all-gather of the real shards reported on its own."""
     out = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--share-gpu", "--backend", "gloo",
-                      "--global-batch", "513", "--no-cpu-baseline", "--parity-all-ranks", "--gather-check", "--allgather"], 2)
+                      "--global-batch", "513", "--full", "--no-cpu-baseline", "--parity-all-ranks", "--gather-check", "--allgather"], 2)
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     assert out["config"]["global_batch"] == 513 and out["config"]["batch_per_gpu"] == 257
     assert "strong scaling" in out["config"]["workload"]
@@ -306,7 +306,7 @@ def test_bench_strong_scaling_two_ranks_on_one_gpu(pkg, need_gpu):
 def test_default_line_is_the_headline_configuration(pkg, need_gpu):
     """no flags beyond the driver's: global batch 65536 on one GPU, the modulus of SURVEY.md section 8, the
     five-multiply arithmetic — checked on a short run (2 steps)"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

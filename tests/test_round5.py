@@ -40,7 +40,7 @@ def test_bench_gpus_2_without_a_launcher_starts_two_ranks(pkg):
     HIP call of its own) and relays rank 0's line, which must say n_gpus 2; 513 rows = a ragged split (257 + 256)"""
     assert pkg.binding.device_count() >= 1, "no HIP device: -m gpu tests need a real MI355X"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--share-gpu",
-           "--backend", "gloo", "--global-batch", "513", "--no-cpu-baseline", "--parity-all-ranks"]
+           "--backend", "gloo", "--global-batch", "513", "--full", "--no-cpu-baseline", "--parity-all-ranks"]
     r = subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -49,6 +49,31 @@ def test_bench_gpus_2_without_a_launcher_starts_two_ranks(pkg):
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     assert out["config"]["global_batch"] == 513
     assert out["parity"]["mismatching_rows"] == 0 and out["parity"]["ranks_checked"] == 2
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_only_and_dumps_what_the_last_step_computed(pkg, oracle, tmp_path):
+    """a plain run (no --full) runs exactly --steps timed steps and leaves out the per-kernel times, parity and the CPU
+    baseline; --dump-outputs writes the transform of the last step, split into exact 32-bit halves, word for word the
+    oracle's transform of the same synthetic rows (8 rows: small enough to be written whole)"""
+    assert pkg.binding.device_count() >= 1, "no HIP device: -m gpu tests need a real MI355X"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--global-batch", "8", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["higher_is_better"] is True
+    assert out["unit"] == "NTT/s" and out["dtype"] == "u64" and out["value"] > 0
+    assert "parity" not in out and "cpu_baseline" not in out and "kernels" not in out["roofline"]
+    assert sorted(os.listdir(tmp_path)) == ["ntt_forward_hi32.npy", "ntt_forward_lo32.npy"]
+    hi, lo = np.load(tmp_path / "ntt_forward_hi32.npy"), np.load(tmp_path / "ntt_forward_lo32.npy")
+    assert hi.dtype == lo.dtype == np.float64 and hi.shape == lo.shape == (8, 65536)
+    words = (hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64)
+    n = 65536
+    want = oracle.ntt(Q61, n, oracle.fill_synthetic(Q61, 0xF4E50005, 0, 8 * n)).reshape(8, n)
+    assert np.array_equal(words, want)
 
 
 @pytest.mark.gpu

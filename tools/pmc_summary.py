@@ -49,7 +49,7 @@ def main():
     fetch, write = per_kernel(fetch_dir, "FETCH_SIZE"), per_kernel(write_dir, "WRITE_SIZE")
     n = 65536
     res = {"source": f"{os.path.relpath(out)}: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on "
-                     f"`python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline` (polynomials per launch from each launch's grid); "
+                     f"`python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline` (polynomials per launch from each launch's grid); "
                      "FETCH_SIZE doubled per MI355X_MICROARCH.md §HBM",
            "polynomials_per_launch": polys, "kernels": {}}
     for rname, f_kb in fetch.items():

@@ -38,7 +38,7 @@ if [ "$2" = "collect" ]; then
 fi
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-parity"
+B="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-parity"
 
 echo "[1/7] GPU parity tests"; date
 timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $OUT/pytest_gpu.txt 2>&1 || { tail -30 $OUT/pytest_gpu.txt; exit 1; }
@@ -57,24 +57,24 @@ python3 tools/pmc_isa.py $OUT/pmc_isa_a $OUT/isa_counters_a.json | grep -E "ntt_
 python3 tools/pmc_isa.py $OUT/pmc_isa_b $OUT/isa_counters_b.json | grep -E "ntt_(fwd|inv)" || true
 
 echo "[3/7] bench.py (contract run)"; date
-timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 
-FHE_PM=0 timeout -k 10 600 python bench.py --no-cpu-baseline > $OUT/bench_pm0.json 2> $OUT/bench_pm0.err    # the Shoup kernels on the same box
+FHE_PM=0 timeout -k 10 600 python bench.py --full --no-cpu-baseline > $OUT/bench_pm0.json 2> $OUT/bench_pm0.err    # the Shoup kernels on the same box
 python3 -c "
 import json
 a=json.loads([l for l in open('$OUT/bench.json') if l.startswith('{')][-1]); b=json.loads([l for l in open('$OUT/bench_pm0.json') if l.startswith('{')][-1])
 print('pseudo-Mersenne', round(a['value']), 'NTT/s step_frac', round(a['roofline']['step_frac'],4), '| Shoup kernels (FHE_PM=0)', round(b['value']), round(b['roofline']['step_frac'],4))"
 
 echo "[4/7] rocprofv3 --kernel-trace --stats of the same command"; date
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o runc --output-format csv -- python3 bench.py --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/rocprof.err
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o runc --output-format csv -- python3 bench.py --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/rocprof.err
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv
 head -4 $OUT/bench_kernel_stats.csv
 
 echo "[5/7] configs 2-4: bench line + kernel stats of the same command"; date
 for c in 2 3 4; do
-  timeout -k 10 300 python bench.py --config $c --cpu-seconds 8 > $OUT/config$c.json 2> $OUT/config$c.err
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats_c$c -o runc --output-format csv -- python3 bench.py --config $c --no-cpu-baseline > $OUT/config${c}_under_rocprof.json 2> $OUT/rocprof_c$c.err
+  timeout -k 10 300 python bench.py --full --config $c --cpu-seconds 8 > $OUT/config$c.json 2> $OUT/config$c.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats_c$c -o runc --output-format csv -- python3 bench.py --full --config $c --no-cpu-baseline > $OUT/config${c}_under_rocprof.json 2> $OUT/rocprof_c$c.err
   cp $(find $OUT/stats_c$c -name "*kernel_stats.csv" | head -1) $OUT/config${c}_kernel_stats.csv
   python3 -c "
 import json,sys
@@ -83,7 +83,7 @@ print('config $c:', round(o['value'],1), o['unit'], 'ms/step', round(o['ms_per_s
 done
 
 echo "[5b] HBM-side traffic of config 4's kernels (PMC, separate passes)"; date
-C4="bench.py --config 4 --steps 3 --warmup 1 --no-cpu-baseline --no-parity"
+C4="bench.py --full --config 4 --steps 3 --warmup 1 --no-cpu-baseline --no-parity"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc4_fetch -o runc --output-format csv -- python3 $C4 > $OUT/pmc4_fetch.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc4_write -o runc --output-format csv -- python3 $C4 > $OUT/pmc4_write.log 2>&1
 { echo "# HBM-side traffic per launch of the config-4 kernels (630 TGGSW x TGLWE, N=1024, k=1, l=64; plain entry point)"
@@ -93,11 +93,11 @@ timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc4_write -
 cat $OUT/config4_pmc_traffic.txt
 
 echo "[6/7] two ranks on one GPU (gloo rendezvous): the multi-rank driver"; date
-timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --share-gpu --backend gloo --global-batch 4096 --no-cpu-baseline --parity-all-ranks --gather-check --allgather > $OUT/bench_2ranks.json 2> $OUT/bench_2ranks.err || tail -5 $OUT/bench_2ranks.err
+timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 3 --warmup 1 --share-gpu --backend gloo --global-batch 4096 --no-cpu-baseline --parity-all-ranks --gather-check --allgather > $OUT/bench_2ranks.json 2> $OUT/bench_2ranks.err || tail -5 $OUT/bench_2ranks.err
 tail -1 $OUT/bench_2ranks.json | cut -c1-300
 
 echo "[6b] ONE rank through RCCL (world size 1): process group, barrier, MAX all-reduce, all-gather of the real shard"; date
-timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 1 --steps 3 --warmup 1 --backend nccl --force-dist --allgather --batch-per-gpu 2048 --no-cpu-baseline > $OUT/bench_rccl_world1.json 2> $OUT/bench_rccl_world1.err || tail -5 $OUT/bench_rccl_world1.err
+timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --full --gpus 1 --steps 3 --warmup 1 --backend nccl --force-dist --allgather --batch-per-gpu 2048 --no-cpu-baseline > $OUT/bench_rccl_world1.json 2> $OUT/bench_rccl_world1.err || tail -5 $OUT/bench_rccl_world1.err
 tail -1 $OUT/bench_rccl_world1.json | python3 -c "import json,sys; o=json.loads(sys.stdin.read()); print(o.get('distributed'), o.get('allgather'))" || true
 
 echo "[7/7] inverse / other sizes / product / next rows (diagnostic)"; date
@@ -114,7 +114,7 @@ FHE_EXT32=0 timeout -k 10 100 python tools/abl_bfv.py >> $OUT/bfv_kernels.txt 2>
 # 2^62 <= q < 2^63 (generic63.hip) beside the headline modulus on this box
 (for ln in 16 12 10; do KBENCH_Q=9223372036844421121 timeout -k 10 120 python tools/kbench.py $ln $((1 << (28 - ln))); done; timeout -k 10 120 python tools/kbench.py 16 4096) > $OUT/q63_kbench.txt 2>&1 || true
 # VALU counters of the BFV kernels (two --pmc passes, as for the pass kernels)
-C3="bench.py --config 3 --steps 3 --warmup 1 --no-cpu-baseline --no-parity"
+C3="bench.py --full --config 3 --steps 3 --warmup 1 --no-cpu-baseline --no-parity"
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS GRBM_GUI_ACTIVE --kernel-trace -d $OUT/pmc3_a -o runc --output-format csv -- python3 $C3 > $OUT/pmc3_a.log 2>&1 || true
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVES SQ_WAIT_INST_LDS SQ_WAIT_INST_ANY --kernel-trace -d $OUT/pmc3_b -o runc --output-format csv -- python3 $C3 > $OUT/pmc3_b.log 2>&1 || true
 python3 tools/pmc_isa.py $OUT/pmc3_a $OUT/config3_counters_a.json > /dev/null 2>&1 || true
@@ -125,11 +125,11 @@ cat $OUT/kbench_16.txt $OUT/kbench_12.txt
 [ -x tools/ubench_fused ] && { timeout -k 10 300 ./tools/ubench_fused 8192 > $OUT/single_pass_bound.txt 2>&1 || true; }
 # q = 1 (mod 2^32): the word-Montgomery kernels against the Shoup ones on this box (NOT BASELINE's modulus); one rank of 8
 QMG=2305842979148922881
-timeout -k 10 300 python bench.py --q $QMG --no-cpu-baseline > $OUT/bench_mg.json 2> $OUT/bench_mg.err || true
-FHE_MG=0 timeout -k 10 300 python bench.py --q $QMG --no-cpu-baseline > $OUT/bench_mg_shoup.json 2> $OUT/bench_mg_shoup.err || true
-timeout -k 10 300 python bench.py --global-batch 8192 --steps 40 --no-cpu-baseline > $OUT/bench_rank_of_8.json 2> $OUT/bench_rank_of_8.err || true
-# `python bench.py --gpus 2` WITHOUT a launcher (it starts its own ranks; both share this GPU, gloo rendezvous)
-env -u RANK -u WORLD_SIZE -u LOCAL_RANK timeout -k 10 300 python bench.py --gpus 2 --steps 3 --warmup 1 --share-gpu --backend gloo --global-batch 4096 --no-cpu-baseline --parity-all-ranks > $OUT/bench_self_launch.json 2> $OUT/bench_self_launch.err || tail -5 $OUT/bench_self_launch.err
+timeout -k 10 300 python bench.py --full --q $QMG --no-cpu-baseline > $OUT/bench_mg.json 2> $OUT/bench_mg.err || true
+FHE_MG=0 timeout -k 10 300 python bench.py --full --q $QMG --no-cpu-baseline > $OUT/bench_mg_shoup.json 2> $OUT/bench_mg_shoup.err || true
+timeout -k 10 300 python bench.py --full --global-batch 8192 --steps 40 --no-cpu-baseline > $OUT/bench_rank_of_8.json 2> $OUT/bench_rank_of_8.err || true
+# `python bench.py --full --gpus 2` WITHOUT a launcher (it starts its own ranks; both share this GPU, gloo rendezvous)
+env -u RANK -u WORLD_SIZE -u LOCAL_RANK timeout -k 10 300 python bench.py --full --gpus 2 --steps 3 --warmup 1 --share-gpu --backend gloo --global-batch 4096 --no-cpu-baseline --parity-all-ranks > $OUT/bench_self_launch.json 2> $OUT/bench_self_launch.err || tail -5 $OUT/bench_self_launch.err
 if [ "${EVID_PERSIST:-0}" != "1" ]; then
   for f in bench_rank_of_8 bench_mg bench_mg_shoup bench_self_launch; do python3 -c "
 import json
@@ -154,14 +154,14 @@ for cfg in two-pass A:64,1,0 B:2,1 D:1,1 E:4,1; do
     python3 tools/pmc_isa.py $OUT/pt_b_$tag $OUT/persist_counters_b_$tag.json | grep -v fill_synthetic; } >> $OUT/persist_counters.txt 2>&1 || true
 done
 cat $OUT/persist_counters.txt || true
-FHE_NTT_PERSIST=A:64,1,0 timeout -k 10 300 python bench.py --no-cpu-baseline > $OUT/bench_persist_A.json 2> $OUT/bench_persist_A.err || true
-FHE_NTT_PERSIST=B:2,1 timeout -k 10 300 python bench.py --no-cpu-baseline > $OUT/bench_persist_B.json 2> $OUT/bench_persist_B.err || true
-FHE_NTT_PERSIST=E:4,1 timeout -k 10 300 python bench.py --no-cpu-baseline > $OUT/bench_persist_E.json 2> $OUT/bench_persist_E.err || true
+FHE_NTT_PERSIST=A:64,1,0 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench_persist_A.json 2> $OUT/bench_persist_A.err || true
+FHE_NTT_PERSIST=B:2,1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench_persist_B.json 2> $OUT/bench_persist_B.err || true
+FHE_NTT_PERSIST=E:4,1 timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench_persist_E.json 2> $OUT/bench_persist_E.err || true
 # q = 1 (mod 2^32): the word-Montgomery forward kernels against the Shoup ones on this box (NOT BASELINE's modulus)
 QMG=2305842979148922881
-timeout -k 10 300 python bench.py --q $QMG --no-cpu-baseline > $OUT/bench_mg.json 2> $OUT/bench_mg.err || true
-FHE_MG=0 timeout -k 10 300 python bench.py --q $QMG --no-cpu-baseline > $OUT/bench_mg_shoup.json 2> $OUT/bench_mg_shoup.err || true
-timeout -k 10 300 python bench.py --global-batch 8192 --steps 40 --no-cpu-baseline > $OUT/bench_rank_of_8.json 2> $OUT/bench_rank_of_8.err || true
+timeout -k 10 300 python bench.py --full --q $QMG --no-cpu-baseline > $OUT/bench_mg.json 2> $OUT/bench_mg.err || true
+FHE_MG=0 timeout -k 10 300 python bench.py --full --q $QMG --no-cpu-baseline > $OUT/bench_mg_shoup.json 2> $OUT/bench_mg_shoup.err || true
+timeout -k 10 300 python bench.py --full --global-batch 8192 --steps 40 --no-cpu-baseline > $OUT/bench_rank_of_8.json 2> $OUT/bench_rank_of_8.err || true
 for f in bench_persist_A bench_persist_B bench_persist_E bench_rank_of_8 bench_mg bench_mg_shoup; do python3 -c "
 import json
 o=json.loads([l for l in open('$OUT/$f.json') if l.startswith('{')][-1]); print('$f', round(o['value']), o['unit'], 'ms/step', round(o['ms_per_step'],3), 'step_frac', round(o['roofline']['step_frac'],4))" || true; done
