@@ -225,6 +225,17 @@ class Oracle:
                                        _ptr(c[0][i]), _ptr(c[1][i]), _ptr(c[2][i]))
         return c[0], c[1], c[2]
 
+    def bfv_relinearize(self, q, n, pq, rlk0, rlk1, c0, c1, c2):
+        """relinearize_204 (bfv/src/lib.rs:251-271) of (c0, c1, c2), each (batch, n) mod q -> (o0, o1)"""
+        C = [_arr(x).reshape(-1, n) for x in (c0, c1, c2)]
+        r0, r1 = _arr(rlk0), _arr(rlk1)
+        batch = C[0].shape[0]
+        o = np.empty((2, batch, n), dtype=np.uint64)
+        for i in range(batch):
+            self.lib.oracle_bfv_relinearize_204(q, n, pq, _ptr(r0), _ptr(r1), _ptr(C[0][i]), _ptr(C[1][i]),
+                                                _ptr(C[2][i]), _ptr(o[0][i]), _ptr(o[1][i]))
+        return o[0], o[1]
+
     def bfv_mul(self, q, n, t, pq, rlk0, rlk1, a0, a1, b0, b1):
         A = [_arr(x).reshape(-1, n) for x in (a0, a1, b0, b1)]
         r0, r1 = _arr(rlk0), _arr(rlk1)

@@ -88,12 +88,13 @@ def test_config4_630_external_products_sharded_like_8_gpus(pkg, oracle):
 
 
 def test_config3_bfv_multiply_n8192_batch(pkg, oracle):
-    """configs[2] at the batch bench.py times (256 ciphertext pairs, N = 8192): every pair of the batch is
-    the same function of its inputs (rows permuted in -> rows permuted out), and two pairs equal the
-    oracle's schoolbook tensor + relinearisation word for word."""
+    """configs[2] at the batch bench.py times (2048 ciphertext pairs, N = 8192): every pair of the batch is
+    the same function of its inputs (rows permuted in -> rows permuted out), and eight pairs equal the
+    oracle's schoolbook tensor + relinearisation word for word — both ends of the batch, either side of the
+    groups of 8 pairs the bfv32 kernels deal out (bfv32.hip), the middle, and one pair drawn at random."""
     import torch
 
-    q, n, t, batch = Q16, 8192, 2, 256
+    q, n, t, batch = Q16, 8192, 2, 2048
     pq = q * q * q
     L, B = pkg.load_library(), pkg.binding
     rng = np.random.default_rng(33)
@@ -107,10 +108,12 @@ def test_config3_bfv_multiply_n8192_batch(pkg, oracle):
     out2 = torch.empty_like(out)
     B._check(L.fhe_bfv_mul_dev(q, n, t, pq, rlk.data_ptr(), ab2.data_ptr(), out2.data_ptr(), batch, st))
     assert torch.equal(out2, out[:, perm])
+    del ab2, out2
     a, r = _u64(ab), _u64(rlk)
-    for i in (0, batch - 1):
+    pairs = (0, 7, 8, 1023, 1024, 2040, 2047, int(np.random.default_rng(2048).integers(9, 2040)))
+    for i in pairs:
         w0, w1 = oracle.bfv_mul(q, n, t, pq, r[0], r[1], a[0, i:i + 1], a[1, i:i + 1], a[2, i:i + 1], a[3, i:i + 1])
-        assert np.array_equal(_u64(out[0, i]), w0[0]) and np.array_equal(_u64(out[1, i]), w1[0])
+        assert np.array_equal(_u64(out[0, i]), w0[0]) and np.array_equal(_u64(out[1, i]), w1[0]), f"pair {i}"
 
 
 # ---- the reference's round-trip loop with fresh randomness ------------------------------------------
