@@ -14,7 +14,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FHE_NTT_LIB") or os.path.join(_HERE, "libfhe_ntt.so")  # env: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip"]
+SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip"]
 HEADERS = ["ntt_kernels.hpp", "ntt_rounds.hpp", "ntt_persist.hpp", "persist_sched.hpp", "digit_mac.hpp", "digit32.hpp", "bfv32.hpp", "smallq.hpp", "ntt32_rounds.hpp", "ntt32_big.hpp", "zq_device.hpp", "capi_internal.hpp", "mac_kernel.hpp", "ntt_kernels.hip",
            os.path.join("..", "..", "include", "fhe_ntt.h"), os.path.join("..", "..", "include", "fhe_ntt_experimental.h")]
 OBJ_DIR = os.path.join(_HERE, "build")
@@ -61,6 +61,9 @@ EXPORTS = [
     "fhe_rq_add_dev", "fhe_rq_sub_dev", "fhe_rq_neg_dev", "fhe_rq_mul_by_u64_dev",
     "fhe_rq_mod_switch_dev", "fhe_rq_mul_div_round_dev", "fhe_rq_decompose_dev",
     "fhe_rq_remodule_dev", "fhe_rq_mul_by_f64_dev", "fhe_rq_div_round_dev",
+    # TFHE bootstrapping (tfhe_boot.hip)
+    "fhe_tfhe_bsk_prepared_words", "fhe_tfhe_bsk_prepare_dev", "fhe_tfhe_blind_rotation_dev",
+    "fhe_tglwe_sample_extraction_dev", "fhe_tlwe_key_switch_dev", "fhe_tfhe_bootstrap_dev",
 ]
 
 
@@ -209,6 +212,13 @@ def load_library():
     L.fhe_tggsw_prepared_words.restype = _sz
     L.fhe_tggsw_prepare_dev.argtypes = [_u64, _uint, _uint, _vp, _vp, _vp]
     L.fhe_tggsw_external_product_prepared_dev.argtypes = [_u64, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_bsk_prepared_words.argtypes = [_u64, _uint, _uint, _uint]
+    L.fhe_tfhe_bsk_prepared_words.restype = _sz
+    L.fhe_tfhe_bsk_prepare_dev.argtypes = [_u64, _uint, _uint, _uint, _vp, _vp, _vp]
+    L.fhe_tfhe_blind_rotation_dev.argtypes = [_u64, _uint, _uint, _uint, _vp, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tglwe_sample_extraction_dev.argtypes = [_u64, _uint, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_tlwe_key_switch_dev.argtypes = [_uint, _uint, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _vp, _vp, _uint, _vp, _vp, _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -442,6 +452,31 @@ def tggsw_external_product(n, k, l, tggsw, tglwe):
 def fill_synthetic_dev(q, seed, first_index, count, d_out, stream=None):
     _check(load_library().fhe_fill_synthetic_dev(int(q), int(seed), int(first_index), int(count),
                                                  d_out, stream))
+
+
+# ---- TFHE bootstrapping (include/fhe_ntt.h; device pointers as ints, words u64) ----------------------------------------
+def tfhe_bsk_prepared_words(n, k, l, n_lwe):
+    return load_library().fhe_tfhe_bsk_prepared_words(n, k, l, n_lwe)
+
+
+def tfhe_bsk_prepare_dev(n, k, l, n_lwe, d_bsk, d_prepared, stream=None):
+    _check(load_library().fhe_tfhe_bsk_prepare_dev(n, k, l, n_lwe, d_bsk, d_prepared, stream))
+
+
+def tfhe_blind_rotation_dev(n, k, l, n_lwe, d_bsk_prepared, d_table, d_lwe, d_out, batch, stream=None):
+    _check(load_library().fhe_tfhe_blind_rotation_dev(n, k, l, n_lwe, d_bsk_prepared, d_table, d_lwe, d_out, batch, stream))
+
+
+def tglwe_sample_extraction_dev(n, k, h, d_tglwe, d_tlwe, batch, stream=None):
+    _check(load_library().fhe_tglwe_sample_extraction_dev(n, k, h, d_tglwe, d_tlwe, batch, stream))
+
+
+def tlwe_key_switch_dev(n_in, n_out, beta, l, d_ksk, d_in, d_out, batch, stream=None):
+    _check(load_library().fhe_tlwe_key_switch_dev(n_in, n_out, beta, l, d_ksk, d_in, d_out, batch, stream))
+
+
+def tfhe_bootstrap_dev(n, k, l, n_lwe, d_bsk_prepared, d_table, ks_l, d_ksk, d_in, d_out, batch, stream=None):
+    _check(load_library().fhe_tfhe_bootstrap_dev(n, k, l, n_lwe, d_bsk_prepared, d_table, ks_l, d_ksk, d_in, d_out, batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

@@ -55,6 +55,8 @@ void fhe_workspace_free_all();
 void fhe_ext32_free_all();   // zring.hip: tables of the two-small-prime (27-bit) products (digit32.hip)
 namespace fhe { struct Ext32Args; }
 int fhe_ext32_tables(uint64_t n, fhe::Ext32Args *a);   // fills the per-prime fields for the current device
+// zring.hip: `keys` TGGSWs [key][(k+1)][l][(k+1)][n] -> keys * fhe_tggsw_prepared_words, in one or two launches (unvalidated)
+int fhe_tggsw_prepare_keys(uint64_t n, unsigned k, unsigned l, uint64_t keys, const void *d_tggsw, void *d_prepared, hipStream_t st);
 namespace fhe { struct SmallQArgs; }
 // fills the modulus-dependent fields when the plan has a 32-bit form on this device (smallq.hip) and FHE_EXT32 is on
 bool fhe_smallq_args(const fhe_ntt_plan *plan, const fhe::DevicePlan &dp, fhe::SmallQArgs *a);

@@ -155,6 +155,9 @@ struct Cfg32 {
 #ifndef FHE_D32_ONEP10
 #define FHE_D32_ONEP10 0          // 1: at n = 1024 a workgroup serves ONE prime (gridDim.y = 2): half the accumulators and tiles
 #endif
+#ifndef FHE_D32_CMUX_WAVES10
+#define FHE_D32_CMUX_WAVES10 3    // waves per SIMD of the CMux source mode at n = 1024
+#endif
 #define FHE_D32_PRAGMA_(x) _Pragma(#x)
 #define FHE_D32_PRAGMA(x) FHE_D32_PRAGMA_(x)
 template <int LP>
@@ -163,6 +166,10 @@ struct Mac32Cfg {
     static constexpr int M = C::M, TPB = C::TPB;
     static constexpr int TH = LP == 12 ? 512 : LP == 10 ? FHE_D32_TH10 : 256;
     static constexpr int WAVES = LP == 10 ? FHE_D32_WAVES10 : 512 / TH;     // __launch_bounds__: minimum waves per SIMD
+    // the CMux source mode (blind rotation) held to the external product's budget: at n = 1024 the scheduler otherwise
+    // takes 183 registers where SRC_DIGITS takes 168, and a SIMD would hold two waves instead of three (at 168 it
+    // spills 20 bytes per lane)
+    static constexpr int CMUX_WAVES = LP == 10 ? FHE_D32_CMUX_WAVES10 : WAVES;
     static constexpr int W = TH / TPB, PPT = M / TH;
     static constexpr bool ONEP = LP == 10 && FHE_D32_ONEP10 != 0;
     static constexpr int NP = ONEP ? 1 : 2;                                  // primes per workgroup
@@ -190,7 +197,7 @@ __global__ __launch_bounds__(256) void ntt32_fwd_key_kernel(Ext32Args a) {
     // output row (t, half, c) is the 32-bit half `half` of source row (t, c) of the key as the reference holds it
     const u64 orow = live ? row : 0, t = orow / (2 * a.key_k1), rem = orow - t * (2 * a.key_k1);
     const u32 half = (u32)(rem / a.key_k1), c = (u32)(rem - (u64)half * a.key_k1);
-    const u64 *__restrict__ src = a.key64 + (t * a.key_k1 + c) * C::M;
+    const u64 *__restrict__ src = a.key64 + blockIdx.z * a.key_stride64 + (t * a.key_k1 + c) * C::M;   // z: key of a batch of keys
     u32 v[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) {
@@ -199,7 +206,7 @@ __global__ __launch_bounds__(256) void ntt32_fwd_key_kernel(Ext32Args a) {
     }
     fwd_rounds32<LP, false, true>(v, lds, ltw, gtw, nullptr, w, tf, p, p2);
     if (live) {
-        u32 *__restrict__ dst = a.key32 + ((u64)prime * a.rows + row) * C::M + tf * 16u;
+        u32 *__restrict__ dst = a.key32 + blockIdx.z * a.key_stride32 + ((u64)prime * a.rows + row) * C::M + tf * 16u;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             uint4 o;
@@ -217,14 +224,26 @@ __global__ __launch_bounds__(256) void ntt32_fwd_key_kernel(Ext32Args a) {
 template <int SRC>
 __device__ __forceinline__ u32 digit32_of(u64 x, u32 l, u32 d) {
     const u32 bit = (u32)(x >> (l - 1u - d)) & 1u;
-    if (SRC == SRC_DIGITS) return bit;
+    if (SRC == SRC_DIGITS || SRC == SRC32_CMUX) return bit;
     return x >= (1ull << (l & 63u)) ? 1u : bit;
+}
+// the source word at position pos of a row.  SRC32_CMUX: X^-e row - row in T64[X]/(X^N+1), e < 2N, i.e.
+// (-1)^floor((pos+e)/N) row[(pos+e) mod N] - row[pos] — one wrap in a thread's positions, the loads stay coalesced
+template <int SRC, int LP>
+__device__ __forceinline__ u64 src_word32(const u64 *__restrict__ row, u32 pos, u32 e) {
+    if constexpr (SRC == SRC32_CMUX) {
+        const u32 j = pos + e;                                            // < 3N
+        const u64 x = row[j & ((1u << LP) - 1u)];
+        return (((j >> LP) & 1u) ? 0ull - x : x) - row[pos];
+    } else {
+        return row[pos];
+    }
 }
 
 // key32 layout: [prime][t][c][n], t = row*l + digit, c < NC (NC = 2 * output rows: half-major, then component).
 // out: partial sums [b][part][prime][c][n] u32 canonical.
 template <int LP, int NC, int SRC>
-__global__ __launch_bounds__((Mac32Cfg<LP>::TH), (Mac32Cfg<LP>::WAVES)) void digit_mac32_kernel(Ext32Args a) {
+__global__ __launch_bounds__((Mac32Cfg<LP>::TH), (SRC == SRC32_CMUX ? Mac32Cfg<LP>::CMUX_WAVES : Mac32Cfg<LP>::WAVES)) void digit_mac32_kernel(Ext32Args a) {
     using C = ContigCfg<LP>;
     using K = Mac32Cfg<LP>;
     constexpr int PPT = K::PPT, W = K::W, TH = K::TH, NP = K::NP;
@@ -256,6 +275,7 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (Mac32Cfg<LP>::WAVES)) void dig
     }
     __syncthreads();
     const u64 *__restrict__ ct = a.src + b * a.ct_stride;
+    const u32 e = SRC == SRC32_CMUX ? a.shift[b * a.shift_stride] : 0u;   // this ciphertext's rotation (blind rotation step)
 
     u64 acc[NP][NC][PPT];
 #pragma unroll
@@ -271,12 +291,16 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (Mac32Cfg<LP>::WAVES)) void dig
         const u32 tt = t < t_end ? t : t_begin;               // idle units redo a valid digit, never multiplied
         const u32 r = tt / a.l, d = tt - r * a.l;
         const u64 *__restrict__ row = ct + (u64)r * n;
+        // the rotation as an opaque value per step: the 16 rotated offsets and signs of a thread are recomputed here
+        // rather than hoisted out of the loop, where they would hold registers through the multiply phase
+        u32 eo = e;
+        if constexpr (SRC == SRC32_CMUX) asm volatile("" : "+s"(eo));
         // the tiles were read by the previous step's multiply phase: barrier first (FRESH = false); every thread then
         // rewrites exactly the slots it gathered in the last exchange, reduced below 2p (a product is below 2 p^2 < 2^55.8)
         if constexpr (K::LOCK) {
             u32 va[16], vb[16];
 #pragma unroll
-            for (int k = 0; k < 16; k++) va[k] = vb[k] = digit32_of<SRC>(row[field_of<C::A0>(tf, k)], a.l, d);
+            for (int k = 0; k < 16; k++) va[k] = vb[k] = digit32_of<SRC>(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo), a.l, d);
             const Tw32 *const lt[2] = {ltw_w[0], ltw_w[1]};
             const u32 *const ll[2] = {llut_w[0], llut_w[1]};
             u32 *const tl[2] = {tile[0], tile[1]};
@@ -296,7 +320,7 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (Mac32Cfg<LP>::WAVES)) void dig
         } else {
             u32 bits = 0;
 #pragma unroll
-            for (int k = 0; k < 16; k++) bits |= digit32_of<SRC>(row[field_of<C::A0>(tf, k)], a.l, d) << k;
+            for (int k = 0; k < 16; k++) bits |= digit32_of<SRC>(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo), a.l, d) << k;
 #pragma unroll
             for (int pr = 0; pr < NP; pr++) {
                 u32 v[16];
@@ -376,10 +400,12 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (Mac32Cfg<LP>::WAVES)) void dig
 // inverse transforms; a thread ends every one of them on the SAME 16 positions, so the lifts meet in registers:
 //   EPI32_TORUS  out[b][c] = lift(S_lo) + (lift(S_hi) << 32)  mod 2^64          (TGGSW x TGLWE)
 //   EPI32_KS     rhs = (lift(S_lo) + lift(S_hi) * 2^32) mod q,   out[b][c] = (c < k ? 0 : glwe[b][c]) - rhs   (glwe.rs:129-136)
+//   EPI32_CMUX   out[b][c] += lift(S_lo) + (lift(S_hi) << 32)  mod 2^64     (blind rotation step: ACC + BSK_j (X^-e ACC - ACC);
+//                every thread reads and writes the same positions, and the step's digit_mac32_kernel has finished)
 // lift = the centred representative modulo pA pB.  (512 threads with the two primes side by side — two transforms in
 // sequence instead of four — was measured: 46 -> 41 us for a single product, but 31 -> 36 us per 630 and 37 -> 43 us per
 // 256 key switches; the sequential form stays.)
-enum : int { EPI32_TORUS = 0, EPI32_KS = 1 };
+enum : int { EPI32_TORUS = 0, EPI32_KS = 1, EPI32_CMUX = 2 };
 template <int LP, int EPI>
 __global__ __launch_bounds__(256) void digit_tail32_kernel(Ext32Args a) {
     using C = ContigCfg<LP>;
@@ -442,13 +468,15 @@ __global__ __launch_bounds__(256) void digit_tail32_kernel(Ext32Args a) {
     }
     if (!active) return;
     const u64 base = (b * k1 + c) * (u64)n;
-    if constexpr (EPI == EPI32_TORUS) {
+    if constexpr (EPI == EPI32_TORUS || EPI == EPI32_CMUX) {
 #pragma unroll
         for (int k = 0; k < 16; k++) {
             u64 lo = S[0][k], hi = S[1][k];
             if (lo >= a.halfP) lo -= a.P;                       // two's complement of the centred value
             if (hi >= a.halfP) hi -= a.P;
-            a.out[base + field_of<C::A0>(tf, k)] = lo + (hi << 32);
+            const u64 pos = base + field_of<C::A0>(tf, k);
+            if constexpr (EPI == EPI32_CMUX) a.out[pos] += lo + (hi << 32);
+            else a.out[pos] = lo + (hi << 32);
         }
     } else {
         const Mod &m = a.mod;
@@ -473,7 +501,7 @@ __global__ __launch_bounds__(256) void digit_tail32_kernel(Ext32Args a) {
 
 // ---- launchers ----------------------------------------------------------------------------------------------------
 template <int LP>
-static hipError_t launch_key32_lp(const Ext32Args &a, hipStream_t st) {
+static hipError_t launch_key32_lp(const Ext32Args &a, hipStream_t st, unsigned keys = 1) {
     using C = ContigCfg<LP>;
     using K = Cfg32<LP>;
     constexpr size_t lds = K::TILE_BYTES + K::TW_BYTES;
@@ -481,8 +509,20 @@ static hipError_t launch_key32_lp(const Ext32Args &a, hipStream_t st) {
     if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     if (hipError_t e = allow_big_lds((const void *)ntt32_fwd_key_kernel<LP>, lds)) return e;
     KernelTimer kt("ntt32_fwd_key", LP, st);
-    hipLaunchKernelGGL((ntt32_fwd_key_kernel<LP>), dim3((unsigned)grid, 2), dim3(256), lds, st, a);
+    hipLaunchKernelGGL((ntt32_fwd_key_kernel<LP>), dim3((unsigned)grid, 2, keys), dim3(256), lds, st, a);
     return hipGetLastError();
+}
+// `keys` TGGSWs (a bootstrapping key): gridDim.z <= 65535 keys per launch
+template <int LP>
+static hipError_t launch_key32_many_lp(const Ext32Args &a0, hipStream_t st, u64 keys) {
+    Ext32Args a = a0;
+    for (u64 z0 = 0; z0 < keys; z0 += 65535) {
+        const unsigned kz = (unsigned)min((u64)65535, keys - z0);
+        a.key64 = a0.key64 + z0 * a0.key_stride64;
+        a.key32 = a0.key32 + z0 * a0.key_stride32;
+        if (hipError_t e = launch_key32_lp<LP>(a, st, kz)) return e;
+    }
+    return hipSuccess;
 }
 template <int LP, int SRC>
 static hipError_t launch_mac32_lp(const Ext32Args &a, hipStream_t st) {
@@ -490,7 +530,7 @@ static hipError_t launch_mac32_lp(const Ext32Args &a, hipStream_t st) {
     const u64 grid = a.batch * a.parts;
     if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     if (hipError_t e = allow_big_lds((const void *)digit_mac32_kernel<LP, 4, SRC>, K::LDS_BYTES)) return e;
-    KernelTimer kt("digit_mac32", LP, st);
+    KernelTimer kt(SRC == SRC32_CMUX ? "digit_mac32_cmux" : "digit_mac32", LP, st);
     hipLaunchKernelGGL((digit_mac32_kernel<LP, 4, SRC>), dim3((unsigned)grid, K::ONEP ? 2u : 1u), dim3(K::TH), K::LDS_BYTES, st, a);
     return hipGetLastError();
 }
@@ -502,7 +542,7 @@ static hipError_t launch_tail32_lp(const Ext32Args &a, hipStream_t st) {
     const u64 grid = (a.batch * (a.k + 1) + C::W - 1) / C::W;
     if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     if (hipError_t e = allow_big_lds((const void *)digit_tail32_kernel<LP, EPI>, lds)) return e;
-    KernelTimer kt(EPI == EPI32_KS ? "digit_tail32_ks" : "digit_tail32", LP, st);
+    KernelTimer kt(EPI == EPI32_KS ? "digit_tail32_ks" : EPI == EPI32_CMUX ? "digit_tail32_cmux" : "digit_tail32", LP, st);
     hipLaunchKernelGGL((digit_tail32_kernel<LP, EPI>), dim3((unsigned)grid), dim3(256), lds, st, a);
     return hipGetLastError();
 }
@@ -520,6 +560,16 @@ bool ks32_shape_supported(u64 n, unsigned k, unsigned l) {
     return (u64)k * l * n <= (1ull << 21);
 }
 uint32_t ext32_units(int log_n) { return log_n >= 8 && log_n <= 12 ? (log_n == 12 ? 2u : 4096u >> log_n) : 0u; }
+// parts: enough workgroups to fill the chip several times over (n <= 1024: four workgroups' worth of LDS per CU),
+// only as many as leave no CU empty above (one or two workgroups per CU: see fhe_glwe_key_switch_dev)
+void ext32_split(u64 n, u64 batch, uint32_t T, uint32_t *parts, uint32_t *tpp) {
+    const u32 W = ext32_units(__builtin_ctzll(n));
+    u32 p = 1;
+    const u64 slots = n <= 1024 ? 2048 : n == 2048 ? 512 : 256;
+    while (p < 8 && batch * p < slots && (T / (p * 2)) >= 2 * W) p *= 2;
+    *parts = p;
+    *tpp = ((T + p - 1) / p + W - 1) / W * W;
+}
 
 #define FHE_LP_SWITCH(FN, ...)                                        \
     switch (log_n) {                                                  \
@@ -532,11 +582,23 @@ uint32_t ext32_units(int log_n) { return log_n >= 8 && log_n <= 12 ? (log_n == 1
     return hipErrorNotSupported;
 #define FHE_COMMA ,
 hipError_t launch_ext32_key(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_key32_lp) }
+hipError_t launch_ext32_key_many(const Ext32Args &a, int log_n, u64 keys, hipStream_t st) {
+    switch (log_n) {
+        case 8: return launch_key32_many_lp<8>(a, st, keys);
+        case 9: return launch_key32_many_lp<9>(a, st, keys);
+        case 10: return launch_key32_many_lp<10>(a, st, keys);
+        case 11: return launch_key32_many_lp<11>(a, st, keys);
+        case 12: return launch_key32_many_lp<12>(a, st, keys);
+    }
+    return hipErrorNotSupported;
+}
 hipError_t launch_ext32_mac(const Ext32Args &a, int log_n, int src_kind, hipStream_t st) {
     if (src_kind == SRC_DIGITS) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC_DIGITS) }
     if (src_kind == SRC_ZQBITS) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC_ZQBITS) }
+    if (src_kind == SRC32_CMUX) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_CMUX) }
     return hipErrorNotSupported;
 }
+hipError_t launch_ext32_tail_cmux(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_CMUX) }
 hipError_t launch_ext32_tail(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_TORUS) }
 hipError_t launch_ext32_tail_ks(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_KS) }
 #undef FHE_LP_SWITCH

@@ -43,14 +43,27 @@ struct Ext32Args {
     u64 two32;                 // 2^32 mod q
     const u64 *glwe;           // the ciphertexts again, for the body row
     uint32_t k;
+    // several keys in one preparation launch (gridDim.z keys): key z at key64 + z*key_stride64, key32 + z*key_stride32
+    u64 key_stride64, key_stride32;
+    // SRC32_CMUX (blind rotation step): ciphertext b's source row r is rot(src_r, e_b) - src_r, e_b = shift[b*shift_stride]
+    const uint32_t *shift;
+    u64 shift_stride;
 };
+
+// source mode of digit_mac32_kernel next to SRC_DIGITS / SRC_ZQBITS (ntt_kernels.hpp): the digits of X^-e ACC - ACC
+enum : int { SRC32_CMUX = 4 };
 
 bool ext32_shape_supported(u64 n, unsigned k, unsigned l);        // TGGSW x TGLWE
 bool ks32_shape_supported(u64 n, unsigned k, unsigned l);         // GLWE::key_switch, base 2
 uint32_t ext32_units(int log_n);                                   // digits per step of the fused kernel
+// parts (workgroups per ciphertext) and digits per part of the fused kernel for `batch` ciphertexts of T digit rows;
+// shared by the external product and the blind rotation's CMux steps
+void ext32_split(u64 n, u64 batch, uint32_t T, uint32_t *parts, uint32_t *tpp);
 hipError_t launch_ext32_key(const Ext32Args &a, int log_n, hipStream_t st);
 hipError_t launch_ext32_mac(const Ext32Args &a, int log_n, int src_kind, hipStream_t st);
 hipError_t launch_ext32_tail(const Ext32Args &a, int log_n, hipStream_t st);
 hipError_t launch_ext32_tail_ks(const Ext32Args &a, int log_n, hipStream_t st);
+hipError_t launch_ext32_tail_cmux(const Ext32Args &a, int log_n, hipStream_t st);   // out[b] += lift (in place)
+hipError_t launch_ext32_key_many(const Ext32Args &a, int log_n, u64 keys, hipStream_t st);   // `keys` TGGSWs, strides above
 
 }  // namespace fhe

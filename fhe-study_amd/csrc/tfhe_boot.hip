@@ -1,0 +1,312 @@
+// tfhe_boot.hip — TFHE bootstrapping on the device: blind rotation, sample extraction, LWE key switch
+// (tfhe/src/tlwe.rs:101-161, tglwe.rs:89-118; the definitions are DESIGN.md §10's, since the reference's
+// blind rotation never runs).
+//
+//   N = ring degree = 2^L, k = GLWE rank, all words u64 wrapping mod 2^64.
+//   mod switch   w -> round(w 2N / 2^64) mod 2N = (((w >> (62 - L)) + 1) >> 1) & (2N - 1)
+//   rot(x, e)    X^-e x in T64[X]/(X^N+1), e < 2N: coefficient i is (-1)^floor((i+e)/N) x[(i+e) mod N]
+//   blind rot.   ACC_0 = rot(v, b~);  ACC_{j+1} = ACC_j + BSK_j [x] (rot(ACC_j, (2N - a~_j) mod 2N) - ACC_j)
+//
+// One step of the blind rotation where the 27-bit form applies (k = 1, 2^8 <= N <= 2^12, digit32.hip) is the external
+// product's own kernel pair in its CMux modes: digit_mac32_kernel<SRC32_CMUX> forms rot(ACC, e_b) - ACC as it loads the
+// digits, digit_tail32_kernel<EPI32_CMUX> adds the lift to ACC in place.  2 n_lwe + 1 launches per blind rotation.
+// Other shapes with a prepared key compose rotate-difference, fhe_tggsw_external_product_prepared_dev and an add.
+#include <algorithm>
+
+#include "capi_internal.hpp"
+#include "digit32.hpp"
+
+using fhe::u32;
+using fhe::u64;
+
+namespace fhe {
+
+__device__ __forceinline__ u32 mod_switch_2n(u64 w, u32 L) { return (u32)((((w >> (62u - L)) + 1u) >> 1) & ((2ull << L) - 1u)); }
+
+// ACC_0[b] = rot(table, b~_b) and shift[b][j] = (2N - a~_j) mod 2N, one grid-stride pass over both
+__global__ __launch_bounds__(256) void tfhe_br_init_kernel(const u64 *__restrict__ lwe, const u64 *__restrict__ table, u64 *__restrict__ acc,
+                                                           u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L, u64 batch) {
+    const u64 N = 1ull << L, k1N = (u64)k1 * N, na = batch * k1N, total = na + batch * n_lwe;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        if (i < na) {
+            const u64 b = i / k1N, r = i - b * k1N;
+            const u64 j = (r & (N - 1)) + mod_switch_2n(lwe[b * (n_lwe + 1ull) + n_lwe], L);
+            const u64 x = table[(r >> L) * N + (j & (N - 1))];
+            acc[i] = ((j >> L) & 1u) ? 0ull - x : x;
+        } else {
+            const u64 q = i - na, b = q / n_lwe;
+            shift[q] = (u32)((2 * N - mod_switch_2n(lwe[b * (n_lwe + 1ull) + (q - b * n_lwe)], L)) & (2 * N - 1));
+        }
+    }
+}
+
+// the composed step (shapes outside the 27-bit form): d[b] = rot(acc[b], e_b) - acc[b], e_b = shift[b * stride]
+__global__ __launch_bounds__(256) void tfhe_rotdiff_kernel(const u64 *__restrict__ acc, const u32 *__restrict__ shift, u64 stride_s,
+                                                           u64 *__restrict__ d, u32 k1, u32 L, u64 batch) {
+    const u64 N = 1ull << L, k1N = (u64)k1 * N, total = batch * k1N;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 b = i / k1N, r = i - b * k1N;
+        const u64 j = (r & (N - 1)) + shift[b * stride_s];
+        const u64 x = acc[b * k1N + (r >> L) * N + (j & (N - 1))];
+        d[i] = (((j >> L) & 1u) ? 0ull - x : x) - acc[i];
+    }
+}
+__global__ __launch_bounds__(256) void tfhe_add_kernel(u64 *__restrict__ acc, const u64 *__restrict__ p, u64 count) {
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) acc[i] += p[i];
+}
+
+// TGLWE::sample_extraction (tglwe.rs:89-115): out[b][c N + j] = j <= h ? a_c[h - j] : -a_c[N + h - j];  out[b][k N] = b[h]
+__global__ __launch_bounds__(256) void tglwe_sample_extract_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, u32 k, u32 L, u32 h,
+                                                                   u64 batch) {
+    const u64 N = 1ull << L, kN = (u64)k * N, per = kN + 1, total = batch * per;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 b = i / per, r = i - b * per;
+        const u64 *src = in + b * (kN + N);
+        if (r == kN) {
+            out[i] = src[kN + h];
+        } else {
+            const u64 c = r >> L, j = r & (N - 1);
+            out[i] = j <= h ? src[c * N + h - j] : 0ull - src[c * N + N + h - j];
+        }
+    }
+}
+
+// TLWE::key_switch (tlwe.rs:101-111), beta = 2:  out[b] = (0 .. 0, b_b) - sum_i sum_{d<l} bit_{l-1-d}(a_{b,i}) ksk[i][d]
+// A workgroup owns KS_TB ciphertexts and KS_TH output columns: every KSK word it reads serves all KS_TB ciphertexts (the
+// key is n_in l (n_out + 1) words, 331 MB at n_in = 1024, l = 64, n_out = 630).  The ciphertext words are uniform across
+// the workgroup, so the digit of a (ciphertext, level) is one select per lane.
+constexpr int KS_TB = 32, KS_TH = 64;
+__global__ __launch_bounds__(KS_TH) void tlwe_key_switch_kernel(const u64 *__restrict__ ksk, const u64 *__restrict__ in, u64 *__restrict__ out,
+                                                                u32 n_in, u32 n_out, u32 l, u64 batch, u32 cblocks) {
+    const u64 tile = blockIdx.x / cblocks;
+    const u32 o = (blockIdx.x - (u32)tile * cblocks) * KS_TH + threadIdx.x;
+    const u64 b0 = tile * KS_TB, row = (u64)n_out + 1, irow = (u64)n_in + 1;
+    const u32 live = (u32)min((u64)KS_TB, batch - b0);
+    const bool on = o <= n_out;
+    const u64 *__restrict__ kc = ksk + (on ? o : n_out);        // idle lanes read a valid column and store nothing
+    const u64 *__restrict__ src = in + b0 * irow;
+    u64 acc[KS_TB];
+#pragma unroll
+    for (int t = 0; t < KS_TB; t++) acc[t] = 0;
+    for (u32 i = 0; i < n_in; i++) {
+        u64 w[KS_TB];
+#pragma unroll
+        for (int t = 0; t < KS_TB; t++) w[t] = (u32)t < live ? src[t * irow + i] : 0ull;
+        const u64 *__restrict__ kr = kc + (u64)i * l * row;
+        for (u32 d = 0; d < l; d++) {
+            const u64 kv = kr[(u64)d * row];
+            const u32 sh = l - 1u - d;
+#pragma unroll
+            for (int t = 0; t < KS_TB; t++) acc[t] += ((w[t] >> sh) & 1u) ? kv : 0ull;
+        }
+    }
+    if (!on) return;
+#pragma unroll
+    for (int t = 0; t < KS_TB; t++)
+        if ((u32)t < live) out[(b0 + t) * row + o] = (o == n_out ? src[t * irow + n_in] : 0ull) - acc[t];
+}
+
+}  // namespace fhe
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+namespace {
+
+bool br_ext32_on(u64 n, unsigned k, unsigned l) { return fhe_ext32_enabled() && fhe::ext32_shape_supported(n, k, l); }
+
+bool overlaps(const void *a, u64 abytes, const void *b, u64 bbytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return abytes && bbytes && x < y + bbytes && y < x + abytes;
+}
+
+int check_ring(uint64_t n, unsigned k, const char *who) {
+    if (n < 2 || (n & (n - 1)) != 0 || n > (1ull << 19))
+        return fhe_fail(FHE_E_BAD_N, "%s: n=%llu must be a power of two in [2, 2^19]", who, (unsigned long long)n);
+    if (k < 1 || k > 64) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= k <= 64", who);
+    return FHE_OK;
+}
+
+int check_br(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const char *who) {
+    int rc = check_ring(n, k, who);
+    if (rc != FHE_OK) return rc;
+    if (l < 1 || l > 64) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= l <= 64 (beta = 2)", who);
+    if (n_lwe < 1) return fhe_fail(FHE_E_INVALID, "%s: n_lwe must be at least 1", who);
+    if (fhe_tfhe_bsk_prepared_words(n, k, l, n_lwe) == 0)
+        return fhe_fail(FHE_E_INVALID, "%s: no prepared bootstrapping key for n=%llu, k=%u, l=%u (fhe_tfhe_bsk_prepared_words is 0)", who,
+                        (unsigned long long)n, k, l);
+    return FHE_OK;
+}
+
+int check_ks(unsigned n_in, unsigned n_out, unsigned beta, unsigned l, const char *who) {
+    if (n_in < 1 || n_out < 1) return fhe_fail(FHE_E_INVALID, "%s: need n_in, n_out >= 1", who);
+    if (beta != 2) return fhe_fail(FHE_E_INVALID, "%s: only beta = 2 is supported (torus.rs:44)", who);
+    if (l < 1 || l > 64) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= l <= 64", who);
+    return FHE_OK;
+}
+
+// the blind rotation proper, arguments validated: ACC lives in d_out
+int blind_rotation(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const void *d_bsk, const void *d_table, const void *d_lwe, void *d_out,
+                   size_t batch, hipStream_t st) {
+    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
+    const u64 T = (u64)k1 * l, words = fhe_tggsw_prepared_words(n, k, l);
+    u64 *acc = (u64 *)d_out;
+    void *wsv = nullptr;
+    int rc;
+    if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &wsv)) != FHE_OK) return rc;
+    u32 *shift = (u32 *)wsv;
+    { fhe::KernelTimer kt_("tfhe_br_init", (int)L, st);
+    hipLaunchKernelGGL(fhe::tfhe_br_init_kernel, dim3(fhe_ew_grid((u64)batch * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_lwe,
+                       (const u64 *)d_table, acc, shift, n_lwe, k1, L, (u64)batch);
+    }
+    LAUNCH_OK("tfhe_br_init_kernel");
+    if (br_ext32_on(n, k, l)) {
+        fhe::Ext32Args a{};
+        if ((rc = fhe_ext32_tables(n, &a)) != FHE_OK) return rc;
+        u32 parts = 1, tpp = 0;
+        fhe::ext32_split(n, batch, (u32)T, &parts, &tpp);
+        if ((rc = fhe_workspace_get(1, (u64)batch * parts * 2 * (2 * k1) * n * 4, st, &wsv)) != FHE_OK) return rc;
+        a.k = k;
+        a.src = acc; a.ct_stride = (u64)k1 * n; a.part32 = (uint32_t *)wsv; a.out = acc; a.batch = batch;
+        a.l = l; a.T = (u32)T; a.parts = parts; a.tpp = tpp;
+        a.shift_stride = n_lwe;
+        for (unsigned j = 0; j < n_lwe; j++) {
+            a.key32 = (uint32_t *)const_cast<void *>(d_bsk) + (u64)j * 2 * words;
+            a.shift = shift + j;
+            hipError_t e = fhe::launch_ext32_mac(a, (int)L, fhe::SRC32_CMUX, st);
+            if (e == hipSuccess) e = fhe::launch_ext32_tail_cmux(a, (int)L, st);
+            if (e != hipSuccess) return fhe_hip_fail(e, "digit32 CMux kernels");
+        }
+        return FHE_OK;
+    }
+    // composed step: D = rot(ACC, e) - ACC, P = BSK_j [x] D, ACC += P
+    const u64 cw = (u64)batch * k1 * n;
+    if ((rc = fhe_workspace_get(6, 2 * cw * 8, st, &wsv)) != FHE_OK) return rc;
+    u64 *D = (u64 *)wsv, *P = D + cw;
+    for (unsigned j = 0; j < n_lwe; j++) {
+        { fhe::KernelTimer kt_("tfhe_rotdiff", (int)L, st);
+        hipLaunchKernelGGL(fhe::tfhe_rotdiff_kernel, dim3(fhe_ew_grid(cw)), dim3(256), 0, st, (const u64 *)acc, (const u32 *)shift + j, (u64)n_lwe, D,
+                           k1, L, (u64)batch);
+        }
+        LAUNCH_OK("tfhe_rotdiff_kernel");
+        if ((rc = fhe_tggsw_external_product_prepared_dev(n, k, l, (const u64 *)d_bsk + (u64)j * words, D, P, batch, st)) != FHE_OK) return rc;
+        { fhe::KernelTimer kt_("tfhe_add", (int)L, st);
+        hipLaunchKernelGGL(fhe::tfhe_add_kernel, dim3(fhe_ew_grid(cw)), dim3(256), 0, st, acc, (const u64 *)P, cw);
+        }
+        LAUNCH_OK("tfhe_add_kernel");
+    }
+    return FHE_OK;
+}
+
+int sample_extraction(uint64_t n, unsigned k, unsigned h, const void *d_tglwe, void *d_tlwe, size_t batch, hipStream_t st) {
+    const u32 L = (u32)__builtin_ctzll(n);
+    { fhe::KernelTimer kt_("tglwe_sample_extract", (int)L, st);
+    hipLaunchKernelGGL(fhe::tglwe_sample_extract_kernel, dim3(fhe_ew_grid((u64)batch * (k * n + 1))), dim3(256), 0, st, (const u64 *)d_tglwe,
+                       (u64 *)d_tlwe, k, L, h, (u64)batch);
+    }
+    LAUNCH_OK("tglwe_sample_extract_kernel");
+    return FHE_OK;
+}
+
+int key_switch(unsigned n_in, unsigned n_out, unsigned l, const void *d_ksk, const void *d_in, void *d_out, size_t batch, hipStream_t st) {
+    const u32 cblocks = (n_out + 1 + fhe::KS_TH - 1) / fhe::KS_TH;
+    const u64 grid = ((u64)batch + fhe::KS_TB - 1) / fhe::KS_TB * cblocks;
+    if (grid > 0x7fffffffull) return fhe_fail(FHE_E_INVALID, "fhe_tlwe_key_switch_dev: batch too large for one launch");
+    { fhe::KernelTimer kt_("tlwe_key_switch", 0, st);
+    hipLaunchKernelGGL(fhe::tlwe_key_switch_kernel, dim3((unsigned)grid), dim3(fhe::KS_TH), 0, st, (const u64 *)d_ksk, (const u64 *)d_in,
+                       (u64 *)d_out, n_in, n_out, l, (u64)batch, cblocks);
+    }
+    LAUNCH_OK("tlwe_key_switch_kernel");
+    return FHE_OK;
+}
+
+}  // namespace
+
+extern "C" size_t fhe_tfhe_bsk_prepared_words(uint64_t n, unsigned k, unsigned l, unsigned n_lwe) {
+    const size_t w = fhe_tggsw_prepared_words(n, k, l);
+    if (w == 0 || n_lwe == 0 || w > SIZE_MAX / n_lwe) return 0;
+    return w * n_lwe;
+}
+
+extern "C" int fhe_tfhe_bsk_prepare_dev(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const void *d_bsk, void *d_prepared, void *hip_stream) {
+    const char *who = "fhe_tfhe_bsk_prepare_dev";
+    int rc = check_br(n, k, l, n_lwe, who);
+    if (rc != FHE_OK) return rc;
+    if (!d_bsk || !d_prepared) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk); REQUIRE_ALIGNED(d_prepared);
+    const u64 bsk_bytes = (u64)n_lwe * (k + 1) * l * (k + 1) * n * 8;
+    if (overlaps(d_bsk, bsk_bytes, d_prepared, fhe_tfhe_bsk_prepared_words(n, k, l, n_lwe) * 8))
+        return fhe_fail(FHE_E_INVALID, "%s: d_prepared overlaps d_bsk", who);
+    return fhe_tggsw_prepare_keys(n, k, l, n_lwe, d_bsk, d_prepared, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_tfhe_blind_rotation_dev(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const void *d_bsk_prepared, const void *d_table,
+                                           const void *d_lwe, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_tfhe_blind_rotation_dev";
+    int rc = check_br(n, k, l, n_lwe, who);
+    if (rc != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    if (!d_bsk_prepared || !d_table || !d_lwe || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_table); REQUIRE_ALIGNED(d_lwe); REQUIRE_ALIGNED(d_out);
+    const u64 out_bytes = (u64)batch * (k + 1) * n * 8;
+    if (overlaps(d_out, out_bytes, d_bsk_prepared, fhe_tfhe_bsk_prepared_words(n, k, l, n_lwe) * 8) ||
+        overlaps(d_out, out_bytes, d_table, (u64)(k + 1) * n * 8) || overlaps(d_out, out_bytes, d_lwe, (u64)batch * (n_lwe + 1ull) * 8))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    return blind_rotation(n, k, l, n_lwe, d_bsk_prepared, d_table, d_lwe, d_out, batch, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_tglwe_sample_extraction_dev(uint64_t n, unsigned k, unsigned h, const void *d_tglwe, void *d_tlwe, size_t batch,
+                                               void *hip_stream) {
+    const char *who = "fhe_tglwe_sample_extraction_dev";
+    int rc = check_ring(n, k, who);
+    if (rc != FHE_OK) return rc;
+    if (h >= n) return fhe_fail(FHE_E_INVALID, "%s: need h < n (h=%u, n=%llu)", who, h, (unsigned long long)n);
+    if (batch == 0) return FHE_OK;
+    if (!d_tglwe || !d_tlwe) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_tglwe); REQUIRE_ALIGNED(d_tlwe);
+    if (overlaps(d_tlwe, (u64)batch * ((u64)k * n + 1) * 8, d_tglwe, (u64)batch * (k + 1) * n * 8))
+        return fhe_fail(FHE_E_INVALID, "%s: d_tlwe overlaps d_tglwe", who);
+    return sample_extraction(n, k, h, d_tglwe, d_tlwe, batch, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_tlwe_key_switch_dev(unsigned n_in, unsigned n_out, unsigned beta, unsigned l, const void *d_ksk, const void *d_in, void *d_out,
+                                       size_t batch, void *hip_stream) {
+    const char *who = "fhe_tlwe_key_switch_dev";
+    int rc = check_ks(n_in, n_out, beta, l, who);
+    if (rc != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    if (!d_ksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
+    const u64 out_bytes = (u64)batch * (n_out + 1ull) * 8;
+    if (overlaps(d_out, out_bytes, d_in, (u64)batch * (n_in + 1ull) * 8) || overlaps(d_out, out_bytes, d_ksk, (u64)n_in * l * (n_out + 1ull) * 8))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    return key_switch(n_in, n_out, l, d_ksk, d_in, d_out, batch, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_tfhe_bootstrap_dev(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const void *d_bsk_prepared, const void *d_table,
+                                      unsigned ks_l, const void *d_ksk, const void *d_in, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_tfhe_bootstrap_dev";
+    int rc = check_br(n, k, l, n_lwe, who);
+    if (rc != FHE_OK) return rc;
+    const u64 kn = (u64)k * n;
+    if (kn > 0xffffffffull) return fhe_fail(FHE_E_INVALID, "%s: k n must fit 32 bits", who);
+    if ((rc = check_ks((unsigned)kn, n_lwe, 2, ks_l, who)) != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    if (!d_bsk_prepared || !d_table || !d_ksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_table); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
+    const u64 out_bytes = (u64)batch * (n_lwe + 1ull) * 8;
+    if (overlaps(d_out, out_bytes, d_bsk_prepared, fhe_tfhe_bsk_prepared_words(n, k, l, n_lwe) * 8) ||
+        overlaps(d_out, out_bytes, d_table, (u64)(k + 1) * n * 8) || overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) ||
+        overlaps(d_out, out_bytes, d_in, out_bytes))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    void *acc = nullptr, *ext = nullptr;
+    if ((rc = fhe_workspace_get(7, (u64)batch * (k + 1) * n * 8, st, &acc)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(8, (u64)batch * (kn + 1) * 8, st, &ext)) != FHE_OK) return rc;
+    // tlwe.rs:150-161: blind rotation -> sample extraction (h = 0) -> key switch back to dimension n_lwe
+    if ((rc = blind_rotation(n, k, l, n_lwe, d_bsk_prepared, d_table, d_in, acc, batch, st)) != FHE_OK) return rc;
+    if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) return rc;
+    return key_switch((unsigned)kn, n_lwe, ks_l, d_ksk, ext, d_out, batch, st);
+}

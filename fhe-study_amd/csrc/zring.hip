@@ -991,25 +991,38 @@ extern "C" int fhe_tggsw_prepare_dev(uint64_t n, unsigned k, unsigned l, const v
     if (!one_prime_form(n, k, l)) return fhe_fail(FHE_E_INVALID, "fhe_tggsw_prepare_dev: no prepared form for n=%llu, k=%u, l=%u (fhe_tggsw_prepared_words is 0)", (unsigned long long)n, k, l);
     if (!d_tggsw || !d_prepared) return fhe_fail(FHE_E_NULL, "fhe_tggsw_prepare_dev: NULL buffer");
     REQUIRE_ALIGNED(d_tggsw); REQUIRE_ALIGNED(d_prepared);
+    return fhe_tggsw_prepare_keys(n, k, l, 1, d_tggsw, d_prepared, (hipStream_t)hip_stream);
+}
+
+// `keys` TGGSWs side by side (a bootstrapping key): key j's prepared form at d_prepared + j * fhe_tggsw_prepared_words.
+// Arguments are the caller's to validate.
+int fhe_tggsw_prepare_keys(uint64_t n, unsigned k, unsigned l, uint64_t keys, const void *d_tggsw, void *d_prepared, hipStream_t st) {
     ZCtx z1;
+    int rc;
     if ((rc = zctx_init(&z1, n, 1)) != FHE_OK) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
     const u32 k1 = k + 1;
     const u64 T = (u64)k1 * l, grows = T * k1;
     if (ext32_on(n, k, l)) {
         // two 27-bit primes (digit32.hip): the halves of every word transformed per prime into d_prepared as u32
-        // [prime][t][half][c][n] — the same number of bytes as the 61-bit form
+        // [prime][t][half][c][n] — the same number of bytes as the 61-bit form; one launch for all the keys (gridDim.z)
         fhe::Ext32Args a{};
         if ((rc = fhe_ext32_tables(n, &a)) != FHE_OK) return rc;
         a.key64 = (const u64 *)d_tggsw; a.key32 = (uint32_t *)d_prepared; a.rows = 2 * grows; a.key_k1 = k1;
-        hipError_t e = fhe::launch_ext32_key(a, (int)z1.dp[0].log_n, st);
+        hipError_t e;
+        if (keys == 1) {
+            e = fhe::launch_ext32_key(a, (int)z1.dp[0].log_n, st);
+        } else {
+            a.key_stride64 = grows * n; a.key_stride32 = 2 * a.rows * n;
+            e = fhe::launch_ext32_key_many(a, (int)z1.dp[0].log_n, keys, st);
+        }
         return e == hipSuccess ? FHE_OK : fhe_hip_fail(e, "ntt32_fwd_key_kernel");
     }
+    // [key][t][c][n] is [key * T + t][c][n]: the split and the transforms see one key of keys * T TGLev rows
     { fhe::KernelTimer kt_("zr_split32", 0, st);
-    hipLaunchKernelGGL(fhe::zr_split32_kernel, dim3(fhe_ew_grid(grows * n)), dim3(256), 0, st, (const u64 *)d_tggsw, (u64 *)d_prepared, T, k1, (u32)n);
+    hipLaunchKernelGGL(fhe::zr_split32_kernel, dim3(fhe_ew_grid(keys * grows * n)), dim3(256), 0, st, (const u64 *)d_tggsw, (u64 *)d_prepared, keys * T, k1, (u32)n);
     }
     LAUNCH_OK("zr_split32_kernel");
-    return z_forward(z1, 0, (const u64 *)d_prepared, (u64 *)d_prepared, 2 * grows, st);          // halves are < 2^32 < P1
+    return z_forward(z1, 0, (const u64 *)d_prepared, (u64 *)d_prepared, keys * 2 * grows, st);          // halves are < 2^32 < P1
 }
 
 extern "C" int fhe_tggsw_external_product_prepared_dev(uint64_t n, unsigned k, unsigned l, const void *d_prepared,
@@ -1031,18 +1044,14 @@ extern "C" int fhe_tggsw_external_product_prepared_dev(uint64_t n, unsigned k, u
     if (ext32_on(n, k, l)) {
         fhe::Ext32Args a{};
         if ((rc = fhe_ext32_tables(n, &a)) != FHE_OK) return rc;
-        // parts: enough workgroups to fill the chip several times over (n <= 1024: four workgroups' worth of LDS per CU),
-        // only as many as leave no CU empty above (one or two workgroups per CU: see fhe_glwe_key_switch_dev)
-        const u32 W = fhe::ext32_units((int)z1.dp[0].log_n);
-        u32 parts32 = 1;
-        const u64 slots = n <= 1024 ? 2048 : n == 2048 ? 512 : 256;
-        while (parts32 < 8 && batch * parts32 < slots && (T / (parts32 * 2)) >= 2 * W) parts32 *= 2;
+        u32 parts32 = 1, tpp = 0;
+        fhe::ext32_split(n, batch, (u32)T, &parts32, &tpp);
         if ((rc = fhe_workspace_get(1, (u64)batch * parts32 * 2 * (2 * k1) * n * 4, st, &wsv)) != FHE_OK) return rc;
         a.k = k;
         a.key32 = (uint32_t *)const_cast<void *>(d_prepared);
         a.src = (const u64 *)d_tglwe; a.ct_stride = (u64)k1 * n; a.part32 = (uint32_t *)wsv; a.out = (u64 *)d_out; a.batch = batch;
         a.l = l; a.T = (u32)T; a.parts = parts32;
-        a.tpp = (((u32)T + parts32 - 1) / parts32 + W - 1) / W * W;
+        a.tpp = tpp;
         hipError_t e = fhe::launch_ext32_mac(a, (int)z1.dp[0].log_n, fhe::SRC_DIGITS, st);
         if (e == hipSuccess) e = fhe::launch_ext32_tail(a, (int)z1.dp[0].log_n, st);
         return e == hipSuccess ? FHE_OK : fhe_hip_fail(e, "digit32 kernels");

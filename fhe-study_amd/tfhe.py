@@ -8,6 +8,11 @@ over the C ABI.
     TGLWE * Tn        tfhe/src/tglwe.rs:182-194        TGLWE.__mul__
     TGLev * Vec<Tn>   tfhe/src/tggsw.rs:139-149        TGLev.__mul__
     TGGSW * TGLWE     tfhe/src/tggsw.rs:45-62          TGGSW.__mul__   (beta = 2, l = 64 as there)
+    TGLWE::left_rotate, sample_extraction   tglwe.rs:89-118     TGLWE.left_rotate, TGLWE.sample_extraction
+    TLWE::key_switch  tfhe/src/tlwe.rs:101-111         TLWE.key_switch (beta = 2)
+    BootstrappingKey  tlwe.rs:163-167                  BootstrappingKey (device-resident: prepared BSK + KSK)
+    blind_rotation, bootstrapping   tlwe.rs:121-161    blind_rotation, bootstrapping (the mod switch
+                                                       rounds to 2N, and the CMux loop runs over all n_lwe key bits)
 """
 import numpy as np
 
@@ -51,6 +56,25 @@ class TGLWE:
         out = binding.tglwe_mul_tn(plaintext.n, k, x, plaintext.coeffs).reshape(x.shape)
         return TGLWE(out[..., :k, :], out[..., k, :])
 
+    def left_rotate(self, h):
+        """multiply by X^-h, h < 2n (ring_torus.rs:118-132 for h < n; h >= n also negates)"""
+        n = self.b.shape[-1]
+        j = np.arange(n) + int(h) % (2 * n)
+        sign = (j // n) % 2 == 1
+        rot = lambda x: np.where(sign, np.uint64(0) - x[..., j % n], x[..., j % n]).astype(np.uint64)
+        return TGLWE(rot(self.a), rot(self.b))
+
+    def sample_extraction(self, h):
+        """TLWE of dimension k n holding coefficient h of the phase (tglwe.rs:89-115), on the device"""
+        torch = _torch()
+        x = self.packed()
+        k1, n = x.shape[-2], x.shape[-1]
+        batch = x.size // (k1 * n)
+        d_in = _to_dev(x)
+        out = torch.empty((batch, (k1 - 1) * n + 1), dtype=torch.int64, device="cuda")
+        binding.tglwe_sample_extraction_dev(n, k1 - 1, h, d_in.data_ptr(), out.data_ptr(), batch)
+        return TLWE(_from_dev(out).reshape(x.shape[:-2] + ((k1 - 1) * n + 1,)))
+
 
 class TGLev:
     """l TGLWEs (tggsw.rs:65): rows [l][(k+1)][n]"""
@@ -84,3 +108,80 @@ class TGGSW:
         x = tglwe.packed()
         out = binding.tggsw_external_product(n, k1 - 1, l, self.rows, x).reshape(x.shape)
         return TGLWE(out[..., : k1 - 1, :], out[..., k1 - 1, :])
+
+
+# ---- TFHE bootstrapping (tfhe/src/tlwe.rs) ----------------------------------------------------------------------
+def _torch():
+    import torch
+
+    return torch
+
+
+def _to_dev(x):
+    return _torch().from_numpy(np.ascontiguousarray(x, dtype=np.uint64).view(np.int64)).cuda()
+
+
+def _from_dev(t):
+    return t.cpu().numpy().view(np.uint64)
+
+
+class TLWE:
+    """LWE ciphertexts [a_0 .. a_{m-1}, b]: `words` is (m + 1,) or (batch, m + 1)"""
+
+    def __init__(self, words):
+        self.words = np.ascontiguousarray(words, dtype=np.uint64)
+
+    @property
+    def dim(self):
+        return self.words.shape[-1] - 1
+
+    def key_switch(self, ksk, l, beta=2):
+        """tlwe.rs:101-111: ksk [n_in][l][n_out + 1] (numpy or a device tensor) -> TLWE of dimension n_out"""
+        torch = _torch()
+        k = ksk if isinstance(ksk, torch.Tensor) else _to_dev(ksk)
+        n_in, n_out = self.dim, k.shape[-1] - 1
+        x = self.words.reshape(-1, n_in + 1)
+        out = torch.empty((x.shape[0], n_out + 1), dtype=torch.int64, device="cuda")
+        dx = _to_dev(x)                  # device buffers are held until the call returns: never a freed temporary's pointer
+        binding.tlwe_key_switch_dev(n_in, n_out, beta, l, k.data_ptr(), dx.data_ptr(), out.data_ptr(), x.shape[0])
+        return TLWE(_from_dev(out).reshape(self.words.shape[:-1] + (n_out + 1,)))
+
+
+class BootstrappingKey:
+    """(Vec<TGGSW>, KSK) of tlwe.rs:163-167 kept on the device: the n_lwe bit-TGGSWs [n_lwe][(k+1)][l][(k+1)][n]
+    prepared once (fhe_tfhe_bsk_prepare_dev), and the KSK [k n][ks_l][n_lwe + 1] back to the LWE key"""
+
+    def __init__(self, n, k, l, n_lwe, bsk, ksk, ks_l=64):
+        torch = _torch()
+        self.n, self.k, self.l, self.n_lwe, self.ks_l = n, k, l, n_lwe, ks_l
+        words = binding.tfhe_bsk_prepared_words(n, k, l, n_lwe)
+        if words == 0:
+            raise binding.FheError(binding.FHE_E_INVALID, f"no prepared bootstrapping key for n={n}, k={k}, l={l}")
+        g = bsk if isinstance(bsk, torch.Tensor) else _to_dev(bsk)
+        self.bsk = torch.empty(words, dtype=torch.int64, device="cuda")
+        binding.tfhe_bsk_prepare_dev(n, k, l, n_lwe, g.data_ptr(), self.bsk.data_ptr())
+        self.ksk = ksk if isinstance(ksk, torch.Tensor) else _to_dev(ksk)
+        torch.cuda.synchronize()
+
+
+def blind_rotation(c, btk, table):
+    """tlwe.rs:121-148 as DESIGN.md §10 defines it: TGLWE that decrypts to X^-phi~ table"""
+    torch = _torch()
+    x = c.words.reshape(-1, btk.n_lwe + 1)
+    out = torch.empty((x.shape[0], btk.k + 1, btk.n), dtype=torch.int64, device="cuda")
+    dt, dx = _to_dev(table.packed()), _to_dev(x)
+    binding.tfhe_blind_rotation_dev(btk.n, btk.k, btk.l, btk.n_lwe, btk.bsk.data_ptr(), dt.data_ptr(), dx.data_ptr(), out.data_ptr(),
+                                    x.shape[0])
+    o = _from_dev(out)
+    return TGLWE(o[:, : btk.k, :], o[:, btk.k, :])
+
+
+def bootstrapping(btk, table, c):
+    """tlwe.rs:150-161: blind rotation, sample extraction at 0, key switch back to dimension n_lwe"""
+    torch = _torch()
+    x = c.words.reshape(-1, btk.n_lwe + 1)
+    out = torch.empty(x.shape, dtype=torch.int64, device="cuda")
+    dt, dx = _to_dev(table.packed()), _to_dev(x)
+    binding.tfhe_bootstrap_dev(btk.n, btk.k, btk.l, btk.n_lwe, btk.bsk.data_ptr(), dt.data_ptr(), btk.ks_l, btk.ksk.data_ptr(),
+                               dx.data_ptr(), out.data_ptr(), x.shape[0])
+    return TLWE(_from_dev(out).reshape(c.words.shape))

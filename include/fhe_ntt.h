@@ -287,6 +287,39 @@ int fhe_tglev_mul(uint64_t n, unsigned k, unsigned l, const uint64_t *tglev, con
 int fhe_tglev_mul_dev(uint64_t n, unsigned k, unsigned l, const void *d_tglev, const void *d_v, void *d_out,
                       size_t batch, void *hip_stream);
 
+/* ---- TFHE bootstrapping (tfhe/src/tlwe.rs:101-161, tglwe.rs:89-118; definitions in DESIGN.md §10) ----
+ * N = n = 2^L, k = GLWE rank, every word u64 wrapping mod 2^64.  A TLWE of dimension m is [a_0 .. a_{m-1}, b]
+ * (m + 1 words); a TGLWE is [(k+1)][n] as above.  Output buffers must not overlap the inputs.
+ *   fhe_tfhe_bsk_prepared_words  u64 words a prepared bootstrapping key holds: n_lwe x fhe_tggsw_prepared_words
+ *                                (0: no prepared form for this shape)
+ *   fhe_tfhe_bsk_prepare_dev     d_bsk [n_lwe][(k+1)][l][(k+1)][n] (TGGSW j encrypts LWE key bit j) -> d_prepared;
+ *                                key j's prepared form is what fhe_tggsw_prepare_dev makes of TGGSW j, at word
+ *                                offset j * fhe_tggsw_prepared_words
+ *   fhe_tfhe_blind_rotation_dev  d_lwe [batch][n_lwe + 1], d_table [(k+1)][n] (the test vector v, one for the batch)
+ *                                -> d_out [batch][(k+1)][n]: with a~ = round(a 2N / 2^64) mod 2N (rounding, not the
+ *                                reference's floor to kN), ACC = X^{-b~} v, then for every j
+ *                                ACC += BSK_j [x] (X^{a~_j} ACC - ACC)  (cmux, tggsw.rs:39-41; [x] as
+ *                                fhe_tggsw_external_product_prepared_dev).  Decrypts to X^{-phi~} v.
+ *   fhe_tglwe_sample_extraction_dev  d_tglwe [batch][(k+1)][n] -> d_tlwe [batch][k n + 1], coefficient h < n
+ *                                (tglwe.rs:89-115)
+ *   fhe_tlwe_key_switch_dev      d_in [batch][n_in + 1], d_ksk [n_in][l][n_out + 1] (TLev of input key bit i under the
+ *                                output key) -> d_out [batch][n_out + 1] = (0 .. 0, b) - sum_i sum_{d<l} bit_{l-1-d}(a_i)
+ *                                ksk[i][d] (tlwe.rs:101-111); beta = 2 only, 1 <= l <= 64
+ *   fhe_tfhe_bootstrap_dev       blind rotation -> sample extraction (h = 0) -> key switch (n_in = k n, n_out = n_lwe,
+ *                                ks_l levels): d_in, d_out [batch][n_lwe + 1] (tlwe.rs:150-161) */
+size_t fhe_tfhe_bsk_prepared_words(uint64_t n, unsigned k, unsigned l, unsigned n_lwe);
+int fhe_tfhe_bsk_prepare_dev(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const void *d_bsk, void *d_prepared,
+                             void *hip_stream);
+int fhe_tfhe_blind_rotation_dev(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
+                                const void *d_table, const void *d_lwe, void *d_out, size_t batch, void *hip_stream);
+int fhe_tglwe_sample_extraction_dev(uint64_t n, unsigned k, unsigned h, const void *d_tglwe, void *d_tlwe, size_t batch,
+                                    void *hip_stream);
+int fhe_tlwe_key_switch_dev(unsigned n_in, unsigned n_out, unsigned beta, unsigned l, const void *d_ksk,
+                            const void *d_in, void *d_out, size_t batch, void *hip_stream);
+int fhe_tfhe_bootstrap_dev(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
+                           const void *d_table, unsigned ks_l, const void *d_ksk, const void *d_in, void *d_out,
+                           size_t batch, void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
