@@ -64,6 +64,10 @@ EXPORTS = [
     # TFHE bootstrapping (tfhe_boot.hip)
     "fhe_tfhe_bsk_prepared_words", "fhe_tfhe_bsk_prepare_dev", "fhe_tfhe_blind_rotation_dev",
     "fhe_tglwe_sample_extraction_dev", "fhe_tlwe_key_switch_dev", "fhe_tfhe_bootstrap_dev",
+    # the signed base-2^b gadget (tfhe_boot.hip)
+    "fhe_tn_gadget_decompose_dev", "fhe_tggsw_gadget_prepared_words", "fhe_tggsw_gadget_prepare_dev",
+    "fhe_tggsw_gadget_external_product_dev", "fhe_tfhe_gadget_bsk_prepared_words", "fhe_tfhe_gadget_bsk_prepare_dev",
+    "fhe_tfhe_gadget_blind_rotation_dev", "fhe_tlwe_gadget_key_switch_dev", "fhe_tfhe_gadget_bootstrap_dev",
 ]
 
 
@@ -219,6 +223,17 @@ def load_library():
     L.fhe_tglwe_sample_extraction_dev.argtypes = [_u64, _uint, _uint, _vp, _vp, _sz, _vp]
     L.fhe_tlwe_key_switch_dev.argtypes = [_uint, _uint, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
     L.fhe_tfhe_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _vp, _vp, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tn_gadget_decompose_dev.argtypes = [_u64, _uint, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_tggsw_gadget_prepared_words.argtypes = [_u64, _uint, _uint, _uint]
+    L.fhe_tggsw_gadget_prepared_words.restype = _sz
+    L.fhe_tggsw_gadget_prepare_dev.argtypes = [_u64, _uint, _uint, _uint, _vp, _vp, _vp]
+    L.fhe_tggsw_gadget_external_product_dev.argtypes = [_u64, _uint, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_gadget_bsk_prepared_words.argtypes = [_u64, _uint, _uint, _uint, _uint]
+    L.fhe_tfhe_gadget_bsk_prepared_words.restype = _sz
+    L.fhe_tfhe_gadget_bsk_prepare_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _vp, _vp]
+    L.fhe_tfhe_gadget_blind_rotation_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tlwe_gadget_key_switch_dev.argtypes = [_uint, _uint, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_gadget_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _vp, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -477,6 +492,46 @@ def tlwe_key_switch_dev(n_in, n_out, beta, l, d_ksk, d_in, d_out, batch, stream=
 
 def tfhe_bootstrap_dev(n, k, l, n_lwe, d_bsk_prepared, d_table, ks_l, d_ksk, d_in, d_out, batch, stream=None):
     _check(load_library().fhe_tfhe_bootstrap_dev(n, k, l, n_lwe, d_bsk_prepared, d_table, ks_l, d_ksk, d_in, d_out, batch, stream))
+
+
+# ---- the signed base-2^b gadget (log_beta = b) --------------------------------------------------------
+def tn_gadget_decompose_dev(n, log_beta, l, d_a, d_out, rows, stream=None):
+    _check(load_library().fhe_tn_gadget_decompose_dev(n, log_beta, l, d_a, d_out, rows, stream))
+
+
+def tggsw_gadget_prepared_words(n, k, log_beta, l):
+    return load_library().fhe_tggsw_gadget_prepared_words(n, k, log_beta, l)
+
+
+def tggsw_gadget_prepare_dev(n, k, log_beta, l, d_tggsw, d_prepared, stream=None):
+    _check(load_library().fhe_tggsw_gadget_prepare_dev(n, k, log_beta, l, d_tggsw, d_prepared, stream))
+
+
+def tggsw_gadget_external_product_dev(n, k, log_beta, l, d_prepared, d_tglwe, d_out, batch, stream=None):
+    _check(load_library().fhe_tggsw_gadget_external_product_dev(n, k, log_beta, l, d_prepared, d_tglwe, d_out, batch, stream))
+
+
+def tfhe_gadget_bsk_prepared_words(n, k, log_beta, l, n_lwe):
+    return load_library().fhe_tfhe_gadget_bsk_prepared_words(n, k, log_beta, l, n_lwe)
+
+
+def tfhe_gadget_bsk_prepare_dev(n, k, log_beta, l, n_lwe, d_bsk, d_prepared, stream=None):
+    _check(load_library().fhe_tfhe_gadget_bsk_prepare_dev(n, k, log_beta, l, n_lwe, d_bsk, d_prepared, stream))
+
+
+def tfhe_gadget_blind_rotation_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_table, d_lwe, d_out, batch, stream=None):
+    _check(load_library().fhe_tfhe_gadget_blind_rotation_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_table, d_lwe, d_out, batch,
+                                                             stream))
+
+
+def tlwe_gadget_key_switch_dev(n_in, n_out, log_beta, l, d_ksk, d_in, d_out, batch, stream=None):
+    _check(load_library().fhe_tlwe_gadget_key_switch_dev(n_in, n_out, log_beta, l, d_ksk, d_in, d_out, batch, stream))
+
+
+def tfhe_gadget_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_table, ks_log_beta, ks_l, d_ksk, d_in, d_out, batch,
+                              stream=None):
+    _check(load_library().fhe_tfhe_gadget_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_table, ks_log_beta, ks_l, d_ksk,
+                                                        d_in, d_out, batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

@@ -78,14 +78,20 @@ __device__ __forceinline__ void exchange32x2(u32 (&va)[16], u32 (&vb)[16], u32 *
         vb[k] = lb[s];
     }
 }
-template <int LP, bool FRESH>
-__device__ __forceinline__ void fwd_rounds32x2_bits(u32 (&va)[16], u32 (&vb)[16], u32 *const (&tile)[2], const Tw32 *const (&ltw)[2],
-                                                    const Tw32 *const (&gtw)[2], const u32 *const (&lut)[2], u32 w, u32 tf,
-                                                    const u32 (&p)[2]) {
+// BITS: round 0 on bits by look-up (va = vb); otherwise on canonical residues (the gadget's signed digits, va != vb)
+template <int LP, bool FRESH, bool BITS = true>
+__device__ __forceinline__ void fwd_rounds32x2(u32 (&va)[16], u32 (&vb)[16], u32 *const (&tile)[2], const Tw32 *const (&ltw)[2],
+                                               const Tw32 *const (&gtw)[2], const u32 *const (&lut)[2], u32 w, u32 tf,
+                                               const u32 (&p)[2]) {
     using C = ContigCfg<LP>;
     const u32 pa = p[0], pa2 = 2u * pa, pb = p[1], pb2 = 2u * pb;
-    round0_bits32<C::R0, true>(va, lut[0], gtw[0], pa, pa2);
-    round0_bits32<C::R0, true>(vb, lut[1], gtw[1], pb, pb2);
+    if constexpr (BITS) {
+        round0_bits32<C::R0, true>(va, lut[0], gtw[0], pa, pa2);
+        round0_bits32<C::R0, true>(vb, lut[1], gtw[1], pb, pb2);
+    } else {
+        round_fwd32<C::R0, 0, true>(va, gtw[0], 1u, pa, pa2);
+        round_fwd32<C::R0, 0, true>(vb, gtw[1], 1u, pb, pb2);
+    }
     if constexpr (C::NR > 1) {
         constexpr int A = C::a_of(1), LS = C::ls0_of(1);
         constexpr bool L = C::in_lds(1);
@@ -227,11 +233,13 @@ __device__ __forceinline__ u32 digit32_of(u64 x, u32 l, u32 d) {
     if (SRC == SRC_DIGITS || SRC == SRC32_CMUX) return bit;
     return x >= (1ull << (l & 63u)) ? 1u : bit;
 }
-// the source word at position pos of a row.  SRC32_CMUX: X^-e row - row in T64[X]/(X^N+1), e < 2N, i.e.
+// SRC32_GADGET / SRC32_GCMUX: digit_d(x) + 2^(b-1) in [0, 2^b), sh = 64 - b (d+1), cadd = gadget_cadd (digit32.hpp)
+__device__ __forceinline__ u32 gadget_field32(u64 x, u64 cadd, u32 sh, u32 mask) { return (u32)((x + cadd) >> sh) & mask; }
+// the source word at position pos of a row.  SRC32_CMUX, SRC32_GCMUX: X^-e row - row in T64[X]/(X^N+1), e < 2N, i.e.
 // (-1)^floor((pos+e)/N) row[(pos+e) mod N] - row[pos] — one wrap in a thread's positions, the loads stay coalesced
 template <int SRC, int LP>
 __device__ __forceinline__ u64 src_word32(const u64 *__restrict__ row, u32 pos, u32 e) {
-    if constexpr (SRC == SRC32_CMUX) {
+    if constexpr (SRC == SRC32_CMUX || SRC == SRC32_GCMUX) {
         const u32 j = pos + e;                                            // < 3N
         const u64 x = row[j & ((1u << LP) - 1u)];
         return (((j >> LP) & 1u) ? 0ull - x : x) - row[pos];
@@ -242,10 +250,16 @@ __device__ __forceinline__ u64 src_word32(const u64 *__restrict__ row, u32 pos, 
 
 // key32 layout: [prime][t][c][n], t = row*l + digit, c < NC (NC = 2 * output rows: half-major, then component).
 // out: partial sums [b][part][prime][c][n] u32 canonical.
+// The gadget modes: a signed digit v enters each prime's transform as its canonical residue
+// (v < 0: p + v), so round 0 is the generic one and the primes' inputs differ; |v| <= 2^(b-1) <= 2^12 < p.
+template <int LP, int SRC>
+constexpr int mac32_waves() { return SRC == SRC32_CMUX || SRC == SRC32_GCMUX ? Mac32Cfg<LP>::CMUX_WAVES : Mac32Cfg<LP>::WAVES; }
 template <int LP, int NC, int SRC>
-__global__ __launch_bounds__((Mac32Cfg<LP>::TH), (SRC == SRC32_CMUX ? Mac32Cfg<LP>::CMUX_WAVES : Mac32Cfg<LP>::WAVES)) void digit_mac32_kernel(Ext32Args a) {
+__global__ __launch_bounds__((Mac32Cfg<LP>::TH), (mac32_waves<LP, SRC>())) void digit_mac32_kernel(Ext32Args a) {
     using C = ContigCfg<LP>;
     using K = Mac32Cfg<LP>;
+    constexpr bool GAD = SRC == SRC32_GADGET || SRC == SRC32_GCMUX;
+    constexpr bool ROT = SRC == SRC32_CMUX || SRC == SRC32_GCMUX;
     constexpr int PPT = K::PPT, W = K::W, TH = K::TH, NP = K::NP;
     const u32 pr0 = K::ONEP ? blockIdx.y : 0u;                      // the first prime this workgroup serves
     static_assert(NP * NC * PPT <= 64, "accumulators");
@@ -275,7 +289,14 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (SRC == SRC32_CMUX ? Mac32Cfg<L
     }
     __syncthreads();
     const u64 *__restrict__ ct = a.src + b * a.ct_stride;
-    const u32 e = SRC == SRC32_CMUX ? a.shift[b * a.shift_stride] : 0u;   // this ciphertext's rotation (blind rotation step)
+    const u32 e = ROT ? a.shift[b * a.shift_stride] : 0u;   // this ciphertext's rotation (blind rotation step)
+    u64 cadd = 0;
+    u32 ghalf = 0, gmask = 0;
+    if constexpr (GAD) {
+        cadd = gadget_cadd(a.log_beta, a.l);
+        ghalf = 1u << (a.log_beta - 1u);
+        gmask = 2u * ghalf - 1u;
+    }
 
     u64 acc[NP][NC][PPT];
 #pragma unroll
@@ -294,20 +315,35 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (SRC == SRC32_CMUX ? Mac32Cfg<L
         // the rotation as an opaque value per step: the 16 rotated offsets and signs of a thread are recomputed here
         // rather than hoisted out of the loop, where they would hold registers through the multiply phase
         u32 eo = e;
-        if constexpr (SRC == SRC32_CMUX) asm volatile("" : "+s"(eo));
+        if constexpr (ROT) asm volatile("" : "+s"(eo));
+        const u32 gsh = GAD ? 64u - a.log_beta * (d + 1u) : 0u;
         // the tiles were read by the previous step's multiply phase: barrier first (FRESH = false); every thread then
         // rewrites exactly the slots it gathered in the last exchange, reduced below 2p (a product is below 2 p^2 < 2^55.8)
         if constexpr (K::LOCK) {
             u32 va[16], vb[16];
+            if constexpr (GAD) {
 #pragma unroll
-            for (int k = 0; k < 16; k++) va[k] = vb[k] = digit32_of<SRC>(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo), a.l, d);
+                for (int k = 0; k < 16; k++) {
+                    const u32 f = gadget_field32(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo), cadd, gsh, gmask);
+                    va[k] = csub_u32(f + (p[0] - ghalf), p[0]);
+                    vb[k] = csub_u32(f + (p[1] - ghalf), p[1]);
+                    // the rotated loads in two waves of eight: all 32 words in flight at once spill at three waves per SIMD
+                    if constexpr (ROT) if (k == 7) __builtin_amdgcn_sched_barrier(0);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; k++) va[k] = vb[k] = digit32_of<SRC>(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo), a.l, d);
+            }
             const Tw32 *const lt[2] = {ltw_w[0], ltw_w[1]};
             const u32 *const ll[2] = {llut_w[0], llut_w[1]};
             u32 *const tl[2] = {tile[0], tile[1]};
 #ifndef FHE_D32_ABLATE_NTT      // timing-only builds (tools/abl_build.sh): the kernel without its transforms / its multiply phase
-            const Tw32 *const gt[2] = {gtw[0], gtw[1]};
+            const Tw32 *gt[2] = {gtw[0], gtw[1]};
+            // GCMUX: the tables' per-thread addresses recomputed per step, not held through it (at three waves per SIMD
+            // they were what spilled)
+            if constexpr (SRC == SRC32_GCMUX) asm volatile("" : "+s"(gt[0]), "+s"(gt[1]));
             const u32 pp[2] = {p[0], p[1]};
-            fwd_rounds32x2_bits<LP, false>(va, vb, tl, lt, gt, ll, w, tf, pp);
+            fwd_rounds32x2<LP, false, !GAD>(va, vb, tl, lt, gt, ll, w, tf, pp);
 #else
             __syncthreads();
 #endif
@@ -319,15 +355,24 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (SRC == SRC32_CMUX ? Mac32Cfg<L
             }
         } else {
             u32 bits = 0;
+            u32 fld[GAD ? 16 : 1];                                  // the gadget's digit fields, both primes take them
+            if constexpr (GAD) {
 #pragma unroll
-            for (int k = 0; k < 16; k++) bits |= digit32_of<SRC>(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo), a.l, d) << k;
+                for (int k = 0; k < 16; k++) fld[k] = gadget_field32(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo), cadd, gsh, gmask);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; k++) bits |= digit32_of<SRC>(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo), a.l, d) << k;
+            }
 #pragma unroll
             for (int pr = 0; pr < NP; pr++) {
                 u32 v[16];
 #pragma unroll
-                for (int k = 0; k < 16; k++) v[k] = (bits >> k) & 1u;
+                for (int k = 0; k < 16; k++) {
+                    if constexpr (GAD) v[k] = csub_u32(fld[k] + (p[pr] - ghalf), p[pr]);
+                    else v[k] = (bits >> k) & 1u;
+                }
 #ifndef FHE_D32_ABLATE_NTT
-                fwd_rounds32<LP, true, false, true>(v, tile[pr], ltw_w[pr], gtw[pr], llut_w[pr], w, tf, p[pr], 2u * p[pr]);
+                fwd_rounds32<LP, !GAD, false, true>(v, tile[pr], ltw_w[pr], gtw[pr], llut_w[pr], w, tf, p[pr], 2u * p[pr]);
 #else
                 __syncthreads();
 #endif
@@ -530,7 +575,7 @@ static hipError_t launch_mac32_lp(const Ext32Args &a, hipStream_t st) {
     const u64 grid = a.batch * a.parts;
     if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     if (hipError_t e = allow_big_lds((const void *)digit_mac32_kernel<LP, 4, SRC>, K::LDS_BYTES)) return e;
-    KernelTimer kt(SRC == SRC32_CMUX ? "digit_mac32_cmux" : "digit_mac32", LP, st);
+    KernelTimer kt(SRC == SRC32_CMUX ? "digit_mac32_cmux" : SRC == SRC32_GADGET ? "digit_mac32_gadget" : SRC == SRC32_GCMUX ? "digit_mac32_gcmux" : "digit_mac32", LP, st);
     hipLaunchKernelGGL((digit_mac32_kernel<LP, 4, SRC>), dim3((unsigned)grid, K::ONEP ? 2u : 1u), dim3(K::TH), K::LDS_BYTES, st, a);
     return hipGetLastError();
 }
@@ -559,6 +604,13 @@ bool ks32_shape_supported(u64 n, unsigned k, unsigned l) {
     if (n < 256 || n > 4096 || (n & (n - 1))) return false;
     return (u64)k * l * n <= (1ull << 21);
 }
+// (k+1) l n (2^32 - 1) 2^(b-1) < P / 2 in integers: 2 T n (2^32 - 1) 2^(b-1) < P, P = pA pB odd (the tail's centred lift)
+bool ext32_gadget_supported(u64 n, unsigned k, unsigned log_beta, unsigned l) {
+    if (k != 1 || l < 1 || log_beta < 1 || log_beta > 64 || (u64)log_beta * l > 64) return false;
+    if (n < 256 || n > 4096 || (n & (n - 1))) return false;
+    const unsigned __int128 bound = (unsigned __int128)((u64)(k + 1) * l * n) * 0xffffffffull << log_beta;   // 2 |half-sum| max
+    return bound < (unsigned __int128)((u64)kExt32PrimeA * kExt32PrimeB);
+}
 uint32_t ext32_units(int log_n) { return log_n >= 8 && log_n <= 12 ? (log_n == 12 ? 2u : 4096u >> log_n) : 0u; }
 // parts: enough workgroups to fill the chip several times over (n <= 1024: four workgroups' worth of LDS per CU),
 // only as many as leave no CU empty above (one or two workgroups per CU: see fhe_glwe_key_switch_dev)
@@ -569,6 +621,18 @@ void ext32_split(u64 n, u64 batch, uint32_t T, uint32_t *parts, uint32_t *tpp) {
     while (p < 8 && batch * p < slots && (T / (p * 2)) >= 2 * W) p *= 2;
     *parts = p;
     *tpp = ((T + p - 1) / p + W - 1) / W * W;
+}
+// gadget T = (k+1) l spans a few steps of W digits (N = 1024, (8, 3): T = 6, W = 4, two steps): one step per part while
+// the chip has room (batch x parts within the slots of ext32_split), one part of all the steps beyond
+void ext32_gadget_split(u64 n, u64 batch, uint32_t T, uint32_t *parts, uint32_t *tpp) {
+    const u32 W = ext32_units(__builtin_ctzll(n));
+    const u32 steps = (T + W - 1) / W;
+    const u64 slots = n <= 1024 ? 2048 : n == 2048 ? 512 : 256;
+    u32 p = 1;
+    while (p < steps && batch * p * 2 <= slots) p *= 2;
+    const u32 per = (steps + p - 1) / p;                       // steps per part; no part is left empty
+    *parts = (steps + per - 1) / per;
+    *tpp = per * W;
 }
 
 #define FHE_LP_SWITCH(FN, ...)                                        \
@@ -596,6 +660,8 @@ hipError_t launch_ext32_mac(const Ext32Args &a, int log_n, int src_kind, hipStre
     if (src_kind == SRC_DIGITS) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC_DIGITS) }
     if (src_kind == SRC_ZQBITS) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC_ZQBITS) }
     if (src_kind == SRC32_CMUX) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_CMUX) }
+    if (src_kind == SRC32_GADGET) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_GADGET) }
+    if (src_kind == SRC32_GCMUX) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_GCMUX) }
     return hipErrorNotSupported;
 }
 hipError_t launch_ext32_tail_cmux(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_CMUX) }

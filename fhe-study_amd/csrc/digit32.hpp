@@ -43,6 +43,7 @@ struct Ext32Args {
     u64 two32;                 // 2^32 mod q
     const u64 *glwe;           // the ciphertexts again, for the body row
     uint32_t k;
+    uint32_t log_beta;         // SRC32_GADGET / SRC32_GCMUX: b of the base 2^b; in k's padding word
     // several keys in one preparation launch (gridDim.z keys): key z at key64 + z*key_stride64, key32 + z*key_stride32
     u64 key_stride64, key_stride32;
     // SRC32_CMUX (blind rotation step): ciphertext b's source row r is rot(src_r, e_b) - src_r, e_b = shift[b*shift_stride]
@@ -50,15 +51,29 @@ struct Ext32Args {
     u64 shift_stride;
 };
 
-// source mode of digit_mac32_kernel next to SRC_DIGITS / SRC_ZQBITS (ntt_kernels.hpp): the digits of X^-e ACC - ACC
-enum : int { SRC32_CMUX = 4 };
+// source modes of digit_mac32_kernel next to SRC_DIGITS / SRC_ZQBITS (ntt_kernels.hpp): the digits of X^-e ACC - ACC;
+// the signed base-2^b digits of DESIGN.md §11 of the rows (SRC32_GADGET) or of X^-e ACC - ACC (SRC32_GCMUX)
+enum : int { SRC32_CMUX = 4, SRC32_GADGET = 5, SRC32_GCMUX = 6 };
 
 bool ext32_shape_supported(u64 n, unsigned k, unsigned l);        // TGGSW x TGLWE
 bool ks32_shape_supported(u64 n, unsigned k, unsigned l);         // GLWE::key_switch, base 2
+// the base-2^b gadget product: k = 1, 2^8 <= n <= 2^12, 1 <= b, b l <= 64, and the half-sum bound
+// (k+1) l n (2^32 - 1) 2^(b-1) below P / 2
+// digit_d(w) + 2^(b-1) = ((w + cadd) >> (64 - b (d+1))) & (2^b - 1) with cadd = the rounding bit 2^(s-1) (s = 64 - b l > 0)
+// plus the balancing constant B 2^s = sum_{d<l} 2^(63 - b d): every level's digit without a carry chain
+__host__ __device__ inline u64 gadget_cadd(uint32_t b, uint32_t l) {
+    const uint32_t s = 64u - b * l;
+    u64 c = s ? 1ull << (s - 1u) : 0ull;
+    for (uint32_t d = 0; d < l; d++) c += 1ull << (63u - b * d);
+    return c;
+}
+bool ext32_gadget_supported(u64 n, unsigned k, unsigned log_beta, unsigned l);
 uint32_t ext32_units(int log_n);                                   // digits per step of the fused kernel
 // parts (workgroups per ciphertext) and digits per part of the fused kernel for `batch` ciphertexts of T digit rows;
 // shared by the external product and the blind rotation's CMux steps
 void ext32_split(u64 n, u64 batch, uint32_t T, uint32_t *parts, uint32_t *tpp);
+// the same for the gadget modes, whose T = (k+1) l is a few steps of ext32_units digits
+void ext32_gadget_split(u64 n, u64 batch, uint32_t T, uint32_t *parts, uint32_t *tpp);
 hipError_t launch_ext32_key(const Ext32Args &a, int log_n, hipStream_t st);
 hipError_t launch_ext32_mac(const Ext32Args &a, int log_n, int src_kind, hipStream_t st);
 hipError_t launch_ext32_tail(const Ext32Args &a, int log_n, hipStream_t st);

@@ -11,6 +11,9 @@
 // product's own kernel pair in its CMux modes: digit_mac32_kernel<SRC32_CMUX> forms rot(ACC, e_b) - ACC as it loads the
 // digits, digit_tail32_kernel<EPI32_CMUX> adds the lift to ACC in place.  2 n_lwe + 1 launches per blind rotation.
 // Other shapes with a prepared key compose rotate-difference, fhe_tggsw_external_product_prepared_dev and an add.
+//
+// The base-2^b gadget has entry points of its own (fhe_*_gadget_*): the same kernel pair in its gadget
+// modes (SRC32_GADGET, SRC32_GCMUX), a key switch by signed digits, and an element-wise decomposition.
 #include <algorithm>
 
 #include "capi_internal.hpp"
@@ -102,6 +105,59 @@ __global__ __launch_bounds__(KS_TH) void tlwe_key_switch_kernel(const u64 *__res
             const u32 sh = l - 1u - d;
 #pragma unroll
             for (int t = 0; t < KS_TB; t++) acc[t] += ((w[t] >> sh) & 1u) ? kv : 0ull;
+        }
+    }
+    if (!on) return;
+#pragma unroll
+    for (int t = 0; t < KS_TB; t++)
+        if ((u32)t < live) out[(b0 + t) * row + o] = (o == n_out ? src[t * irow + n_in] : 0ull) - acc[t];
+}
+
+// ---- the base-2^b gadget ----------------------------------------------------------------------------
+// digit_d(w) = ((w + cadd) >> (64 - b (d+1))) & (2^b - 1)) - 2^(b-1), cadd = gadget_cadd(b, l); 1 <= b <= 64, b l <= 64
+__device__ __forceinline__ u64 gadget_digit(u64 w, u64 cadd, u32 b, u32 d) {
+    const u64 mask = ~0ull >> (64u - b), half = 1ull << (b - 1u);
+    return ((w + cadd) >> (64u - b * (d + 1u)) & mask) - half;        // the signed digit as a wrapping u64
+}
+
+// [rows][n] words -> [rows][l][n] signed digits (i64 words)
+__global__ __launch_bounds__(256) void tn_gadget_decompose_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, u32 L, u32 b, u32 l,
+                                                                  u64 cadd, u64 rows) {
+    const u64 N = 1ull << L, per = (u64)l << L, total = rows * per;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 r = i / per, q = i - r * per;
+        const u32 d = (u32)(q >> L);
+        out[i] = gadget_digit(in[(r << L) + (q & (N - 1))], cadd, b, d);
+    }
+}
+
+// out[b] = (0 .. 0, b_b) - sum_i sum_{d<l} digit_d(a_{b,i}) ksk[i][d], every product a wrapping multiply by the signed
+// digit; tiles as tlwe_key_switch_kernel (every KSK word read once per KS_TB ciphertexts)
+__global__ __launch_bounds__(KS_TH) void tlwe_gadget_key_switch_kernel(const u64 *__restrict__ ksk, const u64 *__restrict__ in,
+                                                                       u64 *__restrict__ out, u32 n_in, u32 n_out, u32 lb, u32 l,
+                                                                       u64 cadd, u64 batch, u32 cblocks) {
+    const u64 tile = blockIdx.x / cblocks;
+    const u32 o = (blockIdx.x - (u32)tile * cblocks) * KS_TH + threadIdx.x;
+    const u64 b0 = tile * KS_TB, row = (u64)n_out + 1, irow = (u64)n_in + 1;
+    const u32 live = (u32)min((u64)KS_TB, batch - b0);
+    const bool on = o <= n_out;
+    const u64 *__restrict__ kc = ksk + (on ? o : n_out);        // idle lanes read a valid column and store nothing
+    const u64 *__restrict__ src = in + b0 * irow;
+    u64 acc[KS_TB];
+#pragma unroll
+    for (int t = 0; t < KS_TB; t++) acc[t] = 0;
+    for (u32 i = 0; i < n_in; i++) {
+        u64 w[KS_TB];
+#pragma unroll
+        for (int t = 0; t < KS_TB; t++) w[t] = ((u32)t < live ? src[t * irow + i] : 0ull) + cadd;
+        const u64 *__restrict__ kr = kc + (u64)i * l * row;
+        for (u32 d = 0; d < l; d++) {
+            const u64 kv = kr[(u64)d * row];
+            const u32 sh = 64u - lb * (d + 1u);
+            const u64 mask = ~0ull >> (64u - lb), half = 1ull << (lb - 1u);
+#pragma unroll
+            for (int t = 0; t < KS_TB; t++) acc[t] += ((w[t] >> sh & mask) - half) * kv;
         }
     }
     if (!on) return;
@@ -222,6 +278,105 @@ int key_switch(unsigned n_in, unsigned n_out, unsigned l, const void *d_ksk, con
     return FHE_OK;
 }
 
+// ---- the base-2^b gadget ----
+int check_gadget(unsigned log_beta, unsigned l, unsigned max_b, const char *who) {
+    if (log_beta < 1 || log_beta > max_b || l < 1 || (u64)log_beta * l > 64)
+        return fhe_fail(FHE_E_INVALID, "%s: need 1 <= log_beta <= %u, l >= 1, log_beta l <= 64 (log_beta=%u, l=%u)", who, max_b, log_beta, l);
+    return FHE_OK;
+}
+
+int check_gext(uint64_t n, unsigned k, unsigned log_beta, unsigned l, const char *who) {
+    int rc = check_ring(n, k, who);
+    if (rc == FHE_OK) rc = check_gadget(log_beta, l, 64, who);
+    if (rc != FHE_OK) return rc;
+    if (!fhe::ext32_gadget_supported(n, k, log_beta, l))
+        return fhe_fail(FHE_E_INVALID, "%s: no gadget product for n=%llu, k=%u, log_beta=%u, l=%u (needs k = 1, 256 <= n <= 4096, "
+                        "(k+1) l n (2^32-1) 2^(log_beta-1) < pA pB / 2)", who, (unsigned long long)n, k, log_beta, l);
+    return FHE_OK;
+}
+
+int check_gbr(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const char *who) {
+    int rc = check_gext(n, k, log_beta, l, who);
+    if (rc != FHE_OK) return rc;
+    if (n_lwe < 1) return fhe_fail(FHE_E_INVALID, "%s: n_lwe must be at least 1", who);
+    return FHE_OK;
+}
+
+int check_gks(unsigned n_in, unsigned n_out, unsigned log_beta, unsigned l, const char *who) {
+    if (n_in < 1 || n_out < 1) return fhe_fail(FHE_E_INVALID, "%s: need n_in, n_out >= 1", who);
+    return check_gadget(log_beta, l, 32, who);
+}
+
+u64 gadget_tggsw_words(uint64_t n, unsigned k, unsigned l) { return (u64)2 * (k + 1) * l * (k + 1) * n; }
+
+// `keys` TGGSWs -> the two-prime layout (digit32.hip ntt32_fwd_key_kernel), whatever FHE_EXT32 says
+int gadget_prepare(uint64_t n, unsigned k, unsigned l, u64 keys, const void *d_tggsw, void *d_prepared, hipStream_t st) {
+    fhe::Ext32Args a{};
+    int rc;
+    if ((rc = fhe_ext32_tables(n, &a)) != FHE_OK) return rc;
+    const u32 k1 = k + 1;
+    const u64 grows = (u64)k1 * l * k1;
+    a.key64 = (const u64 *)d_tggsw; a.key32 = (uint32_t *)d_prepared; a.rows = 2 * grows; a.key_k1 = k1;
+    a.key_stride64 = grows * n; a.key_stride32 = 2 * a.rows * n;
+    const hipError_t e = fhe::launch_ext32_key_many(a, (int)__builtin_ctzll(n), keys, st);
+    return e == hipSuccess ? FHE_OK : fhe_hip_fail(e, "ntt32_fwd_key_kernel (gadget)");
+}
+
+// the mac + tail pair in a gadget mode: src rows of `batch` ciphertexts -> out (EPI32_TORUS) or ACC += (EPI32_CMUX)
+int gadget_args(uint64_t n, unsigned k, unsigned log_beta, unsigned l, size_t batch, hipStream_t st, fhe::Ext32Args *a) {
+    int rc;
+    if ((rc = fhe_ext32_tables(n, a)) != FHE_OK) return rc;
+    const u32 k1 = k + 1, T = k1 * l;
+    u32 parts = 1, tpp = 0;
+    fhe::ext32_gadget_split(n, batch, T, &parts, &tpp);
+    void *wsv = nullptr;
+    if ((rc = fhe_workspace_get(1, (u64)batch * parts * 2 * (2 * k1) * n * 4, st, &wsv)) != FHE_OK) return rc;
+    a->k = k; a->log_beta = log_beta;
+    a->ct_stride = (u64)k1 * n; a->part32 = (uint32_t *)wsv; a->batch = batch;
+    a->l = l; a->T = T; a->parts = parts; a->tpp = tpp;
+    return FHE_OK;
+}
+
+int gadget_blind_rotation(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk, const void *d_table,
+                          const void *d_lwe, void *d_out, size_t batch, hipStream_t st) {
+    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
+    const u64 words = gadget_tggsw_words(n, k, l);
+    u64 *acc = (u64 *)d_out;
+    void *wsv = nullptr;
+    int rc;
+    if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &wsv)) != FHE_OK) return rc;
+    u32 *shift = (u32 *)wsv;
+    { fhe::KernelTimer kt_("tfhe_br_init", (int)L, st);
+    hipLaunchKernelGGL(fhe::tfhe_br_init_kernel, dim3(fhe_ew_grid((u64)batch * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_lwe,
+                       (const u64 *)d_table, acc, shift, n_lwe, k1, L, (u64)batch);
+    }
+    LAUNCH_OK("tfhe_br_init_kernel");
+    fhe::Ext32Args a{};
+    if ((rc = gadget_args(n, k, log_beta, l, batch, st, &a)) != FHE_OK) return rc;
+    a.src = acc; a.out = acc; a.shift_stride = n_lwe;
+    for (unsigned j = 0; j < n_lwe; j++) {
+        a.key32 = (uint32_t *)const_cast<void *>(d_bsk) + (u64)j * 2 * words;
+        a.shift = shift + j;
+        hipError_t e = fhe::launch_ext32_mac(a, (int)L, fhe::SRC32_GCMUX, st);
+        if (e == hipSuccess) e = fhe::launch_ext32_tail_cmux(a, (int)L, st);
+        if (e != hipSuccess) return fhe_hip_fail(e, "digit32 gadget CMux kernels");
+    }
+    return FHE_OK;
+}
+
+int gadget_key_switch(unsigned n_in, unsigned n_out, unsigned log_beta, unsigned l, const void *d_ksk, const void *d_in, void *d_out,
+                      size_t batch, hipStream_t st) {
+    const u32 cblocks = (n_out + 1 + fhe::KS_TH - 1) / fhe::KS_TH;
+    const u64 grid = ((u64)batch + fhe::KS_TB - 1) / fhe::KS_TB * cblocks;
+    if (grid > 0x7fffffffull) return fhe_fail(FHE_E_INVALID, "fhe_tlwe_gadget_key_switch_dev: batch too large for one launch");
+    { fhe::KernelTimer kt_("tlwe_gadget_key_switch", 0, st);
+    hipLaunchKernelGGL(fhe::tlwe_gadget_key_switch_kernel, dim3((unsigned)grid), dim3(fhe::KS_TH), 0, st, (const u64 *)d_ksk, (const u64 *)d_in,
+                       (u64 *)d_out, n_in, n_out, log_beta, l, fhe::gadget_cadd(log_beta, l), (u64)batch, cblocks);
+    }
+    LAUNCH_OK("tlwe_gadget_key_switch_kernel");
+    return FHE_OK;
+}
+
 }  // namespace
 
 extern "C" size_t fhe_tfhe_bsk_prepared_words(uint64_t n, unsigned k, unsigned l, unsigned n_lwe) {
@@ -309,4 +464,137 @@ extern "C" int fhe_tfhe_bootstrap_dev(uint64_t n, unsigned k, unsigned l, unsign
     if ((rc = blind_rotation(n, k, l, n_lwe, d_bsk_prepared, d_table, d_in, acc, batch, st)) != FHE_OK) return rc;
     if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) return rc;
     return key_switch((unsigned)kn, n_lwe, ks_l, d_ksk, ext, d_out, batch, st);
+}
+
+// ---- the base-2^b gadget ------------------------------------------------------------------------------
+extern "C" int fhe_tn_gadget_decompose_dev(uint64_t n, unsigned log_beta, unsigned l, const void *d_a, void *d_out, size_t rows,
+                                           void *hip_stream) {
+    const char *who = "fhe_tn_gadget_decompose_dev";
+    int rc = check_ring(n, 1, who);
+    if (rc == FHE_OK) rc = check_gadget(log_beta, l, 64, who);
+    if (rc != FHE_OK) return rc;
+    if (rows == 0) return FHE_OK;
+    if (!d_a || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_a); REQUIRE_ALIGNED(d_out);
+    if ((u64)rows > (~0ull >> 7) / ((u64)l * n)) return fhe_fail(FHE_E_INVALID, "%s: rows too large", who);
+    if (overlaps(d_out, (u64)rows * l * n * 8, d_a, (u64)rows * n * 8)) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps d_a", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const u32 L = (u32)__builtin_ctzll(n);
+    { fhe::KernelTimer kt_("tn_gadget_decompose", (int)L, st);
+    hipLaunchKernelGGL(fhe::tn_gadget_decompose_kernel, dim3(fhe_ew_grid((u64)rows * l * n)), dim3(256), 0, st, (const u64 *)d_a, (u64 *)d_out,
+                       L, log_beta, l, fhe::gadget_cadd(log_beta, l), (u64)rows);
+    }
+    LAUNCH_OK("tn_gadget_decompose_kernel");
+    return FHE_OK;
+}
+
+extern "C" size_t fhe_tggsw_gadget_prepared_words(uint64_t n, unsigned k, unsigned log_beta, unsigned l) {
+    return fhe::ext32_gadget_supported(n, k, log_beta, l) ? (size_t)gadget_tggsw_words(n, k, l) : 0;
+}
+
+extern "C" int fhe_tggsw_gadget_prepare_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, const void *d_tggsw, void *d_prepared,
+                                            void *hip_stream) {
+    const char *who = "fhe_tggsw_gadget_prepare_dev";
+    int rc = check_gext(n, k, log_beta, l, who);
+    if (rc != FHE_OK) return rc;
+    if (!d_tggsw || !d_prepared) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_tggsw); REQUIRE_ALIGNED(d_prepared);
+    const u64 w = gadget_tggsw_words(n, k, l);
+    if (overlaps(d_tggsw, w / 2 * 8, d_prepared, w * 8)) return fhe_fail(FHE_E_INVALID, "%s: d_prepared overlaps d_tggsw", who);
+    return gadget_prepare(n, k, l, 1, d_tggsw, d_prepared, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_tggsw_gadget_external_product_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, const void *d_prepared,
+                                                     const void *d_tglwe, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_tggsw_gadget_external_product_dev";
+    int rc = check_gext(n, k, log_beta, l, who);
+    if (rc != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    if (!d_prepared || !d_tglwe || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_prepared); REQUIRE_ALIGNED(d_tglwe); REQUIRE_ALIGNED(d_out);
+    const u64 ct_bytes = (u64)batch * (k + 1) * n * 8;
+    if (overlaps(d_out, ct_bytes, d_tglwe, ct_bytes) || overlaps(d_out, ct_bytes, d_prepared, gadget_tggsw_words(n, k, l) * 8))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    fhe::Ext32Args a{};
+    if ((rc = gadget_args(n, k, log_beta, l, batch, st, &a)) != FHE_OK) return rc;
+    a.key32 = (uint32_t *)const_cast<void *>(d_prepared);
+    a.src = (const u64 *)d_tglwe; a.out = (u64 *)d_out;
+    const int L = (int)__builtin_ctzll(n);
+    hipError_t e = fhe::launch_ext32_mac(a, L, fhe::SRC32_GADGET, st);
+    if (e == hipSuccess) e = fhe::launch_ext32_tail(a, L, st);
+    return e == hipSuccess ? FHE_OK : fhe_hip_fail(e, "digit32 gadget kernels");
+}
+
+extern "C" size_t fhe_tfhe_gadget_bsk_prepared_words(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe) {
+    const size_t w = fhe_tggsw_gadget_prepared_words(n, k, log_beta, l);
+    if (w == 0 || n_lwe == 0 || w > SIZE_MAX / n_lwe) return 0;
+    return w * n_lwe;
+}
+
+extern "C" int fhe_tfhe_gadget_bsk_prepare_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk,
+                                               void *d_prepared, void *hip_stream) {
+    const char *who = "fhe_tfhe_gadget_bsk_prepare_dev";
+    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
+    if (rc != FHE_OK) return rc;
+    if (!d_bsk || !d_prepared) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk); REQUIRE_ALIGNED(d_prepared);
+    const u64 w = (u64)n_lwe * gadget_tggsw_words(n, k, l);
+    if (overlaps(d_bsk, w / 2 * 8, d_prepared, w * 8)) return fhe_fail(FHE_E_INVALID, "%s: d_prepared overlaps d_bsk", who);
+    return gadget_prepare(n, k, l, n_lwe, d_bsk, d_prepared, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_tfhe_gadget_blind_rotation_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe,
+                                                  const void *d_bsk_prepared, const void *d_table, const void *d_lwe, void *d_out,
+                                                  size_t batch, void *hip_stream) {
+    const char *who = "fhe_tfhe_gadget_blind_rotation_dev";
+    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
+    if (rc != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    if (!d_bsk_prepared || !d_table || !d_lwe || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_table); REQUIRE_ALIGNED(d_lwe); REQUIRE_ALIGNED(d_out);
+    const u64 out_bytes = (u64)batch * (k + 1) * n * 8;
+    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
+        overlaps(d_out, out_bytes, d_table, (u64)(k + 1) * n * 8) || overlaps(d_out, out_bytes, d_lwe, (u64)batch * (n_lwe + 1ull) * 8))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    return gadget_blind_rotation(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_table, d_lwe, d_out, batch, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_tlwe_gadget_key_switch_dev(unsigned n_in, unsigned n_out, unsigned log_beta, unsigned l, const void *d_ksk,
+                                              const void *d_in, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_tlwe_gadget_key_switch_dev";
+    int rc = check_gks(n_in, n_out, log_beta, l, who);
+    if (rc != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    if (!d_ksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
+    const u64 out_bytes = (u64)batch * (n_out + 1ull) * 8;
+    if (overlaps(d_out, out_bytes, d_in, (u64)batch * (n_in + 1ull) * 8) || overlaps(d_out, out_bytes, d_ksk, (u64)n_in * l * (n_out + 1ull) * 8))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    return gadget_key_switch(n_in, n_out, log_beta, l, d_ksk, d_in, d_out, batch, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_tfhe_gadget_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
+                                             const void *d_table, unsigned ks_log_beta, unsigned ks_l, const void *d_ksk, const void *d_in,
+                                             void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_tfhe_gadget_bootstrap_dev";
+    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
+    if (rc != FHE_OK) return rc;
+    const u64 kn = (u64)k * n;
+    if ((rc = check_gks((unsigned)kn, n_lwe, ks_log_beta, ks_l, who)) != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    if (!d_bsk_prepared || !d_table || !d_ksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_table); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
+    const u64 out_bytes = (u64)batch * (n_lwe + 1ull) * 8;
+    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
+        overlaps(d_out, out_bytes, d_table, (u64)(k + 1) * n * 8) || overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) ||
+        overlaps(d_out, out_bytes, d_in, out_bytes))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    void *acc = nullptr, *ext = nullptr;
+    if ((rc = fhe_workspace_get(7, (u64)batch * (k + 1) * n * 8, st, &acc)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(8, (u64)batch * (kn + 1) * 8, st, &ext)) != FHE_OK) return rc;
+    if ((rc = gadget_blind_rotation(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_table, d_in, acc, batch, st)) != FHE_OK) return rc;
+    if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) return rc;
+    return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, batch, st);
 }

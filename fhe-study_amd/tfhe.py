@@ -13,6 +13,9 @@ over the C ABI.
     BootstrappingKey  tlwe.rs:163-167                  BootstrappingKey (device-resident: prepared BSK + KSK)
     blind_rotation, bootstrapping   tlwe.rs:121-161    blind_rotation, bootstrapping (the mod switch
                                                        rounds to 2N, and the CMux loop runs over all n_lwe key bits)
+    (no counterpart)                                   the signed base-2^b gadget of DESIGN.md §11: gadget_decompose,
+                                                       gadget_external_product, BootstrappingKey(log_beta=...),
+                                                       TLWE.key_switch(log_beta=...)
 """
 import numpy as np
 
@@ -135,31 +138,46 @@ class TLWE:
     def dim(self):
         return self.words.shape[-1] - 1
 
-    def key_switch(self, ksk, l, beta=2):
-        """tlwe.rs:101-111: ksk [n_in][l][n_out + 1] (numpy or a device tensor) -> TLWE of dimension n_out"""
+    def key_switch(self, ksk, l, beta=2, *, log_beta=None):
+        """tlwe.rs:101-111: ksk [n_in][l][n_out + 1] (numpy or a device tensor) -> TLWE of dimension n_out.
+        log_beta = b: the signed base-2^b gadget of DESIGN.md §11 (level d of the KSK holds s_in[i] 2^(64 - b(d+1)))"""
         torch = _torch()
         k = ksk if isinstance(ksk, torch.Tensor) else _to_dev(ksk)
         n_in, n_out = self.dim, k.shape[-1] - 1
         x = self.words.reshape(-1, n_in + 1)
         out = torch.empty((x.shape[0], n_out + 1), dtype=torch.int64, device="cuda")
         dx = _to_dev(x)                  # device buffers are held until the call returns: never a freed temporary's pointer
-        binding.tlwe_key_switch_dev(n_in, n_out, beta, l, k.data_ptr(), dx.data_ptr(), out.data_ptr(), x.shape[0])
+        if log_beta is None:
+            binding.tlwe_key_switch_dev(n_in, n_out, beta, l, k.data_ptr(), dx.data_ptr(), out.data_ptr(), x.shape[0])
+        else:
+            binding.tlwe_gadget_key_switch_dev(n_in, n_out, log_beta, l, k.data_ptr(), dx.data_ptr(), out.data_ptr(), x.shape[0])
         return TLWE(_from_dev(out).reshape(self.words.shape[:-1] + (n_out + 1,)))
 
 
 class BootstrappingKey:
     """(Vec<TGGSW>, KSK) of tlwe.rs:163-167 kept on the device: the n_lwe bit-TGGSWs [n_lwe][(k+1)][l][(k+1)][n]
-    prepared once (fhe_tfhe_bsk_prepare_dev), and the KSK [k n][ks_l][n_lwe + 1] back to the LWE key"""
+    prepared once (fhe_tfhe_bsk_prepare_dev), and the KSK [k n][ks_l][n_lwe + 1] back to the LWE key.
+    log_beta = b: both keys use the signed base-2^b gadget of DESIGN.md §11 (BSK base 2^log_beta with l levels, KSK base
+    2^ks_log_beta with ks_l levels); ks_log_beta is then required."""
 
-    def __init__(self, n, k, l, n_lwe, bsk, ksk, ks_l=64):
+    def __init__(self, n, k, l, n_lwe, bsk, ksk, ks_l=64, *, log_beta=None, ks_log_beta=None):
         torch = _torch()
+        if (log_beta is None) != (ks_log_beta is None):
+            raise ValueError("log_beta and ks_log_beta go together: the gadget bootstrap needs both")
         self.n, self.k, self.l, self.n_lwe, self.ks_l = n, k, l, n_lwe, ks_l
-        words = binding.tfhe_bsk_prepared_words(n, k, l, n_lwe)
+        self.log_beta, self.ks_log_beta = log_beta, ks_log_beta
+        if log_beta is None:
+            words = binding.tfhe_bsk_prepared_words(n, k, l, n_lwe)
+        else:
+            words = binding.tfhe_gadget_bsk_prepared_words(n, k, log_beta, l, n_lwe)
         if words == 0:
-            raise binding.FheError(binding.FHE_E_INVALID, f"no prepared bootstrapping key for n={n}, k={k}, l={l}")
+            raise binding.FheError(binding.FHE_E_INVALID, f"no prepared bootstrapping key for n={n}, k={k}, l={l}, log_beta={log_beta}")
         g = bsk if isinstance(bsk, torch.Tensor) else _to_dev(bsk)
         self.bsk = torch.empty(words, dtype=torch.int64, device="cuda")
-        binding.tfhe_bsk_prepare_dev(n, k, l, n_lwe, g.data_ptr(), self.bsk.data_ptr())
+        if log_beta is None:
+            binding.tfhe_bsk_prepare_dev(n, k, l, n_lwe, g.data_ptr(), self.bsk.data_ptr())
+        else:
+            binding.tfhe_gadget_bsk_prepare_dev(n, k, log_beta, l, n_lwe, g.data_ptr(), self.bsk.data_ptr())
         self.ksk = ksk if isinstance(ksk, torch.Tensor) else _to_dev(ksk)
         torch.cuda.synchronize()
 
@@ -170,8 +188,12 @@ def blind_rotation(c, btk, table):
     x = c.words.reshape(-1, btk.n_lwe + 1)
     out = torch.empty((x.shape[0], btk.k + 1, btk.n), dtype=torch.int64, device="cuda")
     dt, dx = _to_dev(table.packed()), _to_dev(x)
-    binding.tfhe_blind_rotation_dev(btk.n, btk.k, btk.l, btk.n_lwe, btk.bsk.data_ptr(), dt.data_ptr(), dx.data_ptr(), out.data_ptr(),
-                                    x.shape[0])
+    if btk.log_beta is None:
+        binding.tfhe_blind_rotation_dev(btk.n, btk.k, btk.l, btk.n_lwe, btk.bsk.data_ptr(), dt.data_ptr(), dx.data_ptr(), out.data_ptr(),
+                                        x.shape[0])
+    else:
+        binding.tfhe_gadget_blind_rotation_dev(btk.n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), dt.data_ptr(),
+                                               dx.data_ptr(), out.data_ptr(), x.shape[0])
     o = _from_dev(out)
     return TGLWE(o[:, : btk.k, :], o[:, btk.k, :])
 
@@ -182,6 +204,42 @@ def bootstrapping(btk, table, c):
     x = c.words.reshape(-1, btk.n_lwe + 1)
     out = torch.empty(x.shape, dtype=torch.int64, device="cuda")
     dt, dx = _to_dev(table.packed()), _to_dev(x)
-    binding.tfhe_bootstrap_dev(btk.n, btk.k, btk.l, btk.n_lwe, btk.bsk.data_ptr(), dt.data_ptr(), btk.ks_l, btk.ksk.data_ptr(),
-                               dx.data_ptr(), out.data_ptr(), x.shape[0])
+    if btk.log_beta is None:
+        binding.tfhe_bootstrap_dev(btk.n, btk.k, btk.l, btk.n_lwe, btk.bsk.data_ptr(), dt.data_ptr(), btk.ks_l, btk.ksk.data_ptr(),
+                                   dx.data_ptr(), out.data_ptr(), x.shape[0])
+    else:
+        binding.tfhe_gadget_bootstrap_dev(btk.n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), dt.data_ptr(),
+                                          btk.ks_log_beta, btk.ks_l, btk.ksk.data_ptr(), dx.data_ptr(), out.data_ptr(), x.shape[0])
     return TLWE(_from_dev(out).reshape(c.words.shape))
+
+
+# ---- the signed base-2^b gadget -------------------------------------------------------------------
+def gadget_decompose(words, log_beta, l):
+    """words [..][n] u64 -> [..][l][n] int64: the signed digits of every word, level 0 the most significant"""
+    torch = _torch()
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    n = w.shape[-1]
+    rows = w.size // n
+    dw = _to_dev(w.reshape(rows, n))
+    out = torch.empty((rows, l, n), dtype=torch.int64, device="cuda")
+    binding.tn_gadget_decompose_dev(n, log_beta, l, dw.data_ptr(), out.data_ptr(), rows)
+    return out.cpu().numpy().reshape(w.shape[:-1] + (l, n))
+
+
+def gadget_external_product(tggsw, tglwe, log_beta):
+    """sum_i sum_d digit_d(tglwe_i) tggsw[i][d]: tggsw [(k+1)][l][(k+1)][n] with level d encrypting m 2^(64 - b(d+1))"""
+    torch = _torch()
+    rows = np.ascontiguousarray(tggsw.rows if isinstance(tggsw, TGGSW) else tggsw, dtype=np.uint64)
+    k1, l, _, n = rows.shape
+    words = binding.tggsw_gadget_prepared_words(n, k1 - 1, log_beta, l)
+    if words == 0:
+        raise binding.FheError(binding.FHE_E_INVALID, f"no gadget product for n={n}, k={k1 - 1}, log_beta={log_beta}, l={l}")
+    x = tglwe.packed()
+    batch = x.size // (k1 * n)
+    dg, dx = _to_dev(rows), _to_dev(x.reshape(batch, k1, n))
+    prep = torch.empty(words, dtype=torch.int64, device="cuda")
+    out = torch.empty((batch, k1, n), dtype=torch.int64, device="cuda")
+    binding.tggsw_gadget_prepare_dev(n, k1 - 1, log_beta, l, dg.data_ptr(), prep.data_ptr())
+    binding.tggsw_gadget_external_product_dev(n, k1 - 1, log_beta, l, prep.data_ptr(), dx.data_ptr(), out.data_ptr(), batch)
+    o = _from_dev(out).reshape(x.shape)
+    return TGLWE(o[..., : k1 - 1, :], o[..., k1 - 1, :])

@@ -320,6 +320,42 @@ int fhe_tfhe_bootstrap_dev(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, c
                            const void *d_table, unsigned ks_l, const void *d_ksk, const void *d_in, void *d_out,
                            size_t batch, void *hip_stream);
 
+/* ---- TFHE with the signed base-2^b gadget (definitions in DESIGN.md §11) ----
+ * b = log_beta, l levels, 1 <= b, b l <= 64, s = 64 - b l.  Level d (0 = most significant) has gadget value
+ * g_d = 2^(64 - b(d+1)); digit_d(w) in [-2^(b-1), 2^(b-1)) and sum_d digit_d(w) g_d = w rounded half up to its top
+ * b l bits (mod 2^64).  Keys use the layouts of the beta = 2 twins, with level d encrypting m g_d.  The products take
+ * k = 1, 256 <= n <= 4096 and (k+1) l n (2^32 - 1) 2^(b-1) < pA pB / 2 (fhe_tggsw_gadget_prepared_words is 0
+ * otherwise): at n = 1024, b <= 10 for l = 2 and 3.  The key switch takes 1 <= b <= 32.  Outputs must not overlap inputs.
+ *   fhe_tn_gadget_decompose_dev      d_a [rows][n] -> d_out [rows][l][n]: the signed digits as int64 words
+ *   fhe_tggsw_gadget_prepared_words  u64 words of a prepared gadget TGGSW (always the two-prime layout; 0: not admitted)
+ *   fhe_tggsw_gadget_prepare_dev     d_tggsw [(k+1)][l][(k+1)][n] -> d_prepared
+ *   fhe_tggsw_gadget_external_product_dev  d_tglwe [batch][(k+1)][n] -> d_out [batch][(k+1)][n] =
+ *                                    sum_i sum_d digit_d(tglwe_i) TGGSW[i][d]  in T64[X]/(X^n+1)
+ *   fhe_tfhe_gadget_bsk_prepared_words / fhe_tfhe_gadget_bsk_prepare_dev  n_lwe gadget TGGSWs side by side
+ *   fhe_tfhe_gadget_blind_rotation_dev  as fhe_tfhe_blind_rotation_dev with the gadget product
+ *   fhe_tlwe_gadget_key_switch_dev   d_ksk [n_in][l][n_out + 1] (level d: TLev of s_in[i] g_d) -> d_out [batch][n_out + 1]
+ *                                    = (0 .. 0, b) - sum_i sum_d digit_d(a_i) ksk[i][d]
+ *   fhe_tfhe_gadget_bootstrap_dev    gadget blind rotation -> sample extraction (h = 0) -> gadget key switch
+ *                                    (ks_log_beta, ks_l) from dimension k n back to n_lwe */
+int fhe_tn_gadget_decompose_dev(uint64_t n, unsigned log_beta, unsigned l, const void *d_a, void *d_out, size_t rows,
+                                void *hip_stream);
+size_t fhe_tggsw_gadget_prepared_words(uint64_t n, unsigned k, unsigned log_beta, unsigned l);
+int fhe_tggsw_gadget_prepare_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, const void *d_tggsw,
+                                 void *d_prepared, void *hip_stream);
+int fhe_tggsw_gadget_external_product_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, const void *d_prepared,
+                                          const void *d_tglwe, void *d_out, size_t batch, void *hip_stream);
+size_t fhe_tfhe_gadget_bsk_prepared_words(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe);
+int fhe_tfhe_gadget_bsk_prepare_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe,
+                                    const void *d_bsk, void *d_prepared, void *hip_stream);
+int fhe_tfhe_gadget_blind_rotation_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe,
+                                       const void *d_bsk_prepared, const void *d_table, const void *d_lwe, void *d_out,
+                                       size_t batch, void *hip_stream);
+int fhe_tlwe_gadget_key_switch_dev(unsigned n_in, unsigned n_out, unsigned log_beta, unsigned l, const void *d_ksk,
+                                   const void *d_in, void *d_out, size_t batch, void *hip_stream);
+int fhe_tfhe_gadget_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe,
+                                  const void *d_bsk_prepared, const void *d_table, unsigned ks_log_beta, unsigned ks_l,
+                                  const void *d_ksk, const void *d_in, void *d_out, size_t batch, void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
