@@ -68,6 +68,9 @@ EXPORTS = [
     "fhe_tn_gadget_decompose_dev", "fhe_tggsw_gadget_prepared_words", "fhe_tggsw_gadget_prepare_dev",
     "fhe_tggsw_gadget_external_product_dev", "fhe_tfhe_gadget_bsk_prepared_words", "fhe_tfhe_gadget_bsk_prepare_dev",
     "fhe_tfhe_gadget_blind_rotation_dev", "fhe_tlwe_gadget_key_switch_dev", "fhe_tfhe_gadget_bootstrap_dev",
+    # circuit bootstrapping and the CMux with a selector per ciphertext (tfhe_boot.hip)
+    "fhe_tfhe_pfksk_words", "fhe_tlwe_gadget_private_key_switch_dev", "fhe_tggsw_gadget_prepare_many_dev",
+    "fhe_tggsw_gadget_cmux_dev", "fhe_tfhe_circuit_bootstrap_dev",
 ]
 
 
@@ -234,6 +237,12 @@ def load_library():
     L.fhe_tfhe_gadget_blind_rotation_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _vp, _vp, _vp, _sz, _vp]
     L.fhe_tlwe_gadget_key_switch_dev.argtypes = [_uint, _uint, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
     L.fhe_tfhe_gadget_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _vp, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_pfksk_words.argtypes = [_u64, _uint, _uint, _uint]
+    L.fhe_tfhe_pfksk_words.restype = _sz
+    L.fhe_tlwe_gadget_private_key_switch_dev.argtypes = [_u64, _uint, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tggsw_gadget_prepare_many_dev.argtypes = [_u64, _uint, _uint, _uint, _sz, _vp, _vp, _vp]
+    L.fhe_tggsw_gadget_cmux_dev.argtypes = [_u64, _uint, _uint, _uint, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_circuit_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -532,6 +541,29 @@ def tfhe_gadget_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_table,
                               stream=None):
     _check(load_library().fhe_tfhe_gadget_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_table, ks_log_beta, ks_l, d_ksk,
                                                         d_in, d_out, batch, stream))
+
+
+# ---- circuit bootstrapping ----------------------------------------------------------------------------
+def tfhe_pfksk_words(n, k, log_beta, l):
+    return load_library().fhe_tfhe_pfksk_words(n, k, log_beta, l)
+
+
+def tlwe_gadget_private_key_switch_dev(n, k, log_beta, l, d_pfksk, d_in, d_out, batch, stream=None):
+    _check(load_library().fhe_tlwe_gadget_private_key_switch_dev(n, k, log_beta, l, d_pfksk, d_in, d_out, batch, stream))
+
+
+def tggsw_gadget_prepare_many_dev(n, k, log_beta, l, count, d_tggsw, d_prepared, stream=None):
+    _check(load_library().fhe_tggsw_gadget_prepare_many_dev(n, k, log_beta, l, count, d_tggsw, d_prepared, stream))
+
+
+def tggsw_gadget_cmux_dev(n, k, log_beta, l, count, d_prepared, d_idx, d_c0, d_c1, d_out, batch, stream=None):
+    _check(load_library().fhe_tggsw_gadget_cmux_dev(n, k, log_beta, l, count, d_prepared, d_idx, d_c0, d_c1, d_out, batch, stream))
+
+
+def tfhe_circuit_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, cb_log_beta, cb_l, pf_log_beta, pf_l, d_pfksk, d_lwe, d_out,
+                               batch, stream=None):
+    _check(load_library().fhe_tfhe_circuit_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, cb_log_beta, cb_l, pf_log_beta, pf_l,
+                                                         d_pfksk, d_lwe, d_out, batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

@@ -236,10 +236,13 @@ __device__ __forceinline__ u32 digit32_of(u64 x, u32 l, u32 d) {
 // SRC32_GADGET / SRC32_GCMUX: digit_d(x) + 2^(b-1) in [0, 2^b), sh = 64 - b (d+1), cadd = gadget_cadd (digit32.hpp)
 __device__ __forceinline__ u32 gadget_field32(u64 x, u64 cadd, u32 sh, u32 mask) { return (u32)((x + cadd) >> sh) & mask; }
 // the source word at position pos of a row.  SRC32_CMUX, SRC32_GCMUX: X^-e row - row in T64[X]/(X^N+1), e < 2N, i.e.
-// (-1)^floor((pos+e)/N) row[(pos+e) mod N] - row[pos] — one wrap in a thread's positions, the loads stay coalesced
+// (-1)^floor((pos+e)/N) row[(pos+e) mod N] - row[pos] — one wrap in a thread's positions, the loads stay coalesced.
+// SRC32_GSEL: row1[pos] - row[pos] (c1 - c0)
 template <int SRC, int LP>
-__device__ __forceinline__ u64 src_word32(const u64 *__restrict__ row, u32 pos, u32 e) {
-    if constexpr (SRC == SRC32_CMUX || SRC == SRC32_GCMUX) {
+__device__ __forceinline__ u64 src_word32(const u64 *__restrict__ row, u32 pos, u32 e, const u64 *__restrict__ row1 = nullptr) {
+    if constexpr (SRC == SRC32_GSEL) {
+        return row1[pos] - row[pos];
+    } else if constexpr (SRC == SRC32_CMUX || SRC == SRC32_GCMUX) {
         const u32 j = pos + e;                                            // < 3N
         const u64 x = row[j & ((1u << LP) - 1u)];
         return (((j >> LP) & 1u) ? 0ull - x : x) - row[pos];
@@ -252,14 +255,19 @@ __device__ __forceinline__ u64 src_word32(const u64 *__restrict__ row, u32 pos, 
 // out: partial sums [b][part][prime][c][n] u32 canonical.
 // The gadget modes: a signed digit v enters each prime's transform as its canonical residue
 // (v < 0: p + v), so round 0 is the generic one and the primes' inputs differ; |v| <= 2^(b-1) <= 2^12 < p.
+// SRC32_GSEL: the digits of c1 - c0 (src1 - src) against key sel[b] of sel_count prepared keys, held to
+// the CMux modes' budget (two loads per source word, as the rotated ones)
 template <int LP, int SRC>
-constexpr int mac32_waves() { return SRC == SRC32_CMUX || SRC == SRC32_GCMUX ? Mac32Cfg<LP>::CMUX_WAVES : Mac32Cfg<LP>::WAVES; }
+constexpr int mac32_waves() {
+    return SRC == SRC32_CMUX || SRC == SRC32_GCMUX || SRC == SRC32_GSEL ? Mac32Cfg<LP>::CMUX_WAVES : Mac32Cfg<LP>::WAVES;
+}
 template <int LP, int NC, int SRC>
 __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (mac32_waves<LP, SRC>())) void digit_mac32_kernel(Ext32Args a) {
     using C = ContigCfg<LP>;
     using K = Mac32Cfg<LP>;
-    constexpr bool GAD = SRC == SRC32_GADGET || SRC == SRC32_GCMUX;
+    constexpr bool GAD = SRC == SRC32_GADGET || SRC == SRC32_GCMUX || SRC == SRC32_GSEL;
     constexpr bool ROT = SRC == SRC32_CMUX || SRC == SRC32_GCMUX;
+    constexpr bool SEL = SRC == SRC32_GSEL;
     constexpr int PPT = K::PPT, W = K::W, TH = K::TH, NP = K::NP;
     const u32 pr0 = K::ONEP ? blockIdx.y : 0u;                      // the first prime this workgroup serves
     static_assert(NP * NC * PPT <= 64, "accumulators");
@@ -290,6 +298,16 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (mac32_waves<LP, SRC>())) void 
     __syncthreads();
     const u64 *__restrict__ ct = a.src + b * a.ct_stride;
     const u32 e = ROT ? a.shift[b * a.shift_stride] : 0u;   // this ciphertext's rotation (blind rotation step)
+    // SEL: this ciphertext's key; a selector out of range reads key 0 and writes zero partial sums (the product is 0)
+    const u32 *sel_key = nullptr;
+    const u64 *ct1 = nullptr;
+    bool sel_ok = true;
+    if constexpr (SEL) {
+        const u32 s = a.sel[b * a.shift_stride];
+        sel_ok = s < a.sel_count;
+        sel_key = a.key32 + (u64)(sel_ok ? s : 0u) * a.key_stride32;
+        ct1 = a.src1 + b * a.ct_stride;
+    }
     u64 cadd = 0;
     u32 ghalf = 0, gmask = 0;
     if constexpr (GAD) {
@@ -312,6 +330,7 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (mac32_waves<LP, SRC>())) void 
         const u32 tt = t < t_end ? t : t_begin;               // idle units redo a valid digit, never multiplied
         const u32 r = tt / a.l, d = tt - r * a.l;
         const u64 *__restrict__ row = ct + (u64)r * n;
+        const u64 *__restrict__ row1 = SEL ? ct1 + (u64)r * n : nullptr;
         // the rotation as an opaque value per step: the 16 rotated offsets and signs of a thread are recomputed here
         // rather than hoisted out of the loop, where they would hold registers through the multiply phase
         u32 eo = e;
@@ -324,11 +343,11 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (mac32_waves<LP, SRC>())) void 
             if constexpr (GAD) {
 #pragma unroll
                 for (int k = 0; k < 16; k++) {
-                    const u32 f = gadget_field32(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo), cadd, gsh, gmask);
+                    const u32 f = gadget_field32(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo, row1), cadd, gsh, gmask);
                     va[k] = csub_u32(f + (p[0] - ghalf), p[0]);
                     vb[k] = csub_u32(f + (p[1] - ghalf), p[1]);
                     // the rotated loads in two waves of eight: all 32 words in flight at once spill at three waves per SIMD
-                    if constexpr (ROT) if (k == 7) __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (ROT || SEL) if (k == 7) __builtin_amdgcn_sched_barrier(0);
                 }
             } else {
 #pragma unroll
@@ -341,7 +360,7 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (mac32_waves<LP, SRC>())) void 
             const Tw32 *gt[2] = {gtw[0], gtw[1]};
             // GCMUX: the tables' per-thread addresses recomputed per step, not held through it (at three waves per SIMD
             // they were what spilled)
-            if constexpr (SRC == SRC32_GCMUX) asm volatile("" : "+s"(gt[0]), "+s"(gt[1]));
+            if constexpr (SRC == SRC32_GCMUX || SEL) asm volatile("" : "+s"(gt[0]), "+s"(gt[1]));
             const u32 pp[2] = {p[0], p[1]};
             fwd_rounds32x2<LP, false, !GAD>(va, vb, tl, lt, gt, ll, w, tf, pp);
 #else
@@ -358,7 +377,7 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (mac32_waves<LP, SRC>())) void 
             u32 fld[GAD ? 16 : 1];                                  // the gadget's digit fields, both primes take them
             if constexpr (GAD) {
 #pragma unroll
-                for (int k = 0; k < 16; k++) fld[k] = gadget_field32(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo), cadd, gsh, gmask);
+                for (int k = 0; k < 16; k++) fld[k] = gadget_field32(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo, row1), cadd, gsh, gmask);
             } else {
 #pragma unroll
                 for (int k = 0; k < 16; k++) bits |= digit32_of<SRC>(src_word32<SRC, LP>(row, field_of<C::A0>(tf, k), eo), a.l, d) << k;
@@ -397,7 +416,7 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (mac32_waves<LP, SRC>())) void 
                     u32 x[PPT];
 #pragma unroll
                     for (int i = 0; i < PPT; i++) x[i] = tile[pr][pad16(u * C::M + j0 + i)];
-                    const u32 *__restrict__ g = a.key32 + (((u64)(pr0 + pr) * a.T + (t0 + u)) * NC) * n + j0;
+                    const u32 *__restrict__ g = (SEL ? sel_key : a.key32) + (((u64)(pr0 + pr) * a.T + (t0 + u)) * NC) * n + j0;
 #pragma unroll
                     for (int c = 0; c < NC; c++) {
                         u32 gv[PPT];
@@ -436,7 +455,7 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (mac32_waves<LP, SRC>())) void 
 #pragma unroll
         for (int c = 0; c < NC; c++)
 #pragma unroll
-            for (int i = 0; i < PPT; i++) o[(u64)c * n + i] = reduce64_32(acc[pr][c][i], p[pr], a.mu[pr0 + pr]);
+            for (int i = 0; i < PPT; i++) o[(u64)c * n + i] = sel_ok ? reduce64_32(acc[pr][c][i], p[pr], a.mu[pr0 + pr]) : 0u;
     }
 }
 
@@ -447,10 +466,11 @@ __global__ __launch_bounds__((Mac32Cfg<LP>::TH), (mac32_waves<LP, SRC>())) void 
 //   EPI32_KS     rhs = (lift(S_lo) + lift(S_hi) * 2^32) mod q,   out[b][c] = (c < k ? 0 : glwe[b][c]) - rhs   (glwe.rs:129-136)
 //   EPI32_CMUX   out[b][c] += lift(S_lo) + (lift(S_hi) << 32)  mod 2^64     (blind rotation step: ACC + BSK_j (X^-e ACC - ACC);
 //                every thread reads and writes the same positions, and the step's digit_mac32_kernel has finished)
+//   EPI32_SEL    out[b][c] = src[b][c] + lift(S_lo) + (lift(S_hi) << 32)  mod 2^64   (CMux c0 + C_sel (c1 - c0))
 // lift = the centred representative modulo pA pB.  (512 threads with the two primes side by side — two transforms in
 // sequence instead of four — was measured: 46 -> 41 us for a single product, but 31 -> 36 us per 630 and 37 -> 43 us per
 // 256 key switches; the sequential form stays.)
-enum : int { EPI32_TORUS = 0, EPI32_KS = 1, EPI32_CMUX = 2 };
+enum : int { EPI32_TORUS = 0, EPI32_KS = 1, EPI32_CMUX = 2, EPI32_SEL = 3 };
 template <int LP, int EPI>
 __global__ __launch_bounds__(256) void digit_tail32_kernel(Ext32Args a) {
     using C = ContigCfg<LP>;
@@ -513,7 +533,7 @@ __global__ __launch_bounds__(256) void digit_tail32_kernel(Ext32Args a) {
     }
     if (!active) return;
     const u64 base = (b * k1 + c) * (u64)n;
-    if constexpr (EPI == EPI32_TORUS || EPI == EPI32_CMUX) {
+    if constexpr (EPI == EPI32_TORUS || EPI == EPI32_CMUX || EPI == EPI32_SEL) {
 #pragma unroll
         for (int k = 0; k < 16; k++) {
             u64 lo = S[0][k], hi = S[1][k];
@@ -521,6 +541,7 @@ __global__ __launch_bounds__(256) void digit_tail32_kernel(Ext32Args a) {
             if (hi >= a.halfP) hi -= a.P;
             const u64 pos = base + field_of<C::A0>(tf, k);
             if constexpr (EPI == EPI32_CMUX) a.out[pos] += lo + (hi << 32);
+            else if constexpr (EPI == EPI32_SEL) a.out[pos] = a.src[pos] + lo + (hi << 32);
             else a.out[pos] = lo + (hi << 32);
         }
     } else {
@@ -575,7 +596,8 @@ static hipError_t launch_mac32_lp(const Ext32Args &a, hipStream_t st) {
     const u64 grid = a.batch * a.parts;
     if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     if (hipError_t e = allow_big_lds((const void *)digit_mac32_kernel<LP, 4, SRC>, K::LDS_BYTES)) return e;
-    KernelTimer kt(SRC == SRC32_CMUX ? "digit_mac32_cmux" : SRC == SRC32_GADGET ? "digit_mac32_gadget" : SRC == SRC32_GCMUX ? "digit_mac32_gcmux" : "digit_mac32", LP, st);
+    KernelTimer kt(SRC == SRC32_CMUX ? "digit_mac32_cmux" : SRC == SRC32_GADGET ? "digit_mac32_gadget" : SRC == SRC32_GCMUX ? "digit_mac32_gcmux"
+                   : SRC == SRC32_GSEL ? "digit_mac32_gsel" : "digit_mac32", LP, st);
     hipLaunchKernelGGL((digit_mac32_kernel<LP, 4, SRC>), dim3((unsigned)grid, K::ONEP ? 2u : 1u), dim3(K::TH), K::LDS_BYTES, st, a);
     return hipGetLastError();
 }
@@ -587,7 +609,7 @@ static hipError_t launch_tail32_lp(const Ext32Args &a, hipStream_t st) {
     const u64 grid = (a.batch * (a.k + 1) + C::W - 1) / C::W;
     if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     if (hipError_t e = allow_big_lds((const void *)digit_tail32_kernel<LP, EPI>, lds)) return e;
-    KernelTimer kt(EPI == EPI32_KS ? "digit_tail32_ks" : EPI == EPI32_CMUX ? "digit_tail32_cmux" : "digit_tail32", LP, st);
+    KernelTimer kt(EPI == EPI32_KS ? "digit_tail32_ks" : EPI == EPI32_CMUX ? "digit_tail32_cmux" : EPI == EPI32_SEL ? "digit_tail32_sel" : "digit_tail32", LP, st);
     hipLaunchKernelGGL((digit_tail32_kernel<LP, EPI>), dim3((unsigned)grid), dim3(256), lds, st, a);
     return hipGetLastError();
 }
@@ -662,11 +684,13 @@ hipError_t launch_ext32_mac(const Ext32Args &a, int log_n, int src_kind, hipStre
     if (src_kind == SRC32_CMUX) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_CMUX) }
     if (src_kind == SRC32_GADGET) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_GADGET) }
     if (src_kind == SRC32_GCMUX) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_GCMUX) }
+    if (src_kind == SRC32_GSEL) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_GSEL) }
     return hipErrorNotSupported;
 }
 hipError_t launch_ext32_tail_cmux(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_CMUX) }
 hipError_t launch_ext32_tail(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_TORUS) }
 hipError_t launch_ext32_tail_ks(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_KS) }
+hipError_t launch_ext32_tail_sel(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_SEL) }
 #undef FHE_LP_SWITCH
 #undef FHE_COMMA
 

@@ -21,6 +21,7 @@ struct Ext32Args {
     uint32_t *key32;           // [prime][T][half][key_k1][n], NTT domain
     u64 rows;                  // T * 2 * key_k1
     uint32_t key_k1;
+    uint32_t sel_count;        // SRC32_GSEL: prepared keys at key32 (a selector >= sel_count contributes 0); in key_k1's padding word
     // product
     const u64 *src;            // ciphertexts, source row r of ciphertext b at src + b*ct_stride + r*n
     u64 ct_stride;
@@ -41,19 +42,29 @@ struct Ext32Args {
     // key switching tail (digit_tail32_ks_kernel)
     Mod mod;                   // the ring's q
     u64 two32;                 // 2^32 mod q
-    const u64 *glwe;           // the ciphertexts again, for the body row
+    union {
+        const u64 *glwe;       // the ciphertexts again, for the body row
+        const u64 *src1;       // SRC32_GSEL: the second CMux input c1, laid out as src (the source row is c1 - c0)
+    };
     uint32_t k;
     uint32_t log_beta;         // SRC32_GADGET / SRC32_GCMUX: b of the base 2^b; in k's padding word
     // several keys in one preparation launch (gridDim.z keys): key z at key64 + z*key_stride64, key32 + z*key_stride32
     u64 key_stride64, key_stride32;
     // SRC32_CMUX (blind rotation step): ciphertext b's source row r is rot(src_r, e_b) - src_r, e_b = shift[b*shift_stride]
-    const uint32_t *shift;
+    // SRC32_GSEL (CMux with a selector per ciphertext): ciphertext b's key is key32 + sel[b*shift_stride]
+    // * key_stride32; src holds c0, src1 c1, and the tail writes c0 + lift.  The three pointers share their words with
+    // fields the mode does not use, so the layout of every other mode is unchanged.
+    union {
+        const uint32_t *shift;
+        const uint32_t *sel;
+    };
     u64 shift_stride;
 };
 
 // source modes of digit_mac32_kernel next to SRC_DIGITS / SRC_ZQBITS (ntt_kernels.hpp): the digits of X^-e ACC - ACC;
-// the signed base-2^b digits of DESIGN.md §11 of the rows (SRC32_GADGET) or of X^-e ACC - ACC (SRC32_GCMUX)
-enum : int { SRC32_CMUX = 4, SRC32_GADGET = 5, SRC32_GCMUX = 6 };
+// the signed base-2^b digits of DESIGN.md §11 of the rows (SRC32_GADGET) or of X^-e ACC - ACC (SRC32_GCMUX); the same
+// digits of c1 - c0 against a key chosen per ciphertext (SRC32_GSEL)
+enum : int { SRC32_CMUX = 4, SRC32_GADGET = 5, SRC32_GCMUX = 6, SRC32_GSEL = 7 };
 
 bool ext32_shape_supported(u64 n, unsigned k, unsigned l);        // TGGSW x TGLWE
 bool ks32_shape_supported(u64 n, unsigned k, unsigned l);         // GLWE::key_switch, base 2
@@ -79,6 +90,7 @@ hipError_t launch_ext32_mac(const Ext32Args &a, int log_n, int src_kind, hipStre
 hipError_t launch_ext32_tail(const Ext32Args &a, int log_n, hipStream_t st);
 hipError_t launch_ext32_tail_ks(const Ext32Args &a, int log_n, hipStream_t st);
 hipError_t launch_ext32_tail_cmux(const Ext32Args &a, int log_n, hipStream_t st);   // out[b] += lift (in place)
+hipError_t launch_ext32_tail_sel(const Ext32Args &a, int log_n, hipStream_t st);    // out[b] = src[b] + lift (SRC32_GSEL)
 hipError_t launch_ext32_key_many(const Ext32Args &a, int log_n, u64 keys, hipStream_t st);   // `keys` TGGSWs, strides above
 
 }  // namespace fhe

@@ -14,6 +14,10 @@
 //
 // The base-2^b gadget has entry points of its own (fhe_*_gadget_*): the same kernel pair in its gadget
 // modes (SRC32_GADGET, SRC32_GCMUX), a key switch by signed digits, and an element-wise decomposition.
+//
+// Circuit bootstrapping: a private functional key switch TLWE -> TGLWE (all k+1 functions in one pass), a
+// CMux whose TGGSW is chosen per ciphertext (SRC32_GSEL, EPI32_SEL), and the glue that runs the l_cb blind rotations of a
+// batch as one gadget blind rotation over batch l_cb rows and turns them into TGGSW rows.
 #include <algorithm>
 
 #include "capi_internal.hpp"
@@ -164,6 +168,107 @@ __global__ __launch_bounds__(KS_TH) void tlwe_gadget_key_switch_kernel(const u64
 #pragma unroll
     for (int t = 0; t < KS_TB; t++)
         if ((u32)t < live) out[(b0 + t) * row + o] = (o == n_out ? src[t * irow + n_in] : 0ull) - acc[t];
+}
+
+// ---- circuit bootstrapping ---------------------------------------------------------------------------
+// Private functional key switch, k = 1: out[m][r] = sum_{j <= kN} sum_{d < l} digit_d(c_m[j]) pfksk[r][j][d], r <= k, with
+// c_m[kN] the body; key [(k+1)][kN+1][l][cols], cols = (k+1) N, output row (m / group, r, m % group) of [..][(k+1)][group][cols].
+// A wrapping u64 GEMM tiled as tlwe_gadget_key_switch_kernel: a workgroup owns PF_TB ciphertexts and PF_TH columns of every
+// function, so each key word is read once per tile and each digit (an SGPR: the ciphertext words are uniform) is extracted
+// once per wave for all the functions.  digit = f - 2^(b-1) with the field f in [0, 2^b): sum digit key = sum f key -
+// 2^(b-1) sum key, so a term is one v_mad_u64_u32 and one 32-bit multiply of the high half, and sum key is per column.
+constexpr int PF_TB = 32, PF_TH = 64, PF_K1 = 2;
+__global__ __launch_bounds__(PF_TH) void tlwe_private_ks_kernel(const u64 *__restrict__ key, const u64 *__restrict__ in, u64 *__restrict__ out,
+                                                                u32 n_in, u32 cols, u32 lb, u32 l, u64 cadd, u64 batch, u32 group, u32 cblocks) {
+    const u64 tile = blockIdx.x / cblocks;
+    const u32 o = (blockIdx.x - (u32)tile * cblocks) * PF_TH + threadIdx.x;
+    const u64 b0 = tile * PF_TB, irow = (u64)n_in + 1, fstride = irow * l * cols;   // fstride: one function's key
+    const u32 live = (u32)min((u64)PF_TB, batch - b0);
+    const bool on = o < cols;
+    const u64 *__restrict__ kc = key + (on ? o : cols - 1);        // idle lanes read a valid column and store nothing
+    const u64 *__restrict__ src = in + b0 * irow;
+    const u32 sh0 = 64u - lb, mask = (u32)(~0ull >> (64u - lb));
+    u64 acc[PF_K1][PF_TB], ksum[PF_K1];
+#pragma unroll
+    for (int r = 0; r < PF_K1; r++) {
+        ksum[r] = 0;
+#pragma unroll
+        for (int t = 0; t < PF_TB; t++) acc[r][t] = 0;
+    }
+    for (u32 j = 0; j <= n_in; j++) {
+        u64 w[PF_TB];
+#pragma unroll
+        for (int t = 0; t < PF_TB; t++) w[t] = ((u32)t < live ? src[t * irow + j] : 0ull) + cadd;
+        const u64 *__restrict__ kr = kc + (u64)j * l * cols;
+        for (u32 d = 0; d < l; d++) {
+            u64 kv[PF_K1];
+#pragma unroll
+            for (int r = 0; r < PF_K1; r++) kv[r] = kr[r * fstride + (u64)d * cols];
+            const u32 sh = sh0 - lb * d;
+#pragma unroll
+            for (int r = 0; r < PF_K1; r++) ksum[r] += kv[r];
+#pragma unroll
+            for (int t = 0; t < PF_TB; t++) {
+                const u64 f = (u32)(w[t] >> sh) & mask;
+#pragma unroll
+                for (int r = 0; r < PF_K1; r++) acc[r][t] += f * kv[r];
+            }
+        }
+    }
+    if (!on) return;
+    const u64 half = 1ull << (lb - 1u);
+#pragma unroll
+    for (int t = 0; t < PF_TB; t++) {
+        if ((u32)t >= live) continue;
+        const u64 m = b0 + t, bb = m / group, dd = m - bb * group;
+#pragma unroll
+        for (int r = 0; r < PF_K1; r++) out[((bb * PF_K1 + r) * group + dd) * cols + o] = acc[r][t] - half * ksum[r];
+    }
+}
+
+// alpha_d = g_d(b_cb) / 2 = 2^(63 - b_cb (d+1)): the body of level d's trivial table (b_cb l_cb <= 63)
+__device__ __forceinline__ u64 cb_alpha(u32 cb_b, u32 d) { return 1ull << (63u - cb_b * (d + 1u)); }
+
+// tfhe_br_init_kernel with a table per row: row m = b G + d (G = l_cb) starts from rot(v_d, b~) of c_b + (0 .. 0, 2^62), v_d the
+// trivial table whose body is alpha_d in every coefficient (its mask rows are 0); shift[m][j] = (2N - a~_{b,j}) mod 2N
+__global__ __launch_bounds__(256) void tfhe_cb_init_kernel(const u64 *__restrict__ lwe, u64 *__restrict__ acc, u32 *__restrict__ shift,
+                                                           u32 n_lwe, u32 k1, u32 L, u32 G, u32 cb_b, u64 rows) {
+    const u64 N = 1ull << L, k1N = (u64)k1 * N, na = rows * k1N, total = na + rows * n_lwe;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        if (i < na) {
+            const u64 m = i / k1N, r = i - m * k1N, b = m / G;
+            const u32 d = (u32)(m - b * G);
+            if ((r >> L) + 1 < k1) {
+                acc[i] = 0;
+            } else {
+                const u64 j = (r & (N - 1)) + mod_switch_2n(lwe[b * (n_lwe + 1ull) + n_lwe] + (1ull << 62), L);
+                const u64 x = cb_alpha(cb_b, d);
+                acc[i] = ((j >> L) & 1u) ? 0ull - x : x;
+            }
+        } else {
+            const u64 q = i - na, m = q / n_lwe, b = m / G;
+            shift[q] = (u32)((2 * N - mod_switch_2n(lwe[b * (n_lwe + 1ull) + (q - m * n_lwe)], L)) & (2 * N - 1));
+        }
+    }
+}
+
+// T[m] = (0 .. 0, alpha_d) - E, E = sample extraction of ACC[m] at h = 0, d = m mod G: coefficient c N + j of the mask is
+// -a_c[0] for j = 0 and a_c[N - j] otherwise; the body is alpha_d - b[0]
+__global__ __launch_bounds__(256) void tfhe_cb_extract_kernel(const u64 *__restrict__ acc, u64 *__restrict__ out, u32 k, u32 L, u32 G,
+                                                              u32 cb_b, u64 rows) {
+    const u64 N = 1ull << L, kN = (u64)k * N, per = kN + 1, total = rows * per;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 m = i / per, r = i - m * per;
+        const u64 *src = acc + m * (kN + N);
+        if (r == kN) {
+            out[i] = cb_alpha(cb_b, (u32)(m % G)) - src[kN];
+        } else {
+            const u64 c = r >> L, j = r & (N - 1);
+            out[i] = j == 0 ? 0ull - src[c * N] : src[c * N + N - j];
+        }
+    }
 }
 
 }  // namespace fhe
@@ -337,21 +442,13 @@ int gadget_args(uint64_t n, unsigned k, unsigned log_beta, unsigned l, size_t ba
     return FHE_OK;
 }
 
-int gadget_blind_rotation(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk, const void *d_table,
-                          const void *d_lwe, void *d_out, size_t batch, hipStream_t st) {
-    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
+// the n_lwe gadget CMux steps of a blind rotation: ACC [batch][(k+1)][n] in place, shift [batch][n_lwe] from an init kernel
+int gadget_br_steps(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk, u64 *acc, const u32 *shift,
+                    size_t batch, hipStream_t st) {
+    const u32 L = (u32)__builtin_ctzll(n);
     const u64 words = gadget_tggsw_words(n, k, l);
-    u64 *acc = (u64 *)d_out;
-    void *wsv = nullptr;
-    int rc;
-    if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &wsv)) != FHE_OK) return rc;
-    u32 *shift = (u32 *)wsv;
-    { fhe::KernelTimer kt_("tfhe_br_init", (int)L, st);
-    hipLaunchKernelGGL(fhe::tfhe_br_init_kernel, dim3(fhe_ew_grid((u64)batch * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_lwe,
-                       (const u64 *)d_table, acc, shift, n_lwe, k1, L, (u64)batch);
-    }
-    LAUNCH_OK("tfhe_br_init_kernel");
     fhe::Ext32Args a{};
+    int rc;
     if ((rc = gadget_args(n, k, log_beta, l, batch, st, &a)) != FHE_OK) return rc;
     a.src = acc; a.out = acc; a.shift_stride = n_lwe;
     for (unsigned j = 0; j < n_lwe; j++) {
@@ -364,6 +461,22 @@ int gadget_blind_rotation(uint64_t n, unsigned k, unsigned log_beta, unsigned l,
     return FHE_OK;
 }
 
+int gadget_blind_rotation(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk, const void *d_table,
+                          const void *d_lwe, void *d_out, size_t batch, hipStream_t st) {
+    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
+    u64 *acc = (u64 *)d_out;
+    void *wsv = nullptr;
+    int rc;
+    if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &wsv)) != FHE_OK) return rc;
+    u32 *shift = (u32 *)wsv;
+    { fhe::KernelTimer kt_("tfhe_br_init", (int)L, st);
+    hipLaunchKernelGGL(fhe::tfhe_br_init_kernel, dim3(fhe_ew_grid((u64)batch * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_lwe,
+                       (const u64 *)d_table, acc, shift, n_lwe, k1, L, (u64)batch);
+    }
+    LAUNCH_OK("tfhe_br_init_kernel");
+    return gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk, acc, shift, batch, st);
+}
+
 int gadget_key_switch(unsigned n_in, unsigned n_out, unsigned log_beta, unsigned l, const void *d_ksk, const void *d_in, void *d_out,
                       size_t batch, hipStream_t st) {
     const u32 cblocks = (n_out + 1 + fhe::KS_TH - 1) / fhe::KS_TH;
@@ -374,6 +487,40 @@ int gadget_key_switch(unsigned n_in, unsigned n_out, unsigned log_beta, unsigned
                        (u64 *)d_out, n_in, n_out, log_beta, l, fhe::gadget_cadd(log_beta, l), (u64)batch, cblocks);
     }
     LAUNCH_OK("tlwe_gadget_key_switch_kernel");
+    return FHE_OK;
+}
+
+// ---- circuit bootstrapping ----
+// the PFKS shape: k = 1, 2^8 <= n <= 2^12, 1 <= b <= 32, l >= 1, b l <= 64
+bool pfks_shape(uint64_t n, unsigned k, unsigned log_beta, unsigned l) {
+    return k == 1 && n >= 256 && n <= 4096 && (n & (n - 1)) == 0 && log_beta >= 1 && log_beta <= 32 && l >= 1 && (u64)log_beta * l <= 64;
+}
+u64 pfksk_words(uint64_t n, unsigned k, unsigned l) { return (u64)(k + 1) * ((u64)k * n + 1) * l * (k + 1) * n; }
+
+int check_pfks(uint64_t n, unsigned k, unsigned log_beta, unsigned l, const char *who) {
+    int rc = check_ring(n, k, who);
+    if (rc != FHE_OK) return rc;
+    if (!pfks_shape(n, k, log_beta, l))
+        return fhe_fail(FHE_E_INVALID, "%s: no private functional key switch for n=%llu, k=%u, log_beta=%u, l=%u (needs k = 1, "
+                        "256 <= n <= 4096, 1 <= log_beta <= 32, l >= 1, log_beta l <= 64)", who, (unsigned long long)n, k, log_beta, l);
+    return FHE_OK;
+}
+
+// the grid of tlwe_private_ks_kernel for `rows` inputs; 0 when it does not fit one launch
+u64 pfks_grid(uint64_t n, unsigned k, u64 rows) {
+    const u64 cblocks = ((u64)(k + 1) * n + fhe::PF_TH - 1) / fhe::PF_TH;
+    const u64 grid = (rows + fhe::PF_TB - 1) / fhe::PF_TB * cblocks;
+    return grid > 0x7fffffffull ? 0 : grid;
+}
+
+int private_key_switch(uint64_t n, unsigned k, unsigned log_beta, unsigned l, const void *d_key, const void *d_in, void *d_out, u64 rows,
+                       u32 group, hipStream_t st) {
+    const u32 cols = (u32)((k + 1) * n), cblocks = (cols + fhe::PF_TH - 1) / fhe::PF_TH;
+    { fhe::KernelTimer kt_("tlwe_private_ks", (int)__builtin_ctzll(n), st);
+    hipLaunchKernelGGL(fhe::tlwe_private_ks_kernel, dim3((unsigned)pfks_grid(n, k, rows)), dim3(fhe::PF_TH), 0, st, (const u64 *)d_key,
+                       (const u64 *)d_in, (u64 *)d_out, (u32)(k * n), cols, log_beta, l, fhe::gadget_cadd(log_beta, l), rows, group, cblocks);
+    }
+    LAUNCH_OK("tlwe_private_ks_kernel");
     return FHE_OK;
 }
 
@@ -597,4 +744,109 @@ extern "C" int fhe_tfhe_gadget_bootstrap_dev(uint64_t n, unsigned k, unsigned lo
     if ((rc = gadget_blind_rotation(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_table, d_in, acc, batch, st)) != FHE_OK) return rc;
     if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) return rc;
     return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, batch, st);
+}
+
+// ---- circuit bootstrapping ------------------------------------------------------------------------------
+extern "C" size_t fhe_tfhe_pfksk_words(uint64_t n, unsigned k, unsigned log_beta, unsigned l) {
+    return pfks_shape(n, k, log_beta, l) ? (size_t)pfksk_words(n, k, l) : 0;
+}
+
+extern "C" int fhe_tlwe_gadget_private_key_switch_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, const void *d_pfksk,
+                                                      const void *d_in, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_tlwe_gadget_private_key_switch_dev";
+    int rc = check_pfks(n, k, log_beta, l, who);
+    if (rc != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    if (!d_pfksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_pfksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
+    if (pfks_grid(n, k, batch) == 0) return fhe_fail(FHE_E_INVALID, "%s: batch too large for one launch", who);
+    const u64 out_bytes = (u64)batch * (k + 1) * (k + 1) * n * 8;
+    if (overlaps(d_out, out_bytes, d_in, (u64)batch * ((u64)k * n + 1) * 8) || overlaps(d_out, out_bytes, d_pfksk, pfksk_words(n, k, l) * 8))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    return private_key_switch(n, k, log_beta, l, d_pfksk, d_in, d_out, batch, 1, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_tggsw_gadget_prepare_many_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, size_t count, const void *d_tggsw,
+                                                 void *d_prepared, void *hip_stream) {
+    const char *who = "fhe_tggsw_gadget_prepare_many_dev";
+    int rc = check_gext(n, k, log_beta, l, who);
+    if (rc != FHE_OK) return rc;
+    if (count == 0) return FHE_OK;
+    if (!d_tggsw || !d_prepared) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_tggsw); REQUIRE_ALIGNED(d_prepared);
+    const u64 w = gadget_tggsw_words(n, k, l);
+    if ((u64)count > (~0ull >> 4) / w) return fhe_fail(FHE_E_INVALID, "%s: count too large", who);
+    if (overlaps(d_tggsw, count * (w / 2) * 8, d_prepared, count * w * 8)) return fhe_fail(FHE_E_INVALID, "%s: d_prepared overlaps d_tggsw", who);
+    return gadget_prepare(n, k, l, count, d_tggsw, d_prepared, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_tggsw_gadget_cmux_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, size_t count, const void *d_prepared,
+                                         const void *d_idx, const void *d_c0, const void *d_c1, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_tggsw_gadget_cmux_dev";
+    int rc = check_gext(n, k, log_beta, l, who);
+    if (rc != FHE_OK) return rc;
+    if (count < 1 || count > 0xffffffffull) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= count < 2^32 (count=%llu)", who, (unsigned long long)count);
+    const u64 w = gadget_tggsw_words(n, k, l);
+    if ((u64)count > (~0ull >> 4) / w) return fhe_fail(FHE_E_INVALID, "%s: count too large", who);
+    if (batch == 0) return FHE_OK;
+    if (!d_prepared || !d_idx || !d_c0 || !d_c1 || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_prepared); REQUIRE_ALIGNED(d_idx); REQUIRE_ALIGNED(d_c0); REQUIRE_ALIGNED(d_c1); REQUIRE_ALIGNED(d_out);
+    const u64 ct_bytes = (u64)batch * (k + 1) * n * 8;
+    if (overlaps(d_out, ct_bytes, d_c0, ct_bytes) || overlaps(d_out, ct_bytes, d_c1, ct_bytes) || overlaps(d_out, ct_bytes, d_prepared, count * w * 8) ||
+        overlaps(d_out, ct_bytes, d_idx, (u64)batch * 4))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    fhe::Ext32Args a{};
+    if ((rc = gadget_args(n, k, log_beta, l, batch, st, &a)) != FHE_OK) return rc;
+    a.key32 = (uint32_t *)const_cast<void *>(d_prepared); a.key_stride32 = 2 * w; a.sel_count = (uint32_t)count;
+    a.sel = (const uint32_t *)d_idx; a.shift_stride = 1;
+    a.src = (const u64 *)d_c0; a.src1 = (const u64 *)d_c1; a.out = (u64 *)d_out;
+    const int L = (int)__builtin_ctzll(n);
+    hipError_t e = fhe::launch_ext32_mac(a, L, fhe::SRC32_GSEL, st);
+    if (e == hipSuccess) e = fhe::launch_ext32_tail_sel(a, L, st);
+    return e == hipSuccess ? FHE_OK : fhe_hip_fail(e, "digit32 gadget CMux (selector per ciphertext) kernels");
+}
+
+extern "C" int fhe_tfhe_circuit_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
+                                              unsigned cb_log_beta, unsigned cb_l, unsigned pf_log_beta, unsigned pf_l, const void *d_pfksk,
+                                              const void *d_lwe, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_tfhe_circuit_bootstrap_dev";
+    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
+    if (rc == FHE_OK) rc = check_gext(n, k, cb_log_beta, cb_l, who);
+    if (rc == FHE_OK) rc = check_pfks(n, k, pf_log_beta, pf_l, who);
+    if (rc != FHE_OK) return rc;
+    if ((u64)cb_log_beta * cb_l > 63)
+        return fhe_fail(FHE_E_INVALID, "%s: need cb_log_beta cb_l <= 63 (alpha = g / 2 of the last level must be a word)", who);
+    if (batch == 0) return FHE_OK;
+    if (!d_bsk_prepared || !d_pfksk || !d_lwe || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_pfksk); REQUIRE_ALIGNED(d_lwe); REQUIRE_ALIGNED(d_out);
+    const u64 rows = (u64)batch * cb_l;
+    if ((u64)batch > 0xffffffffull || pfks_grid(n, k, rows) == 0 || rows * (k + 1) * n > 0x7fffffffull * 256)
+        return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    const u64 out_bytes = rows * (k + 1) * (k + 1) * n * 8;
+    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
+        overlaps(d_out, out_bytes, d_pfksk, pfksk_words(n, k, pf_l) * 8) || overlaps(d_out, out_bytes, d_lwe, (u64)batch * (n_lwe + 1ull) * 8))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
+    const u64 kn = (u64)k * n;
+    void *accv = nullptr, *tv = nullptr, *shv = nullptr;
+    if ((rc = fhe_workspace_get(7, rows * k1 * n * 8, st, &accv)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(8, rows * (kn + 1) * 8, st, &tv)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(5, rows * n_lwe * 4, st, &shv)) != FHE_OK) return rc;
+    u64 *acc = (u64 *)accv;
+    // the l_cb blind rotations of every input as one blind rotation over batch l_cb rows (row b l_cb + d: level d)
+    { fhe::KernelTimer kt_("tfhe_cb_init", (int)L, st);
+    hipLaunchKernelGGL(fhe::tfhe_cb_init_kernel, dim3(fhe_ew_grid(rows * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_lwe, acc,
+                       (u32 *)shv, n_lwe, k1, L, cb_l, cb_log_beta, rows);
+    }
+    LAUNCH_OK("tfhe_cb_init_kernel");
+    if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, (const u32 *)shv, rows, st)) != FHE_OK) return rc;
+    { fhe::KernelTimer kt_("tfhe_cb_extract", (int)L, st);
+    hipLaunchKernelGGL(fhe::tfhe_cb_extract_kernel, dim3(fhe_ew_grid(rows * (kn + 1))), dim3(256), 0, st, (const u64 *)acc, (u64 *)tv, k, L,
+                       cb_l, cb_log_beta, rows);
+    }
+    LAUNCH_OK("tfhe_cb_extract_kernel");
+    // TGGSW row (r, d) = PFKS_r(T_d): the key switch writes [batch][(k+1)][l_cb][(k+1)][n] directly
+    return private_key_switch(n, k, pf_log_beta, pf_l, d_pfksk, tv, d_out, rows, cb_l, st);
 }

@@ -16,6 +16,9 @@ over the C ABI.
     (no counterpart)                                   the signed base-2^b gadget of DESIGN.md §11: gadget_decompose,
                                                        gadget_external_product, BootstrappingKey(log_beta=...),
                                                        TLWE.key_switch(log_beta=...)
+    cmux (tggsw.rs:39-41, a key bit there)             circuit bootstrapping of DESIGN.md §12: private_key_switch,
+                                                       CircuitBootstrappingKey, circuit_bootstrap, PreparedTGGSWs,
+                                                       cmux (a selector per ciphertext), cmux_tree (vertical packing)
 """
 import numpy as np
 
@@ -243,3 +246,129 @@ def gadget_external_product(tggsw, tglwe, log_beta):
     binding.tggsw_gadget_external_product_dev(n, k1 - 1, log_beta, l, prep.data_ptr(), dx.data_ptr(), out.data_ptr(), batch)
     o = _from_dev(out).reshape(x.shape)
     return TGLWE(o[..., : k1 - 1, :], o[..., k1 - 1, :])
+
+
+# ---- circuit bootstrapping and the CMux with a selector per ciphertext -----------------------------------
+def _dev_words(x):
+    torch = _torch()
+    return x if isinstance(x, torch.Tensor) else _to_dev(x)
+
+
+def private_key_switch(c, pfksk, log_beta, l):
+    """TLWE of dimension k n -> TGLWE per function r <= k: out_r = sum_{j <= kn} sum_d digit_d(c_j) pfksk[r][j][d].
+    pfksk [(k+1)][k n + 1][l][(k+1)][n] (numpy or a device tensor).  The result's a is [.., (k+1)][k][n], b [.., (k+1)][n]."""
+    torch = _torch()
+    k1, n = pfksk.shape[0], pfksk.shape[-1]
+    kn = c.dim
+    size = pfksk.numel() if isinstance(pfksk, torch.Tensor) else np.asarray(pfksk).size
+    if pfksk.shape[1] != kn + 1 or binding.tfhe_pfksk_words(n, k1 - 1, log_beta, l) != size:
+        raise binding.FheError(binding.FHE_E_INVALID, f"pfksk of shape {tuple(pfksk.shape)} does not match dimension {kn}, log_beta={log_beta}, l={l}")
+    x = c.words.reshape(-1, kn + 1)
+    dk, dx = _dev_words(pfksk), _to_dev(x)
+    out = torch.empty((x.shape[0], k1, k1, n), dtype=torch.int64, device="cuda")
+    binding.tlwe_gadget_private_key_switch_dev(n, k1 - 1, log_beta, l, dk.data_ptr(), dx.data_ptr(), out.data_ptr(), x.shape[0])
+    o = _from_dev(out).reshape(c.words.shape[:-1] + (k1, k1, n))
+    return TGLWE(o[..., : k1 - 1, :], o[..., k1 - 1, :])
+
+
+class CircuitBootstrappingKey:
+    """a gadget BootstrappingKey, and the private functional key switching key [(k+1)][k n + 1][pf_l][(k+1)][n] (function
+    r < k: x -> -s_r x, function k: x -> x) kept on the device.  The circuit bootstrap yields gadget TGGSWs with
+    (cb_log_beta, cb_l)."""
+
+    def __init__(self, btk, pfksk, cb_log_beta, cb_l, pf_log_beta, pf_l):
+        torch = _torch()
+        if btk.log_beta is None:
+            raise ValueError("circuit bootstrapping needs a gadget BootstrappingKey (log_beta=...)")
+        if binding.tggsw_gadget_prepared_words(btk.n, btk.k, cb_log_beta, cb_l) == 0 or cb_log_beta * cb_l > 63:
+            raise binding.FheError(binding.FHE_E_INVALID, f"no circuit bootstrap to (cb_log_beta, cb_l) = ({cb_log_beta}, {cb_l})")
+        words = binding.tfhe_pfksk_words(btk.n, btk.k, pf_log_beta, pf_l)
+        self.pfksk = _dev_words(pfksk)
+        if words == 0 or self.pfksk.numel() != words:
+            raise binding.FheError(binding.FHE_E_INVALID, f"pfksk has {self.pfksk.numel()} words, (pf_log_beta, pf_l) = ({pf_log_beta}, {pf_l}) "
+                                   f"needs {words}")
+        self.btk, self.cb_log_beta, self.cb_l, self.pf_log_beta, self.pf_l = btk, cb_log_beta, cb_l, pf_log_beta, pf_l
+        torch.cuda.synchronize()
+
+
+def circuit_bootstrap(cbk, c, *, device=False):
+    """TLWE c (dimension n_lwe) of a bit mu, phase mu 2^63 + e -> raw gadget TGGSWs of mu under the GLWE key:
+    [.., (k+1)][cb_l][(k+1)][n] (numpy; device=True: the int64 device tensor [batch][..], for PreparedTGGSWs)"""
+    torch = _torch()
+    b = cbk.btk
+    x = c.words.reshape(-1, b.n_lwe + 1)
+    k1 = b.k + 1
+    out = torch.empty((x.shape[0], k1, cbk.cb_l, k1, b.n), dtype=torch.int64, device="cuda")
+    dx = _to_dev(x)
+    binding.tfhe_circuit_bootstrap_dev(b.n, b.k, b.log_beta, b.l, b.n_lwe, b.bsk.data_ptr(), cbk.cb_log_beta, cbk.cb_l, cbk.pf_log_beta,
+                                       cbk.pf_l, cbk.pfksk.data_ptr(), dx.data_ptr(), out.data_ptr(), x.shape[0])
+    if device:
+        torch.cuda.synchronize()
+        return out
+    return _from_dev(out).reshape(c.words.shape[:-1] + (k1, cbk.cb_l, k1, b.n))
+
+
+class PreparedTGGSWs:
+    """`count` gadget TGGSWs rows [count][(k+1)][l][(k+1)][n] (numpy or a device tensor) prepared side by side on the
+    device (fhe_tggsw_gadget_prepare_many_dev): the selectors of cmux and cmux_tree"""
+
+    def __init__(self, rows, log_beta):
+        torch = _torch()
+        shape = tuple(rows.shape)
+        if len(shape) != 5 or shape[1] != shape[3]:
+            raise ValueError("rows must be [count][(k+1)][l][(k+1)][n]")
+        self.count, k1, self.l, _, self.n = shape
+        self.k, self.log_beta = k1 - 1, log_beta
+        self.words = binding.tggsw_gadget_prepared_words(self.n, self.k, log_beta, self.l)
+        if self.words == 0:
+            raise binding.FheError(binding.FHE_E_INVALID, f"no gadget product for n={self.n}, k={self.k}, log_beta={log_beta}, l={self.l}")
+        g = _dev_words(rows)
+        self.prepared = torch.empty(self.count * self.words, dtype=torch.int64, device="cuda")
+        binding.tggsw_gadget_prepare_many_dev(self.n, self.k, log_beta, self.l, self.count, g.data_ptr(), self.prepared.data_ptr())
+        torch.cuda.synchronize()
+
+
+def _cmux_dev(sel, d_idx, d_c0, d_c1, batch):
+    torch = _torch()
+    out = torch.empty((batch, sel.k + 1, sel.n), dtype=torch.int64, device="cuda")
+    binding.tggsw_gadget_cmux_dev(sel.n, sel.k, sel.log_beta, sel.l, sel.count, sel.prepared.data_ptr(), d_idx.data_ptr(), d_c0.data_ptr(),
+                                  d_c1.data_ptr(), out.data_ptr(), batch)
+    return out
+
+
+def cmux(sel, idx, c0, c1):
+    """out_j = c0_j + C[idx_j] [x] (c1_j - c0_j), C = the TGGSWs of `sel` (PreparedTGGSWs), idx [batch] (an idx_j >= count
+    gives c0_j); c0, c1 TGLWE batches"""
+    torch = _torch()
+    x0, x1 = c0.packed(), c1.packed()
+    k1, n = sel.k + 1, sel.n
+    batch = x0.size // (k1 * n)
+    if x1.shape != x0.shape or len(idx) != batch:
+        raise ValueError("cmux: c0, c1 and idx must have one entry per ciphertext")
+    di = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.uint32).view(np.int32)).cuda()
+    d0, d1 = _to_dev(x0.reshape(batch, k1, n)), _to_dev(x1.reshape(batch, k1, n))
+    o = _from_dev(_cmux_dev(sel, di, d0, d1, batch)).reshape(x0.shape)
+    return TGLWE(o[..., : k1 - 1, :], o[..., k1 - 1, :])
+
+
+def cmux_tree(sel, bits_idx, table):
+    """vertical packing: table [2^m][(k+1)][n] (TGLWEs, shared by the batch), bits_idx [batch][m] indices into `sel` of the
+    TGGSWs of bit i of each input x (i = 0 the least significant) -> TGLWE [batch] of table[x].  One CMux launch per
+    level: level i halves the candidates with bit i, c0 = entry 2j, c1 = entry 2j + 1."""
+    torch = _torch()
+    tab = table.packed() if isinstance(table, TGLWE) else np.asarray(table, dtype=np.uint64)
+    bits = np.atleast_2d(np.asarray(bits_idx, dtype=np.uint32))
+    batch, m = bits.shape
+    k1, n = sel.k + 1, sel.n
+    if tab.shape != (1 << m, k1, n):
+        raise ValueError(f"cmux_tree: table must be [2^{m}][{k1}][{n}]")
+    cur = _to_dev(tab).unsqueeze(0).expand(batch, -1, -1, -1)           # [batch][2^m][(k+1)][n]
+    db = torch.from_numpy(bits.view(np.int32)).cuda()
+    for i in range(m):
+        half = cur.shape[1] // 2
+        pairs = cur.reshape(batch, half, 2, k1, n)
+        c0, c1 = pairs[:, :, 0].contiguous(), pairs[:, :, 1].contiguous()
+        di = db[:, i].unsqueeze(1).expand(batch, half).contiguous()
+        cur = _cmux_dev(sel, di, c0, c1, batch * half).reshape(batch, half, k1, n)
+    o = _from_dev(cur.reshape(batch, k1, n))
+    return TGLWE(o[:, : k1 - 1, :], o[:, k1 - 1, :])

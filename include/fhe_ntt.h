@@ -356,6 +356,37 @@ int fhe_tfhe_gadget_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, uns
                                   const void *d_bsk_prepared, const void *d_table, unsigned ks_log_beta, unsigned ks_l,
                                   const void *d_ksk, const void *d_in, void *d_out, size_t batch, void *hip_stream);
 
+/* ---- TFHE circuit bootstrapping and a CMux with a selector per ciphertext (definitions in DESIGN.md §12) ----
+ * k = 1, 256 <= n <= 4096; K = the extracted LWE key of the GLWE key s (dimension k n), g_d(b) = 2^(64 - b(d+1)) and
+ * digit_d are §11's.  Outputs must not overlap inputs.
+ *   fhe_tfhe_pfksk_words            u64 words of a private functional key switching key [(k+1)][k n + 1][l][(k+1)][n]
+ *                                   (1 <= b <= 32, b l <= 64; 0 otherwise).  Function r < k is x -> -s_r x, function k
+ *                                   x -> x; entry [r][j][d] is a TGLWE under s of f_r(K~_j) g_d, K~ = (-K_0 .. -K_{kn-1}, 1)
+ *   fhe_tlwe_gadget_private_key_switch_dev  d_in [batch][k n + 1] -> d_out [batch][(k+1)][(k+1)][n]:
+ *                                   out_r = sum_{j <= kn} sum_d digit_d(c_j) pfksk[r][j][d], c_kn the body (wrapping u64)
+ *   fhe_tggsw_gadget_prepare_many_dev  `count` gadget TGGSWs [count][(k+1)][l][(k+1)][n] -> count prepared ones side by
+ *                                   side (count * fhe_tggsw_gadget_prepared_words)
+ *   fhe_tggsw_gadget_cmux_dev       out_j = c0_j + C[idx_j] [x] (c1_j - c0_j): d_prepared holds `count` prepared TGGSWs,
+ *                                   d_idx [batch] u32; an idx_j >= count selects nothing (out_j = c0_j).  c0, c1, out:
+ *                                   [batch][(k+1)][n]
+ *   fhe_tfhe_circuit_bootstrap_dev  d_lwe [batch][n_lwe + 1], phase mu 2^63 + e (mu in {0, 1}) -> d_out
+ *                                   [batch][(k+1)][cb_l][(k+1)][n]: raw gadget TGGSWs of mu with (cb_log_beta, cb_l), for
+ *                                   fhe_tggsw_gadget_prepare(_many)_dev.  BSK (log_beta, l) and (cb_log_beta, cb_l) must be
+ *                                   admitted by fhe_tggsw_gadget_prepared_words, cb_log_beta cb_l <= 63; PFKSK
+ *                                   (pf_log_beta, pf_l) as fhe_tfhe_pfksk_words */
+size_t fhe_tfhe_pfksk_words(uint64_t n, unsigned k, unsigned log_beta, unsigned l);
+int fhe_tlwe_gadget_private_key_switch_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, const void *d_pfksk,
+                                           const void *d_in, void *d_out, size_t batch, void *hip_stream);
+int fhe_tggsw_gadget_prepare_many_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, size_t count,
+                                      const void *d_tggsw, void *d_prepared, void *hip_stream);
+int fhe_tggsw_gadget_cmux_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, size_t count, const void *d_prepared,
+                              const void *d_idx, const void *d_c0, const void *d_c1, void *d_out, size_t batch,
+                              void *hip_stream);
+int fhe_tfhe_circuit_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe,
+                                   const void *d_bsk_prepared, unsigned cb_log_beta, unsigned cb_l, unsigned pf_log_beta,
+                                   unsigned pf_l, const void *d_pfksk, const void *d_lwe, void *d_out, size_t batch,
+                                   void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
