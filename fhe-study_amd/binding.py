@@ -71,7 +71,13 @@ EXPORTS = [
     # circuit bootstrapping and the CMux with a selector per ciphertext (tfhe_boot.hip)
     "fhe_tfhe_pfksk_words", "fhe_tlwe_gadget_private_key_switch_dev", "fhe_tggsw_gadget_prepare_many_dev",
     "fhe_tggsw_gadget_cmux_dev", "fhe_tfhe_circuit_bootstrap_dev",
+    # boolean gates with gate bootstrapping (tfhe_boot.hip)
+    "fhe_tfhe_gate_bootstrap_dev", "fhe_tfhe_gate_mux_dev",
 ]
+
+# FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
+GATES = {"AND": 0, "NAND": 1, "OR": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
+FHE_GATE_COUNT = 10
 
 
 # include/fhe_ntt_experimental.h: the persistent kernels' switches (exported, NOT part of the boundary)
@@ -243,6 +249,8 @@ def load_library():
     L.fhe_tggsw_gadget_prepare_many_dev.argtypes = [_u64, _uint, _uint, _uint, _sz, _vp, _vp, _vp]
     L.fhe_tggsw_gadget_cmux_dev.argtypes = [_u64, _uint, _uint, _uint, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
     L.fhe_tfhe_circuit_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_gate_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _vp, _vp, _sz, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_gate_mux_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _vp, _vp, _sz, _vp, _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -564,6 +572,18 @@ def tfhe_circuit_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, cb_log_
                                batch, stream=None):
     _check(load_library().fhe_tfhe_circuit_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, cb_log_beta, cb_l, pf_log_beta, pf_l,
                                                          d_pfksk, d_lwe, d_out, batch, stream))
+
+
+# ---- boolean gates with gate bootstrapping ---------------------------------------------------------------
+def tfhe_gate_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, d_pool, wires, d_gates, d_out, batch,
+                            stream=None):
+    _check(load_library().fhe_tfhe_gate_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, d_pool, wires,
+                                                      d_gates, d_out, batch, stream))
+
+
+def tfhe_gate_mux_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, d_pool, wires, d_sel, d_out, batch, stream=None):
+    _check(load_library().fhe_tfhe_gate_mux_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, d_pool, wires, d_sel,
+                                                d_out, batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

@@ -18,6 +18,9 @@
 // Circuit bootstrapping: a private functional key switch TLWE -> TGLWE (all k+1 functions in one pass), a
 // CMux whose TGGSW is chosen per ciphertext (SRC32_GSEL, EPI32_SEL), and the glue that runs the l_cb blind rotations of a
 // batch as one gadget blind rotation over batch l_cb rows and turns them into TGGSW rows.
+//
+// Boolean gates: one blind rotation over a batch of mixed gates, since every gate shares the test vector;
+// an init kernel forms each row's combination alpha c_x + beta c_y + o from the pool as it writes ACC_0 and the shifts.
 #include <algorithm>
 
 #include "capi_internal.hpp"
@@ -267,6 +270,73 @@ __global__ __launch_bounds__(256) void tfhe_cb_extract_kernel(const u64 *__restr
         } else {
             const u64 c = r >> L, j = r & (N - 1);
             out[i] = j == 0 ? 0ull - src[c * N] : src[c * N + N - j];
+        }
+    }
+}
+
+// ---- boolean gates ------------------------------------------------------------------------------------
+// bits are phases +-mu, mu = 2^61; op (alpha, beta, o / mu) in FHE_GATE_* order: AND NAND OR NOR XOR XNOR ANDNY ANDYN ORNY ORYN
+constexpr u64 GATE_MU = 1ull << 61;
+constexpr u32 GATE_COUNT = 10, GATE_AND = 0, GATE_ANDNY = 6;
+__constant__ signed char gate_alpha[GATE_COUNT] = {1, -1, 1, -1, 2, -2, -1, 1, -1, 1};
+__constant__ signed char gate_beta[GATE_COUNT] = {1, -1, 1, -1, 2, -2, 1, -1, 1, -1};
+__constant__ signed char gate_o[GATE_COUNT] = {-1, 1, 1, -1, 2, -2, -1, -1, 1, 1};
+
+// word j (j = n_lwe: the body) of alpha c_x + beta c_y + (0 .. 0, o); an op >= GATE_COUNT or an index >= wires gives 0 and
+// reads nothing
+__device__ __forceinline__ u64 gate_word(const u64 *__restrict__ pool, u64 wires, u32 n_lwe, u32 op, u32 x, u32 y, u32 j) {
+    if (op >= GATE_COUNT || x >= wires || y >= wires) return 0;
+    const u64 row = n_lwe + 1ull;
+    const u64 w = (u64)(long long)gate_alpha[op] * pool[x * row + j] + (u64)(long long)gate_beta[op] * pool[y * row + j];
+    return j == n_lwe ? w + (u64)(long long)gate_o[op] * GATE_MU : w;
+}
+
+// tfhe_br_init_kernel over the combined rows, v = (mask 0, body mu) computed in place: ACC_0[m] = rot(v, b~_m),
+// shift[m][j] = (2N - a~_{m,j}) mod 2N.  MUX = false: row m is gate m, desc[m] = (op, x, y).  MUX = true: desc[b] = (s, a, c),
+// row 2b is AND(s, a), row 2b + 1 ANDNY(s, c).  The combined TLWE exists only in registers.
+template <bool MUX>
+__global__ __launch_bounds__(256) void tfhe_gate_init_kernel(const u64 *__restrict__ pool, u64 wires, const u32 *__restrict__ desc,
+                                                             u64 *__restrict__ acc, u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L, u64 rows) {
+    const u64 N = 1ull << L, k1N = (u64)k1 * N, na = rows * k1N, total = na + rows * n_lwe;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 m = i < na ? i / k1N : (i - na) / n_lwe;
+        u32 op, x, y;
+        if (MUX) {
+            const u32 *d = desc + (m >> 1) * 3;
+            op = (m & 1) ? GATE_ANDNY : GATE_AND; x = d[0]; y = d[1 + (m & 1)];
+        } else {
+            const u32 *d = desc + m * 3;
+            op = d[0]; x = d[1]; y = d[2];
+        }
+        if (i < na) {
+            const u64 r = i - m * k1N;
+            if ((r >> L) + 1 < k1) {
+                acc[i] = 0;
+            } else {
+                const u64 j = (r & (N - 1)) + mod_switch_2n(gate_word(pool, wires, n_lwe, op, x, y, n_lwe), L);
+                acc[i] = ((j >> L) & 1u) ? 0ull - GATE_MU : GATE_MU;
+            }
+        } else {
+            const u64 q = i - na;
+            shift[q] = (u32)((2 * N - mod_switch_2n(gate_word(pool, wires, n_lwe, op, x, y, (u32)(q - m * n_lwe)), L)) & (2 * N - 1));
+        }
+    }
+}
+
+// out[b] = E[2b] + E[2b + 1] + (0 .. 0, mu), E = sample extraction of ACC at h = 0 (coefficient c N + j of the mask is
+// a_c[0] for j = 0 and -a_c[N - j] otherwise; the body b[0])
+__global__ __launch_bounds__(256) void tfhe_mux_extract_kernel(const u64 *__restrict__ acc, u64 *__restrict__ out, u32 k, u32 L, u64 batch) {
+    const u64 N = 1ull << L, kN = (u64)k * N, per = kN + 1, total = batch * per;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 b = i / per, r = i - b * per;
+        const u64 *s0 = acc + 2 * b * (kN + N), *s1 = s0 + kN + N;
+        if (r == kN) {
+            out[i] = s0[kN] + s1[kN] + GATE_MU;
+        } else {
+            const u64 c = r >> L, j = r & (N - 1);
+            out[i] = j == 0 ? s0[c * N] + s1[c * N] : 0ull - s0[c * N + N - j] - s1[c * N + N - j];
         }
     }
 }
@@ -849,4 +919,66 @@ extern "C" int fhe_tfhe_circuit_bootstrap_dev(uint64_t n, unsigned k, unsigned l
     LAUNCH_OK("tfhe_cb_extract_kernel");
     // TGGSW row (r, d) = PFKS_r(T_d): the key switch writes [batch][(k+1)][l_cb][(k+1)][n] directly
     return private_key_switch(n, k, pf_log_beta, pf_l, d_pfksk, tv, d_out, rows, cb_l, st);
+}
+
+// ---- boolean gates ---------------------------------------------------------------------------------------
+static_assert(fhe::GATE_COUNT == FHE_GATE_COUNT && fhe::GATE_AND == FHE_GATE_AND && fhe::GATE_ANDNY == FHE_GATE_ANDNY, "gate codes");
+
+namespace {
+// gate init -> the §11 CMux steps over `rows` rows -> extraction (gate: h = 0; MUX: the fused pair sum) -> key switch into d_out
+int gate_entry(bool mux, uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared, unsigned ks_log_beta,
+               unsigned ks_l, const void *d_ksk, const void *d_pool, size_t wires, const void *d_desc, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = mux ? "fhe_tfhe_gate_mux_dev" : "fhe_tfhe_gate_bootstrap_dev";
+    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
+    if (rc != FHE_OK) return rc;
+    const u64 kn = (u64)k * n;
+    if ((rc = check_gks((unsigned)kn, n_lwe, ks_log_beta, ks_l, who)) != FHE_OK) return rc;
+    if (wires < 1) return fhe_fail(FHE_E_INVALID, "%s: need wires >= 1", who);
+    if (batch == 0) return FHE_OK;
+    if (!d_bsk_prepared || !d_ksk || !d_pool || !d_desc || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_pool); REQUIRE_ALIGNED(d_desc); REQUIRE_ALIGNED(d_out);
+    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
+    const u64 rows = (mux ? 2ull : 1ull) * batch;
+    if ((u64)batch > 0xffffffffull || rows * (k1 * n + n_lwe) > 0x7fffffffull * 256 ||
+        ((u64)batch + fhe::KS_TB - 1) / fhe::KS_TB * ((n_lwe + 1ull + fhe::KS_TH - 1) / fhe::KS_TH) > 0x7fffffffull)
+        return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    const u64 out_bytes = (u64)batch * (n_lwe + 1ull) * 8;
+    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
+        overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) || overlaps(d_out, out_bytes, d_desc, (u64)batch * 3 * 4))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps a key or the descriptors", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    void *accv = nullptr, *ext = nullptr, *shv = nullptr;
+    if ((rc = fhe_workspace_get(7, rows * k1 * n * 8, st, &accv)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(8, (u64)batch * (kn + 1) * 8, st, &ext)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(5, rows * n_lwe * 4, st, &shv)) != FHE_OK) return rc;
+    u64 *acc = (u64 *)accv;
+    { fhe::KernelTimer kt_(mux ? "tfhe_mux_init" : "tfhe_gate_init", (int)L, st);
+    hipLaunchKernelGGL(mux ? fhe::tfhe_gate_init_kernel<true> : fhe::tfhe_gate_init_kernel<false>, dim3(fhe_ew_grid(rows * (k1 * n + n_lwe))), dim3(256),
+                       0, st, (const u64 *)d_pool, (u64)wires, (const u32 *)d_desc, acc, (u32 *)shv, n_lwe, k1, L, rows);
+    }
+    LAUNCH_OK("tfhe_gate_init_kernel");
+    if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, (const u32 *)shv, rows, st)) != FHE_OK) return rc;
+    if (mux) {
+        { fhe::KernelTimer kt_("tfhe_mux_extract", (int)L, st);
+        hipLaunchKernelGGL(fhe::tfhe_mux_extract_kernel, dim3(fhe_ew_grid((u64)batch * (kn + 1))), dim3(256), 0, st, (const u64 *)acc, (u64 *)ext, k, L,
+                           (u64)batch);
+        }
+        LAUNCH_OK("tfhe_mux_extract_kernel");
+    } else if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) {
+        return rc;
+    }
+    return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, batch, st);
+}
+}  // namespace
+
+extern "C" int fhe_tfhe_gate_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
+                                           unsigned ks_log_beta, unsigned ks_l, const void *d_ksk, const void *d_pool, size_t wires, const void *d_gates,
+                                           void *d_out, size_t batch, void *hip_stream) {
+    return gate_entry(false, n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, d_pool, wires, d_gates, d_out, batch, hip_stream);
+}
+
+extern "C" int fhe_tfhe_gate_mux_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
+                                     unsigned ks_log_beta, unsigned ks_l, const void *d_ksk, const void *d_pool, size_t wires, const void *d_sel,
+                                     void *d_out, size_t batch, void *hip_stream) {
+    return gate_entry(true, n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, d_pool, wires, d_sel, d_out, batch, hip_stream);
 }

@@ -19,6 +19,9 @@ over the C ABI.
     cmux (tggsw.rs:39-41, a key bit there)             circuit bootstrapping of DESIGN.md §12: private_key_switch,
                                                        CircuitBootstrappingKey, circuit_bootstrap, PreparedTGGSWs,
                                                        cmux (a selector per ciphertext), cmux_tree (vertical packing)
+    (no counterpart)                                   boolean gates of DESIGN.md §13 (bits +-2^61): GATES, gate_bootstrap
+                                                       (a mixed-op batch in one call), mux, gate_not, trivial_bit, and the
+                                                       Circuit netlist (plan levels on the host, evaluate on the device)
 """
 import numpy as np
 
@@ -372,3 +375,255 @@ def cmux_tree(sel, bits_idx, table):
         cur = _cmux_dev(sel, di, c0, c1, batch * half).reshape(batch, half, k1, n)
     o = _from_dev(cur.reshape(batch, k1, n))
     return TGLWE(o[:, : k1 - 1, :], o[:, k1 - 1, :])
+
+
+# ---- boolean gates with gate bootstrapping -----------------------------------------------------------------
+GATES = binding.GATES
+MU = 1 << 61                                     # bit 1 is phase +MU, bit 0 is -MU
+
+
+def _gate_code(op):
+    if isinstance(op, str):
+        if op.upper() not in GATES:
+            raise ValueError(f"unknown gate {op!r}: one of {sorted(GATES)}")
+        return GATES[op.upper()]
+    return int(op)
+
+
+def _gate_key(btk):
+    if btk.log_beta is None:
+        raise ValueError("boolean gates need a gadget BootstrappingKey (log_beta=...)")
+
+
+def trivial_bit(bit, n_lwe):
+    """the noiseless TLWE (0 .. 0, +-MU) of a bit, or of each bit of an array"""
+    bits = np.asarray(bit)
+    words = np.zeros(bits.shape + (n_lwe + 1,), dtype=np.uint64)
+    words[..., n_lwe] = np.where(bits.astype(bool), np.uint64(MU), np.uint64((1 << 64) - MU))
+    return TLWE(words)
+
+
+def gate_not(c):
+    """NOT without a bootstrap: every word negated"""
+    return TLWE((np.uint64(0) - c.words).astype(np.uint64))
+
+
+def _gate_call(btk, mux, pool, desc, batch):
+    """one fhe_tfhe_gate_bootstrap_dev / fhe_tfhe_gate_mux_dev over the host pool [wires][n_lwe + 1] and descriptors [batch][3]"""
+    torch = _torch()
+    _gate_key(btk)
+    dp = _to_dev(pool)
+    dd = torch.from_numpy(np.ascontiguousarray(desc, dtype=np.uint32).view(np.int32)).cuda()
+    out = torch.empty((batch, btk.n_lwe + 1), dtype=torch.int64, device="cuda")
+    f = binding.tfhe_gate_mux_dev if mux else binding.tfhe_gate_bootstrap_dev
+    f(btk.n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), btk.ks_log_beta, btk.ks_l, btk.ksk.data_ptr(), dp.data_ptr(), pool.shape[0],
+      dd.data_ptr(), out.data_ptr(), batch)
+    return _from_dev(out)
+
+
+def gate_bootstrap(btk, ops, a, b):
+    """op(a, b) row by row: `ops` a gate name or code (GATES), or one per row (a mixed batch runs as one call); a, b TLWE
+    batches of the same shape under the LWE key of btk (a gadget BootstrappingKey)"""
+    x, y = a.words.reshape(-1, btk.n_lwe + 1), b.words.reshape(-1, btk.n_lwe + 1)
+    batch = x.shape[0]
+    if y.shape != x.shape:
+        raise ValueError("gate_bootstrap: a and b must have the same shape")
+    if isinstance(ops, str) or np.ndim(ops) == 0:
+        codes = np.full(batch, _gate_code(ops), dtype=np.uint32)
+    else:
+        codes = np.array([_gate_code(o) for o in np.asarray(ops).reshape(-1)], dtype=np.uint32)
+        if len(codes) != batch:
+            raise ValueError("gate_bootstrap: one op per row")
+    i = np.arange(batch, dtype=np.uint32)
+    out = _gate_call(btk, False, np.concatenate([x, y]), np.stack([codes, i, i + batch], axis=1), batch)
+    return TLWE(out.reshape(a.words.shape))
+
+
+def mux(btk, s, a, b):
+    """s ? a : b row by row (two blind rotations, one key switch); s, a, b TLWE batches of the same shape"""
+    rows = [t.words.reshape(-1, btk.n_lwe + 1) for t in (s, a, b)]
+    batch = rows[0].shape[0]
+    if any(r.shape != rows[0].shape for r in rows):
+        raise ValueError("mux: s, a and b must have the same shape")
+    i = np.arange(batch, dtype=np.uint32)
+    out = _gate_call(btk, True, np.concatenate(rows), np.stack([i, i + batch, i + 2 * batch], axis=1), batch)
+    return TLWE(out.reshape(s.words.shape))
+
+
+class CircuitPlan:
+    """Circuit.plan(): pool slots and levels.  Slots: the inputs, the constants and the NOTs of level 0, then per level
+    L >= 1 its gates, its MUXes and its NOTs.  levels[L - 1] = {"level", "gates": (first slot, count), "gate_desc" [count][3]
+    (op, slot x, slot y), "muxes": (first slot, count), "mux_desc" [count][3] (slot s, slot a, slot b)}; nots[L] = list of
+    (slot, root slot, negate): a NOT chain resolved to the bootstrapped (or input, or constant) wire it ends at."""
+
+    def __init__(self, slot, level, n_slots, inputs, consts, levels, nots, outputs):
+        self.slot, self.level, self.n_slots = slot, level, n_slots
+        self.inputs, self.consts, self.levels, self.nots, self.outputs = inputs, consts, levels, nots, outputs
+
+    @property
+    def depth(self):
+        return len(self.levels)
+
+
+class Circuit:
+    """A netlist of boolean gates on encrypted bits.  Every builder returns a wire (an int) and takes only wires defined
+    before it.  Gates and MUXes are bootstrapped (one level each above their highest input); NOT and constants are not.
+    evaluate() runs `batch` independent copies of the circuit with one gate call and at most one MUX call per level."""
+
+    def __init__(self):
+        self._nodes = []            # (kind, args): "input" (), "const" (bit,), "gate" (op, x, y), "not" (x,), "mux" (s, x, y)
+        self._outputs = []
+
+    def _wires(self, *ws):
+        for w in ws:
+            if not isinstance(w, (int, np.integer)) or not 0 <= int(w) < len(self._nodes):
+                raise ValueError(f"wire {w!r} is used before it is defined ({len(self._nodes)} wires so far)")
+        return tuple(int(w) for w in ws)
+
+    def _add(self, kind, *args):
+        self._nodes.append((kind, args))
+        return len(self._nodes) - 1
+
+    def input(self):
+        return self._add("input")
+
+    def const(self, bit):
+        return self._add("const", int(bool(bit)))
+
+    def gate(self, op, x, y):
+        code = _gate_code(op)
+        if not 0 <= code < binding.FHE_GATE_COUNT:
+            raise ValueError(f"gate code {code} out of range")
+        return self._add("gate", code, *self._wires(x, y))
+
+    def not_(self, x):
+        return self._add("not", *self._wires(x))
+
+    def mux(self, s, x, y):
+        return self._add("mux", *self._wires(s, x, y))
+
+    def output(self, x):
+        self._outputs.append(self._wires(x)[0])
+        return x
+
+    @property
+    def n_inputs(self):
+        return sum(k == "input" for k, _ in self._nodes)
+
+    def plan(self):
+        """levels and pool slots (host only)"""
+        level = []
+        for w, (kind, args) in enumerate(self._nodes):
+            ins = args[1:] if kind == "gate" else args if kind in ("not", "mux") else ()
+            if any(not 0 <= x < w for x in ins):
+                raise ValueError(f"wire {w} reads a wire that is not defined before it")
+            if kind in ("input", "const"):
+                level.append(0)
+            elif kind == "not":
+                level.append(level[args[0]])
+            else:
+                level.append(1 + max(level[x] for x in ins))
+        depth = max(level, default=0)
+        root = []                                       # (root wire, negate) of every wire
+        for w, (kind, args) in enumerate(self._nodes):
+            root.append((root[args[0]][0], not root[args[0]][1]) if kind == "not" else (w, False))
+        slot = [None] * len(self._nodes)
+        nxt = 0
+
+        def place(kinds, lev):
+            nonlocal nxt
+            first = nxt
+            for w, (kind, _) in enumerate(self._nodes):
+                if kind in kinds and level[w] == lev:
+                    slot[w] = nxt
+                    nxt += 1
+            return first, nxt - first
+
+        place(("input",), 0)
+        place(("const",), 0)
+        nots = {}
+        place(("not",), 0)
+        levels = []
+        for lev in range(1, depth + 1):
+            g, m = place(("gate",), lev), place(("mux",), lev)
+            place(("not",), lev)
+            levels.append({"level": lev, "gates": g, "muxes": m,
+                           "gate_desc": np.array([(a[0], slot[a[1]], slot[a[2]]) for w, (k, a) in enumerate(self._nodes)
+                                                  if k == "gate" and level[w] == lev], dtype=np.uint32).reshape(-1, 3),
+                           "mux_desc": np.array([tuple(slot[x] for x in a) for w, (k, a) in enumerate(self._nodes)
+                                                 if k == "mux" and level[w] == lev], dtype=np.uint32).reshape(-1, 3)})
+        for lev in range(depth + 1):
+            nots[lev] = [(slot[w], slot[root[w][0]], root[w][1]) for w, (k, _) in enumerate(self._nodes) if k == "not" and level[w] == lev]
+        inputs = [slot[w] for w, (k, _) in enumerate(self._nodes) if k == "input"]
+        consts = [(slot[w], a[0]) for w, (k, a) in enumerate(self._nodes) if k == "const"]
+        return CircuitPlan(slot, level, nxt, inputs, consts, levels, nots, [slot[w] for w in self._outputs])
+
+    def evaluate(self, btk, inputs):
+        """inputs: one TLWE batch [batch][n_lwe + 1] per input wire, in definition order -> one TLWE batch per output.
+        The pool is wire-major: slot w holds rows [w S, w S + batch), S = batch rounded up to even so that every slice
+        starts 16-byte aligned; each level's gate outputs, then its MUX outputs, are one slice of the pool."""
+        torch = _torch()
+        _gate_key(btk)
+        p = self.plan()
+        row = btk.n_lwe + 1
+        xs = [np.asarray(t.words if isinstance(t, TLWE) else t, dtype=np.uint64).reshape(-1, row) for t in inputs]
+        if len(xs) != len(p.inputs):
+            raise ValueError(f"evaluate: {len(p.inputs)} inputs expected, {len(xs)} given")
+        batch = xs[0].shape[0] if xs else 1
+        if any(x.shape[0] != batch for x in xs):
+            raise ValueError("evaluate: every input needs the same batch")
+        S = batch + (batch & 1)
+        if p.n_slots * S >= 1 << 32:
+            raise ValueError("evaluate: the pool needs more than 2^32 rows")
+        fixed = len(p.inputs) + len(p.consts)           # the inputs and constants fill slots [0, fixed)
+        host = np.zeros((fixed, S, row), dtype=np.uint64)
+        for s, x in zip(p.inputs, xs):
+            host[s, :batch] = x
+        for s, bit in p.consts:
+            host[s, :batch] = trivial_bit(np.full(batch, bit), btk.n_lwe).words
+        inst, pad = np.arange(S, dtype=np.uint64), np.arange(S) >= batch
+
+        def expand(desc, mux_):
+            """[count][3] slot descriptors -> [count S][3] row descriptors (padding rows read nothing), in blocks of 4 rows
+            so that every block starts 16-byte aligned"""
+            out = np.empty((len(desc), S, 3), dtype=np.uint64)
+            for c in range(3):
+                v = desc[:, c:c + 1].astype(np.uint64)
+                out[:, :, c] = v * np.uint64(S) + inst[None, :] if mux_ or c else v
+            out[:, pad, :] = 0xFFFFFFFF
+            out = out.reshape(-1, 3)
+            return np.concatenate([out, np.zeros((-len(out) % 4, 3), dtype=np.uint64)])
+
+        descs, offs = [], []                            # every level's descriptors, uploaded once
+        for lv in p.levels:
+            g, m = expand(lv["gate_desc"], False), expand(lv["mux_desc"], True)
+            offs.append((sum(len(d) for d in descs), sum(len(d) for d in descs) + len(g)))
+            descs += [g, m]
+        pool = torch.empty((p.n_slots * S, row), dtype=torch.int64, device="cuda")
+        pool[: fixed * S] = _to_dev(host.reshape(-1, row))
+        dd = torch.from_numpy(np.concatenate(descs or [np.zeros((0, 3))]).astype(np.uint32).view(np.int32)).cuda()
+        nots = []                                       # per level: destination rows, source rows, negate, uploaded once
+        for lev in range(p.depth + 1):
+            n = np.array(p.nots[lev], dtype=np.int64).reshape(-1, 3)
+            rows_of = lambda col: torch.from_numpy((n[:, col:col + 1] * S + np.arange(batch)[None, :]).reshape(-1)).cuda()
+            nots.append((rows_of(0), rows_of(1), torch.from_numpy(np.repeat(n[:, 2] != 0, batch)[:, None]).cuda()) if len(n) else None)
+        st = torch.cuda.current_stream().cuda_stream
+
+        def run_nots(lev):
+            if nots[lev] is not None:
+                dst, src, neg = nots[lev]
+                v = pool[src]
+                pool[dst] = torch.where(neg, -v, v)     # int64 negation wraps: -c mod 2^64
+
+        run_nots(0)
+        for lv, off in zip(p.levels, offs):
+            for (first, count), mux_, o in ((lv["gates"], False, off[0]), (lv["muxes"], True, off[1])):
+                if count:
+                    f = binding.tfhe_gate_mux_dev if mux_ else binding.tfhe_gate_bootstrap_dev
+                    f(btk.n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), btk.ks_log_beta, btk.ks_l, btk.ksk.data_ptr(),
+                      pool.data_ptr(), p.n_slots * S, dd.data_ptr() + o * 12, pool.data_ptr() + first * S * row * 8, count * S, st)
+            run_nots(lv["level"])
+        if not p.outputs:
+            return []
+        outs = _from_dev(torch.stack([pool[s * S:s * S + batch] for s in p.outputs]))
+        return [TLWE(o) for o in outs]

@@ -387,6 +387,37 @@ int fhe_tfhe_circuit_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, un
                                    unsigned pf_l, const void *d_pfksk, const void *d_lwe, void *d_out, size_t batch,
                                    void *hip_stream);
 
+/* ---- TFHE boolean gates with gate bootstrapping (definitions in DESIGN.md §13) ----
+ * The gadget shapes of fhe_tfhe_gadget_bootstrap_dev: BSK (log_beta, l) admitted by fhe_tggsw_gadget_prepared_words,
+ * KSK (ks_log_beta, ks_l) as fhe_tlwe_gadget_key_switch_dev.  A bit is a TLWE of dimension n_lwe with phase +mu (1) or
+ * -mu (0), mu = 2^61; outputs are again bits under the same LWE key.  d_pool [wires][n_lwe + 1] holds the inputs.
+ *   fhe_tfhe_gate_bootstrap_dev  d_gates [batch][3] u32 (op, a, b), ops FHE_GATE_* mixed freely -> d_out [batch][n_lwe + 1]:
+ *                                bootstrap (0 .. 0, o) + alpha c_a + beta c_b (wrapping u64) with the test vector
+ *                                (mask 0, body mu), extract at 0, key switch
+ *   fhe_tfhe_gate_mux_dev        d_sel [batch][3] u32 (s, a, b) -> d_out [batch][n_lwe + 1] = s ? a : b: blind rotations of
+ *                                AND(s, a) and ANDNY(s, b), both extracted at 0, added, + mu on the body, one key switch
+ * A row whose op is >= FHE_GATE_COUNT, or whose indices are not all < wires, combines as all-zero inputs with o = 0 (and
+ * reads no pool word); for a MUX the rule holds per blind rotation: AND(s, a) and ANDNY(s, b).  d_out may lie inside the
+ * pool but must not overlap a row that the descriptors read. */
+#define FHE_GATE_AND 0   /* (alpha, beta, o) = ( 1,  1, -mu) */
+#define FHE_GATE_NAND 1  /*                   (-1, -1, +mu) */
+#define FHE_GATE_OR 2    /*                   ( 1,  1, +mu) */
+#define FHE_GATE_NOR 3   /*                   (-1, -1, -mu) */
+#define FHE_GATE_XOR 4   /*                   ( 2,  2, +2mu) */
+#define FHE_GATE_XNOR 5  /*                   (-2, -2, -2mu) */
+#define FHE_GATE_ANDNY 6 /* !a & b            (-1,  1, -mu) */
+#define FHE_GATE_ANDYN 7 /* a & !b            ( 1, -1, -mu) */
+#define FHE_GATE_ORNY 8  /* !a | b            (-1,  1, +mu) */
+#define FHE_GATE_ORYN 9  /* a | !b            ( 1, -1, +mu) */
+#define FHE_GATE_COUNT 10
+int fhe_tfhe_gate_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe,
+                                const void *d_bsk_prepared, unsigned ks_log_beta, unsigned ks_l, const void *d_ksk,
+                                const void *d_pool, size_t wires, const void *d_gates, void *d_out, size_t batch,
+                                void *hip_stream);
+int fhe_tfhe_gate_mux_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe,
+                          const void *d_bsk_prepared, unsigned ks_log_beta, unsigned ks_l, const void *d_ksk,
+                          const void *d_pool, size_t wires, const void *d_sel, void *d_out, size_t batch, void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.

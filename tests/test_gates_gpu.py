@@ -1,0 +1,228 @@
+"""Boolean gates on the device: fhe_tfhe_gate_bootstrap_dev word for word against the numpy combination
+(tests/_gates_numpy.py) followed by fhe_tfhe_gadget_bootstrap_dev with the mu test vector, fhe_tfhe_gate_mux_dev against
+two gadget blind rotations, extraction, the numpy sum and the gadget key switch; then gates, MUXes, a second level and
+two circuits (a 4-bit adder and a 4-bit maximum over all 256 input pairs) with real keys."""
+import numpy as np
+import pytest
+
+import _gadget_numpy as G
+import _gates_numpy as GN
+import _tfhe_numpy as R
+from test_bootstrap_gpu import _dev, _edge_lwe, _rand_dev, _u64
+
+pytestmark = pytest.mark.gpu
+
+
+def _prepare_bsk(pkg, n, b, l, n_lwe, seed):
+    import torch
+
+    L, B = pkg.load_library(), pkg.binding
+    bsk = _rand_dev((n_lwe, 2, l, 2, n), seed)
+    prep = torch.empty(L.fhe_tfhe_gadget_bsk_prepared_words(n, 1, b, l, n_lwe), dtype=torch.int64, device="cuda")
+    B._check(L.fhe_tfhe_gadget_bsk_prepare_dev(n, 1, b, l, n_lwe, bsk.data_ptr(), prep.data_ptr(), None))
+    return prep
+
+
+def _desc_dev(desc):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(desc, dtype=np.uint32).view(np.int32)).cuda()
+
+
+def _gates_dev(pkg, mux, n, b, l, n_lwe, prep, ks_b, ks_l, ksk, pool, desc):
+    import torch
+
+    L, B = pkg.load_library(), pkg.binding
+    f = L.fhe_tfhe_gate_mux_dev if mux else L.fhe_tfhe_gate_bootstrap_dev
+    out = torch.empty((len(desc), n_lwe + 1), dtype=torch.int64, device="cuda")
+    dp, dd = _dev(pool), _desc_dev(desc)
+    B._check(f(n, 1, b, l, n_lwe, prep.data_ptr(), ks_b, ks_l, ksk.data_ptr(), dp.data_ptr(), pool.shape[0], dd.data_ptr(), out.data_ptr(),
+               len(desc), None))
+    return _u64(out)
+
+
+def _gadget_bootstrap_dev(pkg, n, b, l, n_lwe, prep, ks_b, ks_l, ksk, lwe):
+    import torch
+
+    L, B = pkg.load_library(), pkg.binding
+    out = torch.empty((lwe.shape[0], n_lwe + 1), dtype=torch.int64, device="cuda")
+    dt, dl = _dev(GN.test_vector(n)), _dev(lwe)
+    B._check(L.fhe_tfhe_gadget_bootstrap_dev(n, 1, b, l, n_lwe, prep.data_ptr(), dt.data_ptr(), ks_b, ks_l, ksk.data_ptr(), dl.data_ptr(),
+                                             out.data_ptr(), lwe.shape[0], None))
+    return _u64(out)
+
+
+def _random_desc(rng, batch, wires):
+    """ops over every code plus two invalid ones, indices mostly in range; the first rows pin the invalid cases"""
+    desc = np.stack([rng.integers(0, GN.COUNT + 2, batch), rng.integers(0, wires, batch), rng.integers(0, wires, batch)], axis=1)
+    desc[rng.random(batch) < 0.05, 1] = wires + rng.integers(0, 3)
+    edge = [(GN.COUNT, 0, 1), (0xFFFFFFFF, 1, 2), (0, wires, 0), (4, 0, 0xFFFFFFFF), (9, wires - 1, wires - 1)]
+    desc[: min(batch, len(edge))] = edge[: min(batch, len(edge))]
+    return desc.astype(np.uint32)
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("n,n_lwe,b,l,batch", [(256, 8, 8, 3, 70), (1024, 630, 10, 3, 37), (1024, 16, 8, 3, 1024), (1024, 16, 8, 3, 1025)])
+def test_gate_bootstrap_word_exact(pkg, n, n_lwe, b, l, batch):
+    """a mixed batch (every op, invalid ops, out-of-range indices) = the numpy combination, then the gadget bootstrap with
+    the mu test vector.  BSK (8, 3) at N = 1024 has T = 6: ext32_gadget_split runs two parts up to batch 1024, one above."""
+    ks_b, ks_l = 4, 4
+    rng = np.random.default_rng(n + n_lwe + batch)
+    prep = _prepare_bsk(pkg, n, b, l, n_lwe, 11 + batch)
+    ksk = _rand_dev((n, ks_l, n_lwe + 1), 12 + batch)
+    wires = 23
+    pool = _edge_lwe(rng, wires, n_lwe, n)
+    desc = _random_desc(rng, batch, wires)
+    got = _gates_dev(pkg, False, n, b, l, n_lwe, prep, ks_b, ks_l, ksk, pool, desc)
+    want = _gadget_bootstrap_dev(pkg, n, b, l, n_lwe, prep, ks_b, ks_l, ksk, GN.combine(pool, desc))
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.timeout(600)
+def test_gate_output_inside_the_pool(pkg):
+    """the evaluator's layout: d_out is a slice of the pool after the rows the descriptors read"""
+    import torch
+
+    L, B = pkg.load_library(), pkg.binding
+    n, n_lwe, b, l, ks_b, ks_l, wires, batch = 256, 8, 8, 3, 4, 4, 10, 20      # 10 rows of 9 words: d_out 16-byte aligned
+    rng = np.random.default_rng(5)
+    prep = _prepare_bsk(pkg, n, b, l, n_lwe, 5)
+    ksk = _rand_dev((n, ks_l, n_lwe + 1), 6)
+    pool = _edge_lwe(rng, wires, n_lwe, n)
+    desc = _random_desc(rng, batch, wires)
+    dp = torch.zeros((wires + batch, n_lwe + 1), dtype=torch.int64, device="cuda")
+    dp[:wires] = _dev(pool)
+    dd = _desc_dev(desc)
+    B._check(L.fhe_tfhe_gate_bootstrap_dev(n, 1, b, l, n_lwe, prep.data_ptr(), ks_b, ks_l, ksk.data_ptr(), dp.data_ptr(), wires, dd.data_ptr(),
+                                           dp[wires:].data_ptr(), batch, None))
+    got = _u64(dp)
+    assert np.array_equal(got[:wires], pool)
+    assert np.array_equal(got[wires:], _gates_dev(pkg, False, n, b, l, n_lwe, prep, ks_b, ks_l, ksk, pool, desc))
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("n,n_lwe,b,l,batch", [(256, 8, 8, 3, 33), (1024, 16, 8, 3, 512), (1024, 16, 8, 3, 513)])
+def test_mux_word_exact(pkg, n, n_lwe, b, l, batch):
+    """= two rows per MUX through fhe_tfhe_gadget_blind_rotation_dev, fhe_tglwe_sample_extraction_dev, the numpy sum + mu,
+    fhe_tlwe_gadget_key_switch_dev.  512 / 513 MUXes are 1024 / 1026 blind-rotation rows: either side of the split."""
+    import torch
+
+    L, B = pkg.load_library(), pkg.binding
+    ks_b, ks_l, wires = 4, 4, 17
+    rng = np.random.default_rng(n + batch)
+    prep = _prepare_bsk(pkg, n, b, l, n_lwe, 31 + batch)
+    ksk = _rand_dev((n, ks_l, n_lwe + 1), 32 + batch)
+    pool = _edge_lwe(rng, wires, n_lwe, n)
+    sel = rng.integers(0, wires, (batch, 3)).astype(np.uint32)
+    sel[0], sel[1], sel[2] = (wires, 0, 1), (0, wires + 5, 2), (3, 4, 0xFFFFFFFF)
+    got = _gates_dev(pkg, True, n, b, l, n_lwe, prep, ks_b, ks_l, ksk, pool, sel)
+    rows = GN.mux_rows(pool, sel)
+    acc = torch.empty((2 * batch, 2, n), dtype=torch.int64, device="cuda")
+    ext = torch.empty((2 * batch, n + 1), dtype=torch.int64, device="cuda")
+    dt, dr = _dev(GN.test_vector(n)), _dev(rows)
+    B._check(L.fhe_tfhe_gadget_blind_rotation_dev(n, 1, b, l, n_lwe, prep.data_ptr(), dt.data_ptr(), dr.data_ptr(), acc.data_ptr(), 2 * batch, None))
+    B._check(L.fhe_tglwe_sample_extraction_dev(n, 1, 0, acc.data_ptr(), ext.data_ptr(), 2 * batch, None))
+    summed = _dev(GN.mux_finish(_u64(ext)))
+    want = torch.empty((batch, n_lwe + 1), dtype=torch.int64, device="cuda")
+    B._check(L.fhe_tlwe_gadget_key_switch_dev(n, n_lwe, ks_b, ks_l, ksk.data_ptr(), summed.data_ptr(), want.data_ptr(), batch, None))
+    assert np.array_equal(got, _u64(want))
+
+
+# ---- real keys: DESIGN.md §12's parameters ----------------------------------------------------------------------------
+N, NL, BSK, KSK, SIGMA = 1024, 630, (10, 3), (4, 4), 3.2
+
+
+@pytest.fixture(scope="module")
+def keys(pkg):
+    from fhe_study_amd import tfhe
+
+    B = pkg.binding
+    rng = np.random.default_rng(1313)
+    s_glwe = rng.integers(0, 2, N, dtype=np.uint64)
+    s_lwe = rng.integers(0, 2, NL, dtype=np.uint64)
+    mul = lambda a, x: B.tn_mul(N, a, np.ascontiguousarray(x))
+    bsk = G.tggsw_bits(rng, mul, N, BSK[0], BSK[1], s_glwe, s_lwe, SIGMA)
+    ksk = G.ksk(rng, s_glwe, s_lwe, KSK[0], KSK[1], SIGMA)
+    btk = tfhe.BootstrappingKey(N, 1, BSK[1], NL, bsk, ksk, ks_l=KSK[1], log_beta=BSK[0], ks_log_beta=KSK[0])
+    return btk, s_lwe, rng
+
+
+def _encrypt(rng, s, bits):
+    from fhe_study_amd import tfhe
+
+    return tfhe.TLWE(R.lwe_encrypt(rng, s, [GN.bit_phase(v) for v in np.asarray(bits).reshape(-1)], SIGMA))
+
+
+def _worst(e):
+    return float(np.log2(float(max(abs(x) for x in e))))
+
+
+@pytest.mark.timeout(1200)
+def test_functional_gates_mux_and_a_second_level(pkg, keys):
+    from fhe_study_amd import tfhe
+
+    btk, s, rng = keys
+    reps = 3
+    ops = np.repeat(np.arange(GN.COUNT), 4 * reps)
+    a = np.tile(np.repeat([0, 0, 1, 1], reps), GN.COUNT)
+    b = np.tile(np.repeat([0, 1, 0, 1], reps), GN.COUNT)
+    out = tfhe.gate_bootstrap(btk, ops, _encrypt(rng, s, a), _encrypt(rng, s, b))       # one mixed call, 120 rows
+    want = np.array([GN.TRUTH[GN.NAMES[o]](x, y) for o, x, y in zip(ops, a, b)])
+    assert list(GN.decode(out.words, s)) == list(want)
+    e_gate = GN.phase_error(out.words, s, want)
+    # all eight MUX inputs
+    sel = np.array([(x >> 2) & 1 for x in range(8)] * reps)
+    ma, mb = np.array([(x >> 1) & 1 for x in range(8)] * reps), np.array([x & 1 for x in range(8)] * reps)
+    m = tfhe.mux(btk, _encrypt(rng, s, sel), _encrypt(rng, s, ma), _encrypt(rng, s, mb))
+    mwant = np.where(sel == 1, ma, mb)
+    assert list(GN.decode(m.words, s)) == list(mwant)
+    e_mux = GN.phase_error(m.words, s, mwant)
+    # gate outputs as the inputs of a second level (gates and a MUX), and a NOT in between
+    perm = rng.permutation(len(ops))
+    ops2 = rng.integers(0, GN.COUNT, len(ops))
+    x2 = tfhe.TLWE(out.words[perm])
+    y2 = tfhe.gate_not(out)
+    out2 = tfhe.gate_bootstrap(btk, ops2, x2, y2)
+    want2 = np.array([GN.TRUTH[GN.NAMES[o]](p, 1 - q) for o, p, q in zip(ops2, want[perm], want)])
+    assert list(GN.decode(out2.words, s)) == list(want2)
+    m2 = tfhe.mux(btk, tfhe.TLWE(out.words[:24]), tfhe.TLWE(out2.words[:24]), tfhe.TLWE(out.words[perm[:24]]))
+    mwant2 = np.where(want[:24] == 1, want2[:24], want[perm[:24]])
+    assert list(GN.decode(m2.words, s)) == list(mwant2)
+    e2 = list(GN.phase_error(out2.words, s, want2)) + list(GN.phase_error(m2.words, s, mwant2))
+    print(f"\nworst |error| log2: gates {_worst(e_gate):.1f}, MUX {_worst(e_mux):.1f}, second level {_worst(e2):.1f} "
+          f"(estimate: 2^55 per output; margin: 2^61 for AND/OR-type gates, 2^62 for XOR-type after doubling)")
+    assert max(abs(x) for x in list(e_gate) + list(e_mux) + e2) < 1 << 60
+
+
+def _pairs_inputs(rng, s, bits):
+    xs, ys = np.repeat(np.arange(1 << bits), 1 << bits), np.tile(np.arange(1 << bits), 1 << bits)
+    ins = [_encrypt(rng, s, (xs >> i) & 1) for i in range(bits)] + [_encrypt(rng, s, (ys >> i) & 1) for i in range(bits)]
+    return xs, ys, ins
+
+
+def _value(pkg_outs, s):
+    return sum(GN.decode(o.words, s) << i for i, o in enumerate(pkg_outs))
+
+
+@pytest.mark.timeout(1200)
+def test_circuits_adder_and_maximum_over_all_pairs(pkg, keys):
+    from fhe_study_amd import tfhe
+
+    btk, s, rng = keys
+    xs, ys, ins = _pairs_inputs(rng, s, 4)
+    add = GN.ripple_adder(tfhe.Circuit(), 4)
+    outs = add.evaluate(btk, ins)
+    assert len(outs) == 5 and outs[0].words.shape == (256, NL + 1)
+    assert np.array_equal(_value(outs, s), xs + ys)
+    mx = GN.maximum(tfhe.Circuit(), 4)
+    outs = mx.evaluate(btk, ins)
+    assert np.array_equal(_value(outs, s), np.maximum(xs, ys))
+    # constants and a NOT of an input feed gates directly
+    c = tfhe.Circuit()
+    x = c.input()
+    c.output(c.gate("AND", c.not_(x), c.const(1)))
+    c.output(c.gate("XOR", x, c.const(0)))
+    c.output(c.not_(x))
+    bits = np.arange(8) & 1
+    o = c.evaluate(btk, [_encrypt(rng, s, bits)])
+    assert [list(GN.decode(t.words, s)) for t in o] == [list(1 - bits), list(bits), list(1 - bits)]
