@@ -63,6 +63,20 @@ def external_product(key, ct, b):
     return out
 
 
+def external_product_rows(mul, key, ct, b):
+    """the same product from digit rows against key rows: mul(x [r][n], y [r][n]) -> the r negacyclic products mod 2^64
+    (the C oracle's schoolbook tn_mul), a digit entering as int64.view(uint64).  One product per (ciphertext, i, d, c);
+    nothing here calls the library under test."""
+    key, ct = R.u64(key), R.u64(ct)
+    k1, l, _, n = key.shape
+    batch = ct.shape[0]
+    dig = np.moveaxis(decompose(ct, b, l), -1, -2).view(np.uint64)      # [batch][k1][l][n]
+    x = np.broadcast_to(dig[:, :, :, None, :], (batch, k1, l, k1, n)).reshape(-1, n)
+    y = np.broadcast_to(key[None], (batch, k1, l, k1, n)).reshape(-1, n)
+    prod = R.u64(mul(np.ascontiguousarray(x), np.ascontiguousarray(y))).reshape(batch, k1 * l, k1, n)
+    return prod.sum(axis=1, dtype=np.uint64)                            # wraps mod 2^64
+
+
 def blind_rotation(n, k, b, l, bsk, table, lwe):
     bsk = R.u64(bsk)
     return R.blind_rotation(lambda j, d: external_product(bsk[j], d, b), n, k, l, bsk, table, lwe)

@@ -117,3 +117,22 @@ def maximum(c, bits):
     for i in range(bits):
         c.output(c.mux(ge, x[i], y[i]))
     return c
+
+
+def odd_netlist(c):
+    """three inputs; fan-out, a gate reading one wire twice, a NOT of a NOT, a NOT of a constant, MUXes whose inputs come
+    from different levels, a level with MUXes and no gates, an output that is an input and one wire output twice"""
+    x, y, z = c.input(), c.input(), c.input()
+    one = c.const(1)
+    n_one = c.not_(one)                               # level 0: NOT of a constant
+    g1 = c.gate("AND", x, y)                          # level 1, read four times below
+    g2 = c.gate("XOR", x, x)                          # level 1: the same wire twice
+    g3 = c.gate("OR", g1, n_one)                      # level 2
+    g4 = c.gate("NAND", g1, z)                        # level 2
+    nn = c.not_(c.not_(g4))                           # level 2: resolves to g4
+    m1 = c.mux(g3, x, g2)                             # level 3: inputs of levels 2, 0 and 1
+    m2 = c.mux(nn, g1, one)                           # level 3 has MUXes and no gate
+    g5 = c.gate("ORNY", m1, m2)                       # level 4
+    for w in (g5, x, g5, n_one, nn, m2):
+        c.output(w)
+    return c

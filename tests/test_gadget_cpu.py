@@ -61,6 +61,29 @@ def test_gadget_product_restatement_is_the_message_times_the_rounded_word():
     assert np.array_equal(G.negacyclic(key[0, 0, 0], x), O.tn_mul(n, x, np.broadcast_to(key[0, 0, 0], (3, n)).copy()))
 
 
+@pytest.mark.parametrize("n", [256, 512])
+def test_row_product_restatement_equals_the_toeplitz_one(oracle, n):
+    """G.external_product_rows (digit rows against key rows through the oracle's schoolbook tn_mul) word for word against
+    G.external_product (the u64 Toeplitz matmul), at every (b, l) of SHAPES that the rule admits, with the edge words in
+    the first row, a row whose digits are all -2^(b-1), and a key with a band of 2^64 - 1"""
+    mul = lambda x, y: oracle.tn_mul(n, x, y)
+    ran = []
+    for b, l in SHAPES:
+        if not admitted(n, 1, b, l):
+            continue
+        ran.append((b, l))
+        rng = np.random.default_rng(n + 100 * b + l)
+        key = rng.integers(0, 1 << 64, (2, l, 2, n), dtype=np.uint64, endpoint=False)
+        key[1, l - 1, :, : n // 4] = np.uint64((1 << 64) - 1)
+        ct = rng.integers(0, 1 << 64, (3, 2, n), dtype=np.uint64, endpoint=False)
+        edges = _edge_words(b, l)
+        ct[0, 0, : len(edges)] = edges
+        ct[0, 1, n - len(edges):] = edges
+        ct[1] = np.uint64(edges[5])
+        assert np.array_equal(G.external_product_rows(mul, key, ct, b), G.external_product(key, ct, b)), (b, l)
+    assert {(1, 64), (2, 32), (4, 16), (8, 8), (8, 3), (10, 2), (7, 9), (3, 5)} <= set(ran)      # (13, 4) and wider are refused
+
+
 @pytest.mark.parametrize("b,l,ks_b,ks_l", [(8, 3, 4, 4), (10, 2, 2, 10)])
 def test_noise_free_cpu_gadget_bootstrap(oracle, b, l, ks_b, ks_l):
     """N = 256, k = 1, n_lwe = 8, t = 16 with a bit of padding: every m in [0, 8) bootstraps to f(m)"""

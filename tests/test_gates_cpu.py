@@ -145,6 +145,35 @@ def test_plan_of_the_adder_and_the_maximum():
     assert sum(len(v) for v in q.nots.values()) == 4
 
 
+def test_plan_of_the_odd_netlist_keeps_the_pool_invariants():
+    """GN.odd_netlist (what test_gates_gpu evaluates at odd batches): slots disjoint, every level's outputs one slice
+    right after the slots before it, every descriptor and every NOT reading a slot below the level's first output"""
+    from fhe_study_amd import tfhe
+
+    c = GN.odd_netlist(tfhe.Circuit())
+    p = c.plan()
+    assert sorted(p.slot) == list(range(p.n_slots)) and p.n_slots == len(c._nodes) == 14
+    assert p.depth == 4 and p.inputs == [0, 1, 2] and p.consts == [(3, 1)]
+    assert p.nots[0] == [(4, 3, True)]                                  # the NOT of the constant
+    assert [(L["gates"][1], L["muxes"][1]) for L in p.levels] == [(2, 0), (2, 0), (0, 2), (1, 0)]
+    nxt = 5
+    for L in p.levels:
+        (g0, gn), (m0, mn) = L["gates"], L["muxes"]
+        assert g0 == nxt and m0 == g0 + gn
+        for desc in (L["gate_desc"][:, 1:], L["mux_desc"]):
+            assert desc.size == 0 or int(desc.max()) < g0
+        nxt = m0 + mn
+        for dst, root, neg in p.nots[L["level"]]:
+            assert dst == nxt and root < m0 + mn
+            nxt += 1
+    assert nxt == p.n_slots
+    g1 = p.slot[5]
+    assert sum(int((L["gate_desc"][:, 1:] == g1).sum() + (L["mux_desc"] == g1).sum()) for L in p.levels) == 3      # fan-out
+    assert tuple(p.levels[0]["gate_desc"][1]) == (GN.NAMES.index("XOR"), 0, 0)                                   # one wire twice
+    assert [r[1:] for r in p.nots[2]] == [(p.slot[8], True), (p.slot[8], False)]                                  # NOT of a NOT
+    assert p.outputs[1] == 0 and p.outputs[0] == p.outputs[2] and len(p.outputs) == 6
+
+
 def test_wires_used_before_they_are_defined_are_refused():
     from fhe_study_amd import tfhe
 

@@ -128,6 +128,42 @@ def test_mux_word_exact(pkg, n, n_lwe, b, l, batch):
     assert np.array_equal(got, _u64(want))
 
 
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("batch", [1, 3, 7])
+def test_circuit_at_odd_batches_equals_the_host_evaluation(pkg, batch):
+    """Circuit.evaluate pads an odd batch to batch + 1 rows per wire (descriptors 0xFFFFFFFF in the padding, blocks of four
+    descriptor rows): GN.odd_netlist with toy keys (random words: exactness needs no real keys) gives, word for word, the
+    node-by-node evaluation through tfhe.gate_bootstrap, tfhe.mux, tfhe.gate_not and tfhe.trivial_bit"""
+    from fhe_study_amd import tfhe
+
+    n, n_lwe, b, l, ks_b, ks_l = 256, 8, 8, 3, 4, 4
+    rng = np.random.default_rng(500 + batch)
+    bsk = rng.integers(0, 1 << 64, (n_lwe, 2, l, 2, n), dtype=np.uint64, endpoint=False)
+    ksk = rng.integers(0, 1 << 64, (n, ks_l, n_lwe + 1), dtype=np.uint64, endpoint=False)
+    btk = tfhe.BootstrappingKey(n, 1, l, n_lwe, bsk, ksk, ks_l=ks_l, log_beta=b, ks_log_beta=ks_b)
+    c = GN.odd_netlist(tfhe.Circuit())
+    ins = [tfhe.TLWE(_edge_lwe(rng, max(batch, 2), n_lwe, n)[:batch]) for _ in range(c.n_inputs)]
+    got = c.evaluate(btk, ins)
+    vals, it = [], iter(ins)
+    for kind, args in c._nodes:
+        if kind == "input":
+            vals.append(next(it))
+        elif kind == "const":
+            vals.append(tfhe.trivial_bit(np.full(batch, args[0]), n_lwe))
+        elif kind == "not":
+            vals.append(tfhe.gate_not(vals[args[0]]))
+        elif kind == "gate":
+            vals.append(tfhe.gate_bootstrap(btk, args[0], vals[args[1]], vals[args[2]]))
+        else:
+            vals.append(tfhe.mux(btk, *(vals[a] for a in args)))
+    assert len(got) == len(c._outputs) == 6
+    for o, w in zip(got, c._outputs):
+        assert o.words.shape == (batch, n_lwe + 1)
+        assert np.array_equal(o.words, vals[w].words), w
+    assert np.array_equal(got[1].words, ins[0].words) and np.array_equal(got[0].words, got[2].words)
+    assert got[0].words.any() and not np.array_equal(got[0].words, got[5].words)
+
+
 # ---- real keys: DESIGN.md §12's parameters ----------------------------------------------------------------------------
 N, NL, BSK, KSK, SIGMA = 1024, 630, (10, 3), (4, 4), 3.2
 
