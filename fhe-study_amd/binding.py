@@ -73,11 +73,14 @@ EXPORTS = [
     "fhe_tggsw_gadget_cmux_dev", "fhe_tfhe_circuit_bootstrap_dev",
     # boolean gates with gate bootstrapping (tfhe_boot.hip)
     "fhe_tfhe_gate_bootstrap_dev", "fhe_tfhe_gate_mux_dev",
+    # small integers: a lookup table per row (tfhe_boot.hip)
+    "fhe_tlwe_lincomb_dev", "fhe_tfhe_lut_bootstrap_dev",
 ]
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
 GATES = {"AND": 0, "NAND": 1, "OR": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
 FHE_GATE_COUNT = 10
+FHE_LUT_NONE = 0xFFFFFFFF                    # include/fhe_ntt.h: the index of an operand whose scale is 0, by convention
 
 
 # include/fhe_ntt_experimental.h: the persistent kernels' switches (exported, NOT part of the boundary)
@@ -251,6 +254,8 @@ def load_library():
     L.fhe_tfhe_circuit_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
     L.fhe_tfhe_gate_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _vp, _vp, _sz, _vp, _vp, _sz, _vp]
     L.fhe_tfhe_gate_mux_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _vp, _vp, _sz, _vp, _vp, _sz, _vp]
+    L.fhe_tlwe_lincomb_dev.argtypes = [_uint, _vp, _sz, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_lut_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _vp, _uint, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -584,6 +589,17 @@ def tfhe_gate_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_bet
 def tfhe_gate_mux_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, d_pool, wires, d_sel, d_out, batch, stream=None):
     _check(load_library().fhe_tfhe_gate_mux_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, d_pool, wires, d_sel,
                                                 d_out, batch, stream))
+
+
+# ---- small integers: a lookup table per row ----------------------------------------------------------------
+def tlwe_lincomb_dev(n_lwe, d_pool, wires, d_desc, d_out, batch, stream=None):
+    _check(load_library().fhe_tlwe_lincomb_dev(n_lwe, d_pool, wires, d_desc, d_out, batch, stream))
+
+
+def tfhe_lut_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, t_bits, d_luts, lut_count, d_pool, wires,
+                           d_desc, d_out, batch, stream=None):
+    _check(load_library().fhe_tfhe_lut_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, t_bits, d_luts,
+                                                     lut_count, d_pool, wires, d_desc, d_out, batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

@@ -21,6 +21,14 @@
 //
 // Boolean gates: one blind rotation over a batch of mixed gates, since every gate shares the test vector;
 // an init kernel forms each row's combination alpha c_x + beta c_y + o from the pool as it writes ACC_0 and the shifts.
+//
+// Small integers: the test vector is read only by the init kernel, so a batch in which every row names its
+// own lookup table ([P] torus words, P = 2^t) and its own combination sx c_x + sy c_y + o shares one blind rotation too.
+//   t = t_bits, 1 <= t <= L, Delta = 2^(63 - t): a value x in [0, P) is a TLWE of phase x Delta + e, the top bit padding (0)
+//   table T -> v_T = (mask 0, body v), box = N / P, half = box / 2: v[i] = T[m] for m = (i + half) >> (L - t) < P, else -T[0]
+//   a phase within half a box of x Delta gives T[x] at coefficient 0; with the padding bit set it gives -T[x - P] (negacyclic)
+//   descriptor row [6] u32 (lut, x, y, sx, sy, o_hi), sx, sy int32; a scale of 0 reads nothing; a non-zero scale with an
+//   index >= wires, or (bootstrap only) lut >= lut_count, makes the row invalid: nothing read, an all-zero output row
 #include <algorithm>
 
 #include "capi_internal.hpp"
@@ -337,6 +345,66 @@ __global__ __launch_bounds__(256) void tfhe_mux_extract_kernel(const u64 *__rest
         } else {
             const u64 c = r >> L, j = r & (N - 1);
             out[i] = j == 0 ? s0[c * N] + s1[c * N] : 0ull - s0[c * N + N - j] - s1[c * N + N - j];
+        }
+    }
+}
+
+// ---- small integers: a lookup table per row -----------------------------------------------------------
+// descriptor row (lut, x, y, sx, sy, o_hi), sx and sy int32: c = sx pool[x] + sy pool[y] + (0 .. 0, o_hi 2^32).  An operand
+// whose scale is 0 is never read; one with a non-zero scale and an index >= wires makes the row invalid.
+constexpr u32 LUT_DESC = 6;
+__device__ __forceinline__ bool lut_row_valid(const u32 *__restrict__ d, u64 wires) {
+    return (d[3] == 0 || d[1] < wires) && (d[4] == 0 || d[2] < wires);
+}
+// word j (j = n_lwe: the body) of the combined input of a valid row
+__device__ __forceinline__ u64 lut_word(const u64 *__restrict__ pool, const u32 *__restrict__ d, u32 n_lwe, u32 j) {
+    const u64 row = n_lwe + 1ull;
+    u64 w = j == n_lwe ? (u64)d[5] << 32 : 0ull;
+    if (d[3]) w += (u64)(long long)(int)d[3] * pool[d[1] * row + j];
+    if (d[4]) w += (u64)(long long)(int)d[4] * pool[d[2] * row + j];
+    return w;
+}
+
+// out[m] = the combined input of descriptor row m (the lut word is not looked at); an invalid row gives zeros
+__global__ __launch_bounds__(256) void tlwe_lincomb_kernel(const u64 *__restrict__ pool, u64 wires, const u32 *__restrict__ desc,
+                                                           u64 *__restrict__ out, u32 n_lwe, u64 rows) {
+    const u64 row = n_lwe + 1ull, total = rows * row;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 m = i / row;
+        const u32 *d = desc + m * LUT_DESC;
+        out[i] = lut_row_valid(d, wires) ? lut_word(pool, d, n_lwe, (u32)(i - m * row)) : 0ull;
+    }
+}
+
+// tfhe_gate_init_kernel with a table per row: ACC_0[m] = rot(v_T, b~_m), T = luts[desc[m][0]] ([lut_count][P] torus words,
+// P = 2^t), v_T = (mask 0, body v), v[i] = T[q] for q = (i + half) >> (L - t) < P and -T[0] in the top half box (half =
+// N / 2P, 0 at P = N); shift[m][j] = (2N - a~_{m,j}) mod 2N.  v is never formed: coefficient i reads T at the box of
+// (i + b~) mod N.  An invalid row (lut_row_valid, or lut >= lut_count) reads nothing and writes zeros and zero shifts.
+__global__ __launch_bounds__(256) void tfhe_lut_init_kernel(const u64 *__restrict__ pool, u64 wires, const u32 *__restrict__ desc,
+                                                            const u64 *__restrict__ luts, u64 lut_count, u32 t, u64 *__restrict__ acc,
+                                                            u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L, u64 rows) {
+    const u64 N = 1ull << L, k1N = (u64)k1 * N, na = rows * k1N, total = na + rows * n_lwe;
+    const u64 P = 1ull << t, half = (N >> t) >> 1;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 m = i < na ? i / k1N : (i - na) / n_lwe;
+        const u32 *d = desc + m * LUT_DESC;
+        const bool ok = d[0] < lut_count && lut_row_valid(d, wires);
+        if (i < na) {
+            const u64 r = i - m * k1N;
+            if ((r >> L) + 1 < k1 || !ok) {
+                acc[i] = 0;
+            } else {
+                const u64 j = (r & (N - 1)) + mod_switch_2n(lut_word(pool, d, n_lwe, n_lwe), L);
+                const u64 *T = luts + ((u64)d[0] << t);
+                const u64 q = ((j & (N - 1)) + half) >> (L - t);
+                const u64 x = q < P ? T[q] : 0ull - T[0];
+                acc[i] = ((j >> L) & 1u) ? 0ull - x : x;
+            }
+        } else {
+            const u64 q = i - na;
+            shift[q] = ok ? (u32)((2 * N - mod_switch_2n(lut_word(pool, d, n_lwe, (u32)(q - m * n_lwe)), L)) & (2 * N - 1)) : 0u;
         }
     }
 }
@@ -981,4 +1049,80 @@ extern "C" int fhe_tfhe_gate_mux_dev(uint64_t n, unsigned k, unsigned log_beta, 
                                      unsigned ks_log_beta, unsigned ks_l, const void *d_ksk, const void *d_pool, size_t wires, const void *d_sel,
                                      void *d_out, size_t batch, void *hip_stream) {
     return gate_entry(true, n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, d_pool, wires, d_sel, d_out, batch, hip_stream);
+}
+
+// ---- small integers: a lookup table per row -----------------------------------------------------------------
+static_assert(fhe::LUT_DESC == 6, "descriptor row (lut, x, y, sx, sy, o_hi)");
+
+namespace {
+// what both calls ask of the pool, the descriptors and d_out, overlaps aside; out_bytes = batch (n_lwe + 1) 8 on success
+int check_lut_rows(unsigned n_lwe, const void *d_pool, size_t wires, const void *d_desc, void *d_out, size_t batch, const char *who,
+                   u64 *out_bytes) {
+    if (wires < 1 || batch < 1) return fhe_fail(FHE_E_INVALID, "%s: need wires >= 1 and batch >= 1", who);
+    const u64 row_bytes = (n_lwe + 1ull) * 8;
+    if ((u64)batch > 0xffffffffull || (u64)wires > (~0ull >> 1) / row_bytes || (u64)batch * (n_lwe + 1ull) > 0x7fffffffull * 256)
+        return fhe_fail(FHE_E_INVALID, "%s: batch or wires too large", who);
+    if (!d_pool || !d_desc || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_pool); REQUIRE_ALIGNED(d_desc); REQUIRE_ALIGNED(d_out);
+    *out_bytes = (u64)batch * row_bytes;
+    return FHE_OK;
+}
+}  // namespace
+
+extern "C" int fhe_tlwe_lincomb_dev(unsigned n_lwe, const void *d_pool, size_t wires, const void *d_desc, void *d_out, size_t batch,
+                                    void *hip_stream) {
+    const char *who = "fhe_tlwe_lincomb_dev";
+    if (n_lwe < 1) return fhe_fail(FHE_E_INVALID, "%s: n_lwe must be at least 1", who);
+    u64 out_bytes = 0;
+    int rc = check_lut_rows(n_lwe, d_pool, wires, d_desc, d_out, batch, who, &out_bytes);
+    if (rc != FHE_OK) return rc;
+    if (overlaps(d_out, out_bytes, d_desc, (u64)batch * fhe::LUT_DESC * 4)) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the descriptors", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    { fhe::KernelTimer kt_("tlwe_lincomb", 0, st);
+    hipLaunchKernelGGL(fhe::tlwe_lincomb_kernel, dim3(fhe_ew_grid((u64)batch * (n_lwe + 1ull))), dim3(256), 0, st, (const u64 *)d_pool, (u64)wires,
+                       (const u32 *)d_desc, (u64 *)d_out, n_lwe, (u64)batch);
+    }
+    LAUNCH_OK("tlwe_lincomb_kernel");
+    return FHE_OK;
+}
+
+// lut init -> the §11 CMux steps -> extraction at h = 0 -> key switch into d_out: 2 n_lwe + 3 launches whatever the mix of tables
+extern "C" int fhe_tfhe_lut_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
+                                          unsigned ks_log_beta, unsigned ks_l, const void *d_ksk, unsigned t_bits, const void *d_luts,
+                                          size_t lut_count, const void *d_pool, size_t wires, const void *d_desc, void *d_out, size_t batch,
+                                          void *hip_stream) {
+    const char *who = "fhe_tfhe_lut_bootstrap_dev";
+    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
+    if (rc != FHE_OK) return rc;
+    const u64 kn = (u64)k * n;
+    if ((rc = check_gks((unsigned)kn, n_lwe, ks_log_beta, ks_l, who)) != FHE_OK) return rc;
+    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
+    if (t_bits < 1 || t_bits > L) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= t_bits <= log2 n (t_bits=%u, n=%llu)", who, t_bits, (unsigned long long)n);
+    if (lut_count < 1 || (u64)lut_count > 0xffffffffull)
+        return fhe_fail(FHE_E_INVALID, "%s: need 1 <= lut_count < 2^32 (lut_count=%llu)", who, (unsigned long long)lut_count);
+    u64 out_bytes = 0;
+    if ((rc = check_lut_rows(n_lwe, d_pool, wires, d_desc, d_out, batch, who, &out_bytes)) != FHE_OK) return rc;
+    if (!d_bsk_prepared || !d_ksk || !d_luts) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_luts);
+    if ((u64)batch * (k1 * n + n_lwe) > 0x7fffffffull * 256 ||
+        ((u64)batch + fhe::KS_TB - 1) / fhe::KS_TB * ((n_lwe + 1ull + fhe::KS_TH - 1) / fhe::KS_TH) > 0x7fffffffull)
+        return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
+        overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) || overlaps(d_out, out_bytes, d_luts, ((u64)lut_count << t_bits) * 8) ||
+        overlaps(d_out, out_bytes, d_desc, (u64)batch * fhe::LUT_DESC * 4))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps a key, the tables or the descriptors", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    void *accv = nullptr, *ext = nullptr, *shv = nullptr;
+    if ((rc = fhe_workspace_get(7, (u64)batch * k1 * n * 8, st, &accv)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(8, (u64)batch * (kn + 1) * 8, st, &ext)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &shv)) != FHE_OK) return rc;
+    u64 *acc = (u64 *)accv;
+    { fhe::KernelTimer kt_("tfhe_lut_init", (int)L, st);
+    hipLaunchKernelGGL(fhe::tfhe_lut_init_kernel, dim3(fhe_ew_grid((u64)batch * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_pool, (u64)wires,
+                       (const u32 *)d_desc, (const u64 *)d_luts, (u64)lut_count, t_bits, acc, (u32 *)shv, n_lwe, k1, L, (u64)batch);
+    }
+    LAUNCH_OK("tfhe_lut_init_kernel");
+    if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, (const u32 *)shv, batch, st)) != FHE_OK) return rc;
+    if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) return rc;
+    return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, batch, st);
 }

@@ -22,6 +22,9 @@ over the C ABI.
     (no counterpart)                                   boolean gates of DESIGN.md §13 (bits +-2^61): GATES, gate_bootstrap
                                                        (a mixed-op batch in one call), mux, gate_not, trivial_bit, and the
                                                        Circuit netlist (plan levels on the host, evaluate on the device)
+    (no counterpart)                                   small integers of DESIGN.md §14 (x in [0, 2^t) is phase x 2^(63-t)):
+                                                       encode_int, trivial_int, make_lut, lincomb, lut_bootstrap (a table
+                                                       per row in one call), and the LutCircuit netlist
 """
 import numpy as np
 
@@ -623,6 +626,277 @@ class Circuit:
                     f(btk.n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), btk.ks_log_beta, btk.ks_l, btk.ksk.data_ptr(),
                       pool.data_ptr(), p.n_slots * S, dd.data_ptr() + o * 12, pool.data_ptr() + first * S * row * 8, count * S, st)
             run_nots(lv["level"])
+        if not p.outputs:
+            return []
+        outs = _from_dev(torch.stack([pool[s * S:s * S + batch] for s in p.outputs]))
+        return [TLWE(o) for o in outs]
+
+
+# ---- small integers: a lookup table per row in one bootstrap ---------------------------------------------------
+LUT_NONE = binding.FHE_LUT_NONE                  # the index of an operand whose scale is 0, by convention
+
+
+def _lut_key(btk):
+    if btk.log_beta is None:
+        raise ValueError("lookup-table bootstraps need a gadget BootstrappingKey (log_beta=...)")
+
+
+def encode_int(x, t_bits):
+    """the torus word x Delta mod 2^64, Delta = 2^(63 - t_bits), of a value or of each value of an array (Python integers,
+    so a negative value wraps)"""
+    if np.ndim(x) == 0:
+        return np.uint64((int(x) << (63 - t_bits)) % (1 << 64))
+    return np.array([(int(v) << (63 - t_bits)) % (1 << 64) for v in np.asarray(x).reshape(-1)], dtype=np.uint64).reshape(np.shape(x))
+
+
+def trivial_int(x, t_bits, n_lwe):
+    """the noiseless TLWE (0 .. 0, x Delta) of a value, or of each value of an array"""
+    words = np.zeros(np.shape(x) + (n_lwe + 1,), dtype=np.uint64)
+    words[..., n_lwe] = encode_int(x, t_bits)
+    return TLWE(words)
+
+
+def make_lut(f, t_bits, out=None):
+    """[2^t_bits] torus words: entry x is out(f(x)); `out` maps a value to its torus word (default: value Delta mod 2^64)"""
+    enc = (lambda v: encode_int(v, t_bits)) if out is None else out
+    return np.array([int(enc(f(x))) % (1 << 64) for x in range(1 << t_bits)], dtype=np.uint64)
+
+
+def _lut_desc(desc_rows):
+    """[rows][6] (lut, x, y, sx, sy, o_hi), scales signed -> u32 words"""
+    d = np.asarray(desc_rows, dtype=np.int64).reshape(-1, 6)
+    return np.ascontiguousarray((d & 0xFFFFFFFF).astype(np.uint32))
+
+
+def _desc_dev(desc):
+    return _torch().from_numpy(desc.view(np.int32)).cuda()
+
+
+def _pool_rows(pool):
+    w = np.asarray(pool.words if isinstance(pool, TLWE) else pool, dtype=np.uint64)
+    return w.reshape(-1, w.shape[-1])
+
+
+def lincomb(desc_rows, pool):
+    """fhe_tlwe_lincomb_dev: row m = sx pool[x] + sy pool[y] + (0 .. 0, o_hi 2^32) of descriptor row m = (lut, x, y, sx, sy,
+    o_hi) (the lut word is ignored); pool [wires][n_lwe + 1].  No bootstrap."""
+    torch = _torch()
+    p, desc = _pool_rows(pool), _lut_desc(desc_rows)
+    dp, dd = _to_dev(p), _desc_dev(desc)
+    out = torch.empty((len(desc), p.shape[1]), dtype=torch.int64, device="cuda")
+    binding.tlwe_lincomb_dev(p.shape[1] - 1, dp.data_ptr(), p.shape[0], dd.data_ptr(), out.data_ptr(), len(desc))
+    return TLWE(_from_dev(out))
+
+
+def lut_bootstrap(btk, t_bits, luts, desc, pool):
+    """fhe_tfhe_lut_bootstrap_dev: row m bootstraps its combined input (as lincomb) through table luts[lut] ([lut_count][2^t_bits]
+    torus words, see make_lut) -> TLWE [rows][n_lwe + 1] under the LWE key of btk (a gadget BootstrappingKey)"""
+    torch = _torch()
+    _lut_key(btk)
+    p, d = _pool_rows(pool), _lut_desc(desc)
+    tabs = np.ascontiguousarray(np.asarray(luts, dtype=np.uint64).reshape(-1, 1 << t_bits))
+    dp, dd, dl = _to_dev(p), _desc_dev(d), _to_dev(tabs)
+    out = torch.empty((len(d), btk.n_lwe + 1), dtype=torch.int64, device="cuda")
+    binding.tfhe_lut_bootstrap_dev(btk.n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), btk.ks_log_beta, btk.ks_l, btk.ksk.data_ptr(),
+                                   t_bits, dl.data_ptr(), tabs.shape[0], dp.data_ptr(), p.shape[0], dd.data_ptr(), out.data_ptr(), len(d))
+    return TLWE(_from_dev(out))
+
+
+class LutCircuitPlan:
+    """LutCircuit.plan(): pool slots, levels and sub-levels.  Slots: the inputs, the constants and the `lin` wires of level 0
+    (sub-level by sub-level), then per level L >= 1 its `lut` wires and its `lin` wires (sub-level by sub-level).
+    levels[L - 1] = {"level", "luts": (first slot, count), "lut_desc" [count][6]}; lins[L] = one {"slots": (first slot, count),
+    "desc" [count][6]} per sub-level, in order.  A descriptor is (table, slot x, slot y, sx, sy, const): an operand whose scale
+    is 0 has slot LUT_NONE, and const is still a value (evaluate turns it into o_hi for its t_bits)."""
+
+    def __init__(self, slot, level, sub, n_slots, inputs, consts, levels, lins, outputs, tables):
+        self.slot, self.level, self.sub, self.n_slots = slot, level, sub, n_slots
+        self.inputs, self.consts, self.levels, self.lins, self.outputs, self.tables = inputs, consts, levels, lins, outputs, tables
+
+    @property
+    def depth(self):
+        return len(self.levels)
+
+
+class LutCircuit:
+    """A netlist of table lookups and linear nodes on encrypted small integers (values in [0, 2^t), see encode_int).  Every
+    builder returns a wire (an int) and takes only wires defined before it.  `lut` wires are bootstrapped (one level above
+    their highest operand); `lin` wires, inputs and constants are not.  evaluate() runs `batch` independent copies with one
+    fhe_tfhe_lut_bootstrap_dev per level and one fhe_tlwe_lincomb_dev per sub-level of `lin` wires."""
+
+    def __init__(self):
+        self._nodes = []            # (kind, args): "input" (), "const" (value,), "lin" (x, sx, y, sy, const), "lut" (table, x, sx, y, sy, const)
+        self._outputs = []
+        self._tables, self._table_index = [], {}
+
+    def _add(self, kind, *args):
+        self._nodes.append((kind, args))
+        return len(self._nodes) - 1
+
+    def _operands(self, x, sx, y, sy, const):
+        """-> (x, sx, y, sy, const) with a zero-scale operand's wire None"""
+        sx, sy = int(sx), (0 if y is None else int(sy))
+        for s in (sx, sy):
+            if not -(1 << 31) <= s < 1 << 31:
+                raise ValueError(f"scale {s} does not fit an int32")
+        ws = []
+        for w, s in ((x, sx), (y, sy)):
+            if s == 0:
+                ws.append(None)
+                continue
+            if not isinstance(w, (int, np.integer)) or not 0 <= int(w) < len(self._nodes):
+                raise ValueError(f"wire {w!r} is used before it is defined ({len(self._nodes)} wires so far)")
+            ws.append(int(w))
+        return ws[0], sx, ws[1], sy, int(const)
+
+    def input(self):
+        return self._add("input")
+
+    def const(self, value):
+        return self._add("const", int(value))
+
+    def lin(self, x, sx=1, y=None, sy=0, const=0):
+        """sx x + sy y + const, no bootstrap (the noise of the operands adds up with their scales)"""
+        return self._add("lin", *self._operands(x, sx, y, sy, const))
+
+    def lut(self, table, x, sx=1, y=None, sy=0, const=0):
+        """table[sx x + sy y + const], bootstrapped; table: [2^t] torus words (make_lut).  Identical tables are stored once."""
+        ops = self._operands(x, sx, y, sy, const)
+        tab = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1)
+        key = tab.tobytes()
+        if key not in self._table_index:
+            self._table_index[key] = len(self._tables)
+            self._tables.append(tab)
+        return self._add("lut", self._table_index[key], *ops)
+
+    def output(self, w):
+        if not isinstance(w, (int, np.integer)) or not 0 <= int(w) < len(self._nodes):
+            raise ValueError(f"wire {w!r} is used before it is defined ({len(self._nodes)} wires so far)")
+        self._outputs.append(int(w))
+        return w
+
+    @property
+    def n_inputs(self):
+        return sum(k == "input" for k, _ in self._nodes)
+
+    @property
+    def tables(self):
+        return list(self._tables)
+
+    def plan(self):
+        """levels, sub-levels and pool slots (host only)"""
+        level, sub = [], []
+        for w, (kind, args) in enumerate(self._nodes):
+            a = args[1:] if kind == "lut" else args
+            ins = [v for v in (a[0], a[2]) if v is not None] if kind in ("lin", "lut") else []
+            if any(not 0 <= v < w for v in ins):
+                raise ValueError(f"wire {w} reads a wire that is not defined before it")
+            top = max((level[v] for v in ins), default=0)
+            if kind == "lut":
+                level.append(1 + top)
+                sub.append(-1)
+            elif kind == "lin":
+                level.append(top)
+                sub.append(1 + max((sub[v] for v in ins if level[v] == top and self._nodes[v][0] == "lin"), default=-1))
+            else:
+                level.append(0)
+                sub.append(-1)
+        depth = max(level, default=0)
+        slot = [None] * len(self._nodes)
+        nxt = 0
+
+        def place(kind, lev, sb=-1):
+            nonlocal nxt
+            first, ws = nxt, []
+            for w, (k, _) in enumerate(self._nodes):
+                if k == kind and level[w] == lev and sub[w] == sb:
+                    slot[w] = nxt
+                    nxt += 1
+                    ws.append(w)
+            return (first, nxt - first), ws
+
+        def descs(ws):
+            rows = []
+            for w in ws:
+                kind, args = self._nodes[w]
+                t, (x, sx, y, sy, c) = (args[0], args[1:]) if kind == "lut" else (LUT_NONE, args)
+                rows.append((t, LUT_NONE if x is None else slot[x], LUT_NONE if y is None else slot[y], sx, sy, c))
+            return np.array(rows, dtype=np.int64).reshape(-1, 6)
+
+        place("input", 0)
+        place("const", 0)
+        levels, lins = [], {}
+        for lev in range(depth + 1):
+            if lev:
+                span, ws = place("lut", lev)
+                levels.append({"level": lev, "luts": span, "lut_desc": descs(ws)})
+            lins[lev] = []
+            for sb in range(1 + max((sub[w] for w in range(len(slot)) if level[w] == lev), default=-1)):
+                span, ws = place("lin", lev, sb)
+                lins[lev].append({"slots": span, "desc": descs(ws)})
+        inputs = [slot[w] for w, (k, _) in enumerate(self._nodes) if k == "input"]
+        consts = [(slot[w], a[0]) for w, (k, a) in enumerate(self._nodes) if k == "const"]
+        return LutCircuitPlan(slot, level, sub, nxt, inputs, consts, levels, lins, [slot[w] for w in self._outputs], self.tables)
+
+    def evaluate(self, btk, inputs, t_bits):
+        """inputs: one TLWE batch [batch][n_lwe + 1] per input wire, in definition order -> one TLWE batch per output.
+        The pool is wire-major as Circuit.evaluate's: slot w holds rows [w S, w S + batch), S = batch rounded up to even so
+        that every slice (and every block of descriptors, 24 bytes a row) starts 16-byte aligned; the padding copy of a wire
+        is an invalid row.  Tables, constants and descriptors are uploaded once; the host waits only for the outputs."""
+        torch = _torch()
+        _lut_key(btk)
+        p = self.plan()
+        row = btk.n_lwe + 1
+        xs = [np.asarray(t.words if isinstance(t, TLWE) else t, dtype=np.uint64).reshape(-1, row) for t in inputs]
+        if len(xs) != len(p.inputs):
+            raise ValueError(f"evaluate: {len(p.inputs)} inputs expected, {len(xs)} given")
+        batch = xs[0].shape[0] if xs else 1
+        if any(x.shape[0] != batch for x in xs):
+            raise ValueError("evaluate: every input needs the same batch")
+        if any(len(t) != 1 << t_bits for t in p.tables):
+            raise ValueError(f"evaluate: every table needs 2^{t_bits} words")
+        S = batch + (batch & 1)
+        if p.n_slots * S >= 1 << 32:
+            raise ValueError("evaluate: the pool needs more than 2^32 rows")
+        fixed = len(p.inputs) + len(p.consts)           # the inputs and constants fill slots [0, fixed)
+        host = np.zeros((fixed, S, row), dtype=np.uint64)
+        for s, x in zip(p.inputs, xs):
+            host[s, :batch] = x
+        for s, v in p.consts:
+            host[s, :batch] = trivial_int(np.full(batch, v), t_bits, btk.n_lwe).words
+        inst, pad = np.arange(S, dtype=np.int64), np.arange(S) >= batch
+
+        def expand(desc):
+            """[count][6] slot descriptors -> [count S][6] row descriptors; a padding row names wire LUT_NONE with scale 1"""
+            out = np.repeat(desc[:, None, :], S, axis=1)
+            for c in (1, 2):
+                out[:, :, c] = np.where(out[:, :, c] == LUT_NONE, LUT_NONE, out[:, :, c] * S + inst[None, :])
+            out[:, :, 5] = [[int(encode_int(v, t_bits)) >> 32] * S for v in desc[:, 5]]
+            out[:, pad, :] = (LUT_NONE, LUT_NONE, LUT_NONE, 1, 0, 0)
+            return out.reshape(-1, 6)
+
+        calls, descs, off = [], [], 0                   # (lut?, first slot, count, descriptor row offset), in issue order
+        for lev in range(p.depth + 1):
+            groups = ([(True, p.levels[lev - 1]["luts"], p.levels[lev - 1]["lut_desc"])] if lev else []) + \
+                     [(False, g["slots"], g["desc"]) for g in p.lins[lev]]
+            for is_lut, (first, count), d in groups:
+                if count:
+                    calls.append((is_lut, first, count, off))
+                    descs.append(expand(d))
+                    off += count * S
+        pool = torch.empty((p.n_slots * S, row), dtype=torch.int64, device="cuda")
+        pool[: fixed * S] = _to_dev(host.reshape(-1, row))
+        dd = _desc_dev(_lut_desc(np.concatenate(descs))) if descs else None
+        dl = _to_dev(np.stack(p.tables)) if p.tables else None
+        st = torch.cuda.current_stream().cuda_stream
+        for is_lut, first, count, o in calls:
+            d_desc, d_out = dd.data_ptr() + o * 24, pool.data_ptr() + first * S * row * 8
+            if is_lut:
+                binding.tfhe_lut_bootstrap_dev(btk.n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), btk.ks_log_beta, btk.ks_l,
+                                               btk.ksk.data_ptr(), t_bits, dl.data_ptr(), len(p.tables), pool.data_ptr(), p.n_slots * S, d_desc,
+                                               d_out, count * S, st)
+            else:
+                binding.tlwe_lincomb_dev(btk.n_lwe, pool.data_ptr(), p.n_slots * S, d_desc, d_out, count * S, st)
         if not p.outputs:
             return []
         outs = _from_dev(torch.stack([pool[s * S:s * S + batch] for s in p.outputs]))

@@ -418,6 +418,31 @@ int fhe_tfhe_gate_mux_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l,
                           const void *d_bsk_prepared, unsigned ks_log_beta, unsigned ks_l, const void *d_ksk,
                           const void *d_pool, size_t wires, const void *d_sel, void *d_out, size_t batch, void *hip_stream);
 
+/* ---- TFHE small integers: a lookup table per row in one bootstrap (definitions in DESIGN.md §14) ----
+ * The gadget shapes of the gates above (k = 1, 2^8 <= n = 2^L <= 2^12; anything else is FHE_E_INVALID).  t = t_bits,
+ * 1 <= t <= L, P = 2^t, Delta = 2^(63 - t): a value x in [0, P) is a TLWE of phase x Delta + e; the top bit is padding, 0.
+ *   d_luts [lut_count][P] u64 torus words (not values: an output may use any encoding).  Table T stands for the test vector
+ *          (mask 0, body v), v[i] = T[m] for m = (i + half) >> (L - t) < P and 0 - T[0] otherwise, half = N / 2P (0 at
+ *          P = N); it is never written out.  A phase within half a box of x Delta gives T[x]; a row whose padding bit is set
+ *          gives 0 - T[x - P] (negacyclic).
+ *   d_desc [batch][6] u32 (lut, x, y, sx, sy, o_hi), sx and sy read as int32: the combined input of a row is
+ *          c = sx pool[x] + sy pool[y] + (0 .. 0, o_hi 2^32) (wrapping u64; Delta >= 2^51, so any multiple of Delta is an
+ *          o_hi).  An operand whose scale is 0 is never read and its index may be anything (FHE_LUT_NONE by convention).
+ *          A row is invalid if an operand with a non-zero scale has an index >= wires, or, in the bootstrap only, if
+ *          lut >= lut_count: it reads no pool or table word and its output row is all-zero words.
+ *   fhe_tlwe_lincomb_dev        d_out [batch][n_lwe + 1] = c of each row; the lut word is ignored; no bootstrap
+ *   fhe_tfhe_lut_bootstrap_dev  d_out [batch][n_lwe + 1]: combine, mod switch, ACC_0 = rot(v_lut, b~), the n_lwe CMux steps,
+ *                               extraction at 0, key switch: 2 n_lwe + 3 launches whatever the mix of tables
+ * batch, wires and lut_count must be at least 1.  d_out may lie inside the pool but must not overlap a row that the
+ * descriptors read. */
+#define FHE_LUT_NONE 0xFFFFFFFFu
+int fhe_tlwe_lincomb_dev(unsigned n_lwe, const void *d_pool, size_t wires, const void *d_desc, void *d_out, size_t batch,
+                         void *hip_stream);
+int fhe_tfhe_lut_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe,
+                               const void *d_bsk_prepared, unsigned ks_log_beta, unsigned ks_l, const void *d_ksk,
+                               unsigned t_bits, const void *d_luts, size_t lut_count, const void *d_pool, size_t wires,
+                               const void *d_desc, void *d_out, size_t batch, void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
