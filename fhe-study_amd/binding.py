@@ -75,6 +75,8 @@ EXPORTS = [
     "fhe_tfhe_gate_bootstrap_dev", "fhe_tfhe_gate_mux_dev",
     # small integers: a lookup table per row (tfhe_boot.hip)
     "fhe_tlwe_lincomb_dev", "fhe_tfhe_lut_bootstrap_dev",
+    # small integers: several tables from one blind rotation (tfhe_boot.hip)
+    "fhe_tfhe_lut_many_bootstrap_dev",
 ]
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
@@ -256,6 +258,8 @@ def load_library():
     L.fhe_tfhe_gate_mux_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _vp, _vp, _sz, _vp, _vp, _sz, _vp]
     L.fhe_tlwe_lincomb_dev.argtypes = [_uint, _vp, _sz, _vp, _vp, _sz, _vp]
     L.fhe_tfhe_lut_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _vp, _uint, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_lut_many_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _vp, _uint, _uint, _vp, _sz, _vp, _sz, _vp, _vp,
+                                                  _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -600,6 +604,13 @@ def tfhe_lut_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta
                            d_desc, d_out, batch, stream=None):
     _check(load_library().fhe_tfhe_lut_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, t_bits, d_luts,
                                                      lut_count, d_pool, wires, d_desc, d_out, batch, stream))
+
+
+def tfhe_lut_many_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, t_bits, nu, d_luts, lut_count, d_pool,
+                                wires, d_desc, d_out, batch, stream=None):
+    """d_out [2^nu][batch][n_lwe + 1], function-major"""
+    _check(load_library().fhe_tfhe_lut_many_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, t_bits, nu,
+                                                          d_luts, lut_count, d_pool, wires, d_desc, d_out, batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

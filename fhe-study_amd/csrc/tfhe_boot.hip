@@ -29,6 +29,13 @@
 //   a phase within half a box of x Delta gives T[x] at coefficient 0; with the padding bit set it gives -T[x - P] (negacyclic)
 //   descriptor row [6] u32 (lut, x, y, sx, sy, o_hi), sx, sy int32; a scale of 0 reads nothing; a non-zero scale with an
 //   index >= wires, or (bootstrap only) lut >= lut_count, makes the row invalid: nothing read, an all-zero output row
+//
+// Several tables from one blind rotation (the many-output bootstrap of ePrint 2021/729): nu = 0 .. min(L - t, 4),
+// F = 2^nu.  The mod switch rounds to multiples of F, ms_nu(w) = ((((w >> (62 - L + nu)) + 1) >> 1) << nu) & (2N - 1), on the
+// body and on every mask word; a row's lut word names the first of F consecutive tables, interleaved in the test vector:
+//   v[i] = T_h[q], h = i mod F, q = (i - h + half) >> (L - t), and 0 - T_h[0] where q = P (never at nu = L - t)
+// so after the one rotation coefficient h holds T_h[x] (0 - T_h[x - P] with the padding bit set).  A row is also invalid if
+// lut + F > lut_count; all F of its output rows are zero.  Output [F][batch][n_lwe + 1]: function h of row m is row h batch + m.
 #include <algorithm>
 
 #include "capi_internal.hpp"
@@ -405,6 +412,71 @@ __global__ __launch_bounds__(256) void tfhe_lut_init_kernel(const u64 *__restric
         } else {
             const u64 q = i - na;
             shift[q] = ok ? (u32)((2 * N - mod_switch_2n(lut_word(pool, d, n_lwe, (u32)(q - m * n_lwe)), L)) & (2 * N - 1)) : 0u;
+        }
+    }
+}
+
+// ---- small integers: several tables from one blind rotation ---------------------------------------------
+// nu low bits of every mod-switched word are forced to 0: ms_nu(w) = round(w / 2^(63 - L + nu)) 2^nu mod 2N, so a row's
+// accumulator is rotated by a multiple of F = 2^nu and coefficients 0 .. F - 1 of the result all come from the box the
+// phase fell into.  ms_0 is mod_switch_2n.
+__device__ __forceinline__ u32 mod_switch_nu(u64 w, u32 L, u32 nu) {
+    return (u32)(((((w >> (62u - L + nu)) + 1u) >> 1) << nu) & ((2ull << L) - 1u));
+}
+
+// The nu-aware twin of tfhe_lut_init_kernel, organised by row: a workgroup takes a row (grid-stride over rows), so the
+// descriptor, the validity, the combined body and b~ are workgroup-uniform and formed once per row; its lanes then write the
+// row's k1 N accumulator words two at a time (16-byte stores) and its n_lwe shifts, both coalesced.  The row's lut word
+// names the first of F consecutive tables T_0 .. T_{F-1}; the test vector interleaves them, v[i] = T_h[q] with h = i mod F,
+// q = (i - h + half) >> (L - t), and 0 - T_h[0] where q = P (never at F = box); v is never formed.  A row is invalid under
+// lut_row_valid or if lut + F > lut_count (64-bit): it reads no pool or table word and writes zeros and zero shifts.
+__global__ __launch_bounds__(256) void tfhe_lut_many_init_kernel(const u64 *__restrict__ pool, u64 wires, const u32 *__restrict__ desc,
+                                                                 const u64 *__restrict__ luts, u64 lut_count, u32 t, u32 nu,
+                                                                 u64 *__restrict__ acc, u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L,
+                                                                 u64 rows) {
+    const u64 N = 1ull << L, k1N = (u64)k1 * N, body0 = k1N - N;
+    const u64 P = 1ull << t, half = (N >> t) >> 1, F = 1ull << nu;
+    for (u64 m = blockIdx.x; m < rows; m += gridDim.x) {
+        const u32 *d = desc + m * LUT_DESC;
+        const bool ok = (u64)d[0] + F <= lut_count && lut_row_valid(d, wires);
+        const u64 bt = ok ? mod_switch_nu(lut_word(pool, d, n_lwe, n_lwe), L, nu) : 0;
+        u64 *row = acc + m * k1N;
+        for (u64 p = 2ull * threadIdx.x; p < k1N; p += 512) {        // N >= 2: a pair never straddles a component
+            ulonglong2 v = make_ulonglong2(0, 0);
+            if (ok && p >= body0) {
+                u64 x[2];
+#pragma unroll
+                for (u32 e = 0; e < 2; e++) {
+                    const u64 j = (p - body0 + e) + bt, i = j & (N - 1), h = i & (F - 1);
+                    const u64 q = (i - h + half) >> (L - t);
+                    const u64 *T = luts + (((u64)d[0] + h) << t);
+                    const u64 w = q < P ? T[q] : 0ull - T[0];
+                    x[e] = ((j >> L) & 1u) ? 0ull - w : w;
+                }
+                v = make_ulonglong2(x[0], x[1]);
+            }
+            *reinterpret_cast<ulonglong2 *>(row + p) = v;
+        }
+        for (u32 j = threadIdx.x; j < n_lwe; j += 256)
+            shift[m * n_lwe + j] = ok ? (u32)((2 * N - mod_switch_nu(lut_word(pool, d, n_lwe, j), L, nu)) & (2 * N - 1)) : 0u;
+    }
+}
+
+// TGLWE::sample_extraction (tglwe_sample_extract_kernel's rule) at h = 0 .. F - 1 in one pass: acc [batch][(k+1)][N] ->
+// out [F][batch][k N + 1], function-major.  Every mask word a_c[s] is read once and stored F times: it is coefficient
+// (h - s) mod N of extraction h, negated where s > h.  The body of extraction h is b[h]: only the first F body words are read.
+__global__ __launch_bounds__(256) void tfhe_many_extract_kernel(const u64 *__restrict__ acc, u64 *__restrict__ out, u32 k, u32 L, u32 nu,
+                                                                u64 batch) {
+    const u64 N = 1ull << L, kN = (u64)k * N, F = 1ull << nu, per = kN + F, orow = kN + 1, total = batch * per;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 b = i / per, r = i - b * per;
+        const u64 x = acc[b * (kN + N) + r];                             // r >= kN: body word r - kN < F
+        if (r >= kN) {
+            out[((r - kN) * batch + b) * orow + kN] = x;
+        } else {
+            const u64 c = r >> L, s = r & (N - 1);
+            for (u64 h = 0; h < F; h++) out[(h * batch + b) * orow + c * N + ((h - s) & (N - 1))] = s <= h ? x : 0ull - x;
         }
     }
 }
@@ -1125,4 +1197,55 @@ extern "C" int fhe_tfhe_lut_bootstrap_dev(uint64_t n, unsigned k, unsigned log_b
     if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, (const u32 *)shv, batch, st)) != FHE_OK) return rc;
     if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) return rc;
     return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, batch, st);
+}
+
+// ---- small integers: several tables from one blind rotation ----------------------------------------------------
+// many init -> the §11 CMux steps over `batch` rows -> extraction at h = 0 .. F - 1 -> one key switch over the F batch extracted
+// rows into d_out [F][batch][n_lwe + 1]: 2 n_lwe + 3 launches whatever nu is
+extern "C" int fhe_tfhe_lut_many_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
+                                               unsigned ks_log_beta, unsigned ks_l, const void *d_ksk, unsigned t_bits, unsigned nu,
+                                               const void *d_luts, size_t lut_count, const void *d_pool, size_t wires, const void *d_desc,
+                                               void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_tfhe_lut_many_bootstrap_dev";
+    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
+    if (rc != FHE_OK) return rc;
+    const u64 kn = (u64)k * n;
+    if ((rc = check_gks((unsigned)kn, n_lwe, ks_log_beta, ks_l, who)) != FHE_OK) return rc;
+    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
+    if (t_bits < 1 || t_bits > L) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= t_bits <= log2 n (t_bits=%u, n=%llu)", who, t_bits, (unsigned long long)n);
+    if (nu > 4 || nu > L - t_bits)
+        return fhe_fail(FHE_E_INVALID, "%s: need nu <= min(log2 n - t_bits, 4) (nu=%u, t_bits=%u, n=%llu)", who, nu, t_bits, (unsigned long long)n);
+    if (lut_count < 1 || (u64)lut_count > 0xffffffffull)
+        return fhe_fail(FHE_E_INVALID, "%s: need 1 <= lut_count < 2^32 (lut_count=%llu)", who, (unsigned long long)lut_count);
+    u64 row_bytes = 0;                                                  // check_lut_rows: one function's slice, batch rows
+    if ((rc = check_lut_rows(n_lwe, d_pool, wires, d_desc, d_out, batch, who, &row_bytes)) != FHE_OK) return rc;
+    if (!d_bsk_prepared || !d_ksk || !d_luts) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_luts);
+    const u64 F = 1ull << nu, frows = F * (u64)batch;                   // the extraction and the key switch see F batch rows
+    if ((u64)batch * (k1 * n + n_lwe) > 0x7fffffffull * 256 || frows > 0xffffffffull || frows * (kn + 1) > 0x7fffffffull * 256 ||
+        (frows + fhe::KS_TB - 1) / fhe::KS_TB * ((n_lwe + 1ull + fhe::KS_TH - 1) / fhe::KS_TH) > 0x7fffffffull)
+        return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    const u64 out_bytes = F * row_bytes;
+    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
+        overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) || overlaps(d_out, out_bytes, d_luts, ((u64)lut_count << t_bits) * 8) ||
+        overlaps(d_out, out_bytes, d_desc, (u64)batch * fhe::LUT_DESC * 4))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps a key, the tables or the descriptors", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    void *accv = nullptr, *ext = nullptr, *shv = nullptr;
+    if ((rc = fhe_workspace_get(7, (u64)batch * k1 * n * 8, st, &accv)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(8, frows * (kn + 1) * 8, st, &ext)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &shv)) != FHE_OK) return rc;
+    u64 *acc = (u64 *)accv;
+    { fhe::KernelTimer kt_("tfhe_lut_many_init", (int)L, st);
+    hipLaunchKernelGGL(fhe::tfhe_lut_many_init_kernel, dim3((unsigned)std::min<u64>(batch, 256 * 16)), dim3(256), 0, st, (const u64 *)d_pool,
+                       (u64)wires, (const u32 *)d_desc, (const u64 *)d_luts, (u64)lut_count, t_bits, nu, acc, (u32 *)shv, n_lwe, k1, L, (u64)batch);
+    }
+    LAUNCH_OK("tfhe_lut_many_init_kernel");
+    if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, (const u32 *)shv, batch, st)) != FHE_OK) return rc;
+    { fhe::KernelTimer kt_("tfhe_many_extract", (int)L, st);
+    hipLaunchKernelGGL(fhe::tfhe_many_extract_kernel, dim3(fhe_ew_grid((u64)batch * (kn + F))), dim3(256), 0, st, (const u64 *)acc, (u64 *)ext, k, L,
+                       nu, (u64)batch);
+    }
+    LAUNCH_OK("tfhe_many_extract_kernel");
+    return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, frows, st);
 }

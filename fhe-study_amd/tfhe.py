@@ -25,6 +25,8 @@ over the C ABI.
     (no counterpart)                                   small integers of DESIGN.md §14 (x in [0, 2^t) is phase x 2^(63-t)):
                                                        encode_int, trivial_int, make_lut, lincomb, lut_bootstrap (a table
                                                        per row in one call), and the LutCircuit netlist
+    (no counterpart)                                   several tables from one blind rotation:
+                                                       lut_many_bootstrap, LutCircuit.plan / evaluate with share=nu_max
 """
 import numpy as np
 
@@ -702,16 +704,37 @@ def lut_bootstrap(btk, t_bits, luts, desc, pool):
     return TLWE(_from_dev(out))
 
 
+def lut_many_bootstrap(btk, t_bits, nu, luts, desc, pool):
+    """fhe_tfhe_lut_many_bootstrap_dev: row m bootstraps its combined input (as lincomb) once and looks it up in the 2^nu
+    consecutive tables luts[lut], .., luts[lut + 2^nu - 1] -> TLWE [2^nu][rows][n_lwe + 1], function-major.  Each unit of nu
+    costs one bit of mod-switch precision."""
+    torch = _torch()
+    _lut_key(btk)
+    p, d = _pool_rows(pool), _lut_desc(desc)
+    tabs = np.ascontiguousarray(np.asarray(luts, dtype=np.uint64).reshape(-1, 1 << t_bits))
+    dp, dd, dl = _to_dev(p), _desc_dev(d), _to_dev(tabs)
+    out = torch.empty((1 << nu, len(d), btk.n_lwe + 1), dtype=torch.int64, device="cuda")
+    binding.tfhe_lut_many_bootstrap_dev(btk.n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), btk.ks_log_beta, btk.ks_l,
+                                        btk.ksk.data_ptr(), t_bits, nu, dl.data_ptr(), tabs.shape[0], dp.data_ptr(), p.shape[0], dd.data_ptr(),
+                                        out.data_ptr(), len(d))
+    return TLWE(_from_dev(out))
+
+
 class LutCircuitPlan:
     """LutCircuit.plan(): pool slots, levels and sub-levels.  Slots: the inputs, the constants and the `lin` wires of level 0
     (sub-level by sub-level), then per level L >= 1 its `lut` wires and its `lin` wires (sub-level by sub-level).
     levels[L - 1] = {"level", "luts": (first slot, count), "lut_desc" [count][6]}; lins[L] = one {"slots": (first slot, count),
     "desc" [count][6]} per sub-level, in order.  A descriptor is (table, slot x, slot y, sx, sy, const): an operand whose scale
-    is 0 has slot LUT_NONE, and const is still a value (evaluate turns it into o_hi for its t_bits)."""
+    is 0 has slot LUT_NONE, and const is still a value (evaluate turns it into o_hi for its t_bits).
+    plan(share >= 1) only: `luts` holds the level's nu = 0 wires, and levels[L - 1]["many"] lists, for each nu that occurs,
+    {"nu", "block": first slot, "chunks": G, "desc" [G][6]}: 2^nu G slots after the nu = 0 wires, function h of chunk g at
+    block + h G + g (a function a chunk does not fill is scratch: no wire has that slot); a descriptor's table word indexes
+    many_tables[nu], the list of [2^t] tables in which every chunk's 2^nu tables are consecutive."""
 
-    def __init__(self, slot, level, sub, n_slots, inputs, consts, levels, lins, outputs, tables):
+    def __init__(self, slot, level, sub, n_slots, inputs, consts, levels, lins, outputs, tables, many_tables=None):
         self.slot, self.level, self.sub, self.n_slots = slot, level, sub, n_slots
         self.inputs, self.consts, self.levels, self.lins, self.outputs, self.tables = inputs, consts, levels, lins, outputs, tables
+        self.many_tables = many_tables or {}
 
     @property
     def depth(self):
@@ -783,8 +806,29 @@ class LutCircuit:
     def tables(self):
         return list(self._tables)
 
-    def plan(self):
-        """levels, sub-levels and pool slots (host only)"""
+    def _share_chunks(self, ws, share):
+        """the `lut` wires ws of one level -> (the nu = 0 wires, {nu: chunks}): wires with identical operands (x, sx, y, sy,
+        const) form a class, in definition order; a class is cut into chunks of at most 2^share wires; a chunk of c > 1
+        wires has nu = ceil(log2 c), a chunk of one wire is a nu = 0 wire"""
+        classes = {}
+        for w in ws:
+            classes.setdefault(self._nodes[w][1][1:], []).append(w)
+        singles, chunks = [], {}
+        for members in classes.values():
+            for i in range(0, len(members), 1 << share):
+                ch = members[i:i + (1 << share)]
+                if len(ch) == 1:
+                    singles.append(ch[0])
+                else:
+                    chunks.setdefault((len(ch) - 1).bit_length(), []).append(ch)
+        return sorted(singles), chunks
+
+    def plan(self, share=0):
+        """levels, sub-levels and pool slots (host only).  share = nu_max >= 1 lets `lut` wires of one level with identical
+        operands share a blind rotation, up to 2^nu_max of them (LutCircuitPlan); share = 0 is the plan of
+        one bootstrap per `lut` wire."""
+        if not 0 <= int(share) <= 4:
+            raise ValueError(f"plan: share must be in 0 .. 4 (share={share})")
         level, sub = [], []
         for w, (kind, args) in enumerate(self._nodes):
             a = args[1:] if kind == "lut" else args
@@ -815,19 +859,48 @@ class LutCircuit:
                     ws.append(w)
             return (first, nxt - first), ws
 
-        def descs(ws):
+        def descs(ws, tabs=None):
             rows = []
-            for w in ws:
+            for i, w in enumerate(ws):
                 kind, args = self._nodes[w]
                 t, (x, sx, y, sy, c) = (args[0], args[1:]) if kind == "lut" else (LUT_NONE, args)
-                rows.append((t, LUT_NONE if x is None else slot[x], LUT_NONE if y is None else slot[y], sx, sy, c))
+                rows.append((t if tabs is None else tabs[i], LUT_NONE if x is None else slot[x], LUT_NONE if y is None else slot[y], sx, sy, c))
             return np.array(rows, dtype=np.int64).reshape(-1, 6)
+
+        many_tables, many_index = {}, {}
+
+        def place_shared(lev):
+            """the `lut` wires of a level under share >= 1: the nu = 0 wires, then one block of 2^nu G slots per nu"""
+            nonlocal nxt
+            singles, chunks = self._share_chunks([w for w, (k, _) in enumerate(self._nodes) if k == "lut" and level[w] == lev], share)
+            first = nxt
+            for w in singles:
+                slot[w] = nxt
+                nxt += 1
+            many = []
+            for nu in sorted(chunks):
+                G, F, firsts = len(chunks[nu]), 1 << nu, []
+                for g, ch in enumerate(chunks[nu]):
+                    for h, w in enumerate(ch):
+                        slot[w] = nxt + h * G + g
+                    ids = [self._nodes[w][1][0] for w in ch]
+                    ids = tuple(ids + [ids[0]] * (F - len(ids)))            # a function the chunk does not fill repeats its first table
+                    if (nu, ids) not in many_index:
+                        tabs = many_tables.setdefault(nu, [])
+                        many_index[nu, ids] = len(tabs)
+                        tabs.extend(self._tables[i] for i in ids)
+                    firsts.append(many_index[nu, ids])
+                many.append({"nu": nu, "block": nxt, "chunks": G, "desc": descs([ch[0] for ch in chunks[nu]], firsts)})
+                nxt += F * G
+            return {"level": lev, "luts": (first, len(singles)), "lut_desc": descs(singles), "many": many}
 
         place("input", 0)
         place("const", 0)
         levels, lins = [], {}
         for lev in range(depth + 1):
-            if lev:
+            if lev and share:
+                levels.append(place_shared(lev))
+            elif lev:
                 span, ws = place("lut", lev)
                 levels.append({"level": lev, "luts": span, "lut_desc": descs(ws)})
             lins[lev] = []
@@ -836,16 +909,22 @@ class LutCircuit:
                 lins[lev].append({"slots": span, "desc": descs(ws)})
         inputs = [slot[w] for w, (k, _) in enumerate(self._nodes) if k == "input"]
         consts = [(slot[w], a[0]) for w, (k, a) in enumerate(self._nodes) if k == "const"]
-        return LutCircuitPlan(slot, level, sub, nxt, inputs, consts, levels, lins, [slot[w] for w in self._outputs], self.tables)
+        return LutCircuitPlan(slot, level, sub, nxt, inputs, consts, levels, lins, [slot[w] for w in self._outputs], self.tables, many_tables)
 
-    def evaluate(self, btk, inputs, t_bits):
+    def evaluate(self, btk, inputs, t_bits, share=0):
         """inputs: one TLWE batch [batch][n_lwe + 1] per input wire, in definition order -> one TLWE batch per output.
         The pool is wire-major as Circuit.evaluate's: slot w holds rows [w S, w S + batch), S = batch rounded up to even so
         that every slice (and every block of descriptors, 24 bytes a row) starts 16-byte aligned; the padding copy of a wire
-        is an invalid row.  Tables, constants and descriptors are uploaded once; the host waits only for the outputs."""
+        is an invalid row.  Tables, constants and descriptors are uploaded once; the host waits only for the outputs.
+        share = nu_max >= 1 (plan(share)): per level, `lut` wires with identical operands share one blind rotation, up to
+        2^nu_max of them, through one fhe_tfhe_lut_many_bootstrap_dev per nu that occurs.  Each unit of nu costs one bit of
+        message space at equal failure rate: the mod switch rounds to multiples of 2^nu, so its error doubles with every
+        unit, and t_bits has to shrink by as much to keep the margin.  share <= log2 n - t_bits."""
         torch = _torch()
         _lut_key(btk)
-        p = self.plan()
+        if share > int(btk.n).bit_length() - 1 - t_bits:
+            raise ValueError(f"evaluate: share={share} needs share <= log2 n - t_bits = {int(btk.n).bit_length() - 1 - t_bits}")
+        p = self.plan(share)
         row = btk.n_lwe + 1
         xs = [np.asarray(t.words if isinstance(t, TLWE) else t, dtype=np.uint64).reshape(-1, row) for t in inputs]
         if len(xs) != len(p.inputs):
@@ -875,23 +954,30 @@ class LutCircuit:
             out[:, pad, :] = (LUT_NONE, LUT_NONE, LUT_NONE, 1, 0, 0)
             return out.reshape(-1, 6)
 
-        calls, descs, off = [], [], 0                   # (lut?, first slot, count, descriptor row offset), in issue order
+        calls, descs, off = [], [], 0                   # (nu, or None: lincomb; first slot; rows / S; descriptor row offset), in issue order
         for lev in range(p.depth + 1):
-            groups = ([(True, p.levels[lev - 1]["luts"], p.levels[lev - 1]["lut_desc"])] if lev else []) + \
-                     [(False, g["slots"], g["desc"]) for g in p.lins[lev]]
-            for is_lut, (first, count), d in groups:
+            lv = p.levels[lev - 1] if lev else {}
+            groups = ([(0, lv["luts"], lv["lut_desc"])] if lev else []) + \
+                     [(m["nu"], (m["block"], m["chunks"]), m["desc"]) for m in lv.get("many", [])] + \
+                     [(None, g["slots"], g["desc"]) for g in p.lins[lev]]
+            for nu, (first, count), d in groups:
                 if count:
-                    calls.append((is_lut, first, count, off))
+                    calls.append((nu, first, count, off))
                     descs.append(expand(d))
                     off += count * S
         pool = torch.empty((p.n_slots * S, row), dtype=torch.int64, device="cuda")
         pool[: fixed * S] = _to_dev(host.reshape(-1, row))
         dd = _desc_dev(_lut_desc(np.concatenate(descs))) if descs else None
         dl = _to_dev(np.stack(p.tables)) if p.tables else None
+        dm = {nu: _to_dev(np.stack(tabs)) for nu, tabs in p.many_tables.items()}
         st = torch.cuda.current_stream().cuda_stream
-        for is_lut, first, count, o in calls:
+        for nu, first, count, o in calls:
             d_desc, d_out = dd.data_ptr() + o * 24, pool.data_ptr() + first * S * row * 8
-            if is_lut:
+            if nu:                                      # [2^nu][count S] rows: function h of chunk g fills slot first + h count + g
+                binding.tfhe_lut_many_bootstrap_dev(btk.n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), btk.ks_log_beta, btk.ks_l,
+                                                    btk.ksk.data_ptr(), t_bits, nu, dm[nu].data_ptr(), len(p.many_tables[nu]), pool.data_ptr(),
+                                                    p.n_slots * S, d_desc, d_out, count * S, st)
+            elif nu == 0:
                 binding.tfhe_lut_bootstrap_dev(btk.n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), btk.ks_log_beta, btk.ks_l,
                                                btk.ksk.data_ptr(), t_bits, dl.data_ptr(), len(p.tables), pool.data_ptr(), p.n_slots * S, d_desc,
                                                d_out, count * S, st)

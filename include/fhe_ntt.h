@@ -443,6 +443,28 @@ int fhe_tfhe_lut_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsign
                                unsigned t_bits, const void *d_luts, size_t lut_count, const void *d_pool, size_t wires,
                                const void *d_desc, void *d_out, size_t batch, void *hip_stream);
 
+/* ---- TFHE small integers: several lookup tables from one blind rotation (definitions in DESIGN.md §15) ----
+ * The many-output bootstrap of Chillotti, Ligier, Orfila and Tap (ePrint 2021/729, "PBSmanyLUT") on the shapes, keys,
+ * encoding and descriptors of fhe_tfhe_lut_bootstrap_dev above.  nu: 0 <= nu <= min(L - t_bits, 4), F = 2^nu.
+ *   mod switch  ms_nu(w) = ((((w >> (62 - L + nu)) + 1) >> 1) << nu) & (2N - 1): rounding to a multiple of F in Z_2N, applied
+ *          to the body and to every mask word of the combined input (ms_0 is the mod switch of every other call), so each
+ *          unit of nu costs one bit of mod-switch precision.
+ *   d_luts [lut_count][P]: a row's lut word names the first of F consecutive tables T_0 .. T_{F-1}.  The test vector
+ *          interleaves them: for i < N, h = i mod F, q = (i - h + half) >> (L - t), v[i] = T_h[q] if q < P, else 0 - T_h[0]
+ *          (q = P never occurs at nu = L - t); it is never written out.  After the one blind rotation coefficient h holds
+ *          T_h[x] for phases within half a box of x Delta, and 0 - T_h[x - P] with the padding bit set.
+ *   d_desc as above.  A row is invalid under the operand rule above or if lut + F > lut_count (in 64 bits): it reads no
+ *          pool or table word and all F of its output rows are all-zero words.
+ *   d_out  [F][batch][n_lwe + 1], function-major: function h of row m is row h batch + m.
+ * Combine, ms_nu, ACC_0 = rot(v, b~), the n_lwe CMux steps, extraction of coefficients 0 .. F - 1 in one launch, one key
+ * switch over the F batch rows: 2 n_lwe + 3 launches whatever nu is.  With nu = 0 every output word is
+ * fhe_tfhe_lut_bootstrap_dev's.  d_out (all F batch rows) must not overlap a key, the tables or the descriptors
+ * (FHE_E_INVALID); it may lie inside the pool but must not overlap a row that the descriptors read. */
+int fhe_tfhe_lut_many_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe,
+                                    const void *d_bsk_prepared, unsigned ks_log_beta, unsigned ks_l, const void *d_ksk,
+                                    unsigned t_bits, unsigned nu, const void *d_luts, size_t lut_count, const void *d_pool,
+                                    size_t wires, const void *d_desc, void *d_out, size_t batch, void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
