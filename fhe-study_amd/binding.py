@@ -77,6 +77,8 @@ EXPORTS = [
     "fhe_tlwe_lincomb_dev", "fhe_tfhe_lut_bootstrap_dev",
     # small integers: several tables from one blind rotation (tfhe_boot.hip)
     "fhe_tfhe_lut_many_bootstrap_dev",
+    # packing key switch and the bootstrap with a test vector per row (tfhe_boot.hip)
+    "fhe_tfhe_pksk_words", "fhe_tlwe_gadget_packing_key_switch_dev", "fhe_tglwe_box_expand_dev", "fhe_tfhe_gadget_bootstrap_rows_dev",
 ]
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
@@ -260,6 +262,11 @@ def load_library():
     L.fhe_tfhe_lut_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _vp, _uint, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp]
     L.fhe_tfhe_lut_many_bootstrap_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _uint, _uint, _vp, _uint, _uint, _vp, _sz, _vp, _sz, _vp, _vp,
                                                   _sz, _vp]
+    L.fhe_tfhe_pksk_words.argtypes = [_u64, _uint, _uint, _uint, _uint]
+    L.fhe_tfhe_pksk_words.restype = _sz
+    L.fhe_tlwe_gadget_packing_key_switch_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _vp, _sz, _sz, _sz, _uint, _vp, _sz, _vp]
+    L.fhe_tglwe_box_expand_dev.argtypes = [_u64, _uint, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_gadget_bootstrap_rows_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _vp, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -611,6 +618,28 @@ def tfhe_lut_many_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log
     """d_out [2^nu][batch][n_lwe + 1], function-major"""
     _check(load_library().fhe_tfhe_lut_many_bootstrap_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, ks_log_beta, ks_l, d_ksk, t_bits, nu,
                                                           d_luts, lut_count, d_pool, wires, d_desc, d_out, batch, stream))
+
+
+# ---- packing key switch and the bootstrap with a test vector per row (DESIGN.md §16) --------------------------------------
+def tfhe_pksk_words(n, k, n_in, log_beta, l):
+    return load_library().fhe_tfhe_pksk_words(n, k, n_in, log_beta, l)
+
+
+def tlwe_gadget_packing_key_switch_dev(n, k, n_in, log_beta, l, d_pksk, d_in, in_group_stride, in_item_stride, count, log_stride, d_out, groups,
+                                       stream=None):
+    """d_out [groups][(k+1)][n]; ciphertext i of group g starts at word g in_group_stride + i in_item_stride of d_in"""
+    _check(load_library().fhe_tlwe_gadget_packing_key_switch_dev(n, k, n_in, log_beta, l, d_pksk, d_in, in_group_stride, in_item_stride, count,
+                                                                 log_stride, d_out, groups, stream))
+
+
+def tglwe_box_expand_dev(n, k, t_bits, d_in, d_out, batch, stream=None):
+    _check(load_library().fhe_tglwe_box_expand_dev(n, k, t_bits, d_in, d_out, batch, stream))
+
+
+def tfhe_gadget_bootstrap_rows_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_tables, ks_log_beta, ks_l, d_ksk, d_in, d_out, batch, stream=None):
+    """fhe_tfhe_gadget_bootstrap_dev with d_tables [batch][(k+1)][n]: a full TGLWE test vector per row"""
+    _check(load_library().fhe_tfhe_gadget_bootstrap_rows_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_tables, ks_log_beta, ks_l, d_ksk, d_in,
+                                                             d_out, batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

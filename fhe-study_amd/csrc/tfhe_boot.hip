@@ -481,6 +481,125 @@ __global__ __launch_bounds__(256) void tfhe_many_extract_kernel(const u64 *__res
     }
 }
 
+// ---- packing key switch and the bootstrap with a test vector per row -------------------------------------
+// Public functional key switch TLWE -> TGLWE, `count` ciphertexts of a group packed at stride 2^ls, k = 1:
+//   out_g[r][c] = [r = k] sum_i b_{g,i} [c = i stride] - sum_i sum_j sum_d sg(i, c) digit_d(a_{g,i,j}) key[j][d][r][(c - i stride) mod N]
+// sg = -1 where c < i stride (X^(i stride) wraps), key [n_in][l][(k+1)][N]; ciphertext (g, i) starts at word g gstride + i istride.
+// tlwe_private_ks_kernel's wrapping GEMM with a rotated key read: a workgroup owns PK_TG groups and PK_TH columns of one
+// component, so the key word a lane fetches for column c - i stride serves all PK_TG groups; the ciphertext words are
+// uniform (SGPRs), each field is extracted once per wave, and the sign goes on the key word, which keeps the
+// f - 2^(b-1) / sum key form: a term is one v_mad_u64_u32 and one 32-bit multiply of the high half.  PK_TG = 16: the 16
+// ciphertext words of a (j, i) step are 32 SGPRs and stay in SGPRs (32 groups spill them into VGPR lanes), and 16
+// accumulators leave eight waves per SIMD.  A slot past the last group re-reads the last live row and stores nothing.
+constexpr int PK_TG = 16, PK_TH = 64;
+// the sums of one lane: acc[t] = sum f kv over (j, i, d) for the tile's group t, ksum = sum kv.  FULL: all PK_TG slots live
+template <bool FULL>
+__device__ __forceinline__ void packing_ks_sums(const u64 *__restrict__ kc, const u64 *__restrict__ src, u32 n_in, u32 N, u64 kstep, u32 lb, u32 l,
+                                                u64 cadd, u64 gstride, u64 istride, u32 count, u32 ls, u32 live, u32 c, u64 (&acc)[PK_TG], u64 &ksum) {
+    const u32 sh0 = 64u - lb, mask = (u32)(~0ull >> (64u - lb));
+    for (u32 j = 0; j < n_in; j++) {
+        const u64 *__restrict__ kr = kc + (u64)j * l * kstep;
+        for (u32 i = 0; i < count; i++) {
+            u64 w[PK_TG];
+            const u64 *__restrict__ p = src + i * istride + j;
+#pragma unroll
+            for (int t = 0; t < PK_TG; t++) {
+                w[t] = *p + cadd;
+                p += FULL || (u32)t + 1u < live ? gstride : 0ull;
+            }
+            const u32 at = i << ls, col = (c - at) & (N - 1u);
+            const bool wrap = c < at;
+            for (u32 d = 0; d < l; d++) {
+                const u64 kw = kr[(u64)d * kstep + col], kv = wrap ? 0ull - kw : kw;
+                const u32 sh = sh0 - lb * d;
+                ksum += kv;
+#pragma unroll
+                for (int t = 0; t < PK_TG; t++) acc[t] += (u64)((u32)(w[t] >> sh) & mask) * kv;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(PK_TH) void tlwe_packing_ks_kernel(const u64 *__restrict__ key, const u64 *__restrict__ in, u64 *__restrict__ out,
+                                                                u32 n_in, u32 L, u32 k1, u32 lb, u32 l, u64 cadd, u64 gstride, u64 istride,
+                                                                u32 count, u32 ls, u64 groups, u32 cblocks) {
+    const u64 tile = blockIdx.x / cblocks;
+    const u32 cb = blockIdx.x - (u32)tile * cblocks, N = 1u << L;
+    const u32 r = (cb * PK_TH) >> L, c = ((cb * PK_TH) & (N - 1u)) + threadIdx.x;     // N is a multiple of PK_TH: every lane is live
+    const u64 g0 = tile * PK_TG, kstep = (u64)k1 << L;                               // kstep: one (j, d) entry of the key
+    const u32 live = (u32)min((u64)PK_TG, groups - g0);
+    const u64 *__restrict__ kc = key + ((u64)r << L);
+    const u64 *__restrict__ src = in + g0 * gstride;
+    u64 acc[PK_TG], ksum = 0;
+#pragma unroll
+    for (int t = 0; t < PK_TG; t++) acc[t] = 0;
+    if (live == PK_TG)
+        packing_ks_sums<true>(kc, src, n_in, N, kstep, lb, l, cadd, gstride, istride, count, ls, live, c, acc, ksum);
+    else
+        packing_ks_sums<false>(kc, src, n_in, N, kstep, lb, l, cadd, gstride, istride, count, ls, live, c, acc, ksum);
+    const u64 half = 1ull << (lb - 1u);
+    const u32 slot = c >> ls;
+    const bool body = r + 1u == k1 && (c & ((1u << ls) - 1u)) == 0 && slot < count;   // coefficient i stride of the body holds b_{g,i}
+#pragma unroll
+    for (int t = 0; t < PK_TG; t++)
+        if ((u32)t < live) out[(((g0 + t) * k1 + r) << L) + c] = (body ? src[t * gstride + slot * istride + n_in] : 0ull) - (acc[t] - half * ksum);
+}
+
+// out = X^-half (1 + X + .. + X^(box-1)) in on every component row, box = N >> t, half = box / 2: out[i] is the sum of the
+// window in~[i + half - box + 1 .. i + half] of the negacyclic extension (in~[j + N] = -in~[j]).  A workgroup takes a row:
+// the row's inclusive prefix sums S (wrapping u64) are formed in LDS, each lane scanning a chunk of N / 256 words and the
+// 256 chunk totals scanned in 8 steps, and with E(j) = S[j] (0 <= j < N), S[N-1] - S[j - N] (j >= N), S[N-1] - S[j + N]
+// (j < 0; E(-1) = 0) the window is E(i + half) - E(i + half - box): O(N) per row.  t = L copies the row.
+__global__ __launch_bounds__(256) void tglwe_box_expand_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, u32 L, u32 t, u64 rows) {
+    __shared__ u64 S[4096], part[256];
+    const u32 N = 1u << L, chunk = N >> 8, box = N >> t, half = box >> 1;
+    for (u64 row = blockIdx.x; row < rows; row += gridDim.x) {
+        const u64 *__restrict__ src = in + (row << L);
+        for (u32 i = threadIdx.x; i < N; i += 256) S[i] = src[i];
+        __syncthreads();
+        u64 run = 0;
+        for (u32 e = 0; e < chunk; e++) {
+            run += S[threadIdx.x * chunk + e];
+            S[threadIdx.x * chunk + e] = run;
+        }
+        part[threadIdx.x] = run;
+        __syncthreads();
+        for (u32 step = 1; step < 256; step <<= 1) {
+            const u64 add = threadIdx.x >= step ? part[threadIdx.x - step] : 0ull;
+            __syncthreads();
+            part[threadIdx.x] += add;
+            __syncthreads();
+        }
+        const u64 total = part[255];
+        auto E = [&](int j) -> u64 {
+            const u32 m = (u32)j & (N - 1u), q = m >> (L - 8u);
+            const u64 s = S[m] + (q ? part[q - 1u] : 0ull);
+            return (j < 0 || j >= (int)N) ? total - s : s;
+        };
+        for (u32 i = threadIdx.x; i < N; i += 256) out[(row << L) + i] = E((int)(i + half)) - E((int)(i + half) - (int)box);
+        __syncthreads();
+    }
+}
+
+// tfhe_br_init_kernel with a test vector per row: ACC_0[b] = rot(tables[b], b~_b) over all k + 1 components (the tables are
+// full TGLWEs, mask rows included), shift[b][j] = (2N - a~_j) mod 2N
+__global__ __launch_bounds__(256) void tfhe_br_rows_init_kernel(const u64 *__restrict__ lwe, const u64 *__restrict__ tables, u64 *__restrict__ acc,
+                                                                u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L, u64 batch) {
+    const u64 N = 1ull << L, k1N = (u64)k1 * N, na = batch * k1N, total = na + batch * n_lwe;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        if (i < na) {
+            const u64 b = i / k1N, r = i - b * k1N;
+            const u64 j = (r & (N - 1)) + mod_switch_2n(lwe[b * (n_lwe + 1ull) + n_lwe], L);
+            const u64 x = tables[b * k1N + (r >> L) * N + (j & (N - 1))];
+            acc[i] = ((j >> L) & 1u) ? 0ull - x : x;
+        } else {
+            const u64 q = i - na, b = q / n_lwe;
+            shift[q] = (u32)((2 * N - mod_switch_2n(lwe[b * (n_lwe + 1ull) + (q - b * n_lwe)], L)) & (2 * N - 1));
+        }
+    }
+}
+
 }  // namespace fhe
 
 // ---- host side -----------------------------------------------------------------------------------------------------
@@ -1248,4 +1367,110 @@ extern "C" int fhe_tfhe_lut_many_bootstrap_dev(uint64_t n, unsigned k, unsigned 
     }
     LAUNCH_OK("tfhe_many_extract_kernel");
     return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, frows, st);
+}
+
+// ---- packing key switch and the bootstrap with a test vector per row ---------------------------------------
+namespace {
+// the packing shape: §12's PFKS shape (k = 1, 2^8 <= n <= 2^12, 1 <= b <= 32, l >= 1, b l <= 64) and n_in >= 1
+bool pks_shape(uint64_t n, unsigned k, unsigned n_in, unsigned log_beta, unsigned l) { return n_in >= 1 && pfks_shape(n, k, log_beta, l); }
+u64 pksk_words(uint64_t n, unsigned k, unsigned n_in, unsigned l) { return (u64)n_in * l * (k + 1) * n; }
+bool mul_fits(u64 a, u64 b, u64 limit) { return b == 0 || a <= limit / b; }
+}  // namespace
+
+extern "C" size_t fhe_tfhe_pksk_words(uint64_t n, unsigned k, unsigned n_in, unsigned log_beta, unsigned l) {
+    return pks_shape(n, k, n_in, log_beta, l) ? (size_t)pksk_words(n, k, n_in, l) : 0;
+}
+
+extern "C" int fhe_tlwe_gadget_packing_key_switch_dev(uint64_t n, unsigned k, unsigned n_in, unsigned log_beta, unsigned l, const void *d_pksk,
+                                                      const void *d_in, size_t in_group_stride, size_t in_item_stride, size_t count,
+                                                      unsigned log_stride, void *d_out, size_t groups, void *hip_stream) {
+    const char *who = "fhe_tlwe_gadget_packing_key_switch_dev";
+    int rc = check_ring(n, k, who);
+    if (rc != FHE_OK) return rc;
+    if (!pks_shape(n, k, n_in, log_beta, l))
+        return fhe_fail(FHE_E_INVALID, "%s: no packing key switch for n=%llu, k=%u, n_in=%u, log_beta=%u, l=%u (needs k = 1, 256 <= n <= 4096, "
+                        "n_in >= 1, 1 <= log_beta <= 32, l >= 1, log_beta l <= 64)", who, (unsigned long long)n, k, n_in, log_beta, l);
+    const u32 L = (u32)__builtin_ctzll(n), k1 = k + 1;
+    if (groups < 1 || count < 1 || log_stride > L || (u64)count > (n >> log_stride))
+        return fhe_fail(FHE_E_INVALID, "%s: need groups >= 1, count >= 1, log_stride <= log2 n and count << log_stride <= n (groups=%llu, "
+                        "count=%llu, log_stride=%u)", who, (unsigned long long)groups, (unsigned long long)count, log_stride);
+    if ((u64)in_group_stride <= n_in || (u64)in_item_stride <= n_in)
+        return fhe_fail(FHE_E_INVALID, "%s: both input strides must be at least n_in + 1 words", who);
+    if (!d_pksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_pksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
+    const u32 cblocks = (u32)(k1 * n / fhe::PK_TH);
+    const u64 tiles = ((u64)groups - 1) / fhe::PK_TG + 1, word_limit = ~0ull >> 4;      // every extent in bytes fits 61 bits
+    if (tiles * cblocks > 0x7fffffffull || !mul_fits((u64)groups, (u64)k1 * n, word_limit) || !mul_fits((u64)groups - 1, in_group_stride, word_limit / 2) ||
+        !mul_fits((u64)count - 1, in_item_stride, word_limit / 2 - n_in - 1))
+        return fhe_fail(FHE_E_INVALID, "%s: groups or the input strides are too large for one launch", who);
+    const u64 in_words = ((u64)groups - 1) * in_group_stride + ((u64)count - 1) * in_item_stride + n_in + 1;
+    const u64 out_bytes = (u64)groups * k1 * n * 8;
+    if (overlaps(d_out, out_bytes, d_pksk, pksk_words(n, k, n_in, l) * 8) || overlaps(d_out, out_bytes, d_in, in_words * 8))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key or the input", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    { fhe::KernelTimer kt_("tlwe_packing_ks", (int)L, st);
+    hipLaunchKernelGGL(fhe::tlwe_packing_ks_kernel, dim3((unsigned)(tiles * cblocks)), dim3(fhe::PK_TH), 0, st, (const u64 *)d_pksk, (const u64 *)d_in,
+                       (u64 *)d_out, n_in, L, k1, log_beta, l, fhe::gadget_cadd(log_beta, l), (u64)in_group_stride, (u64)in_item_stride, (u32)count,
+                       log_stride, (u64)groups, cblocks);
+    }
+    LAUNCH_OK("tlwe_packing_ks_kernel");
+    return FHE_OK;
+}
+
+extern "C" int fhe_tglwe_box_expand_dev(uint64_t n, unsigned k, unsigned t_bits, const void *d_in, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_tglwe_box_expand_dev";
+    int rc = check_ring(n, k, who);
+    if (rc != FHE_OK) return rc;
+    if (k != 1 || n < 256 || n > 4096)
+        return fhe_fail(FHE_E_INVALID, "%s: needs k = 1, 256 <= n <= 4096 (n=%llu, k=%u)", who, (unsigned long long)n, k);
+    const u32 L = (u32)__builtin_ctzll(n), k1 = k + 1;
+    if (t_bits < 1 || t_bits > L) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= t_bits <= log2 n (t_bits=%u, n=%llu)", who, t_bits, (unsigned long long)n);
+    if (batch == 0) return FHE_OK;
+    if (!d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
+    if (!mul_fits((u64)batch, (u64)k1 * n, ~0ull >> 4)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    const u64 rows = (u64)batch * k1, bytes = rows * n * 8;
+    if (overlaps(d_out, bytes, d_in, bytes)) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps d_in", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    { fhe::KernelTimer kt_("tglwe_box_expand", (int)L, st);
+    hipLaunchKernelGGL(fhe::tglwe_box_expand_kernel, dim3((unsigned)std::min<u64>(rows, 256 * 16)), dim3(256), 0, st, (const u64 *)d_in, (u64 *)d_out, L,
+                       t_bits, rows);
+    }
+    LAUNCH_OK("tglwe_box_expand_kernel");
+    return FHE_OK;
+}
+
+// rows init -> the §11 CMux steps -> extraction at h = 0 -> gadget key switch: fhe_tfhe_gadget_bootstrap_dev with d_tables
+// [batch][(k+1)][n] in place of the one table, 2 n_lwe + 3 launches
+extern "C" int fhe_tfhe_gadget_bootstrap_rows_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
+                                                  const void *d_tables, unsigned ks_log_beta, unsigned ks_l, const void *d_ksk, const void *d_in,
+                                                  void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_tfhe_gadget_bootstrap_rows_dev";
+    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
+    if (rc != FHE_OK) return rc;
+    const u64 kn = (u64)k * n;
+    if ((rc = check_gks((unsigned)kn, n_lwe, ks_log_beta, ks_l, who)) != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    if (!d_bsk_prepared || !d_tables || !d_ksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_tables); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
+    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
+    const u64 out_bytes = (u64)batch * (n_lwe + 1ull) * 8;
+    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
+        overlaps(d_out, out_bytes, d_tables, (u64)batch * k1 * n * 8) || overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) ||
+        overlaps(d_out, out_bytes, d_in, out_bytes))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    void *accv = nullptr, *ext = nullptr, *shv = nullptr;
+    if ((rc = fhe_workspace_get(7, (u64)batch * k1 * n * 8, st, &accv)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(8, (u64)batch * (kn + 1) * 8, st, &ext)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &shv)) != FHE_OK) return rc;
+    u64 *acc = (u64 *)accv;
+    { fhe::KernelTimer kt_("tfhe_br_rows_init", (int)L, st);
+    hipLaunchKernelGGL(fhe::tfhe_br_rows_init_kernel, dim3(fhe_ew_grid((u64)batch * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_in,
+                       (const u64 *)d_tables, acc, (u32 *)shv, n_lwe, k1, L, (u64)batch);
+    }
+    LAUNCH_OK("tfhe_br_rows_init_kernel");
+    if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, (const u32 *)shv, batch, st)) != FHE_OK) return rc;
+    if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) return rc;
+    return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, batch, st);
 }

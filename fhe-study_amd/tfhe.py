@@ -27,6 +27,9 @@ over the C ABI.
                                                        per row in one call), and the LutCircuit netlist
     (no counterpart)                                   several tables from one blind rotation:
                                                        lut_many_bootstrap, LutCircuit.plan / evaluate with share=nu_max
+    (no counterpart)                                   two-digit tree lookups: PackingKeySwitchKey,
+                                                       packing_key_switch (TLWEs -> one TGLWE), box_expand, bootstrap_rows
+                                                       (a test vector per row), tree_lookup (table2d[x][y], t bits each)
 """
 import numpy as np
 
@@ -987,3 +990,128 @@ class LutCircuit:
             return []
         outs = _from_dev(torch.stack([pool[s * S:s * S + batch] for s in p.outputs]))
         return [TLWE(o) for o in outs]
+
+
+# ---- packing key switch, a test vector per row and two-digit tree lookups ----------------------------------------
+class PackingKeySwitchKey:
+    """the packing key switching key [n_in][l][(k+1)][n] (numpy or a device tensor) kept on the device: entry [j][d] is a
+    TGLWE under the GLWE key of the constant polynomial K_in[j] 2^(64 - log_beta (d+1)), K_in the key of the TLWEs that
+    are packed (in tree_lookup: the LWE key of the BootstrappingKey, n_in = n_lwe)"""
+
+    def __init__(self, pksk, log_beta, l):
+        torch = _torch()
+        shape = tuple(pksk.shape)
+        if len(shape) != 4 or shape[1] != l:
+            raise ValueError("pksk must be [n_in][l][(k+1)][n]")
+        self.n_in, self.l, k1, self.n = shape
+        self.k, self.log_beta = k1 - 1, log_beta
+        words = binding.tfhe_pksk_words(self.n, self.k, self.n_in, log_beta, l)
+        self.pksk = _dev_words(pksk)
+        if words == 0 or self.pksk.numel() != words:
+            raise binding.FheError(binding.FHE_E_INVALID, f"no packing key switch for pksk of shape {shape}, (log_beta, l) = ({log_beta}, {l})")
+        torch.cuda.synchronize()
+
+
+def packing_key_switch(pk, c, log_stride):
+    """c: TLWEs [groups][count][n_in + 1] (or [count][n_in + 1]: one group) under the key `pk` switches from -> TGLWE
+    [groups] whose phase holds phase(c_{g,i}) at coefficient i 2^log_stride (count 2^log_stride <= n)"""
+    torch = _torch()
+    w = c.words if c.words.ndim == 3 else c.words[None]
+    groups, count, row = w.shape
+    if row != pk.n_in + 1:
+        raise ValueError(f"packing_key_switch: the TLWEs have dimension {row - 1}, the key switches from {pk.n_in}")
+    dx = _to_dev(w)
+    out = torch.empty((groups, pk.k + 1, pk.n), dtype=torch.int64, device="cuda")
+    binding.tlwe_gadget_packing_key_switch_dev(pk.n, pk.k, pk.n_in, pk.log_beta, pk.l, pk.pksk.data_ptr(), dx.data_ptr(), count * row, row, count,
+                                               log_stride, out.data_ptr(), groups)
+    o = _from_dev(out)
+    o = o if c.words.ndim == 3 else o[0]
+    return TGLWE(o[..., : pk.k, :], o[..., pk.k, :])
+
+
+def box_expand(tglwe, t_bits):
+    """every component times X^-half (1 + X + .. + X^(box-1)), box = n >> t_bits, half = box / 2: a packed TGLWE holding m_q
+    at coefficient q box becomes the test vector (make_lut's expansion) of the table q -> m_q"""
+    torch = _torch()
+    x = tglwe.packed()
+    k1, n = x.shape[-2], x.shape[-1]
+    batch = x.size // (k1 * n)
+    dx = _to_dev(x.reshape(batch, k1, n))
+    out = torch.empty((batch, k1, n), dtype=torch.int64, device="cuda")
+    binding.tglwe_box_expand_dev(n, k1 - 1, t_bits, dx.data_ptr(), out.data_ptr(), batch)
+    o = _from_dev(out).reshape(x.shape)
+    return TGLWE(o[..., : k1 - 1, :], o[..., k1 - 1, :])
+
+
+def bootstrap_rows(btk, tables, c):
+    """bootstrapping with a test vector per row: tables is a TGLWE batch (full TGLWEs, e.g. encrypted test vectors from
+    box_expand), row b of c rotates tables[b]; btk a gadget BootstrappingKey"""
+    torch = _torch()
+    _lut_key(btk)
+    x = c.words.reshape(-1, btk.n_lwe + 1)
+    t = tables.packed().reshape(-1, btk.k + 1, btk.n)
+    if t.shape[0] != x.shape[0]:
+        raise ValueError("bootstrap_rows: one test vector per row")
+    out = torch.empty(x.shape, dtype=torch.int64, device="cuda")
+    dt, dx = _to_dev(t), _to_dev(x)
+    binding.tfhe_gadget_bootstrap_rows_dev(btk.n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), dt.data_ptr(), btk.ks_log_beta,
+                                           btk.ks_l, btk.ksk.data_ptr(), dx.data_ptr(), out.data_ptr(), x.shape[0])
+    return TLWE(_from_dev(out).reshape(c.words.shape))
+
+
+def tree_lookup(btk, pksk, t_bits, table2d, x, y, nu=0, *, which=None):
+    """table2d[x][y] of two encrypted t_bits-bit digits (the tree-based functional bootstrap): table2d
+    [P][P] torus words (P = 2^t_bits, any output encoding, as make_lut's `out`); x, y TLWE batches under the LWE key of btk;
+    pksk a PackingKeySwitchKey from that LWE key to the GLWE key.  Level 1 looks y up in the P tables table2d[j]: nu = 0
+    is one fhe_tfhe_lut_bootstrap_dev over P batch rows, nu = t_bits one fhe_tfhe_lut_many_bootstrap_dev over batch rows
+    (t_bits <= min(log2 n - t_bits, 4); it costs t_bits bits of mod-switch precision).  Then one packing key
+    switch (count P, stride box), one box expansion and one bootstrap_rows on x, all on the device: the host waits only
+    for the result.  Both digits keep the padding bit of DESIGN.md §14.  A batch may mix functions: table2d [R][P][P] with
+    which [batch] naming each row's table (default: table 0)."""
+    torch = _torch()
+    _lut_key(btk)
+    n, row, P = btk.n, btk.n_lwe + 1, 1 << t_bits
+    L = int(n).bit_length() - 1
+    if nu not in (0, t_bits):
+        raise ValueError(f"tree_lookup: nu must be 0 or t_bits (nu={nu}, t_bits={t_bits})")
+    if not 1 <= t_bits <= L or (nu and t_bits > min(L - t_bits, 4)):
+        raise ValueError(f"tree_lookup: t_bits={t_bits} does not fit n={n}" + (" with nu = t_bits" if nu else ""))
+    if (pksk.n, pksk.k, pksk.n_in) != (n, btk.k, btk.n_lwe):
+        raise ValueError("tree_lookup: the packing key must switch from the LWE key of btk to its GLWE key")
+    tabs = np.ascontiguousarray(np.asarray(table2d, dtype=np.uint64))
+    tabs = tabs[None] if tabs.ndim == 2 else tabs
+    xs, ys = x.words.reshape(-1, row), y.words.reshape(-1, row)
+    batch = xs.shape[0]
+    if tabs.shape[1:] != (P, P) or ys.shape != xs.shape:
+        raise ValueError(f"tree_lookup: table2d must be [{P}][{P}] (or [R][{P}][{P}]) and x, y batches of the same shape")
+    first = np.zeros(batch, dtype=np.int64) if which is None else np.asarray(which, dtype=np.int64).reshape(-1) * P
+    if len(first) != batch or first.min() < 0 or first.max() >= len(tabs) * P:
+        raise ValueError("tree_lookup: `which` needs one table index below len(table2d) per row")
+    dx, dy, dl = _to_dev(xs), _to_dev(ys), _to_dev(tabs)
+    lvl1 = torch.empty((P * batch, row), dtype=torch.int64, device="cuda")
+    g = np.arange(batch, dtype=np.int64)
+    if nu:                                                          # [P][batch] rows, function-major: item j of group g is row j batch + g
+        desc = np.stack([first, g, np.full(batch, LUT_NONE), np.ones(batch, dtype=np.int64),
+                         np.zeros(batch, dtype=np.int64), np.zeros(batch, dtype=np.int64)], axis=1)
+        dd = _desc_dev(_lut_desc(desc))
+        binding.tfhe_lut_many_bootstrap_dev(n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), btk.ks_log_beta, btk.ks_l,
+                                            btk.ksk.data_ptr(), t_bits, nu, dl.data_ptr(), len(tabs) * P, dy.data_ptr(), batch, dd.data_ptr(),
+                                            lvl1.data_ptr(), batch)
+        gstride, istride = row, batch * row
+    else:                                                           # [batch][P] rows: row g P + j looks y_g up in table2d[j]
+        gg, jj = np.repeat(g, P), np.tile(np.arange(P, dtype=np.int64), batch)
+        desc = np.stack([jj + np.repeat(first, P), gg, np.full(P * batch, LUT_NONE), np.ones(P * batch, dtype=np.int64), np.zeros(P * batch, dtype=np.int64),
+                         np.zeros(P * batch, dtype=np.int64)], axis=1)
+        dd = _desc_dev(_lut_desc(desc))
+        binding.tfhe_lut_bootstrap_dev(n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), btk.ks_log_beta, btk.ks_l, btk.ksk.data_ptr(),
+                                       t_bits, dl.data_ptr(), len(tabs) * P, dy.data_ptr(), batch, dd.data_ptr(), lvl1.data_ptr(), P * batch)
+        gstride, istride = P * row, row
+    packed = torch.empty((batch, btk.k + 1, n), dtype=torch.int64, device="cuda")
+    tv = torch.empty_like(packed)
+    out = torch.empty((batch, row), dtype=torch.int64, device="cuda")
+    binding.tlwe_gadget_packing_key_switch_dev(n, btk.k, btk.n_lwe, pksk.log_beta, pksk.l, pksk.pksk.data_ptr(), lvl1.data_ptr(), gstride, istride, P,
+                                               L - t_bits, packed.data_ptr(), batch)
+    binding.tglwe_box_expand_dev(n, btk.k, t_bits, packed.data_ptr(), tv.data_ptr(), batch)
+    binding.tfhe_gadget_bootstrap_rows_dev(n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), tv.data_ptr(), btk.ks_log_beta, btk.ks_l,
+                                           btk.ksk.data_ptr(), dx.data_ptr(), out.data_ptr(), batch)
+    return TLWE(_from_dev(out).reshape(x.words.shape))

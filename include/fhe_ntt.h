@@ -465,6 +465,40 @@ int fhe_tfhe_lut_many_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, u
                                     unsigned t_bits, unsigned nu, const void *d_luts, size_t lut_count, const void *d_pool,
                                     size_t wires, const void *d_desc, void *d_out, size_t batch, void *hip_stream);
 
+/* ---- TFHE packing key switch and a bootstrap with a test vector per row (definitions in DESIGN.md §16) ----
+ * The pieces of the tree-based functional bootstrap of Guimaraes, Borin and Aranha (TCHES 2021/2): LWE results of one
+ * lookup are packed into a TGLWE (the public functional key switch of Chillotti et al., J. Cryptology 2020), which a
+ * second blind rotation reads as its test vector.  k = 1, 2^8 <= n = 2^L <= 2^12, u64 wrapping words, digit_d, g_d and
+ * gadget_cadd are §11's; anything else is FHE_E_INVALID.  Outputs must not overlap inputs.
+ *   fhe_tfhe_pksk_words   u64 words of a packing key switching key [n_in][l][(k+1)][n] (n_in >= 1, 1 <= b <= 32,
+ *          b l <= 64; 0 otherwise).  Entry [j][d] is a TGLWE under s of the constant polynomial K_in[j] g_d(b), K_in the
+ *          key of the input TLWEs.
+ *   fhe_tlwe_gadget_packing_key_switch_dev   KS(c) = (0, b X^0) - sum_j sum_d digit_d(a_j) pksk[j][d] for c = (a, b); a
+ *          group packs `count` ciphertexts at stride = 2^log_stride (count >= 1, count stride <= n):
+ *          out_g = sum_{i < count} X^(i stride) KS(c_{g,i}) in T64[X]/(X^n + 1), d_out [groups][(k+1)][n].  Ciphertext i
+ *          of group g starts at word g in_group_stride + i in_item_stride of d_in; both strides are at least n_in + 1
+ *          and the addressed rows must not alias.  A contiguous [groups][count][n_in + 1] block has strides
+ *          (count (n_in + 1), n_in + 1); fhe_tfhe_lut_many_bootstrap_dev's [F][batch][n_lwe + 1] has (n_lwe + 1,
+ *          batch (n_lwe + 1)).  Only d_in itself need be 16-byte aligned.  groups = 0 is FHE_E_INVALID.
+ *   fhe_tglwe_box_expand_dev   1 <= t_bits <= L, box = n >> t_bits, half = box / 2: every component row becomes
+ *          X^(-half) (1 + X + .. + X^(box-1)) times itself, out[i] = sum_{u < box} in~[i + half - u] with in~ the negacyclic
+ *          extension.  A packed TGLWE holding m_q at coefficient q box becomes §14's test vector of the table q -> m_q;
+ *          t_bits = L copies.  d_in, d_out [batch][(k+1)][n].
+ *   fhe_tfhe_gadget_bootstrap_rows_dev   fhe_tfhe_gadget_bootstrap_dev with a test vector per row: d_tables
+ *          [batch][(k+1)][n] holds full TGLWEs (mask rows included) and row b of d_in rotates row b of d_tables over all
+ *          k + 1 components; then the n_lwe CMux steps, extraction at 0 and the gadget key switch: 2 n_lwe + 3 launches. */
+size_t fhe_tfhe_pksk_words(uint64_t n, unsigned k, unsigned n_in, unsigned log_beta, unsigned l);
+int fhe_tlwe_gadget_packing_key_switch_dev(uint64_t n, unsigned k, unsigned n_in, unsigned log_beta, unsigned l,
+                                           const void *d_pksk, const void *d_in, size_t in_group_stride,
+                                           size_t in_item_stride, size_t count, unsigned log_stride, void *d_out,
+                                           size_t groups, void *hip_stream);
+int fhe_tglwe_box_expand_dev(uint64_t n, unsigned k, unsigned t_bits, const void *d_in, void *d_out, size_t batch,
+                             void *hip_stream);
+int fhe_tfhe_gadget_bootstrap_rows_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe,
+                                       const void *d_bsk_prepared, const void *d_tables, unsigned ks_log_beta,
+                                       unsigned ks_l, const void *d_ksk, const void *d_in, void *d_out, size_t batch,
+                                       void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
