@@ -14,7 +14,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FHE_NTT_LIB") or os.path.join(_HERE, "libfhe_ntt.so")  # env: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip"]
+SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip", "tfhe_client.hip"]
 HEADERS = ["ntt_kernels.hpp", "ntt_rounds.hpp", "ntt_persist.hpp", "persist_sched.hpp", "digit_mac.hpp", "digit32.hpp", "bfv32.hpp", "smallq.hpp", "ntt32_rounds.hpp", "ntt32_big.hpp", "zq_device.hpp", "capi_internal.hpp", "mac_kernel.hpp", "ntt_kernels.hip",
            os.path.join("..", "..", "include", "fhe_ntt.h"), os.path.join("..", "..", "include", "fhe_ntt_experimental.h")]
 OBJ_DIR = os.path.join(_HERE, "build")
@@ -79,12 +79,16 @@ EXPORTS = [
     "fhe_tfhe_lut_many_bootstrap_dev",
     # packing key switch and the bootstrap with a test vector per row (tfhe_boot.hip)
     "fhe_tfhe_pksk_words", "fhe_tlwe_gadget_packing_key_switch_dev", "fhe_tglwe_box_expand_dev", "fhe_tfhe_gadget_bootstrap_rows_dev",
+    # key generation, encryption and decryption: the client side (tfhe_client.hip)
+    "fhe_tfhe_stream_words_dev", "fhe_tlwe_encrypt_dev", "fhe_tlwe_phase_dev", "fhe_tglwe_encrypt_dev", "fhe_tglwe_phase_dev",
 ]
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
 GATES = {"AND": 0, "NAND": 1, "OR": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
 FHE_GATE_COUNT = 10
 FHE_LUT_NONE = 0xFFFFFFFF                    # include/fhe_ntt.h: the index of an operand whose scale is 0, by convention
+FHE_STREAM_MASK, FHE_STREAM_ERR, FHE_STREAM_KEY = 1, 2, 3    # include/fhe_ntt.h: the purposes of the random stream
+FHE_STREAM_BITS = 1                          # flag of fhe_tfhe_stream_words_dev: every word AND 1
 
 
 # include/fhe_ntt_experimental.h: the persistent kernels' switches (exported, NOT part of the boundary)
@@ -267,6 +271,11 @@ def load_library():
     L.fhe_tlwe_gadget_packing_key_switch_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _vp, _sz, _sz, _sz, _uint, _vp, _sz, _vp]
     L.fhe_tglwe_box_expand_dev.argtypes = [_u64, _uint, _uint, _vp, _vp, _sz, _vp]
     L.fhe_tfhe_gadget_bootstrap_rows_dev.argtypes = [_u64, _uint, _uint, _uint, _uint, _vp, _vp, _uint, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tfhe_stream_words_dev.argtypes = [ctypes.c_char_p, _uint, _u64, _u64, _uint, _vp, _sz, _vp]
+    L.fhe_tlwe_encrypt_dev.argtypes = [_uint, ctypes.c_char_p, _u64, _vp, _vp, _vp, _uint, _uint, _vp, _sz, _vp]
+    L.fhe_tlwe_phase_dev.argtypes = [_uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_tglwe_encrypt_dev.argtypes = [_u64, _uint, ctypes.c_char_p, _u64, _vp, _vp, _sz, _vp, _uint, _uint, _vp, _sz, _vp]
+    L.fhe_tglwe_phase_dev.argtypes = [_u64, _uint, _vp, _vp, _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -640,6 +649,36 @@ def tfhe_gadget_bootstrap_rows_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_t
     """fhe_tfhe_gadget_bootstrap_dev with d_tables [batch][(k+1)][n]: a full TGLWE test vector per row"""
     _check(load_library().fhe_tfhe_gadget_bootstrap_rows_dev(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_tables, ks_log_beta, ks_l, d_ksk, d_in,
                                                              d_out, batch, stream))
+
+
+# ---- key generation, encryption and decryption (DESIGN.md §17; seed: 32 bytes, the ChaCha20 key) ---------------------------
+def _seed(seed):
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError(f"the seed is the 32-byte ChaCha20 key ({len(seed)} bytes given)")
+    return seed
+
+
+def tfhe_stream_words_dev(seed, purpose, first_row, row_words, d_out, rows, bits=False, stream=None):
+    """d_out [rows][row_words]: the stream words of rows first_row .. under `purpose`; bits: every word AND 1"""
+    _check(load_library().fhe_tfhe_stream_words_dev(_seed(seed), purpose, first_row, row_words, FHE_STREAM_BITS if bits else 0, d_out, rows, stream))
+
+
+def tlwe_encrypt_dev(n, seed, first_row, d_key, d_mu, d_cdt, m, log_scale, d_out, batch, stream=None):
+    _check(load_library().fhe_tlwe_encrypt_dev(n, _seed(seed), first_row, d_key, d_mu, d_cdt, m, log_scale, d_out, batch, stream))
+
+
+def tlwe_phase_dev(n, d_key, d_in, d_out, batch, stream=None):
+    _check(load_library().fhe_tlwe_phase_dev(n, d_key, d_in, d_out, batch, stream))
+
+
+def tglwe_encrypt_dev(n, k, seed, first_row, d_key, d_msg, msg_stride, d_cdt, m, log_scale, d_out, rows, stream=None):
+    """d_msg None: M = 0; msg_stride 0: one message polynomial for every row"""
+    _check(load_library().fhe_tglwe_encrypt_dev(n, k, _seed(seed), first_row, d_key, d_msg, msg_stride, d_cdt, m, log_scale, d_out, rows, stream))
+
+
+def tglwe_phase_dev(n, k, d_key, d_in, d_out, rows, stream=None):
+    _check(load_library().fhe_tglwe_phase_dev(n, k, d_key, d_in, d_out, rows, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

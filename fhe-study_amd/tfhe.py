@@ -30,6 +30,10 @@ over the C ABI.
     (no counterpart)                                   two-digit tree lookups: PackingKeySwitchKey,
                                                        packing_key_switch (TLWEs -> one TGLWE), box_expand, bootstrap_rows
                                                        (a test vector per row), tree_lookup (table2d[x][y], t bits each)
+    (no counterpart)                                   the client side: cdt_table, ClientKey (generate,
+                                                       bootstrapping_key, circuit_bootstrapping_key, packing_key_switch_key,
+                                                       encrypt_int / encrypt_bit, decrypt_int / decrypt_bit, phase) and the
+                                                       message builders of the keys (bsk_messages, ksk_messages, ..)
 """
 import numpy as np
 
@@ -1115,3 +1119,260 @@ def tree_lookup(btk, pksk, t_bits, table2d, x, y, nu=0, *, which=None):
     binding.tfhe_gadget_bootstrap_rows_dev(n, btk.k, btk.log_beta, btk.l, btk.n_lwe, btk.bsk.data_ptr(), tv.data_ptr(), btk.ks_log_beta, btk.ks_l,
                                            btk.ksk.data_ptr(), dx.data_ptr(), out.data_ptr(), batch)
     return TLWE(_from_dev(out).reshape(x.words.shape))
+
+
+# ---- key generation, encryption and decryption: the client side ------------------------------------------------
+def cdt_table(sigma):
+    """the error table of fhe_tlwe_encrypt_dev / fhe_tglwe_encrypt_dev for a discrete Gaussian of deviation sigma: strictly
+    increasing u64 thresholds below 2^63, entry i = round(2^63 P(magnitude <= i)) for P(0) ~ rho(0), P(j) ~ 2 rho(j), rho(x) =
+    exp(-x^2 / 2 sigma^2), j <= ceil(12 sigma).  The tail whose thresholds no longer differ at 2^-63 (or reach 2^63) is cut:
+    its mass, below 2^-62, falls on the last magnitude kept.  sigma = 0 gives the empty table (no error).  Computed with
+    50-digit decimals, so the rounding of the thresholds is the only error."""
+    import decimal
+    from fractions import Fraction
+
+    sigma = float(sigma)
+    if sigma < 0 or not np.isfinite(sigma):
+        raise ValueError(f"cdt_table: sigma={sigma} must be a finite number >= 0")
+    if sigma == 0:
+        return np.zeros(0, dtype=np.uint64)
+    top = int(np.ceil(12 * sigma))
+    if top > 1024:
+        raise ValueError(f"cdt_table: sigma={sigma} needs more than 1024 thresholds; use a smaller sigma with log_scale")
+    with decimal.localcontext() as ctx:
+        ctx.prec = 50
+        two_s2 = 2 * decimal.Decimal(sigma) ** 2
+        rho = [Fraction((-(decimal.Decimal(j) ** 2) / two_s2).exp()) for j in range(top + 1)]
+    weights = [rho[0]] + [2 * r for r in rho[1:]]
+    total, run, out = sum(weights), Fraction(0), []
+    for wgt in weights[:-1]:
+        run += wgt
+        thr = round(run / total * (1 << 63))
+        if thr >= 1 << 63 or (out and thr <= out[-1]):
+            break
+        out.append(thr)
+    return np.array(out, dtype=np.uint64)
+
+
+def _gadget_i64(log_beta, l):
+    """g_d = 2^(64 - b(d+1)) of DESIGN.md §11 as int64 words (2^63 wraps to the most negative value)"""
+    if not (1 <= log_beta and 1 <= l and log_beta * l <= 64):
+        raise ValueError(f"gadget (log_beta, l) = ({log_beta}, {l}) needs 1 <= log_beta, 1 <= l and log_beta l <= 64")
+    g = [1 << (64 - log_beta * (d + 1)) for d in range(l)]
+    return [x - (1 << 64) if x >= 1 << 63 else x for x in g]
+
+
+def _i64(x, like=None):
+    """0/1 key words (numpy u64 or a torch tensor) as a torch int64 tensor, on the device of `like` if given"""
+    torch = _torch()
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.uint64).view(np.int64))
+    return t if like is None else t.to(like.device)
+
+
+# The message builders: what each key encrypts, as int64 torch tensors on the device of the keys they are given (wrapping
+# arithmetic; no hot path: a key is built once).  Each returns one message per sample, in the order of the key's layout.
+def bsk_messages(s_glwe, s_lwe, log_beta, l):
+    """gadget BSK [n_lwe][(k+1)][l][(k+1)][N], k = 1 -> messages [n_lwe][2][l][N]: TGLev 0 of bit i holds -S bit_i g_d, TGLev 1
+    the constant polynomial bit_i g_d"""
+    torch = _torch()
+    S, bits = _i64(s_glwe), _i64(s_lwe, _i64(s_glwe))
+    g = torch.tensor(_gadget_i64(log_beta, l), dtype=torch.int64, device=S.device)
+    mu = torch.zeros((len(bits), 2, l, len(S)), dtype=torch.int64, device=S.device)
+    bg = bits[:, None] * g[None, :]
+    mu[:, 0] = -(bg[:, :, None] * S[None, None, :])
+    mu[:, 1, :, 0] = bg
+    return mu
+
+
+def ksk_messages(s_in, log_beta, l):
+    """gadget KSK [n_in][l][n_out + 1] -> message words [n_in][l]: s_in[i] g_d"""
+    torch = _torch()
+    s = _i64(s_in)
+    return s[:, None] * torch.tensor(_gadget_i64(log_beta, l), dtype=torch.int64, device=s.device)[None, :]
+
+
+def pfksk_messages(s_glwe, log_beta, l):
+    """PFKSK [(k+1)][k N + 1][l][(k+1)][N], k = 1 -> messages [2][N + 1][l][N]: with K~ = (-S_0 .. -S_{N-1}, 1), entry [0][j][d]
+    holds -S K~_j g_d and entry [1][j][d] the constant polynomial K~_j g_d"""
+    torch = _torch()
+    S = _i64(s_glwe)
+    g = torch.tensor(_gadget_i64(log_beta, l), dtype=torch.int64, device=S.device)
+    kt = torch.cat([-S, torch.ones(1, dtype=torch.int64, device=S.device)])
+    sc = kt[:, None] * g[None, :]
+    mu = torch.zeros((2, len(S) + 1, l, len(S)), dtype=torch.int64, device=S.device)
+    mu[0] = -(sc[:, :, None] * S[None, None, :])
+    mu[1, :, :, 0] = sc
+    return mu
+
+
+def pksk_messages(s_in, n, log_beta, l):
+    """PKSK [n_in][l][(k+1)][N] -> messages [n_in][l][N]: the constant polynomial K_in[j] g_d"""
+    torch = _torch()
+    s = _i64(s_in)
+    mu = torch.zeros((len(s), l, n), dtype=torch.int64, device=s.device)
+    mu[:, :, 0] = ksk_messages(s, log_beta, l)
+    return mu
+
+
+class ClientKey:
+    """Both secrets of the §11-§16 evaluator, resident on the device, and everything made from them: evaluation keys,
+    ciphertexts, phases.  k = 1.  The 32-byte seed is the whole secret: every key bit, mask word and error
+    sample is a word of the ChaCha20 stream it keys, addressed by (purpose, row index).
+
+    Row indices.  Secret keys: KEY row 0 is the LWE key, KEY row 1 the GLWE key.  Samples (MASK and ERR rows, LWE and TGLWE
+    alike) are dealt out so that no two samples of one seed share a row:
+        [0, 2^56)                       fresh encryptions, in the order of the encrypt_* calls (the key keeps the next row)
+        [1 2^56 + slot 2^40, ..)        bootstrapping_key: the n_lwe 2 l TGLWE rows of the BSK, then the N ks_l LWE rows of the KSK
+        [2 2^56 + slot 2^40, ..)        circuit_bootstrapping_key: the 2 (N + 1) pf_l TGLWE rows of the PFKSK
+        [3 2^56 + slot 2^40, ..)        packing_key_switch_key: the n_lwe l TGLWE rows of the PKSK
+    A builder refuses a `slot` (0 <= slot < 2^16) it has already used on this object: a second key of the same kind needs a
+    slot of its own.  A ClientKey regenerated from the same seed starts its counters again: do not encrypt fresh data under
+    both.  noise = (sigma, log_scale): errors are a discrete Gaussian of deviation sigma (cdt_table) times 2^log_scale."""
+
+    ENCRYPT_ROWS = 1 << 56
+    BSK_BASE, PFKSK_BASE, PKSK_BASE = 1 << 56, 2 << 56, 3 << 56
+    SLOT_ROWS = 1 << 40
+
+    def __init__(self, seed, n, n_lwe, s_lwe, s_glwe, noise):
+        self.seed, self.n, self.k, self.n_lwe, self.noise = bytes(seed), n, 1, n_lwe, noise
+        self.s_lwe, self.s_glwe = s_lwe, s_glwe
+        self._next_row, self._slots, self._cdt = 0, set(), {}
+
+    @classmethod
+    def generate(cls, seed, n, n_lwe, noise=(3.2, 0)):
+        """both binary secrets from the KEY stream of `seed` (32 bytes): s_lwe [n_lwe] and s_glwe [n], int64 device tensors"""
+        torch = _torch()
+        if n_lwe < 1 or n < 256 or n > 4096 or n & (n - 1):
+            raise binding.FheError(binding.FHE_E_INVALID, f"ClientKey: needs n_lwe >= 1 and n a power of two in [256, 4096] (n={n}, n_lwe={n_lwe})")
+        s_lwe = torch.empty(n_lwe, dtype=torch.int64, device="cuda")
+        s_glwe = torch.empty(n, dtype=torch.int64, device="cuda")
+        binding.tfhe_stream_words_dev(seed, binding.FHE_STREAM_KEY, 0, n_lwe, s_lwe.data_ptr(), 1, bits=True)
+        binding.tfhe_stream_words_dev(seed, binding.FHE_STREAM_KEY, 1, n, s_glwe.data_ptr(), 1, bits=True)
+        torch.cuda.synchronize()
+        return cls(seed, n, n_lwe, s_lwe, s_glwe, noise)
+
+    # -- plumbing ---------------------------------------------------------------------------------------------------
+    def _noise(self, noise):
+        """-> (device table or None, m, log_scale)"""
+        sigma, log_scale = self.noise if noise is None else noise
+        if sigma not in self._cdt:
+            tab = cdt_table(sigma)
+            self._cdt[sigma] = (_to_dev(tab) if len(tab) else None, len(tab))
+        d, m = self._cdt[sigma]
+        return d, m, int(log_scale)
+
+    def _take_slot(self, kind, base, slot):
+        if not 0 <= int(slot) < 1 << 16:
+            raise ValueError(f"{kind}: slot must be in [0, 2^16)")
+        if (kind, int(slot)) in self._slots:
+            raise ValueError(f"{kind}: slot {slot} of this seed is already used; a second key needs a slot of its own")
+        self._slots.add((kind, int(slot)))
+        return base + int(slot) * self.SLOT_ROWS
+
+    def _tglwe_rows(self, first_row, messages, noise):
+        """messages [rows][N] (an int64 device tensor of any shape [..][N]) -> TGLWE samples [rows][2][N] on rows first_row .."""
+        torch = _torch()
+        d_cdt, m, log_scale = self._noise(noise)
+        msg = messages.reshape(-1, self.n).contiguous()
+        out = torch.empty((msg.shape[0], 2, self.n), dtype=torch.int64, device="cuda")
+        binding.tglwe_encrypt_dev(self.n, 1, self.seed, first_row, self.s_glwe.data_ptr(), msg.data_ptr(), self.n, d_cdt.data_ptr() if m else None, m,
+                                  log_scale, out.data_ptr(), msg.shape[0])
+        return out
+
+    def _tlwe_rows(self, first_row, s, mu, noise):
+        """message words mu [rows] (int64 device tensor) -> LWE samples [rows][len(s) + 1] under s"""
+        torch = _torch()
+        d_cdt, m, log_scale = self._noise(noise)
+        mu = mu.reshape(-1).contiguous()
+        out = torch.empty((mu.shape[0], len(s) + 1), dtype=torch.int64, device="cuda")
+        binding.tlwe_encrypt_dev(len(s), self.seed, first_row, s.data_ptr(), mu.data_ptr(), d_cdt.data_ptr() if m else None, m, log_scale,
+                                 out.data_ptr(), mu.shape[0])
+        return out
+
+    # -- evaluation keys --------------------------------------------------------------------------------------------
+    def bootstrapping_key(self, bsk, ksk, noise=None, slot=0):
+        """bsk = (log_beta, l), ksk = (ks_log_beta, ks_l) -> the gadget BootstrappingKey: the BSK of the LWE key bits under the
+        GLWE key, and the KSK from the extracted GLWE key back to the LWE key"""
+        (b, l), (ks_b, ks_l) = bsk, ksk
+        if binding.tfhe_gadget_bsk_prepared_words(self.n, 1, b, l, self.n_lwe) == 0:
+            raise binding.FheError(binding.FHE_E_INVALID, f"no gadget bootstrapping key for n={self.n}, (log_beta, l) = ({b}, {l})")
+        _gadget_i64(ks_b, ks_l)
+        first = self._take_slot("bootstrapping_key", self.BSK_BASE, slot)
+        rows = self._tglwe_rows(first, bsk_messages(self.s_glwe, self.s_lwe, b, l), noise)
+        kk = self._tlwe_rows(first + self.n_lwe * 2 * l, self.s_lwe, ksk_messages(self.s_glwe, ks_b, ks_l), noise)
+        return BootstrappingKey(self.n, 1, l, self.n_lwe, rows.reshape(self.n_lwe, 2, l, 2, self.n), kk.reshape(self.n, ks_l, self.n_lwe + 1),
+                                ks_l=ks_l, log_beta=b, ks_log_beta=ks_b)
+
+    def circuit_bootstrapping_key(self, btk, cb, pf, noise=None, slot=0):
+        """btk: a gadget BootstrappingKey of this key; cb = (cb_log_beta, cb_l), pf = (pf_log_beta, pf_l) -> CircuitBootstrappingKey
+        with a PFKSK built here"""
+        (cb_b, cb_l), (pf_b, pf_l) = cb, pf
+        if (btk.n, btk.k, btk.n_lwe) != (self.n, 1, self.n_lwe):
+            raise ValueError("circuit_bootstrapping_key: btk is not a key of this ClientKey's shape")
+        if binding.tfhe_pfksk_words(self.n, 1, pf_b, pf_l) == 0:
+            raise binding.FheError(binding.FHE_E_INVALID, f"no private key switch for n={self.n}, (pf_log_beta, pf_l) = ({pf_b}, {pf_l})")
+        first = self._take_slot("circuit_bootstrapping_key", self.PFKSK_BASE, slot)
+        rows = self._tglwe_rows(first, pfksk_messages(self.s_glwe, pf_b, pf_l), noise)
+        return CircuitBootstrappingKey(btk, rows.reshape(2, self.n + 1, pf_l, 2, self.n), cb_b, cb_l, pf_b, pf_l)
+
+    def packing_key_switch_key(self, pks, noise=None, slot=0):
+        """pks = (log_beta, l) -> the PackingKeySwitchKey from the LWE key to the GLWE key"""
+        b, l = pks
+        if binding.tfhe_pksk_words(self.n, 1, self.n_lwe, b, l) == 0:
+            raise binding.FheError(binding.FHE_E_INVALID, f"no packing key switch for n={self.n}, n_in={self.n_lwe}, (log_beta, l) = ({b}, {l})")
+        first = self._take_slot("packing_key_switch_key", self.PKSK_BASE, slot)
+        rows = self._tglwe_rows(first, pksk_messages(self.s_lwe, self.n, b, l), noise)
+        return PackingKeySwitchKey(rows.reshape(self.n_lwe, l, 2, self.n), b, l)
+
+    # -- ciphertexts ------------------------------------------------------------------------------------------------
+    def encrypt_words(self, mu, noise=None):
+        """torus words mu (any shape) -> TLWE of the same leading shape under the LWE key, on fresh rows"""
+        torch = _torch()
+        w = np.ascontiguousarray(mu, dtype=np.uint64)
+        if self._next_row + w.size > self.ENCRYPT_ROWS:
+            raise ValueError("encrypt: this seed's 2^56 encryption rows are used up")
+        out = self._tlwe_rows(self._next_row, self.s_lwe, _to_dev(w.reshape(-1)), noise)
+        self._next_row += w.size
+        return TLWE(_from_dev(out).reshape(w.shape + (self.n_lwe + 1,)))
+
+    def encrypt_int(self, x, t_bits, noise=None):
+        """values in [0, 2^t_bits) in §14's encoding (encode_int): phase x 2^(63 - t_bits) + e, the top bit padding"""
+        return self.encrypt_words(encode_int(x, t_bits), noise)
+
+    def encrypt_bit(self, bit, noise=None, *, msb=False):
+        """bits in §13's gate encoding, phase +-2^61; msb=True: phase bit 2^63, what circuit_bootstrap takes (§12)"""
+        bits = np.asarray(bit).astype(bool)
+        words = np.where(bits, np.uint64(1 << 63), np.uint64(0)) if msb else np.where(bits, np.uint64(MU), np.uint64((1 << 64) - MU))
+        return self.encrypt_words(words.astype(np.uint64), noise)
+
+    def phase(self, c):
+        """b - <a, s> of a TLWE (under the LWE key, or under the extracted GLWE key when its dimension is n != n_lwe), or
+        B - A S of a TGLWE: u64 words"""
+        torch = _torch()
+        if isinstance(c, TGLWE):
+            x = c.packed()
+            d = _to_dev(x.reshape(-1, 2, self.n))
+            out = torch.empty((d.shape[0], self.n), dtype=torch.int64, device="cuda")
+            binding.tglwe_phase_dev(self.n, 1, self.s_glwe.data_ptr(), d.data_ptr(), out.data_ptr(), d.shape[0])
+            return _from_dev(out).reshape(x.shape[:-2] + (self.n,))
+        w = c.words if isinstance(c, TLWE) else np.asarray(c, dtype=np.uint64)
+        s = self.s_lwe if w.shape[-1] - 1 == self.n_lwe else self.s_glwe
+        if w.shape[-1] - 1 != len(s):
+            raise ValueError(f"phase: a TLWE of dimension {w.shape[-1] - 1} is under neither key ({self.n_lwe}, {self.n})")
+        d = _to_dev(w.reshape(-1, len(s) + 1))
+        out = torch.empty(d.shape[0], dtype=torch.int64, device="cuda")
+        binding.tlwe_phase_dev(len(s), s.data_ptr(), d.data_ptr(), out.data_ptr(), d.shape[0])
+        return _from_dev(out).reshape(w.shape[:-1])
+
+    def decrypt_int(self, c, t_bits, *, padding=False):
+        """round(phase / Delta) mod 2^t_bits, Delta = 2^(63 - t_bits) (padding=True: mod 2^(t_bits + 1), the padding bit kept)"""
+        p = self.phase(c)
+        v = ((p >> np.uint64(62 - t_bits)) + np.uint64(1)) >> np.uint64(1)
+        return v.astype(np.int64) & ((2 << t_bits) - 1 if padding else (1 << t_bits) - 1)
+
+    def decrypt_bit(self, c, *, msb=False):
+        """gate encoding: 1 where the centred phase is positive; msb=True: round(phase / 2^63) mod 2"""
+        p = self.phase(c)
+        if msb:
+            return ((((p >> np.uint64(62)) + np.uint64(1)) >> np.uint64(1)) & np.uint64(1)).astype(np.int64)
+        return (p.view(np.int64) > 0).astype(np.int64)

@@ -499,6 +499,46 @@ int fhe_tfhe_gadget_bootstrap_rows_dev(uint64_t n, unsigned k, unsigned log_beta
                                        unsigned ks_l, const void *d_ksk, const void *d_in, void *d_out, size_t batch,
                                        void *hip_stream);
 
+/* ---- TFHE key generation, encryption and decryption: the client side (definitions in DESIGN.md §17) ----
+ * Exact and independent of launch geometry; u64 wrapping words.  `seed` is a HOST pointer to 32 bytes, the ChaCha20 key
+ * (RFC 8439: 32-bit block counter, 96-bit nonce, 20 rounds); it is the whole secret.  A row (one LWE sample, one TGLWE
+ * sample, one secret key) has the nonce (purpose, row index lo, row index hi); block c of a row (counter c, from 0) gives
+ * 8 stream words, word j = output u32 word 2j | output u32 word 2j + 1 << 32; stream word i is word i mod 8 of block
+ * i div 8.  Mask word i of a row is FHE_STREAM_MASK word i, secret-key bit i is FHE_STREAM_KEY word i AND 1, error sample i
+ * is drawn from FHE_STREAM_ERR word i.  Two samples of one seed must never share a row index.
+ *   errors   d_cdt [m] strictly increasing thresholds below 2^63, m <= 1024 (m = 0: no error, d_cdt may be NULL).  For a
+ *            stream word u, r = u >> 1: the magnitude is the number of i with cdt[i] <= r, negative when u AND 1; the
+ *            error word is the signed value << log_scale (0 <= log_scale <= 63), wrapping.  The table is checked on a host
+ *            copy in every call that takes one, which synchronises hip_stream.
+ *   keys     d_key holds 0/1 words; only bit 0 of a word is read.
+ *   fhe_tfhe_stream_words_dev  d_out [rows][row_words] = stream words 0 .. row_words - 1 of rows first_row .. of `purpose`
+ *            (1 <= row_words <= 2^35, i.e. at most 2^32 blocks); FHE_STREAM_BITS: every word AND 1 (a secret key)
+ *   fhe_tlwe_encrypt_dev       d_out [batch][n + 1], row r = [a_0 .. a_{n-1}, b] with a = the mask words of row first_row + r
+ *            and b = sum a_i s_i + d_mu[r] + e (d_mu NULL: 0), e from error sample 0 of the row; any n >= 1; one fused
+ *            kernel.
+ *   fhe_tlwe_phase_dev         d_out [batch] = b - sum a_i s_i of d_in [batch][n + 1]
+ *   fhe_tglwe_encrypt_dev      k = 1, 2^8 <= n = 2^L <= 2^12.  d_out [rows][(k+1)][n], row r = (A, A S + M_r + E) in
+ *            T64[X]/(X^n + 1) with A the n mask words and E the n error samples of row first_row + r; M_r = d_msg +
+ *            r msg_stride (msg_stride = 0: one message for every row, otherwise >= n; d_msg NULL: M = 0)
+ *   fhe_tglwe_phase_dev        d_out [rows][n] = B - A S of d_in [rows][(k+1)][n]
+ * Every device buffer of these five entry points needs 8-byte alignment and nothing more (LWE rows hold n + 1 words, and a
+ * msg_stride may be odd).  Anything outside these ranges, first_row + rows past 2^64, and an output that overlaps the key,
+ * the messages or the table is FHE_E_INVALID and writes nothing; batch (rows) = 0 is a no-op. */
+#define FHE_STREAM_MASK 1u
+#define FHE_STREAM_ERR 2u
+#define FHE_STREAM_KEY 3u
+#define FHE_STREAM_BITS 1u /* flag of fhe_tfhe_stream_words_dev */
+int fhe_tfhe_stream_words_dev(const uint8_t *seed, unsigned purpose, uint64_t first_row, uint64_t row_words, unsigned flags,
+                              void *d_out, size_t rows, void *hip_stream);
+int fhe_tlwe_encrypt_dev(unsigned n, const uint8_t *seed, uint64_t first_row, const void *d_key, const void *d_mu,
+                         const void *d_cdt, unsigned m, unsigned log_scale, void *d_out, size_t batch, void *hip_stream);
+int fhe_tlwe_phase_dev(unsigned n, const void *d_key, const void *d_in, void *d_out, size_t batch, void *hip_stream);
+int fhe_tglwe_encrypt_dev(uint64_t n, unsigned k, const uint8_t *seed, uint64_t first_row, const void *d_key,
+                          const void *d_msg, size_t msg_stride, const void *d_cdt, unsigned m, unsigned log_scale,
+                          void *d_out, size_t rows, void *hip_stream);
+int fhe_tglwe_phase_dev(uint64_t n, unsigned k, const void *d_key, const void *d_in, void *d_out, size_t rows,
+                        void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
