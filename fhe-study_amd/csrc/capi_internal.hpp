@@ -75,6 +75,15 @@ static inline bool fhe_misaligned(const void *p) { return (reinterpret_cast<uint
             return fhe_fail(FHE_E_INVALID, #p " must be 16-byte aligned (got %p)", (const void *)(p)); \
     } while (0)
 
+// argument checks shared by the entry points: do two device ranges intersect (an empty or NULL one never does), does a b
+// stay within limit, and the extent in words whose size in bytes still fits 61 bits
+static inline bool overlaps(const void *a, fhe::u64 abytes, const void *b, fhe::u64 bbytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && abytes && bbytes && x < y + bbytes && y < x + abytes;
+}
+static inline bool mul_fits(fhe::u64 a, fhe::u64 b, fhe::u64 limit) { return b == 0 || a <= limit / b; }
+constexpr fhe::u64 kWordLimit = ~0ull >> 4;
+
 // grid of a grid-stride element-wise kernel: at most 16 blocks of 256 per CU
 static inline unsigned fhe_ew_grid(fhe::u64 count) {
     fhe::u64 g = (count + 255) / 256;

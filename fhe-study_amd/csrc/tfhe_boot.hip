@@ -36,7 +36,22 @@
 //   v[i] = T_h[q], h = i mod F, q = (i - h + half) >> (L - t), and 0 - T_h[0] where q = P (never at nu = L - t)
 // so after the one rotation coefficient h holds T_h[x] (0 - T_h[x - P] with the padding bit set).  A row is also invalid if
 // lut + F > lut_count; all F of its output rows are zero.  Output [F][batch][n_lwe + 1]: function h of row m is row h batch + m.
+//
+// How the file is put together.  Device side: every blind rotation starts from ACC_0[m] = rot(v_m, b~_m) and shift[m][j] =
+// (2N - a~_{m,j}) mod 2N, written by one element-wise body (br_init_body) over a row source that says what names row m (its
+// index or its decoded descriptor), whether it is valid, what its LWE word j is and what coefficient i of its test vector is: TableRows (one table or one a row; tfhe_br_init_kernel),
+// CbLevels (§12), GateRows<MUX> (§13), LutRows (§14).  Each kernel is a thin instantiation; tfhe_lut_many_init_kernel (§15)
+// keeps its organisation by row and shares lut_row_ok / lut_word / lut_coeff with LutRows.  nega_sign / nega_read and rot_shift
+// are the negacyclic read and the shift wherever they occur.  The LWE key switch is one tile (tlwe_ks_kernel) over a digit
+// policy: BitDigit (beta = 2) and SignedDigit (§11).  extract0_word is the sample extraction at h = 0 that tfhe_cb_extract_kernel
+// and tfhe_mux_extract_kernel combine; tfhe_many_extract_kernel scatters (one read, F stores) and states the rule itself.
+// Host side: launch() is a timed launch with its check; ks_grid, bsk_bytes, ksk_bytes and overlaps_any are the limits and
+// extents every entry point uses.  A gadget bootstrap is a BootShape (a BrShape and the key switch's gadget) and three stages: check_boot, boot_workspace (slots 7, 8,
+// 5), and after the entry point's own init launch finish_boot (CMux steps, the extraction it names, key switch).
 #include <algorithm>
+#include <initializer_list>
+#include <cstdio>
+#include <type_traits>
 
 #include "capi_internal.hpp"
 #include "digit32.hpp"
@@ -46,24 +61,69 @@ using fhe::u64;
 
 namespace fhe {
 
-__device__ __forceinline__ u32 mod_switch_2n(u64 w, u32 L) { return (u32)((((w >> (62u - L)) + 1u) >> 1) & ((2ull << L) - 1u)); }
+// ms_nu(w) = round(w / 2^(63 - L + nu)) 2^nu mod 2N: the mod switch with its nu low bits forced to 0, so a row's
+// accumulator is rotated by a multiple of F = 2^nu and coefficients 0 .. F - 1 of the result all come from the box the
+// phase fell into.  nu = 0 is the plain mod switch.
+__device__ __forceinline__ u32 mod_switch_nu(u64 w, u32 L, u32 nu) {
+    return (u32)(((((w >> (62u - L + nu)) + 1u) >> 1) << nu) & ((2ull << L) - 1u));
+}
+__device__ __forceinline__ u32 mod_switch_2n(u64 w, u32 L) { return mod_switch_nu(w, L, 0); }
+// the CMux step's exponent for the mask word w: (2N - ms_nu(w)) mod 2N
+__device__ __forceinline__ u32 rot_shift(u64 w, u32 L, u32 nu = 0) {
+    return (u32)(((2ull << L) - mod_switch_nu(w, L, nu)) & ((2ull << L) - 1));
+}
+// the negacyclic extension at index j in [0, 2N): x is the word at j mod N, negated in the second half
+__device__ __forceinline__ u64 nega_sign(u64 x, u64 j, u32 L) { return ((j >> L) & 1u) ? 0ull - x : x; }
+__device__ __forceinline__ u64 nega_read(const u64 *__restrict__ row, u64 j, u32 L) { return nega_sign(row[j & ((1ull << L) - 1)], j, L); }
 
-// ACC_0[b] = rot(table, b~_b) and shift[b][j] = (2N - a~_j) mod 2N, one grid-stride pass over both
-__global__ __launch_bounds__(256) void tfhe_br_init_kernel(const u64 *__restrict__ lwe, const u64 *__restrict__ table, u64 *__restrict__ acc,
-                                                           u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L, u64 batch) {
-    const u64 N = 1ull << L, k1N = (u64)k1 * N, na = batch * k1N, total = na + batch * n_lwe;
+// ---- the init of a blind rotation ----------------------------------------------------------------------------------------
+// ACC_0[m] = rot(v_m, b~_m) and shift[m][j] = (2N - a~_{m,j}) mod 2N, one grid-stride pass over both; an invalid row gets
+// zeros and zero shifts and reads nothing.  A row source Src says where row m comes from:
+//   row(m)            what names row m: its index, or its decoded descriptor
+//   valid(row)        is the row valid?
+//   word(row, j)      LWE word j of the row, j = n_lwe the body
+//   coeff(row, c, i)  coefficient i of component c of its test vector v_m (never formed in memory)
+//   BODY_ONLY         v_m has zero mask components: they are written without reading anything
+//   DESCRIPTOR        row(m) reads a descriptor: it is decoded, and valid() asked, once per element ahead of the split
+template <class Src>
+__device__ __forceinline__ void br_init_body(const Src s, u64 *__restrict__ acc, u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L, u64 rows) {
+    const u64 N = 1ull << L, k1N = (u64)k1 * N, na = rows * k1N, total = na + rows * n_lwe;
     const u64 stride = (u64)gridDim.x * 256;
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 md = Src::DESCRIPTOR ? (i < na ? i / k1N : (i - na) / n_lwe) : 0;      // a descriptor is decoded once, ahead of the split
+        const auto rd = s.row(md);
+        const bool ok = Src::DESCRIPTOR ? s.valid(rd) : true;
         if (i < na) {
-            const u64 b = i / k1N, r = i - b * k1N;
-            const u64 j = (r & (N - 1)) + mod_switch_2n(lwe[b * (n_lwe + 1ull) + n_lwe], L);
-            const u64 x = table[(r >> L) * N + (j & (N - 1))];
-            acc[i] = ((j >> L) & 1u) ? 0ull - x : x;
+            const u64 m = Src::DESCRIPTOR ? md : i / k1N, r = i - m * k1N, c = r >> L;
+            const auto row = Src::DESCRIPTOR ? rd : s.row(m);
+            if ((Src::BODY_ONLY && c + 1 < k1) || !ok) {
+                acc[i] = 0;
+            } else {
+                const u64 j = (r & (N - 1)) + mod_switch_2n(s.word(row, n_lwe), L);
+                acc[i] = nega_sign(s.coeff(row, c, j & (N - 1)), j, L);
+            }
         } else {
-            const u64 q = i - na, b = q / n_lwe;
-            shift[q] = (u32)((2 * N - mod_switch_2n(lwe[b * (n_lwe + 1ull) + (q - b * n_lwe)], L)) & (2 * N - 1));
+            const u64 q = i - na, m = Src::DESCRIPTOR ? md : q / n_lwe;
+            shift[q] = ok ? rot_shift(s.word(Src::DESCRIPTOR ? rd : s.row(m), (u32)(q - m * n_lwe)), L) : 0u;
         }
     }
+}
+
+// rows of lwe [rows][n_lwe + 1]; the test vector of row m is the TGLWE at table + m tstride (all k + 1 components, mask
+// rows included): tstride = 0 is one table for the batch, tstride = (k+1) N a table per row
+struct TableRows {
+    const u64 *__restrict__ lwe, *__restrict__ table;
+    u64 tstride;
+    u32 n_lwe, L;
+    static constexpr bool BODY_ONLY = false, DESCRIPTOR = false;
+    __device__ __forceinline__ u64 row(u64 m) const { return m; }
+    __device__ __forceinline__ bool valid(u64) const { return true; }
+    __device__ __forceinline__ u64 word(u64 m, u32 j) const { return lwe[m * (n_lwe + 1ull) + j]; }
+    __device__ __forceinline__ u64 coeff(u64 m, u64 c, u64 i) const { return table[m * tstride + (c << L) + i]; }
+};
+__global__ __launch_bounds__(256) void tfhe_br_init_kernel(const u64 *__restrict__ lwe, const u64 *__restrict__ table, u64 tstride,
+                                                           u64 *__restrict__ acc, u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L, u64 batch) {
+    br_init_body(TableRows{lwe, table, tstride, n_lwe, L}, acc, shift, n_lwe, k1, L, batch);
 }
 
 // the composed step (shapes outside the 27-bit form): d[b] = rot(acc[b], e_b) - acc[b], e_b = shift[b * stride]
@@ -74,8 +134,7 @@ __global__ __launch_bounds__(256) void tfhe_rotdiff_kernel(const u64 *__restrict
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
         const u64 b = i / k1N, r = i - b * k1N;
         const u64 j = (r & (N - 1)) + shift[b * stride_s];
-        const u64 x = acc[b * k1N + (r >> L) * N + (j & (N - 1))];
-        d[i] = (((j >> L) & 1u) ? 0ull - x : x) - acc[i];
+        d[i] = nega_read(acc + b * k1N + (r >> L) * N, j, L) - acc[i];
     }
 }
 __global__ __launch_bounds__(256) void tfhe_add_kernel(u64 *__restrict__ acc, const u64 *__restrict__ p, u64 count) {
@@ -100,13 +159,25 @@ __global__ __launch_bounds__(256) void tglwe_sample_extract_kernel(const u64 *__
     }
 }
 
-// TLWE::key_switch (tlwe.rs:101-111), beta = 2:  out[b] = (0 .. 0, b_b) - sum_i sum_{d<l} bit_{l-1-d}(a_{b,i}) ksk[i][d]
+// word r of the extraction at h = 0: a_c[0] at r = c N, -a_c[N - j] at r = c N + j, and b[0] + body_add at r = k N, with
+// read(at) the word at index `at` of the TGLWE (or the sum of that word over several), under one decision
+template <class Read>
+__device__ __forceinline__ u64 extract0_word(u64 r, u64 kN, u32 L, u64 body_add, Read read) {
+    if (r == kN) return read(kN) + body_add;
+    const u64 N = 1ull << L, c = r >> L, j = r & (N - 1);
+    return j == 0 ? read(c * N) : 0ull - read(c * N + N - j);
+}
+
+// TLWE key switch:  out[b] = (0 .. 0, b_b) - sum_i sum_{d<l} digit_d(a_{b,i}) ksk[i][d]
 // A workgroup owns KS_TB ciphertexts and KS_TH output columns: every KSK word it reads serves all KS_TB ciphertexts (the
 // key is n_in l (n_out + 1) words, 331 MB at n_in = 1024, l = 64, n_out = 630).  The ciphertext words are uniform across
-// the workgroup, so the digit of a (ciphertext, level) is one select per lane.
+// the workgroup, so the digit of a (ciphertext, level) is one operation per lane.  A digit policy says what a digit is:
+//   prepare(w)        the word as the digits are taken from it
+//   term(w, d, kv)    digit_d(w) kv, w prepared
 constexpr int KS_TB = 32, KS_TH = 64;
-__global__ __launch_bounds__(KS_TH) void tlwe_key_switch_kernel(const u64 *__restrict__ ksk, const u64 *__restrict__ in, u64 *__restrict__ out,
-                                                                u32 n_in, u32 n_out, u32 l, u64 batch, u32 cblocks) {
+template <class Digit>
+__global__ __launch_bounds__(KS_TH) void tlwe_ks_kernel(const u64 *__restrict__ ksk, const u64 *__restrict__ in, u64 *__restrict__ out, u32 n_in,
+                                                        u32 n_out, u32 l, u64 batch, u32 cblocks, const Digit dg) {
     const u64 tile = blockIdx.x / cblocks;
     const u32 o = (blockIdx.x - (u32)tile * cblocks) * KS_TH + threadIdx.x;
     const u64 b0 = tile * KS_TB, row = (u64)n_out + 1, irow = (u64)n_in + 1;
@@ -120,13 +191,12 @@ __global__ __launch_bounds__(KS_TH) void tlwe_key_switch_kernel(const u64 *__res
     for (u32 i = 0; i < n_in; i++) {
         u64 w[KS_TB];
 #pragma unroll
-        for (int t = 0; t < KS_TB; t++) w[t] = (u32)t < live ? src[t * irow + i] : 0ull;
+        for (int t = 0; t < KS_TB; t++) w[t] = dg.prepare((u32)t < live ? src[t * irow + i] : 0ull);
         const u64 *__restrict__ kr = kc + (u64)i * l * row;
         for (u32 d = 0; d < l; d++) {
             const u64 kv = kr[(u64)d * row];
-            const u32 sh = l - 1u - d;
 #pragma unroll
-            for (int t = 0; t < KS_TB; t++) acc[t] += ((w[t] >> sh) & 1u) ? kv : 0ull;
+            for (int t = 0; t < KS_TB; t++) acc[t] += dg.term(w[t], d, kv);
         }
     }
     if (!on) return;
@@ -134,6 +204,13 @@ __global__ __launch_bounds__(KS_TH) void tlwe_key_switch_kernel(const u64 *__res
     for (int t = 0; t < KS_TB; t++)
         if ((u32)t < live) out[(b0 + t) * row + o] = (o == n_out ? src[t * irow + n_in] : 0ull) - acc[t];
 }
+
+// TLWE::key_switch (tlwe.rs:101-111), beta = 2: digit_d(w) = bit l - 1 - d of w, a select of the key word
+struct BitDigit {
+    u32 l;
+    __device__ __forceinline__ u64 prepare(u64 w) const { return w; }
+    __device__ __forceinline__ u64 term(u64 w, u32 d, u64 kv) const { return ((w >> (l - 1u - d)) & 1u) ? kv : 0ull; }
+};
 
 // ---- the base-2^b gadget ----------------------------------------------------------------------------
 // digit_d(w) = ((w + cadd) >> (64 - b (d+1))) & (2^b - 1)) - 2^(b-1), cadd = gadget_cadd(b, l); 1 <= b <= 64, b l <= 64
@@ -154,44 +231,21 @@ __global__ __launch_bounds__(256) void tn_gadget_decompose_kernel(const u64 *__r
     }
 }
 
-// out[b] = (0 .. 0, b_b) - sum_i sum_{d<l} digit_d(a_{b,i}) ksk[i][d], every product a wrapping multiply by the signed
-// digit; tiles as tlwe_key_switch_kernel (every KSK word read once per KS_TB ciphertexts)
-__global__ __launch_bounds__(KS_TH) void tlwe_gadget_key_switch_kernel(const u64 *__restrict__ ksk, const u64 *__restrict__ in,
-                                                                       u64 *__restrict__ out, u32 n_in, u32 n_out, u32 lb, u32 l,
-                                                                       u64 cadd, u64 batch, u32 cblocks) {
-    const u64 tile = blockIdx.x / cblocks;
-    const u32 o = (blockIdx.x - (u32)tile * cblocks) * KS_TH + threadIdx.x;
-    const u64 b0 = tile * KS_TB, row = (u64)n_out + 1, irow = (u64)n_in + 1;
-    const u32 live = (u32)min((u64)KS_TB, batch - b0);
-    const bool on = o <= n_out;
-    const u64 *__restrict__ kc = ksk + (on ? o : n_out);        // idle lanes read a valid column and store nothing
-    const u64 *__restrict__ src = in + b0 * irow;
-    u64 acc[KS_TB];
-#pragma unroll
-    for (int t = 0; t < KS_TB; t++) acc[t] = 0;
-    for (u32 i = 0; i < n_in; i++) {
-        u64 w[KS_TB];
-#pragma unroll
-        for (int t = 0; t < KS_TB; t++) w[t] = ((u32)t < live ? src[t * irow + i] : 0ull) + cadd;
-        const u64 *__restrict__ kr = kc + (u64)i * l * row;
-        for (u32 d = 0; d < l; d++) {
-            const u64 kv = kr[(u64)d * row];
-            const u32 sh = 64u - lb * (d + 1u);
-            const u64 mask = ~0ull >> (64u - lb), half = 1ull << (lb - 1u);
-#pragma unroll
-            for (int t = 0; t < KS_TB; t++) acc[t] += ((w[t] >> sh & mask) - half) * kv;
-        }
+// the key switch by signed digits: the word carries cadd, every product is a wrapping multiply by the signed digit
+struct SignedDigit {
+    u32 lb;
+    u64 cadd;
+    __device__ __forceinline__ u64 prepare(u64 w) const { return w + cadd; }
+    __device__ __forceinline__ u64 term(u64 w, u32 d, u64 kv) const {
+        const u64 mask = ~0ull >> (64u - lb), half = 1ull << (lb - 1u);
+        return ((w >> (64u - lb * (d + 1u)) & mask) - half) * kv;
     }
-    if (!on) return;
-#pragma unroll
-    for (int t = 0; t < KS_TB; t++)
-        if ((u32)t < live) out[(b0 + t) * row + o] = (o == n_out ? src[t * irow + n_in] : 0ull) - acc[t];
-}
+};
 
 // ---- circuit bootstrapping ---------------------------------------------------------------------------
 // Private functional key switch, k = 1: out[m][r] = sum_{j <= kN} sum_{d < l} digit_d(c_m[j]) pfksk[r][j][d], r <= k, with
 // c_m[kN] the body; key [(k+1)][kN+1][l][cols], cols = (k+1) N, output row (m / group, r, m % group) of [..][(k+1)][group][cols].
-// A wrapping u64 GEMM tiled as tlwe_gadget_key_switch_kernel: a workgroup owns PF_TB ciphertexts and PF_TH columns of every
+// A wrapping u64 GEMM tiled as tlwe_ks_kernel: a workgroup owns PF_TB ciphertexts and PF_TH columns of every
 // function, so each key word is read once per tile and each digit (an SGPR: the ciphertext words are uniform) is extracted
 // once per wave for all the functions.  digit = f - 2^(b-1) with the field f in [0, 2^b): sum digit key = sum f key -
 // 2^(b-1) sum key, so a term is one v_mad_u64_u32 and one 32-bit multiply of the high half, and sum key is per column.
@@ -247,32 +301,22 @@ __global__ __launch_bounds__(PF_TH) void tlwe_private_ks_kernel(const u64 *__res
 // alpha_d = g_d(b_cb) / 2 = 2^(63 - b_cb (d+1)): the body of level d's trivial table (b_cb l_cb <= 63)
 __device__ __forceinline__ u64 cb_alpha(u32 cb_b, u32 d) { return 1ull << (63u - cb_b * (d + 1u)); }
 
-// tfhe_br_init_kernel with a table per row: row m = b G + d (G = l_cb) starts from rot(v_d, b~) of c_b + (0 .. 0, 2^62), v_d the
-// trivial table whose body is alpha_d in every coefficient (its mask rows are 0); shift[m][j] = (2N - a~_{b,j}) mod 2N
+// row m = b G + d (G = l_cb) is c_b + (0 .. 0, 2^62) under v_d, the trivial table whose body is alpha_d in every coefficient
+struct CbLevels {
+    const u64 *__restrict__ lwe;
+    u32 n_lwe, G, cb_b;
+    static constexpr bool BODY_ONLY = true, DESCRIPTOR = false;
+    __device__ __forceinline__ u64 row(u64 m) const { return m; }
+    __device__ __forceinline__ bool valid(u64) const { return true; }
+    __device__ __forceinline__ u64 word(u64 m, u32 j) const { return lwe[m / G * (n_lwe + 1ull) + j] + (j == n_lwe ? 1ull << 62 : 0ull); }
+    __device__ __forceinline__ u64 coeff(u64 m, u64, u64) const { return cb_alpha(cb_b, (u32)(m % G)); }
+};
 __global__ __launch_bounds__(256) void tfhe_cb_init_kernel(const u64 *__restrict__ lwe, u64 *__restrict__ acc, u32 *__restrict__ shift,
                                                            u32 n_lwe, u32 k1, u32 L, u32 G, u32 cb_b, u64 rows) {
-    const u64 N = 1ull << L, k1N = (u64)k1 * N, na = rows * k1N, total = na + rows * n_lwe;
-    const u64 stride = (u64)gridDim.x * 256;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-        if (i < na) {
-            const u64 m = i / k1N, r = i - m * k1N, b = m / G;
-            const u32 d = (u32)(m - b * G);
-            if ((r >> L) + 1 < k1) {
-                acc[i] = 0;
-            } else {
-                const u64 j = (r & (N - 1)) + mod_switch_2n(lwe[b * (n_lwe + 1ull) + n_lwe] + (1ull << 62), L);
-                const u64 x = cb_alpha(cb_b, d);
-                acc[i] = ((j >> L) & 1u) ? 0ull - x : x;
-            }
-        } else {
-            const u64 q = i - na, m = q / n_lwe, b = m / G;
-            shift[q] = (u32)((2 * N - mod_switch_2n(lwe[b * (n_lwe + 1ull) + (q - m * n_lwe)], L)) & (2 * N - 1));
-        }
-    }
+    br_init_body(CbLevels{lwe, n_lwe, G, cb_b}, acc, shift, n_lwe, k1, L, rows);
 }
 
-// T[m] = (0 .. 0, alpha_d) - E, E = sample extraction of ACC[m] at h = 0, d = m mod G: coefficient c N + j of the mask is
-// -a_c[0] for j = 0 and a_c[N - j] otherwise; the body is alpha_d - b[0]
+// T[m] = (0 .. 0, alpha_d) - E, E the extraction of ACC[m] at h = 0, d = m mod G
 __global__ __launch_bounds__(256) void tfhe_cb_extract_kernel(const u64 *__restrict__ acc, u64 *__restrict__ out, u32 k, u32 L, u32 G,
                                                               u32 cb_b, u64 rows) {
     const u64 N = 1ull << L, kN = (u64)k * N, per = kN + 1, total = rows * per;
@@ -280,12 +324,7 @@ __global__ __launch_bounds__(256) void tfhe_cb_extract_kernel(const u64 *__restr
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
         const u64 m = i / per, r = i - m * per;
         const u64 *src = acc + m * (kN + N);
-        if (r == kN) {
-            out[i] = cb_alpha(cb_b, (u32)(m % G)) - src[kN];
-        } else {
-            const u64 c = r >> L, j = r & (N - 1);
-            out[i] = j == 0 ? 0ull - src[c * N] : src[c * N + N - j];
-        }
+        out[i] = 0ull - extract0_word(r, kN, L, 0ull - cb_alpha(cb_b, (u32)(m % G)), [&](u64 at) { return src[at]; });
     }
 }
 
@@ -306,53 +345,42 @@ __device__ __forceinline__ u64 gate_word(const u64 *__restrict__ pool, u64 wires
     return j == n_lwe ? w + (u64)(long long)gate_o[op] * GATE_MU : w;
 }
 
-// tfhe_br_init_kernel over the combined rows, v = (mask 0, body mu) computed in place: ACC_0[m] = rot(v, b~_m),
-// shift[m][j] = (2N - a~_{m,j}) mod 2N.  MUX = false: row m is gate m, desc[m] = (op, x, y).  MUX = true: desc[b] = (s, a, c),
-// row 2b is AND(s, a), row 2b + 1 ANDNY(s, c).  The combined TLWE exists only in registers.
+// the combined rows under v = (mask 0, body mu).  MUX = false: row m is gate m, desc[m] = (op, x, y).  MUX = true: desc[b] =
+// (s, a, c), row 2b is AND(s, a), row 2b + 1 ANDNY(s, c).  The combined TLWE exists only in registers.
+template <bool MUX>
+struct GateRows {
+    const u64 *__restrict__ pool;
+    u64 wires;
+    const u32 *__restrict__ desc;
+    u32 n_lwe;
+    static constexpr bool BODY_ONLY = true, DESCRIPTOR = true;
+    struct Row { u32 op, x, y; };
+    __device__ __forceinline__ Row row(u64 m) const {
+        if (MUX) {
+            const u32 *d = desc + (m >> 1) * 3;
+            return {(m & 1) ? GATE_ANDNY : GATE_AND, d[0], d[1 + (m & 1)]};
+        }
+        const u32 *d = desc + m * 3;
+        return {d[0], d[1], d[2]};
+    }
+    __device__ __forceinline__ bool valid(Row) const { return true; }          // gate_word is 0 where the row names nothing
+    __device__ __forceinline__ u64 word(Row g, u32 j) const { return gate_word(pool, wires, n_lwe, g.op, g.x, g.y, j); }
+    __device__ __forceinline__ u64 coeff(Row, u64, u64) const { return GATE_MU; }
+};
 template <bool MUX>
 __global__ __launch_bounds__(256) void tfhe_gate_init_kernel(const u64 *__restrict__ pool, u64 wires, const u32 *__restrict__ desc,
                                                              u64 *__restrict__ acc, u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L, u64 rows) {
-    const u64 N = 1ull << L, k1N = (u64)k1 * N, na = rows * k1N, total = na + rows * n_lwe;
-    const u64 stride = (u64)gridDim.x * 256;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-        const u64 m = i < na ? i / k1N : (i - na) / n_lwe;
-        u32 op, x, y;
-        if (MUX) {
-            const u32 *d = desc + (m >> 1) * 3;
-            op = (m & 1) ? GATE_ANDNY : GATE_AND; x = d[0]; y = d[1 + (m & 1)];
-        } else {
-            const u32 *d = desc + m * 3;
-            op = d[0]; x = d[1]; y = d[2];
-        }
-        if (i < na) {
-            const u64 r = i - m * k1N;
-            if ((r >> L) + 1 < k1) {
-                acc[i] = 0;
-            } else {
-                const u64 j = (r & (N - 1)) + mod_switch_2n(gate_word(pool, wires, n_lwe, op, x, y, n_lwe), L);
-                acc[i] = ((j >> L) & 1u) ? 0ull - GATE_MU : GATE_MU;
-            }
-        } else {
-            const u64 q = i - na;
-            shift[q] = (u32)((2 * N - mod_switch_2n(gate_word(pool, wires, n_lwe, op, x, y, (u32)(q - m * n_lwe)), L)) & (2 * N - 1));
-        }
-    }
+    br_init_body(GateRows<MUX>{pool, wires, desc, n_lwe}, acc, shift, n_lwe, k1, L, rows);
 }
 
-// out[b] = E[2b] + E[2b + 1] + (0 .. 0, mu), E = sample extraction of ACC at h = 0 (coefficient c N + j of the mask is
-// a_c[0] for j = 0 and -a_c[N - j] otherwise; the body b[0])
+// out[b] = E[2b] + E[2b + 1] + (0 .. 0, mu), E the extraction of ACC at h = 0
 __global__ __launch_bounds__(256) void tfhe_mux_extract_kernel(const u64 *__restrict__ acc, u64 *__restrict__ out, u32 k, u32 L, u64 batch) {
     const u64 N = 1ull << L, kN = (u64)k * N, per = kN + 1, total = batch * per;
     const u64 stride = (u64)gridDim.x * 256;
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
         const u64 b = i / per, r = i - b * per;
-        const u64 *s0 = acc + 2 * b * (kN + N), *s1 = s0 + kN + N;
-        if (r == kN) {
-            out[i] = s0[kN] + s1[kN] + GATE_MU;
-        } else {
-            const u64 c = r >> L, j = r & (N - 1);
-            out[i] = j == 0 ? s0[c * N] + s1[c * N] : 0ull - s0[c * N + N - j] - s1[c * N + N - j];
-        }
+        const u64 *s0 = acc + 2 * b * (kN + N);
+        out[i] = extract0_word(r, kN, L, GATE_MU, [&](u64 at) { return s0[at] + s0[kN + N + at]; });
     }
 }
 
@@ -384,61 +412,52 @@ __global__ __launch_bounds__(256) void tlwe_lincomb_kernel(const u64 *__restrict
     }
 }
 
-// tfhe_gate_init_kernel with a table per row: ACC_0[m] = rot(v_T, b~_m), T = luts[desc[m][0]] ([lut_count][P] torus words,
-// P = 2^t), v_T = (mask 0, body v), v[i] = T[q] for q = (i + half) >> (L - t) < P and -T[0] in the top half box (half =
-// N / 2P, 0 at P = N); shift[m][j] = (2N - a~_{m,j}) mod 2N.  v is never formed: coefficient i reads T at the box of
-// (i + b~) mod N.  An invalid row (lut_row_valid, or lut >= lut_count) reads nothing and writes zeros and zero shifts.
+// a row whose lut word names the first of F consecutive tables is valid under lut_row_valid and lut + F <= lut_count (64-bit)
+__device__ __forceinline__ bool lut_row_ok(const u32 *__restrict__ d, u64 wires, u64 lut_count, u64 F) {
+    return (u64)d[0] + F <= lut_count && lut_row_valid(d, wires);
+}
+// coefficient i of the body of the test vector that interleaves tables lut .. lut + F - 1 ([P] torus words each, P = 2^t,
+// F = 2^nu): T_h[q] with h = i mod F, q = (i - h + half) >> (L - t), half = N / 2P, and 0 - T_h[0] in the top half box (q = P)
+__device__ __forceinline__ u64 lut_coeff(const u64 *__restrict__ luts, u32 lut, u32 t, u32 nu, u32 L, u64 i) {
+    const u64 P = 1ull << t, half = ((1ull << L) >> t) >> 1, h = i & ((1ull << nu) - 1);
+    const u64 q = (i - h + half) >> (L - t);
+    const u64 *T = luts + (((u64)lut + h) << t);
+    return q < P ? T[q] : 0ull - T[0];
+}
+
+// descriptor rows under v_T = (mask 0, body lut_coeff), T = luts[desc[m][0]], one table a row (F = 1)
+struct LutRows {
+    const u64 *__restrict__ pool;
+    u64 wires;
+    const u32 *__restrict__ desc;
+    const u64 *__restrict__ luts;
+    u64 lut_count;
+    u32 t, n_lwe, L;
+    static constexpr bool BODY_ONLY = true, DESCRIPTOR = true;
+    __device__ __forceinline__ const u32 *row(u64 m) const { return desc + m * LUT_DESC; }
+    __device__ __forceinline__ bool valid(const u32 *d) const { return lut_row_ok(d, wires, lut_count, 1); }
+    __device__ __forceinline__ u64 word(const u32 *d, u32 j) const { return lut_word(pool, d, n_lwe, j); }
+    __device__ __forceinline__ u64 coeff(const u32 *d, u64, u64 i) const { return lut_coeff(luts, d[0], t, 0, L, i); }
+};
 __global__ __launch_bounds__(256) void tfhe_lut_init_kernel(const u64 *__restrict__ pool, u64 wires, const u32 *__restrict__ desc,
                                                             const u64 *__restrict__ luts, u64 lut_count, u32 t, u64 *__restrict__ acc,
                                                             u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L, u64 rows) {
-    const u64 N = 1ull << L, k1N = (u64)k1 * N, na = rows * k1N, total = na + rows * n_lwe;
-    const u64 P = 1ull << t, half = (N >> t) >> 1;
-    const u64 stride = (u64)gridDim.x * 256;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-        const u64 m = i < na ? i / k1N : (i - na) / n_lwe;
-        const u32 *d = desc + m * LUT_DESC;
-        const bool ok = d[0] < lut_count && lut_row_valid(d, wires);
-        if (i < na) {
-            const u64 r = i - m * k1N;
-            if ((r >> L) + 1 < k1 || !ok) {
-                acc[i] = 0;
-            } else {
-                const u64 j = (r & (N - 1)) + mod_switch_2n(lut_word(pool, d, n_lwe, n_lwe), L);
-                const u64 *T = luts + ((u64)d[0] << t);
-                const u64 q = ((j & (N - 1)) + half) >> (L - t);
-                const u64 x = q < P ? T[q] : 0ull - T[0];
-                acc[i] = ((j >> L) & 1u) ? 0ull - x : x;
-            }
-        } else {
-            const u64 q = i - na;
-            shift[q] = ok ? (u32)((2 * N - mod_switch_2n(lut_word(pool, d, n_lwe, (u32)(q - m * n_lwe)), L)) & (2 * N - 1)) : 0u;
-        }
-    }
+    br_init_body(LutRows{pool, wires, desc, luts, lut_count, t, n_lwe, L}, acc, shift, n_lwe, k1, L, rows);
 }
 
 // ---- small integers: several tables from one blind rotation ---------------------------------------------
-// nu low bits of every mod-switched word are forced to 0: ms_nu(w) = round(w / 2^(63 - L + nu)) 2^nu mod 2N, so a row's
-// accumulator is rotated by a multiple of F = 2^nu and coefficients 0 .. F - 1 of the result all come from the box the
-// phase fell into.  ms_0 is mod_switch_2n.
-__device__ __forceinline__ u32 mod_switch_nu(u64 w, u32 L, u32 nu) {
-    return (u32)(((((w >> (62u - L + nu)) + 1u) >> 1) << nu) & ((2ull << L) - 1u));
-}
-
-// The nu-aware twin of tfhe_lut_init_kernel, organised by row: a workgroup takes a row (grid-stride over rows), so the
+// LutRows at F = 2^nu tables a row and the mod switch ms_nu, organised by row: a workgroup takes a row (grid-stride over rows), so the
 // descriptor, the validity, the combined body and b~ are workgroup-uniform and formed once per row; its lanes then write the
-// row's k1 N accumulator words two at a time (16-byte stores) and its n_lwe shifts, both coalesced.  The row's lut word
-// names the first of F consecutive tables T_0 .. T_{F-1}; the test vector interleaves them, v[i] = T_h[q] with h = i mod F,
-// q = (i - h + half) >> (L - t), and 0 - T_h[0] where q = P (never at F = box); v is never formed.  A row is invalid under
-// lut_row_valid or if lut + F > lut_count (64-bit): it reads no pool or table word and writes zeros and zero shifts.
+// row's k1 N accumulator words two at a time (16-byte stores) and its n_lwe shifts, both coalesced.  An invalid row
+// (lut_row_ok) reads no pool or table word and writes zeros and zero shifts.
 __global__ __launch_bounds__(256) void tfhe_lut_many_init_kernel(const u64 *__restrict__ pool, u64 wires, const u32 *__restrict__ desc,
                                                                  const u64 *__restrict__ luts, u64 lut_count, u32 t, u32 nu,
                                                                  u64 *__restrict__ acc, u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L,
                                                                  u64 rows) {
     const u64 N = 1ull << L, k1N = (u64)k1 * N, body0 = k1N - N;
-    const u64 P = 1ull << t, half = (N >> t) >> 1, F = 1ull << nu;
     for (u64 m = blockIdx.x; m < rows; m += gridDim.x) {
         const u32 *d = desc + m * LUT_DESC;
-        const bool ok = (u64)d[0] + F <= lut_count && lut_row_valid(d, wires);
+        const bool ok = lut_row_ok(d, wires, lut_count, 1ull << nu);
         const u64 bt = ok ? mod_switch_nu(lut_word(pool, d, n_lwe, n_lwe), L, nu) : 0;
         u64 *row = acc + m * k1N;
         for (u64 p = 2ull * threadIdx.x; p < k1N; p += 512) {        // N >= 2: a pair never straddles a component
@@ -447,18 +466,15 @@ __global__ __launch_bounds__(256) void tfhe_lut_many_init_kernel(const u64 *__re
                 u64 x[2];
 #pragma unroll
                 for (u32 e = 0; e < 2; e++) {
-                    const u64 j = (p - body0 + e) + bt, i = j & (N - 1), h = i & (F - 1);
-                    const u64 q = (i - h + half) >> (L - t);
-                    const u64 *T = luts + (((u64)d[0] + h) << t);
-                    const u64 w = q < P ? T[q] : 0ull - T[0];
-                    x[e] = ((j >> L) & 1u) ? 0ull - w : w;
+                    const u64 j = (p - body0 + e) + bt;
+                    x[e] = nega_sign(lut_coeff(luts, d[0], t, nu, L, j & (N - 1)), j, L);
                 }
                 v = make_ulonglong2(x[0], x[1]);
             }
             *reinterpret_cast<ulonglong2 *>(row + p) = v;
         }
         for (u32 j = threadIdx.x; j < n_lwe; j += 256)
-            shift[m * n_lwe + j] = ok ? (u32)((2 * N - mod_switch_nu(lut_word(pool, d, n_lwe, j), L, nu)) & (2 * N - 1)) : 0u;
+            shift[m * n_lwe + j] = ok ? rot_shift(lut_word(pool, d, n_lwe, j), L, nu) : 0u;
     }
 }
 
@@ -581,25 +597,6 @@ __global__ __launch_bounds__(256) void tglwe_box_expand_kernel(const u64 *__rest
     }
 }
 
-// tfhe_br_init_kernel with a test vector per row: ACC_0[b] = rot(tables[b], b~_b) over all k + 1 components (the tables are
-// full TGLWEs, mask rows included), shift[b][j] = (2N - a~_j) mod 2N
-__global__ __launch_bounds__(256) void tfhe_br_rows_init_kernel(const u64 *__restrict__ lwe, const u64 *__restrict__ tables, u64 *__restrict__ acc,
-                                                                u32 *__restrict__ shift, u32 n_lwe, u32 k1, u32 L, u64 batch) {
-    const u64 N = 1ull << L, k1N = (u64)k1 * N, na = batch * k1N, total = na + batch * n_lwe;
-    const u64 stride = (u64)gridDim.x * 256;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-        if (i < na) {
-            const u64 b = i / k1N, r = i - b * k1N;
-            const u64 j = (r & (N - 1)) + mod_switch_2n(lwe[b * (n_lwe + 1ull) + n_lwe], L);
-            const u64 x = tables[b * k1N + (r >> L) * N + (j & (N - 1))];
-            acc[i] = ((j >> L) & 1u) ? 0ull - x : x;
-        } else {
-            const u64 q = i - na, b = q / n_lwe;
-            shift[q] = (u32)((2 * N - mod_switch_2n(lwe[b * (n_lwe + 1ull) + (q - b * n_lwe)], L)) & (2 * N - 1));
-        }
-    }
-}
-
 }  // namespace fhe
 
 // ---- host side -----------------------------------------------------------------------------------------------------
@@ -607,9 +604,36 @@ namespace {
 
 bool br_ext32_on(u64 n, unsigned k, unsigned l) { return fhe_ext32_enabled() && fhe::ext32_shape_supported(n, k, l); }
 
-bool overlaps(const void *a, u64 abytes, const void *b, u64 bbytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return abytes && bbytes && x < y + bbytes && y < x + abytes;
+// does [d_out, d_out + out_bytes) intersect one of the inputs {pointer, bytes}?
+struct Extent { const void *p; u64 bytes; };
+bool overlaps_any(const void *d_out, u64 out_bytes, std::initializer_list<Extent> inputs) {
+    for (const Extent &e : inputs)
+        if (overlaps(d_out, out_bytes, e.p, e.bytes)) return true;
+    return false;
+}
+
+// a kernel argument as its parameter type: device pointers arrive as void *, and an integer may widen but not narrow
+template <class P, class A>
+P kernel_arg(A a) {
+    static_assert(!(std::is_integral<P>::value && std::is_integral<A>::value) || sizeof(A) <= sizeof(P), "narrowing kernel argument: cast it at the call");
+    return static_cast<P>(a);
+}
+// one timed launch (tag L for the timer) and its check: the FHE_* code.  A launch error names kernel_name, <label>_kernel if NULL.
+template <class... P, class... A>
+int launch_named(const char *label, const char *kernel_name, int L, hipStream_t st, void (*kernel)(P...), unsigned grid, unsigned block, A... args) {
+    {
+        fhe::KernelTimer kt_(label, L, st);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, kernel_arg<P>(args)...);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return FHE_OK;
+    char name[64];
+    snprintf(name, sizeof name, "%s_kernel", label);
+    return fhe_hip_fail(e, kernel_name ? kernel_name : name);
+}
+template <class K, class... A>
+int launch(const char *label, int L, hipStream_t st, K kernel, unsigned grid, unsigned block, A... args) {
+    return launch_named(label, nullptr, L, st, kernel, grid, block, args...);
 }
 
 int check_ring(uint64_t n, unsigned k, const char *who) {
@@ -637,6 +661,13 @@ int check_ks(unsigned n_in, unsigned n_out, unsigned beta, unsigned l, const cha
     return FHE_OK;
 }
 
+// ACC_0 and the shifts of `batch` rows of d_lwe: one table (tstride 0, "tfhe_br_init") or one a row ((k+1) n, "tfhe_br_rows_init")
+int br_init(const char *label, uint64_t n, unsigned k, unsigned n_lwe, const void *d_lwe, const void *d_table, u64 tstride, u64 *acc, u32 *shift,
+            size_t batch, hipStream_t st) {
+    return launch(label, __builtin_ctzll(n), st, fhe::tfhe_br_init_kernel, fhe_ew_grid((u64)batch * ((k + 1) * n + n_lwe)), 256, d_lwe, d_table,
+                  tstride, acc, shift, n_lwe, k + 1, __builtin_ctzll(n), batch);
+}
+
 // the blind rotation proper, arguments validated: ACC lives in d_out
 int blind_rotation(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const void *d_bsk, const void *d_table, const void *d_lwe, void *d_out,
                    size_t batch, hipStream_t st) {
@@ -647,11 +678,7 @@ int blind_rotation(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const voi
     int rc;
     if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &wsv)) != FHE_OK) return rc;
     u32 *shift = (u32 *)wsv;
-    { fhe::KernelTimer kt_("tfhe_br_init", (int)L, st);
-    hipLaunchKernelGGL(fhe::tfhe_br_init_kernel, dim3(fhe_ew_grid((u64)batch * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_lwe,
-                       (const u64 *)d_table, acc, shift, n_lwe, k1, L, (u64)batch);
-    }
-    LAUNCH_OK("tfhe_br_init_kernel");
+    if ((rc = br_init("tfhe_br_init", n, k, n_lwe, d_lwe, d_table, 0, acc, shift, batch, st)) != FHE_OK) return rc;
     if (br_ext32_on(n, k, l)) {
         fhe::Ext32Args a{};
         if ((rc = fhe_ext32_tables(n, &a)) != FHE_OK) return rc;
@@ -676,40 +703,39 @@ int blind_rotation(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const voi
     if ((rc = fhe_workspace_get(6, 2 * cw * 8, st, &wsv)) != FHE_OK) return rc;
     u64 *D = (u64 *)wsv, *P = D + cw;
     for (unsigned j = 0; j < n_lwe; j++) {
-        { fhe::KernelTimer kt_("tfhe_rotdiff", (int)L, st);
-        hipLaunchKernelGGL(fhe::tfhe_rotdiff_kernel, dim3(fhe_ew_grid(cw)), dim3(256), 0, st, (const u64 *)acc, (const u32 *)shift + j, (u64)n_lwe, D,
-                           k1, L, (u64)batch);
-        }
-        LAUNCH_OK("tfhe_rotdiff_kernel");
+        if ((rc = launch("tfhe_rotdiff", L, st, fhe::tfhe_rotdiff_kernel, fhe_ew_grid(cw), 256, acc, shift + j, n_lwe, D, k1, L, batch)) != FHE_OK)
+            return rc;
         if ((rc = fhe_tggsw_external_product_prepared_dev(n, k, l, (const u64 *)d_bsk + (u64)j * words, D, P, batch, st)) != FHE_OK) return rc;
-        { fhe::KernelTimer kt_("tfhe_add", (int)L, st);
-        hipLaunchKernelGGL(fhe::tfhe_add_kernel, dim3(fhe_ew_grid(cw)), dim3(256), 0, st, acc, (const u64 *)P, cw);
-        }
-        LAUNCH_OK("tfhe_add_kernel");
+        if ((rc = launch("tfhe_add", L, st, fhe::tfhe_add_kernel, fhe_ew_grid(cw), 256, acc, P, cw)) != FHE_OK) return rc;
     }
     return FHE_OK;
 }
 
 int sample_extraction(uint64_t n, unsigned k, unsigned h, const void *d_tglwe, void *d_tlwe, size_t batch, hipStream_t st) {
     const u32 L = (u32)__builtin_ctzll(n);
-    { fhe::KernelTimer kt_("tglwe_sample_extract", (int)L, st);
-    hipLaunchKernelGGL(fhe::tglwe_sample_extract_kernel, dim3(fhe_ew_grid((u64)batch * (k * n + 1))), dim3(256), 0, st, (const u64 *)d_tglwe,
-                       (u64 *)d_tlwe, k, L, h, (u64)batch);
-    }
-    LAUNCH_OK("tglwe_sample_extract_kernel");
-    return FHE_OK;
+    return launch("tglwe_sample_extract", L, st, fhe::tglwe_sample_extract_kernel, fhe_ew_grid((u64)batch * (k * n + 1)), 256, d_tglwe, d_tlwe, k, L, h,
+                  batch);
+}
+
+// the grid of tlwe_ks_kernel for `rows` inputs; 0 when it does not fit one launch
+u64 ks_grid(u64 rows, unsigned n_out) {
+    const u64 grid = (rows + fhe::KS_TB - 1) / fhe::KS_TB * ((n_out + 1ull + fhe::KS_TH - 1) / fhe::KS_TH);
+    return grid > 0x7fffffffull ? 0 : grid;
+}
+u64 ksk_bytes(u64 n_in, unsigned l, unsigned n_out) { return n_in * l * (n_out + 1ull) * 8; }
+
+// both key switches, arguments validated but for the grid: the tile with the digit policy of `name`
+template <class Digit>
+int key_switch_launch(const char *name, unsigned n_in, unsigned n_out, unsigned l, const Digit &dg, const void *d_ksk, const void *d_in, void *d_out,
+                      size_t batch, hipStream_t st) {
+    const u32 cblocks = (n_out + 1 + fhe::KS_TH - 1) / fhe::KS_TH;       // 32 bits like the kernel's column index: 0 from n_out = 2^32 - 64 on,
+    const u64 grid = cblocks ? ks_grid(batch, n_out) : 0;                // an empty grid that the launch reports
+    if (cblocks && grid == 0) return fhe_fail(FHE_E_INVALID, "fhe_%s_dev: batch too large for one launch", name);
+    return launch(name, 0, st, fhe::tlwe_ks_kernel<Digit>, (unsigned)grid, fhe::KS_TH, d_ksk, d_in, d_out, n_in, n_out, l, batch, cblocks, dg);
 }
 
 int key_switch(unsigned n_in, unsigned n_out, unsigned l, const void *d_ksk, const void *d_in, void *d_out, size_t batch, hipStream_t st) {
-    const u32 cblocks = (n_out + 1 + fhe::KS_TH - 1) / fhe::KS_TH;
-    const u64 grid = ((u64)batch + fhe::KS_TB - 1) / fhe::KS_TB * cblocks;
-    if (grid > 0x7fffffffull) return fhe_fail(FHE_E_INVALID, "fhe_tlwe_key_switch_dev: batch too large for one launch");
-    { fhe::KernelTimer kt_("tlwe_key_switch", 0, st);
-    hipLaunchKernelGGL(fhe::tlwe_key_switch_kernel, dim3((unsigned)grid), dim3(fhe::KS_TH), 0, st, (const u64 *)d_ksk, (const u64 *)d_in,
-                       (u64 *)d_out, n_in, n_out, l, (u64)batch, cblocks);
-    }
-    LAUNCH_OK("tlwe_key_switch_kernel");
-    return FHE_OK;
+    return key_switch_launch("tlwe_key_switch", n_in, n_out, l, fhe::BitDigit{l}, d_ksk, d_in, d_out, batch, st);
 }
 
 // ---- the base-2^b gadget ----
@@ -742,6 +768,7 @@ int check_gks(unsigned n_in, unsigned n_out, unsigned log_beta, unsigned l, cons
 }
 
 u64 gadget_tggsw_words(uint64_t n, unsigned k, unsigned l) { return (u64)2 * (k + 1) * l * (k + 1) * n; }
+u64 bsk_bytes(uint64_t n, unsigned k, unsigned l, unsigned n_lwe) { return (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8; }
 
 // `keys` TGGSWs -> the two-prime layout (digit32.hip ntt32_fwd_key_kernel), whatever FHE_EXT32 says
 int gadget_prepare(uint64_t n, unsigned k, unsigned l, u64 keys, const void *d_tggsw, void *d_prepared, hipStream_t st) {
@@ -792,31 +819,72 @@ int gadget_br_steps(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsig
 
 int gadget_blind_rotation(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk, const void *d_table,
                           const void *d_lwe, void *d_out, size_t batch, hipStream_t st) {
-    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
     u64 *acc = (u64 *)d_out;
     void *wsv = nullptr;
     int rc;
     if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &wsv)) != FHE_OK) return rc;
     u32 *shift = (u32 *)wsv;
-    { fhe::KernelTimer kt_("tfhe_br_init", (int)L, st);
-    hipLaunchKernelGGL(fhe::tfhe_br_init_kernel, dim3(fhe_ew_grid((u64)batch * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_lwe,
-                       (const u64 *)d_table, acc, shift, n_lwe, k1, L, (u64)batch);
-    }
-    LAUNCH_OK("tfhe_br_init_kernel");
+    if ((rc = br_init("tfhe_br_init", n, k, n_lwe, d_lwe, d_table, 0, acc, shift, batch, st)) != FHE_OK) return rc;
     return gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk, acc, shift, batch, st);
 }
 
 int gadget_key_switch(unsigned n_in, unsigned n_out, unsigned log_beta, unsigned l, const void *d_ksk, const void *d_in, void *d_out,
                       size_t batch, hipStream_t st) {
-    const u32 cblocks = (n_out + 1 + fhe::KS_TH - 1) / fhe::KS_TH;
-    const u64 grid = ((u64)batch + fhe::KS_TB - 1) / fhe::KS_TB * cblocks;
-    if (grid > 0x7fffffffull) return fhe_fail(FHE_E_INVALID, "fhe_tlwe_gadget_key_switch_dev: batch too large for one launch");
-    { fhe::KernelTimer kt_("tlwe_gadget_key_switch", 0, st);
-    hipLaunchKernelGGL(fhe::tlwe_gadget_key_switch_kernel, dim3((unsigned)grid), dim3(fhe::KS_TH), 0, st, (const u64 *)d_ksk, (const u64 *)d_in,
-                       (u64 *)d_out, n_in, n_out, log_beta, l, fhe::gadget_cadd(log_beta, l), (u64)batch, cblocks);
+    return key_switch_launch("tlwe_gadget_key_switch", n_in, n_out, l, fhe::SignedDigit{log_beta, fhe::gadget_cadd(log_beta, l)}, d_ksk, d_in,
+                             d_out, batch, st);
+}
+
+// ---- the stages of a gadget bootstrap: checks, workspace, and everything after the init kernel ----
+struct BrShape {                                                                     // the blind rotation's part
+    uint64_t n;
+    unsigned k, log_beta, l, n_lwe;
+    u32 k1() const { return k + 1; }
+    u32 L() const { return (u32)__builtin_ctzll(n); }
+    u64 kn() const { return (u64)k * n; }
+    u64 init_items(u64 rows) const { return rows * (k1() * n + n_lwe); }             // what an element-wise init kernel walks
+};
+struct BootShape : BrShape {                                                         // and the key switch back to n_lwe
+    unsigned ks_log_beta, ks_l;
+};
+u64 bsk_bytes(const BrShape &s) { return bsk_bytes(s.n, s.k, s.l, s.n_lwe); }
+u64 ksk_bytes(const BootShape &s) { return ksk_bytes(s.kn(), s.ks_l, s.n_lwe); }
+constexpr u64 kEwLimit = 0x7fffffffull * 256;                                        // items of one element-wise launch
+
+int check_boot(const BootShape &s, const char *who) {
+    const int rc = check_gbr(s.n, s.k, s.log_beta, s.l, s.n_lwe, who);
+    return rc != FHE_OK ? rc : check_gks((unsigned)s.kn(), s.n_lwe, s.ks_log_beta, s.ks_l, who);
+}
+
+// the accumulators [acc_rows][(k+1)][n], the extracted rows [ext_rows][k n + 1] and the shifts [acc_rows][n_lwe]
+int boot_workspace(const BrShape &s, u64 acc_rows, u64 ext_rows, hipStream_t st, u64 **acc, u64 **ext, u32 **shift) {
+    int rc;
+    if ((rc = fhe_workspace_get(7, acc_rows * s.k1() * s.n * 8, st, (void **)acc)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(8, ext_rows * (s.kn() + 1) * 8, st, (void **)ext)) != FHE_OK) return rc;
+    return fhe_workspace_get(5, acc_rows * s.n_lwe * 4, st, (void **)shift);
+}
+
+// after the init kernel: the §11 CMux steps over the accumulators, the extraction into ext, the key switch into d_out.
+//   EXT_H0     one accumulator a row, extraction at h = 0
+//   EXT_MUX    two accumulators a row, out = E[2b] + E[2b + 1] + (0 .. 0, mu)
+//   EXT_MANY   extraction at h = 0 .. 2^nu - 1, function-major: 2^nu batch rows go through the key switch
+enum Extraction { EXT_H0, EXT_MUX, EXT_MANY };
+int finish_boot(const BootShape &s, Extraction how, unsigned nu, const void *d_bsk, const void *d_ksk, u64 *acc, const u32 *shift, u64 *ext,
+                void *d_out, size_t batch, hipStream_t st) {
+    const u32 L = s.L();
+    int rc = gadget_br_steps(s.n, s.k, s.log_beta, s.l, s.n_lwe, d_bsk, acc, shift, (how == EXT_MUX ? 2 : 1) * batch, st);
+    if (rc != FHE_OK) return rc;
+    u64 ks_rows = batch;
+    if (how == EXT_H0) {
+        rc = sample_extraction(s.n, s.k, 0, acc, ext, batch, st);
+    } else if (how == EXT_MUX) {
+        rc = launch("tfhe_mux_extract", L, st, fhe::tfhe_mux_extract_kernel, fhe_ew_grid((u64)batch * (s.kn() + 1)), 256, acc, ext, s.k, L, batch);
+    } else {
+        ks_rows = (u64)batch << nu;
+        rc = launch("tfhe_many_extract", L, st, fhe::tfhe_many_extract_kernel, fhe_ew_grid((u64)batch * (s.kn() + (1ull << nu))), 256, acc, ext, s.k,
+                    L, nu, batch);
     }
-    LAUNCH_OK("tlwe_gadget_key_switch_kernel");
-    return FHE_OK;
+    if (rc != FHE_OK) return rc;
+    return gadget_key_switch((unsigned)s.kn(), s.n_lwe, s.ks_log_beta, s.ks_l, d_ksk, ext, d_out, ks_rows, st);
 }
 
 // ---- circuit bootstrapping ----
@@ -845,12 +913,8 @@ u64 pfks_grid(uint64_t n, unsigned k, u64 rows) {
 int private_key_switch(uint64_t n, unsigned k, unsigned log_beta, unsigned l, const void *d_key, const void *d_in, void *d_out, u64 rows,
                        u32 group, hipStream_t st) {
     const u32 cols = (u32)((k + 1) * n), cblocks = (cols + fhe::PF_TH - 1) / fhe::PF_TH;
-    { fhe::KernelTimer kt_("tlwe_private_ks", (int)__builtin_ctzll(n), st);
-    hipLaunchKernelGGL(fhe::tlwe_private_ks_kernel, dim3((unsigned)pfks_grid(n, k, rows)), dim3(fhe::PF_TH), 0, st, (const u64 *)d_key,
-                       (const u64 *)d_in, (u64 *)d_out, (u32)(k * n), cols, log_beta, l, fhe::gadget_cadd(log_beta, l), rows, group, cblocks);
-    }
-    LAUNCH_OK("tlwe_private_ks_kernel");
-    return FHE_OK;
+    return launch("tlwe_private_ks", __builtin_ctzll(n), st, fhe::tlwe_private_ks_kernel, (unsigned)pfks_grid(n, k, rows), fhe::PF_TH, d_key, d_in,
+                  d_out, (u32)(k * n), cols, log_beta, l, fhe::gadget_cadd(log_beta, l), rows, group, cblocks);
 }
 
 }  // namespace
@@ -882,8 +946,8 @@ extern "C" int fhe_tfhe_blind_rotation_dev(uint64_t n, unsigned k, unsigned l, u
     if (!d_bsk_prepared || !d_table || !d_lwe || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_table); REQUIRE_ALIGNED(d_lwe); REQUIRE_ALIGNED(d_out);
     const u64 out_bytes = (u64)batch * (k + 1) * n * 8;
-    if (overlaps(d_out, out_bytes, d_bsk_prepared, fhe_tfhe_bsk_prepared_words(n, k, l, n_lwe) * 8) ||
-        overlaps(d_out, out_bytes, d_table, (u64)(k + 1) * n * 8) || overlaps(d_out, out_bytes, d_lwe, (u64)batch * (n_lwe + 1ull) * 8))
+    if (overlaps_any(d_out, out_bytes, {{d_bsk_prepared, fhe_tfhe_bsk_prepared_words(n, k, l, n_lwe) * 8}, {d_table, (u64)(k + 1) * n * 8},
+                                        {d_lwe, (u64)batch * (n_lwe + 1ull) * 8}}))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
     return blind_rotation(n, k, l, n_lwe, d_bsk_prepared, d_table, d_lwe, d_out, batch, (hipStream_t)hip_stream);
 }
@@ -911,7 +975,7 @@ extern "C" int fhe_tlwe_key_switch_dev(unsigned n_in, unsigned n_out, unsigned b
     if (!d_ksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
     const u64 out_bytes = (u64)batch * (n_out + 1ull) * 8;
-    if (overlaps(d_out, out_bytes, d_in, (u64)batch * (n_in + 1ull) * 8) || overlaps(d_out, out_bytes, d_ksk, (u64)n_in * l * (n_out + 1ull) * 8))
+    if (overlaps_any(d_out, out_bytes, {{d_in, (u64)batch * (n_in + 1ull) * 8}, {d_ksk, ksk_bytes(n_in, l, n_out)}}))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
     return key_switch(n_in, n_out, l, d_ksk, d_in, d_out, batch, (hipStream_t)hip_stream);
 }
@@ -928,9 +992,8 @@ extern "C" int fhe_tfhe_bootstrap_dev(uint64_t n, unsigned k, unsigned l, unsign
     if (!d_bsk_prepared || !d_table || !d_ksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_table); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
     const u64 out_bytes = (u64)batch * (n_lwe + 1ull) * 8;
-    if (overlaps(d_out, out_bytes, d_bsk_prepared, fhe_tfhe_bsk_prepared_words(n, k, l, n_lwe) * 8) ||
-        overlaps(d_out, out_bytes, d_table, (u64)(k + 1) * n * 8) || overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) ||
-        overlaps(d_out, out_bytes, d_in, out_bytes))
+    if (overlaps_any(d_out, out_bytes, {{d_bsk_prepared, fhe_tfhe_bsk_prepared_words(n, k, l, n_lwe) * 8}, {d_table, (u64)(k + 1) * n * 8},
+                                        {d_ksk, ksk_bytes(kn, ks_l, n_lwe)}, {d_in, out_bytes}}))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
     hipStream_t st = (hipStream_t)hip_stream;
     void *acc = nullptr, *ext = nullptr;
@@ -956,12 +1019,8 @@ extern "C" int fhe_tn_gadget_decompose_dev(uint64_t n, unsigned log_beta, unsign
     if (overlaps(d_out, (u64)rows * l * n * 8, d_a, (u64)rows * n * 8)) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps d_a", who);
     hipStream_t st = (hipStream_t)hip_stream;
     const u32 L = (u32)__builtin_ctzll(n);
-    { fhe::KernelTimer kt_("tn_gadget_decompose", (int)L, st);
-    hipLaunchKernelGGL(fhe::tn_gadget_decompose_kernel, dim3(fhe_ew_grid((u64)rows * l * n)), dim3(256), 0, st, (const u64 *)d_a, (u64 *)d_out,
-                       L, log_beta, l, fhe::gadget_cadd(log_beta, l), (u64)rows);
-    }
-    LAUNCH_OK("tn_gadget_decompose_kernel");
-    return FHE_OK;
+    return launch("tn_gadget_decompose", L, st, fhe::tn_gadget_decompose_kernel, fhe_ew_grid((u64)rows * l * n), 256, d_a, d_out, L, log_beta, l,
+                  fhe::gadget_cadd(log_beta, l), rows);
 }
 
 extern "C" size_t fhe_tggsw_gadget_prepared_words(uint64_t n, unsigned k, unsigned log_beta, unsigned l) {
@@ -1030,8 +1089,8 @@ extern "C" int fhe_tfhe_gadget_blind_rotation_dev(uint64_t n, unsigned k, unsign
     if (!d_bsk_prepared || !d_table || !d_lwe || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_table); REQUIRE_ALIGNED(d_lwe); REQUIRE_ALIGNED(d_out);
     const u64 out_bytes = (u64)batch * (k + 1) * n * 8;
-    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
-        overlaps(d_out, out_bytes, d_table, (u64)(k + 1) * n * 8) || overlaps(d_out, out_bytes, d_lwe, (u64)batch * (n_lwe + 1ull) * 8))
+    if (overlaps_any(d_out, out_bytes, {{d_bsk_prepared, bsk_bytes(n, k, l, n_lwe)}, {d_table, (u64)(k + 1) * n * 8},
+                                        {d_lwe, (u64)batch * (n_lwe + 1ull) * 8}}))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
     return gadget_blind_rotation(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_table, d_lwe, d_out, batch, (hipStream_t)hip_stream);
 }
@@ -1045,34 +1104,41 @@ extern "C" int fhe_tlwe_gadget_key_switch_dev(unsigned n_in, unsigned n_out, uns
     if (!d_ksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
     const u64 out_bytes = (u64)batch * (n_out + 1ull) * 8;
-    if (overlaps(d_out, out_bytes, d_in, (u64)batch * (n_in + 1ull) * 8) || overlaps(d_out, out_bytes, d_ksk, (u64)n_in * l * (n_out + 1ull) * 8))
+    if (overlaps_any(d_out, out_bytes, {{d_in, (u64)batch * (n_in + 1ull) * 8}, {d_ksk, ksk_bytes(n_in, l, n_out)}}))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
     return gadget_key_switch(n_in, n_out, log_beta, l, d_ksk, d_in, d_out, batch, (hipStream_t)hip_stream);
 }
 
+namespace {
+// fhe_tfhe_gadget_bootstrap_dev (table_rows = 0: one table) and fhe_tfhe_gadget_bootstrap_rows_dev (table_rows = 1: d_table holds
+// [batch][(k+1)][n]): init -> the CMux steps -> extraction at h = 0 -> gadget key switch, 2 n_lwe + 3 launches
+int table_bootstrap(const char *who, const char *init_label, const BootShape &s, const void *d_bsk_prepared, const void *d_table, u64 table_rows,
+                    const void *d_ksk, const void *d_in, void *d_out, size_t batch, hipStream_t st) {
+    int rc = check_boot(s, who);
+    if (rc != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    if (!d_bsk_prepared || !d_table || !d_ksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk_prepared);
+    if (fhe_misaligned(d_table))                                        // REQUIRE_ALIGNED under the entry point's name for the argument
+        return fhe_fail(FHE_E_INVALID, "%s must be 16-byte aligned (got %p)", table_rows ? "d_tables" : "d_table", d_table);
+    REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
+    const u64 out_bytes = (u64)batch * (s.n_lwe + 1ull) * 8, table_bytes = (u64)s.k1() * s.n * 8;
+    if (overlaps_any(d_out, out_bytes, {{d_bsk_prepared, bsk_bytes(s)}, {d_table, table_rows ? (u64)batch * table_bytes : table_bytes},
+                                        {d_ksk, ksk_bytes(s)}, {d_in, out_bytes}}))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
+    u64 *acc = nullptr, *ext = nullptr;
+    u32 *shift = nullptr;
+    if ((rc = boot_workspace(s, batch, batch, st, &acc, &ext, &shift)) != FHE_OK) return rc;
+    if ((rc = br_init(init_label, s.n, s.k, s.n_lwe, d_in, d_table, table_rows * s.k1() * s.n, acc, shift, batch, st)) != FHE_OK) return rc;
+    return finish_boot(s, EXT_H0, 0, d_bsk_prepared, d_ksk, acc, shift, ext, d_out, batch, st);
+}
+}  // namespace
+
 extern "C" int fhe_tfhe_gadget_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
                                              const void *d_table, unsigned ks_log_beta, unsigned ks_l, const void *d_ksk, const void *d_in,
                                              void *d_out, size_t batch, void *hip_stream) {
-    const char *who = "fhe_tfhe_gadget_bootstrap_dev";
-    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
-    if (rc != FHE_OK) return rc;
-    const u64 kn = (u64)k * n;
-    if ((rc = check_gks((unsigned)kn, n_lwe, ks_log_beta, ks_l, who)) != FHE_OK) return rc;
-    if (batch == 0) return FHE_OK;
-    if (!d_bsk_prepared || !d_table || !d_ksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
-    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_table); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
-    const u64 out_bytes = (u64)batch * (n_lwe + 1ull) * 8;
-    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
-        overlaps(d_out, out_bytes, d_table, (u64)(k + 1) * n * 8) || overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) ||
-        overlaps(d_out, out_bytes, d_in, out_bytes))
-        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
-    hipStream_t st = (hipStream_t)hip_stream;
-    void *acc = nullptr, *ext = nullptr;
-    if ((rc = fhe_workspace_get(7, (u64)batch * (k + 1) * n * 8, st, &acc)) != FHE_OK) return rc;
-    if ((rc = fhe_workspace_get(8, (u64)batch * (kn + 1) * 8, st, &ext)) != FHE_OK) return rc;
-    if ((rc = gadget_blind_rotation(n, k, log_beta, l, n_lwe, d_bsk_prepared, d_table, d_in, acc, batch, st)) != FHE_OK) return rc;
-    if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) return rc;
-    return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, batch, st);
+    return table_bootstrap("fhe_tfhe_gadget_bootstrap_dev", "tfhe_br_init", {n, k, log_beta, l, n_lwe, ks_log_beta, ks_l}, d_bsk_prepared, d_table, 0,
+                           d_ksk, d_in, d_out, batch, (hipStream_t)hip_stream);
 }
 
 // ---- circuit bootstrapping ------------------------------------------------------------------------------
@@ -1150,32 +1216,26 @@ extern "C" int fhe_tfhe_circuit_bootstrap_dev(uint64_t n, unsigned k, unsigned l
     if (!d_bsk_prepared || !d_pfksk || !d_lwe || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_pfksk); REQUIRE_ALIGNED(d_lwe); REQUIRE_ALIGNED(d_out);
     const u64 rows = (u64)batch * cb_l;
-    if ((u64)batch > 0xffffffffull || pfks_grid(n, k, rows) == 0 || rows * (k + 1) * n > 0x7fffffffull * 256)
+    if ((u64)batch > 0xffffffffull || pfks_grid(n, k, rows) == 0 || rows * (k + 1) * n > kEwLimit)
         return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
     const u64 out_bytes = rows * (k + 1) * (k + 1) * n * 8;
-    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
-        overlaps(d_out, out_bytes, d_pfksk, pfksk_words(n, k, pf_l) * 8) || overlaps(d_out, out_bytes, d_lwe, (u64)batch * (n_lwe + 1ull) * 8))
+    if (overlaps_any(d_out, out_bytes, {{d_bsk_prepared, bsk_bytes(n, k, l, n_lwe)}, {d_pfksk, pfksk_words(n, k, pf_l) * 8},
+                                        {d_lwe, (u64)batch * (n_lwe + 1ull) * 8}}))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
-    const u64 kn = (u64)k * n;
-    void *accv = nullptr, *tv = nullptr, *shv = nullptr;
-    if ((rc = fhe_workspace_get(7, rows * k1 * n * 8, st, &accv)) != FHE_OK) return rc;
-    if ((rc = fhe_workspace_get(8, rows * (kn + 1) * 8, st, &tv)) != FHE_OK) return rc;
-    if ((rc = fhe_workspace_get(5, rows * n_lwe * 4, st, &shv)) != FHE_OK) return rc;
-    u64 *acc = (u64 *)accv;
+    const BrShape s{n, k, log_beta, l, n_lwe};                           // no LWE key switch: the rows go through the private one
+    const u32 L = s.L();
+    u64 *acc = nullptr, *tv = nullptr;
+    u32 *shift = nullptr;
+    if ((rc = boot_workspace(s, rows, rows, st, &acc, &tv, &shift)) != FHE_OK) return rc;
     // the l_cb blind rotations of every input as one blind rotation over batch l_cb rows (row b l_cb + d: level d)
-    { fhe::KernelTimer kt_("tfhe_cb_init", (int)L, st);
-    hipLaunchKernelGGL(fhe::tfhe_cb_init_kernel, dim3(fhe_ew_grid(rows * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_lwe, acc,
-                       (u32 *)shv, n_lwe, k1, L, cb_l, cb_log_beta, rows);
-    }
-    LAUNCH_OK("tfhe_cb_init_kernel");
-    if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, (const u32 *)shv, rows, st)) != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("tfhe_cb_extract", (int)L, st);
-    hipLaunchKernelGGL(fhe::tfhe_cb_extract_kernel, dim3(fhe_ew_grid(rows * (kn + 1))), dim3(256), 0, st, (const u64 *)acc, (u64 *)tv, k, L,
-                       cb_l, cb_log_beta, rows);
-    }
-    LAUNCH_OK("tfhe_cb_extract_kernel");
+    if ((rc = launch("tfhe_cb_init", L, st, fhe::tfhe_cb_init_kernel, fhe_ew_grid(s.init_items(rows)), 256, d_lwe, acc, shift, n_lwe, s.k1(), L, cb_l,
+                     cb_log_beta, rows)) != FHE_OK)
+        return rc;
+    if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, shift, rows, st)) != FHE_OK) return rc;
+    if ((rc = launch("tfhe_cb_extract", L, st, fhe::tfhe_cb_extract_kernel, fhe_ew_grid(rows * (s.kn() + 1)), 256, acc, tv, k, L, cb_l, cb_log_beta,
+                     rows)) != FHE_OK)
+        return rc;
     // TGGSW row (r, d) = PFKS_r(T_d): the key switch writes [batch][(k+1)][l_cb][(k+1)][n] directly
     return private_key_switch(n, k, pf_log_beta, pf_l, d_pfksk, tv, d_out, rows, cb_l, st);
 }
@@ -1188,45 +1248,27 @@ namespace {
 int gate_entry(bool mux, uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared, unsigned ks_log_beta,
                unsigned ks_l, const void *d_ksk, const void *d_pool, size_t wires, const void *d_desc, void *d_out, size_t batch, void *hip_stream) {
     const char *who = mux ? "fhe_tfhe_gate_mux_dev" : "fhe_tfhe_gate_bootstrap_dev";
-    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
+    const BootShape s{n, k, log_beta, l, n_lwe, ks_log_beta, ks_l};
+    int rc = check_boot(s, who);
     if (rc != FHE_OK) return rc;
-    const u64 kn = (u64)k * n;
-    if ((rc = check_gks((unsigned)kn, n_lwe, ks_log_beta, ks_l, who)) != FHE_OK) return rc;
     if (wires < 1) return fhe_fail(FHE_E_INVALID, "%s: need wires >= 1", who);
     if (batch == 0) return FHE_OK;
     if (!d_bsk_prepared || !d_ksk || !d_pool || !d_desc || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_pool); REQUIRE_ALIGNED(d_desc); REQUIRE_ALIGNED(d_out);
-    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
     const u64 rows = (mux ? 2ull : 1ull) * batch;
-    if ((u64)batch > 0xffffffffull || rows * (k1 * n + n_lwe) > 0x7fffffffull * 256 ||
-        ((u64)batch + fhe::KS_TB - 1) / fhe::KS_TB * ((n_lwe + 1ull + fhe::KS_TH - 1) / fhe::KS_TH) > 0x7fffffffull)
+    if ((u64)batch > 0xffffffffull || s.init_items(rows) > kEwLimit || ks_grid(batch, n_lwe) == 0)
         return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
-    const u64 out_bytes = (u64)batch * (n_lwe + 1ull) * 8;
-    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
-        overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) || overlaps(d_out, out_bytes, d_desc, (u64)batch * 3 * 4))
+    if (overlaps_any(d_out, (u64)batch * (n_lwe + 1ull) * 8, {{d_bsk_prepared, bsk_bytes(s)}, {d_ksk, ksk_bytes(s)}, {d_desc, (u64)batch * 3 * 4}}))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps a key or the descriptors", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    void *accv = nullptr, *ext = nullptr, *shv = nullptr;
-    if ((rc = fhe_workspace_get(7, rows * k1 * n * 8, st, &accv)) != FHE_OK) return rc;
-    if ((rc = fhe_workspace_get(8, (u64)batch * (kn + 1) * 8, st, &ext)) != FHE_OK) return rc;
-    if ((rc = fhe_workspace_get(5, rows * n_lwe * 4, st, &shv)) != FHE_OK) return rc;
-    u64 *acc = (u64 *)accv;
-    { fhe::KernelTimer kt_(mux ? "tfhe_mux_init" : "tfhe_gate_init", (int)L, st);
-    hipLaunchKernelGGL(mux ? fhe::tfhe_gate_init_kernel<true> : fhe::tfhe_gate_init_kernel<false>, dim3(fhe_ew_grid(rows * (k1 * n + n_lwe))), dim3(256),
-                       0, st, (const u64 *)d_pool, (u64)wires, (const u32 *)d_desc, acc, (u32 *)shv, n_lwe, k1, L, rows);
-    }
-    LAUNCH_OK("tfhe_gate_init_kernel");
-    if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, (const u32 *)shv, rows, st)) != FHE_OK) return rc;
-    if (mux) {
-        { fhe::KernelTimer kt_("tfhe_mux_extract", (int)L, st);
-        hipLaunchKernelGGL(fhe::tfhe_mux_extract_kernel, dim3(fhe_ew_grid((u64)batch * (kn + 1))), dim3(256), 0, st, (const u64 *)acc, (u64 *)ext, k, L,
-                           (u64)batch);
-        }
-        LAUNCH_OK("tfhe_mux_extract_kernel");
-    } else if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) {
+    u64 *acc = nullptr, *ext = nullptr;
+    u32 *shift = nullptr;
+    if ((rc = boot_workspace(s, rows, batch, st, &acc, &ext, &shift)) != FHE_OK) return rc;
+    if ((rc = launch_named(mux ? "tfhe_mux_init" : "tfhe_gate_init", "tfhe_gate_init_kernel", s.L(), st,
+                     mux ? fhe::tfhe_gate_init_kernel<true> : fhe::tfhe_gate_init_kernel<false>, fhe_ew_grid(s.init_items(rows)), 256, d_pool, wires,
+                     d_desc, acc, shift, n_lwe, s.k1(), s.L(), rows)) != FHE_OK)
         return rc;
-    }
-    return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, batch, st);
+    return finish_boot(s, mux ? EXT_MUX : EXT_H0, 0, d_bsk_prepared, d_ksk, acc, shift, ext, d_out, batch, st);
 }
 }  // namespace
 
@@ -1251,12 +1293,47 @@ int check_lut_rows(unsigned n_lwe, const void *d_pool, size_t wires, const void 
                    u64 *out_bytes) {
     if (wires < 1 || batch < 1) return fhe_fail(FHE_E_INVALID, "%s: need wires >= 1 and batch >= 1", who);
     const u64 row_bytes = (n_lwe + 1ull) * 8;
-    if ((u64)batch > 0xffffffffull || (u64)wires > (~0ull >> 1) / row_bytes || (u64)batch * (n_lwe + 1ull) > 0x7fffffffull * 256)
+    if ((u64)batch > 0xffffffffull || (u64)wires > (~0ull >> 1) / row_bytes || (u64)batch * (n_lwe + 1ull) > kEwLimit)
         return fhe_fail(FHE_E_INVALID, "%s: batch or wires too large", who);
     if (!d_pool || !d_desc || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     REQUIRE_ALIGNED(d_pool); REQUIRE_ALIGNED(d_desc); REQUIRE_ALIGNED(d_out);
     *out_bytes = (u64)batch * row_bytes;
     return FHE_OK;
+}
+
+// fhe_tfhe_lut_bootstrap_dev (many = false, nu = 0: tfhe_lut_init, extraction at h = 0) and fhe_tfhe_lut_many_bootstrap_dev (the row-organised
+// init, extraction at h = 0 .. F - 1, F = 2^nu, d_out [F][batch][n_lwe + 1]): init -> the CMux steps -> extraction -> one key switch over the
+// F batch extracted rows, 2 n_lwe + 3 launches whatever the mix of tables and whatever nu is
+int lut_entry(bool many, const BootShape &s, const void *d_bsk_prepared, const void *d_ksk, unsigned t_bits, unsigned nu, const void *d_luts,
+              size_t lut_count, const void *d_pool, size_t wires, const void *d_desc, void *d_out, size_t batch, hipStream_t st) {
+    const char *who = many ? "fhe_tfhe_lut_many_bootstrap_dev" : "fhe_tfhe_lut_bootstrap_dev";
+    int rc = check_boot(s, who);
+    if (rc != FHE_OK) return rc;
+    const u32 L = s.L(), n_lwe = s.n_lwe;
+    if (t_bits < 1 || t_bits > L) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= t_bits <= log2 n (t_bits=%u, n=%llu)", who, t_bits, (unsigned long long)s.n);
+    if (nu > 4 || nu > L - t_bits)
+        return fhe_fail(FHE_E_INVALID, "%s: need nu <= min(log2 n - t_bits, 4) (nu=%u, t_bits=%u, n=%llu)", who, nu, t_bits, (unsigned long long)s.n);
+    if (lut_count < 1 || (u64)lut_count > 0xffffffffull)
+        return fhe_fail(FHE_E_INVALID, "%s: need 1 <= lut_count < 2^32 (lut_count=%llu)", who, (unsigned long long)lut_count);
+    u64 row_bytes = 0;                                                  // check_lut_rows: one function's slice, batch rows
+    if ((rc = check_lut_rows(n_lwe, d_pool, wires, d_desc, d_out, batch, who, &row_bytes)) != FHE_OK) return rc;
+    if (!d_bsk_prepared || !d_ksk || !d_luts) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_luts);
+    const u64 F = 1ull << nu, frows = F * (u64)batch;                   // the extraction and the key switch see F batch rows
+    if (s.init_items(batch) > kEwLimit || frows > 0xffffffffull || frows * (s.kn() + 1) > kEwLimit || ks_grid(frows, n_lwe) == 0)
+        return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (overlaps_any(d_out, F * row_bytes, {{d_bsk_prepared, bsk_bytes(s)}, {d_ksk, ksk_bytes(s)}, {d_luts, ((u64)lut_count << t_bits) * 8},
+                                            {d_desc, (u64)batch * fhe::LUT_DESC * 4}}))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps a key, the tables or the descriptors", who);
+    u64 *acc = nullptr, *ext = nullptr;
+    u32 *shift = nullptr;
+    if ((rc = boot_workspace(s, batch, frows, st, &acc, &ext, &shift)) != FHE_OK) return rc;
+    rc = many ? launch("tfhe_lut_many_init", L, st, fhe::tfhe_lut_many_init_kernel, (unsigned)std::min<u64>(batch, 256 * 16), 256, d_pool, wires, d_desc,
+                       d_luts, lut_count, t_bits, nu, acc, shift, n_lwe, s.k1(), L, batch)
+              : launch("tfhe_lut_init", L, st, fhe::tfhe_lut_init_kernel, fhe_ew_grid(s.init_items(batch)), 256, d_pool, wires, d_desc, d_luts, lut_count,
+                       t_bits, acc, shift, n_lwe, s.k1(), L, batch);
+    if (rc != FHE_OK) return rc;
+    return finish_boot(s, many ? EXT_MANY : EXT_H0, nu, d_bsk_prepared, d_ksk, acc, shift, ext, d_out, batch, st);
 }
 }  // namespace
 
@@ -1269,104 +1346,25 @@ extern "C" int fhe_tlwe_lincomb_dev(unsigned n_lwe, const void *d_pool, size_t w
     if (rc != FHE_OK) return rc;
     if (overlaps(d_out, out_bytes, d_desc, (u64)batch * fhe::LUT_DESC * 4)) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the descriptors", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    { fhe::KernelTimer kt_("tlwe_lincomb", 0, st);
-    hipLaunchKernelGGL(fhe::tlwe_lincomb_kernel, dim3(fhe_ew_grid((u64)batch * (n_lwe + 1ull))), dim3(256), 0, st, (const u64 *)d_pool, (u64)wires,
-                       (const u32 *)d_desc, (u64 *)d_out, n_lwe, (u64)batch);
-    }
-    LAUNCH_OK("tlwe_lincomb_kernel");
-    return FHE_OK;
+    return launch("tlwe_lincomb", 0, st, fhe::tlwe_lincomb_kernel, fhe_ew_grid((u64)batch * (n_lwe + 1ull)), 256, d_pool, wires, d_desc, d_out, n_lwe,
+                  batch);
 }
 
-// lut init -> the §11 CMux steps -> extraction at h = 0 -> key switch into d_out: 2 n_lwe + 3 launches whatever the mix of tables
 extern "C" int fhe_tfhe_lut_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
                                           unsigned ks_log_beta, unsigned ks_l, const void *d_ksk, unsigned t_bits, const void *d_luts,
                                           size_t lut_count, const void *d_pool, size_t wires, const void *d_desc, void *d_out, size_t batch,
                                           void *hip_stream) {
-    const char *who = "fhe_tfhe_lut_bootstrap_dev";
-    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
-    if (rc != FHE_OK) return rc;
-    const u64 kn = (u64)k * n;
-    if ((rc = check_gks((unsigned)kn, n_lwe, ks_log_beta, ks_l, who)) != FHE_OK) return rc;
-    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
-    if (t_bits < 1 || t_bits > L) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= t_bits <= log2 n (t_bits=%u, n=%llu)", who, t_bits, (unsigned long long)n);
-    if (lut_count < 1 || (u64)lut_count > 0xffffffffull)
-        return fhe_fail(FHE_E_INVALID, "%s: need 1 <= lut_count < 2^32 (lut_count=%llu)", who, (unsigned long long)lut_count);
-    u64 out_bytes = 0;
-    if ((rc = check_lut_rows(n_lwe, d_pool, wires, d_desc, d_out, batch, who, &out_bytes)) != FHE_OK) return rc;
-    if (!d_bsk_prepared || !d_ksk || !d_luts) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
-    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_luts);
-    if ((u64)batch * (k1 * n + n_lwe) > 0x7fffffffull * 256 ||
-        ((u64)batch + fhe::KS_TB - 1) / fhe::KS_TB * ((n_lwe + 1ull + fhe::KS_TH - 1) / fhe::KS_TH) > 0x7fffffffull)
-        return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
-    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
-        overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) || overlaps(d_out, out_bytes, d_luts, ((u64)lut_count << t_bits) * 8) ||
-        overlaps(d_out, out_bytes, d_desc, (u64)batch * fhe::LUT_DESC * 4))
-        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps a key, the tables or the descriptors", who);
-    hipStream_t st = (hipStream_t)hip_stream;
-    void *accv = nullptr, *ext = nullptr, *shv = nullptr;
-    if ((rc = fhe_workspace_get(7, (u64)batch * k1 * n * 8, st, &accv)) != FHE_OK) return rc;
-    if ((rc = fhe_workspace_get(8, (u64)batch * (kn + 1) * 8, st, &ext)) != FHE_OK) return rc;
-    if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &shv)) != FHE_OK) return rc;
-    u64 *acc = (u64 *)accv;
-    { fhe::KernelTimer kt_("tfhe_lut_init", (int)L, st);
-    hipLaunchKernelGGL(fhe::tfhe_lut_init_kernel, dim3(fhe_ew_grid((u64)batch * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_pool, (u64)wires,
-                       (const u32 *)d_desc, (const u64 *)d_luts, (u64)lut_count, t_bits, acc, (u32 *)shv, n_lwe, k1, L, (u64)batch);
-    }
-    LAUNCH_OK("tfhe_lut_init_kernel");
-    if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, (const u32 *)shv, batch, st)) != FHE_OK) return rc;
-    if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) return rc;
-    return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, batch, st);
+    return lut_entry(false, {n, k, log_beta, l, n_lwe, ks_log_beta, ks_l}, d_bsk_prepared, d_ksk, t_bits, 0, d_luts, lut_count, d_pool, wires, d_desc,
+                     d_out, batch, (hipStream_t)hip_stream);
 }
 
 // ---- small integers: several tables from one blind rotation ----------------------------------------------------
-// many init -> the §11 CMux steps over `batch` rows -> extraction at h = 0 .. F - 1 -> one key switch over the F batch extracted
-// rows into d_out [F][batch][n_lwe + 1]: 2 n_lwe + 3 launches whatever nu is
 extern "C" int fhe_tfhe_lut_many_bootstrap_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
                                                unsigned ks_log_beta, unsigned ks_l, const void *d_ksk, unsigned t_bits, unsigned nu,
                                                const void *d_luts, size_t lut_count, const void *d_pool, size_t wires, const void *d_desc,
                                                void *d_out, size_t batch, void *hip_stream) {
-    const char *who = "fhe_tfhe_lut_many_bootstrap_dev";
-    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
-    if (rc != FHE_OK) return rc;
-    const u64 kn = (u64)k * n;
-    if ((rc = check_gks((unsigned)kn, n_lwe, ks_log_beta, ks_l, who)) != FHE_OK) return rc;
-    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
-    if (t_bits < 1 || t_bits > L) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= t_bits <= log2 n (t_bits=%u, n=%llu)", who, t_bits, (unsigned long long)n);
-    if (nu > 4 || nu > L - t_bits)
-        return fhe_fail(FHE_E_INVALID, "%s: need nu <= min(log2 n - t_bits, 4) (nu=%u, t_bits=%u, n=%llu)", who, nu, t_bits, (unsigned long long)n);
-    if (lut_count < 1 || (u64)lut_count > 0xffffffffull)
-        return fhe_fail(FHE_E_INVALID, "%s: need 1 <= lut_count < 2^32 (lut_count=%llu)", who, (unsigned long long)lut_count);
-    u64 row_bytes = 0;                                                  // check_lut_rows: one function's slice, batch rows
-    if ((rc = check_lut_rows(n_lwe, d_pool, wires, d_desc, d_out, batch, who, &row_bytes)) != FHE_OK) return rc;
-    if (!d_bsk_prepared || !d_ksk || !d_luts) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
-    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_luts);
-    const u64 F = 1ull << nu, frows = F * (u64)batch;                   // the extraction and the key switch see F batch rows
-    if ((u64)batch * (k1 * n + n_lwe) > 0x7fffffffull * 256 || frows > 0xffffffffull || frows * (kn + 1) > 0x7fffffffull * 256 ||
-        (frows + fhe::KS_TB - 1) / fhe::KS_TB * ((n_lwe + 1ull + fhe::KS_TH - 1) / fhe::KS_TH) > 0x7fffffffull)
-        return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
-    const u64 out_bytes = F * row_bytes;
-    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
-        overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) || overlaps(d_out, out_bytes, d_luts, ((u64)lut_count << t_bits) * 8) ||
-        overlaps(d_out, out_bytes, d_desc, (u64)batch * fhe::LUT_DESC * 4))
-        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps a key, the tables or the descriptors", who);
-    hipStream_t st = (hipStream_t)hip_stream;
-    void *accv = nullptr, *ext = nullptr, *shv = nullptr;
-    if ((rc = fhe_workspace_get(7, (u64)batch * k1 * n * 8, st, &accv)) != FHE_OK) return rc;
-    if ((rc = fhe_workspace_get(8, frows * (kn + 1) * 8, st, &ext)) != FHE_OK) return rc;
-    if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &shv)) != FHE_OK) return rc;
-    u64 *acc = (u64 *)accv;
-    { fhe::KernelTimer kt_("tfhe_lut_many_init", (int)L, st);
-    hipLaunchKernelGGL(fhe::tfhe_lut_many_init_kernel, dim3((unsigned)std::min<u64>(batch, 256 * 16)), dim3(256), 0, st, (const u64 *)d_pool,
-                       (u64)wires, (const u32 *)d_desc, (const u64 *)d_luts, (u64)lut_count, t_bits, nu, acc, (u32 *)shv, n_lwe, k1, L, (u64)batch);
-    }
-    LAUNCH_OK("tfhe_lut_many_init_kernel");
-    if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, (const u32 *)shv, batch, st)) != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("tfhe_many_extract", (int)L, st);
-    hipLaunchKernelGGL(fhe::tfhe_many_extract_kernel, dim3(fhe_ew_grid((u64)batch * (kn + F))), dim3(256), 0, st, (const u64 *)acc, (u64 *)ext, k, L,
-                       nu, (u64)batch);
-    }
-    LAUNCH_OK("tfhe_many_extract_kernel");
-    return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, frows, st);
+    return lut_entry(true, {n, k, log_beta, l, n_lwe, ks_log_beta, ks_l}, d_bsk_prepared, d_ksk, t_bits, nu, d_luts, lut_count, d_pool, wires, d_desc,
+                     d_out, batch, (hipStream_t)hip_stream);
 }
 
 // ---- packing key switch and the bootstrap with a test vector per row ---------------------------------------
@@ -1374,7 +1372,6 @@ namespace {
 // the packing shape: §12's PFKS shape (k = 1, 2^8 <= n <= 2^12, 1 <= b <= 32, l >= 1, b l <= 64) and n_in >= 1
 bool pks_shape(uint64_t n, unsigned k, unsigned n_in, unsigned log_beta, unsigned l) { return n_in >= 1 && pfks_shape(n, k, log_beta, l); }
 u64 pksk_words(uint64_t n, unsigned k, unsigned n_in, unsigned l) { return (u64)n_in * l * (k + 1) * n; }
-bool mul_fits(u64 a, u64 b, u64 limit) { return b == 0 || a <= limit / b; }
 }  // namespace
 
 extern "C" size_t fhe_tfhe_pksk_words(uint64_t n, unsigned k, unsigned n_in, unsigned log_beta, unsigned l) {
@@ -1399,22 +1396,17 @@ extern "C" int fhe_tlwe_gadget_packing_key_switch_dev(uint64_t n, unsigned k, un
     if (!d_pksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     REQUIRE_ALIGNED(d_pksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
     const u32 cblocks = (u32)(k1 * n / fhe::PK_TH);
-    const u64 tiles = ((u64)groups - 1) / fhe::PK_TG + 1, word_limit = ~0ull >> 4;      // every extent in bytes fits 61 bits
-    if (tiles * cblocks > 0x7fffffffull || !mul_fits((u64)groups, (u64)k1 * n, word_limit) || !mul_fits((u64)groups - 1, in_group_stride, word_limit / 2) ||
-        !mul_fits((u64)count - 1, in_item_stride, word_limit / 2 - n_in - 1))
+    const u64 tiles = ((u64)groups - 1) / fhe::PK_TG + 1;                                // every extent in bytes fits 61 bits
+    if (tiles * cblocks > 0x7fffffffull || !mul_fits((u64)groups, (u64)k1 * n, kWordLimit) || !mul_fits((u64)groups - 1, in_group_stride, kWordLimit / 2) ||
+        !mul_fits((u64)count - 1, in_item_stride, kWordLimit / 2 - n_in - 1))
         return fhe_fail(FHE_E_INVALID, "%s: groups or the input strides are too large for one launch", who);
     const u64 in_words = ((u64)groups - 1) * in_group_stride + ((u64)count - 1) * in_item_stride + n_in + 1;
     const u64 out_bytes = (u64)groups * k1 * n * 8;
-    if (overlaps(d_out, out_bytes, d_pksk, pksk_words(n, k, n_in, l) * 8) || overlaps(d_out, out_bytes, d_in, in_words * 8))
+    if (overlaps_any(d_out, out_bytes, {{d_pksk, pksk_words(n, k, n_in, l) * 8}, {d_in, in_words * 8}}))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key or the input", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    { fhe::KernelTimer kt_("tlwe_packing_ks", (int)L, st);
-    hipLaunchKernelGGL(fhe::tlwe_packing_ks_kernel, dim3((unsigned)(tiles * cblocks)), dim3(fhe::PK_TH), 0, st, (const u64 *)d_pksk, (const u64 *)d_in,
-                       (u64 *)d_out, n_in, L, k1, log_beta, l, fhe::gadget_cadd(log_beta, l), (u64)in_group_stride, (u64)in_item_stride, (u32)count,
-                       log_stride, (u64)groups, cblocks);
-    }
-    LAUNCH_OK("tlwe_packing_ks_kernel");
-    return FHE_OK;
+    return launch("tlwe_packing_ks", L, st, fhe::tlwe_packing_ks_kernel, (unsigned)(tiles * cblocks), fhe::PK_TH, d_pksk, d_in, d_out, n_in, L, k1,
+                  log_beta, l, fhe::gadget_cadd(log_beta, l), in_group_stride, in_item_stride, (u32)count, log_stride, groups, cblocks);
 }
 
 extern "C" int fhe_tglwe_box_expand_dev(uint64_t n, unsigned k, unsigned t_bits, const void *d_in, void *d_out, size_t batch, void *hip_stream) {
@@ -1428,49 +1420,16 @@ extern "C" int fhe_tglwe_box_expand_dev(uint64_t n, unsigned k, unsigned t_bits,
     if (batch == 0) return FHE_OK;
     if (!d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
-    if (!mul_fits((u64)batch, (u64)k1 * n, ~0ull >> 4)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!mul_fits((u64)batch, (u64)k1 * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
     const u64 rows = (u64)batch * k1, bytes = rows * n * 8;
     if (overlaps(d_out, bytes, d_in, bytes)) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps d_in", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    { fhe::KernelTimer kt_("tglwe_box_expand", (int)L, st);
-    hipLaunchKernelGGL(fhe::tglwe_box_expand_kernel, dim3((unsigned)std::min<u64>(rows, 256 * 16)), dim3(256), 0, st, (const u64 *)d_in, (u64 *)d_out, L,
-                       t_bits, rows);
-    }
-    LAUNCH_OK("tglwe_box_expand_kernel");
-    return FHE_OK;
+    return launch("tglwe_box_expand", L, st, fhe::tglwe_box_expand_kernel, (unsigned)std::min<u64>(rows, 256 * 16), 256, d_in, d_out, L, t_bits, rows);
 }
 
-// rows init -> the §11 CMux steps -> extraction at h = 0 -> gadget key switch: fhe_tfhe_gadget_bootstrap_dev with d_tables
-// [batch][(k+1)][n] in place of the one table, 2 n_lwe + 3 launches
 extern "C" int fhe_tfhe_gadget_bootstrap_rows_dev(uint64_t n, unsigned k, unsigned log_beta, unsigned l, unsigned n_lwe, const void *d_bsk_prepared,
                                                   const void *d_tables, unsigned ks_log_beta, unsigned ks_l, const void *d_ksk, const void *d_in,
                                                   void *d_out, size_t batch, void *hip_stream) {
-    const char *who = "fhe_tfhe_gadget_bootstrap_rows_dev";
-    int rc = check_gbr(n, k, log_beta, l, n_lwe, who);
-    if (rc != FHE_OK) return rc;
-    const u64 kn = (u64)k * n;
-    if ((rc = check_gks((unsigned)kn, n_lwe, ks_log_beta, ks_l, who)) != FHE_OK) return rc;
-    if (batch == 0) return FHE_OK;
-    if (!d_bsk_prepared || !d_tables || !d_ksk || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
-    REQUIRE_ALIGNED(d_bsk_prepared); REQUIRE_ALIGNED(d_tables); REQUIRE_ALIGNED(d_ksk); REQUIRE_ALIGNED(d_in); REQUIRE_ALIGNED(d_out);
-    const u32 k1 = k + 1, L = (u32)__builtin_ctzll(n);
-    const u64 out_bytes = (u64)batch * (n_lwe + 1ull) * 8;
-    if (overlaps(d_out, out_bytes, d_bsk_prepared, (u64)n_lwe * gadget_tggsw_words(n, k, l) * 8) ||
-        overlaps(d_out, out_bytes, d_tables, (u64)batch * k1 * n * 8) || overlaps(d_out, out_bytes, d_ksk, kn * ks_l * (n_lwe + 1ull) * 8) ||
-        overlaps(d_out, out_bytes, d_in, out_bytes))
-        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an input", who);
-    hipStream_t st = (hipStream_t)hip_stream;
-    void *accv = nullptr, *ext = nullptr, *shv = nullptr;
-    if ((rc = fhe_workspace_get(7, (u64)batch * k1 * n * 8, st, &accv)) != FHE_OK) return rc;
-    if ((rc = fhe_workspace_get(8, (u64)batch * (kn + 1) * 8, st, &ext)) != FHE_OK) return rc;
-    if ((rc = fhe_workspace_get(5, (u64)batch * n_lwe * 4, st, &shv)) != FHE_OK) return rc;
-    u64 *acc = (u64 *)accv;
-    { fhe::KernelTimer kt_("tfhe_br_rows_init", (int)L, st);
-    hipLaunchKernelGGL(fhe::tfhe_br_rows_init_kernel, dim3(fhe_ew_grid((u64)batch * (k1 * n + n_lwe))), dim3(256), 0, st, (const u64 *)d_in,
-                       (const u64 *)d_tables, acc, (u32 *)shv, n_lwe, k1, L, (u64)batch);
-    }
-    LAUNCH_OK("tfhe_br_rows_init_kernel");
-    if ((rc = gadget_br_steps(n, k, log_beta, l, n_lwe, d_bsk_prepared, acc, (const u32 *)shv, batch, st)) != FHE_OK) return rc;
-    if ((rc = sample_extraction(n, k, 0, acc, ext, batch, st)) != FHE_OK) return rc;
-    return gadget_key_switch((unsigned)kn, n_lwe, ks_log_beta, ks_l, d_ksk, ext, d_out, batch, st);
+    return table_bootstrap("fhe_tfhe_gadget_bootstrap_rows_dev", "tfhe_br_rows_init", {n, k, log_beta, l, n_lwe, ks_log_beta, ks_l}, d_bsk_prepared,
+                           d_tables, 1, d_ksk, d_in, d_out, batch, (hipStream_t)hip_stream);
 }

@@ -204,15 +204,9 @@ __global__ __launch_bounds__(256) void tglwe_phase_epilogue_kernel(const u64 *__
 // ---- host side -----------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr u64 kWordLimit = ~0ull >> 4;          // every extent in bytes fits 61 bits
 constexpr int kClientSlot = 9;                  // fhe_workspace_get slot of the TGLWE staging rows (fhe_tn_mul_dev takes slot 1)
 constexpr u64 kChunkWords = 1ull << 21;         // TGLWE rows are processed 2^21 coefficients at a time: 48 MiB of staging
 
-bool overlaps(const void *a, u64 abytes, const void *b, u64 bbytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return a && b && abytes && bbytes && x < y + bbytes && y < x + abytes;
-}
-bool mul_fits(u64 a, u64 b, u64 limit) { return b == 0 || a <= limit / b; }
 bool misaligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
 
 fhe::ChaChaKey seed_key(const uint8_t *seed) {
