@@ -1,9 +1,15 @@
-// capi_internal.hpp — shared between capi.hip (plans, transforms) and zring.hip (exact
-// integer products built on them).  Not part of the public boundary.
+// capi_internal.hpp — what the sources of the library share behind the public boundary: the plan and its device tables,
+// the services of capi.hip (error reporting, device plans, workspace, staging pool, switches), and the host helpers every
+// entry point is written with: the argument checks (REQUIRE_ALIGNED, overlaps / overlaps_any, mul_fits, check_ring),
+// the timed launch with its check (launch / launch_named) and the staging of host buffers around a *_dev call
+// (FheHostStage, fhe_host_call).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
+#include <initializer_list>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -90,11 +96,50 @@ static inline unsigned fhe_ew_grid(fhe::u64 count) {
     if (g > 256 * 16) g = 256 * 16;
     return (unsigned)(g ? g : 1);
 }
-#define LAUNCH_OK(what)                                      \
-    do {                                                     \
-        hipError_t e_ = hipGetLastError();                   \
-        if (e_ != hipSuccess) return fhe_hip_fail(e_, what); \
-    } while (0)
+// does [d_out, d_out + out_bytes) intersect one of the inputs {pointer, bytes}?
+struct Extent { const void *p; fhe::u64 bytes; };
+static inline bool overlaps_any(const void *d_out, fhe::u64 out_bytes, std::initializer_list<Extent> inputs) {
+    for (const Extent &e : inputs)
+        if (overlaps(d_out, out_bytes, e.p, e.bytes)) return true;
+    return false;
+}
+
+// the ring size every polynomial entry point accepts, and with k the TGLWE dimension as well
+static inline int check_ring(uint64_t n, const char *who) {
+    if (n < 2 || (n & (n - 1)) != 0 || n > (1ull << 19))
+        return fhe_fail(FHE_E_BAD_N, "%s: n=%llu must be a power of two in [2, 2^19]", who, (unsigned long long)n);
+    return FHE_OK;
+}
+static inline int check_ring(uint64_t n, unsigned k, const char *who) {
+    int rc = check_ring(n, who);
+    if (rc != FHE_OK) return rc;
+    if (k < 1 || k > 64) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= k <= 64", who);
+    return FHE_OK;
+}
+
+// a kernel argument as its parameter type: device pointers arrive as void *, and an integer may widen but not narrow
+template <class P, class A>
+P kernel_arg(A a) {
+    static_assert(!(std::is_integral<P>::value && std::is_integral<A>::value) || sizeof(A) <= sizeof(P), "narrowing kernel argument: cast it at the call");
+    return static_cast<P>(a);
+}
+// one timed launch (tag L for the timer) and its check: the FHE_* code.  A launch error names kernel_name, <label>_kernel if NULL.
+template <class... P, class... A>
+int launch_named(const char *label, const char *kernel_name, int L, hipStream_t st, void (*kernel)(P...), unsigned grid, unsigned block, A... args) {
+    {
+        fhe::KernelTimer kt_(label, L, st);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, kernel_arg<P>(args)...);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return FHE_OK;
+    char name[64];
+    snprintf(name, sizeof name, "%s_kernel", label);
+    return fhe_hip_fail(e, kernel_name ? kernel_name : name);
+}
+template <class K, class... A>
+int launch(const char *label, int L, hipStream_t st, K kernel, unsigned grid, unsigned block, A... args) {
+    return launch_named(label, nullptr, L, st, kernel, grid, block, args...);
+}
 
 // Staging of HOST buffers around a *_dev entry point: uploads on the calling thread's stream
 // (hipStreamPerThread, for which the library workspace is per thread: no lock is needed); the
@@ -127,3 +172,20 @@ struct FheHostStage {
         return FHE_OK;
     }
 };
+
+// A host-buffer entry point after its own argument checks: the device check, the inputs {host pointer, bytes} uploaded in
+// order, the output buffer, `call(d)` — the *_dev call on hipStreamPerThread with d[i] input i and d[N] the output — and
+// the download.
+struct FheHostIn { const void *h; size_t bytes; };
+template <size_t N, class F>
+int fhe_host_call(const FheHostIn (&in)[N], void *out, size_t out_bytes, F call) {
+    int dev, rc = fhe_current_device(&dev);
+    if (rc != FHE_OK) return rc;
+    FheHostStage hs;
+    void *d[N + 1];
+    for (size_t i = 0; i < N; i++)
+        if ((rc = hs.up(in[i].h, in[i].bytes, &d[i])) != FHE_OK) return rc;
+    if ((rc = hs.up(nullptr, out_bytes, &d[N])) != FHE_OK) return rc;
+    if ((rc = call(d)) != FHE_OK) return rc;
+    return hs.down(out, d[N], out_bytes);
+}

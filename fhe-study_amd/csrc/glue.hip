@@ -182,12 +182,7 @@ static int ew_call(const fhe_ntt_plan *plan, const void *a, const void *b, void 
     int dev, rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
     const u64 count = batch * plan->n;
-    { fhe::KernelTimer kt_("ew", 0, (hipStream_t)stream);
-    hipLaunchKernelGGL((fhe::ew_kernel<OP>), dim3(fhe_ew_grid(count)), dim3(256), 0, (hipStream_t)stream, (const u64 *)a,
-                       (const u64 *)b, (u64 *)c, count, plan->mod, s);
-    }
-    LAUNCH_OK(who);
-    return FHE_OK;
+    return launch_named("ew", who, 0, (hipStream_t)stream, fhe::ew_kernel<OP>, fhe_ew_grid(count), 256, a, b, c, count, plan->mod, s);
 }
 extern "C" int fhe_rq_add_dev(const fhe_ntt_plan *plan, const void *d_a, const void *d_b, void *d_c, size_t batch, void *st) {
     return ew_call<fhe::Ew::Add>(plan, d_a, d_b, d_c, batch, 0, st, "fhe_rq_add_dev");
@@ -208,11 +203,7 @@ extern "C" int fhe_rq_mod_switch_dev(uint64_t q, uint64_t p, const void *d_a, vo
     if (!d_a || !d_c) return fhe_fail(FHE_E_NULL, "fhe_rq_mod_switch_dev: NULL buffer");
     int dev, rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("mod_switch", 0, (hipStream_t)st);
-    hipLaunchKernelGGL(fhe::mod_switch_kernel, dim3(fhe_ew_grid(count)), dim3(256), 0, (hipStream_t)st, (const u64 *)d_a, (u64 *)d_c, (u64)count, (u64)q, (u64)p);
-    }
-    LAUNCH_OK("mod_switch_kernel");
-    return FHE_OK;
+    return launch("mod_switch", 0, (hipStream_t)st, fhe::mod_switch_kernel, fhe_ew_grid(count), 256, d_a, d_c, count, q, p);
 }
 extern "C" int fhe_rq_mul_div_round_dev(uint64_t q, uint64_t num, uint64_t den, const void *d_a, void *d_c, size_t count, void *st) {
     if (q == 0 || den == 0 || (q >> 63)) return fhe_fail(FHE_E_BAD_Q, "fhe_rq_mul_div_round_dev: need 0 < q < 2^63, den > 0");
@@ -220,11 +211,7 @@ extern "C" int fhe_rq_mul_div_round_dev(uint64_t q, uint64_t num, uint64_t den, 
     if (!d_a || !d_c) return fhe_fail(FHE_E_NULL, "fhe_rq_mul_div_round_dev: NULL buffer");
     int dev, rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("rq_mul_div_round", 0, (hipStream_t)st);
-    hipLaunchKernelGGL(fhe::rq_mul_div_round_kernel, dim3(fhe_ew_grid(count)), dim3(256), 0, (hipStream_t)st, (const u64 *)d_a, (u64 *)d_c, (u64)count, (u64)q, (u64)num, (u64)den);
-    }
-    LAUNCH_OK("rq_mul_div_round_kernel");
-    return FHE_OK;
+    return launch("rq_mul_div_round", 0, (hipStream_t)st, fhe::rq_mul_div_round_kernel, fhe_ew_grid(count), 256, d_a, d_c, count, q, num, den);
 }
 extern "C" int fhe_rq_remodule_dev(uint64_t p, const void *d_a, void *d_c, size_t count, void *st) {
     if (p == 0) return fhe_fail(FHE_E_BAD_Q, "fhe_rq_remodule_dev: p = 0");
@@ -232,11 +219,7 @@ extern "C" int fhe_rq_remodule_dev(uint64_t p, const void *d_a, void *d_c, size_
     if (!d_a || !d_c) return fhe_fail(FHE_E_NULL, "fhe_rq_remodule_dev: NULL buffer");
     int dev, rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("ewf", 0, (hipStream_t)st);
-    hipLaunchKernelGGL((fhe::ewf_kernel<fhe::EwF::Remodule>), dim3(fhe_ew_grid(count)), dim3(256), 0, (hipStream_t)st, (const u64 *)d_a, (u64 *)d_c, (u64)count, (u64)p, (u64)0, 0.0);
-    }
-    LAUNCH_OK("ewf_kernel<Remodule>");
-    return FHE_OK;
+    return launch_named("ewf", "ewf_kernel<Remodule>", 0, (hipStream_t)st, fhe::ewf_kernel<fhe::EwF::Remodule>, fhe_ew_grid(count), 256, d_a, d_c, count, p, 0, 0.0);
 }
 extern "C" int fhe_rq_mul_by_f64_dev(uint64_t q, double s, const void *d_a, void *d_c, size_t count, void *st) {
     if (q == 0 || (q >> 63)) return fhe_fail(FHE_E_BAD_Q, "fhe_rq_mul_by_f64_dev: need 0 < q < 2^63");
@@ -244,11 +227,7 @@ extern "C" int fhe_rq_mul_by_f64_dev(uint64_t q, double s, const void *d_a, void
     if (!d_a || !d_c) return fhe_fail(FHE_E_NULL, "fhe_rq_mul_by_f64_dev: NULL buffer");
     int dev, rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("ewf", 0, (hipStream_t)st);
-    hipLaunchKernelGGL((fhe::ewf_kernel<fhe::EwF::MulF64>), dim3(fhe_ew_grid(count)), dim3(256), 0, (hipStream_t)st, (const u64 *)d_a, (u64 *)d_c, (u64)count, (u64)q, (u64)0, s);
-    }
-    LAUNCH_OK("ewf_kernel<MulF64>");
-    return FHE_OK;
+    return launch_named("ewf", "ewf_kernel<MulF64>", 0, (hipStream_t)st, fhe::ewf_kernel<fhe::EwF::MulF64>, fhe_ew_grid(count), 256, d_a, d_c, count, q, 0, s);
 }
 extern "C" int fhe_rq_div_round_dev(uint64_t q, uint64_t s, const void *d_a, void *d_c, size_t count, void *st) {
     if (q == 0 || (q >> 63)) return fhe_fail(FHE_E_BAD_Q, "fhe_rq_div_round_dev: need 0 < q < 2^63");
@@ -257,11 +236,7 @@ extern "C" int fhe_rq_div_round_dev(uint64_t q, uint64_t s, const void *d_a, voi
     if (!d_a || !d_c) return fhe_fail(FHE_E_NULL, "fhe_rq_div_round_dev: NULL buffer");
     int dev, rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("ewf", 0, (hipStream_t)st);
-    hipLaunchKernelGGL((fhe::ewf_kernel<fhe::EwF::DivRound>), dim3(fhe_ew_grid(count)), dim3(256), 0, (hipStream_t)st, (const u64 *)d_a, (u64 *)d_c, (u64)count, (u64)q, (u64)s, 0.0);
-    }
-    LAUNCH_OK("ewf_kernel<DivRound>");
-    return FHE_OK;
+    return launch_named("ewf", "ewf_kernel<DivRound>", 0, (hipStream_t)st, fhe::ewf_kernel<fhe::EwF::DivRound>, fhe_ew_grid(count), 256, d_a, d_c, count, q, s, 0.0);
 }
 // Argument ranges in which Zq::decompose (zq.rs:141-190) is defined.  Outside them the reference
 // panics (`beta.pow(l)` overflowing u32 and `>> i` with i >= 64 in a debug build, `q / beta^i` = 0
@@ -289,11 +264,7 @@ extern "C" int fhe_rq_decompose_dev(uint64_t q, uint64_t n, unsigned beta, unsig
     if (!d_a || !d_out) return fhe_fail(FHE_E_NULL, "fhe_rq_decompose_dev: NULL buffer");
     int dev, rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("decompose", 0, (hipStream_t)st);
-    hipLaunchKernelGGL(fhe::decompose_kernel, dim3(fhe_ew_grid(rows * n)), dim3(256), 0, (hipStream_t)st, (const u64 *)d_a, (u64 *)d_out, (u64)rows, (u32)n, (u64)q, (u32)beta, (u32)l, (u32)1, (u64)n);
-    }
-    LAUNCH_OK("decompose_kernel");
-    return FHE_OK;
+    return launch("decompose", 0, (hipStream_t)st, fhe::decompose_kernel, fhe_ew_grid(rows * n), 256, d_a, d_out, rows, (u32)n, q, beta, l, 1, n);
 }
 
 // ---- N3 ------------------------------------------------------------------------------------
@@ -326,10 +297,7 @@ extern "C" int fhe_tr_dot_dev(const fhe_ntt_plan *plan, const void *d_a, const v
     if (!b_ev) { if ((rc = fwd(plan, dp, B, WB, rows, st)) != FHE_OK) return rc; B = WB; }
     u64 *C = out_ev ? (u64 *)d_c : WC;
     // T = k terms, nc = 1 output row, "G" = A per batch element
-    { fhe::KernelTimer kt_("mac_rows", 0, st);
-    fhe::launch_mac_rows(dp.arith == fhe::kArStrict63, fhe_ew_grid(fhe::mac_rows_threads(batch, 1, n)), st, A, B, C, (u64)batch, (u32)n, (u32)k, (u32)1, (u64)k * n, plan->mod);
-    }
-    LAUNCH_OK("mac_rows_kernel");
+    if ((rc = fhe_mac_rows(dp.arith == fhe::kArStrict63, st, A, B, C, batch, (u32)n, k, 1, (u64)k * n, plan->mod)) != FHE_OK) return rc;
     return out_ev ? FHE_OK : inv(plan, dp, C, (u64 *)d_c, batch, st);
 }
 
@@ -354,10 +322,7 @@ extern "C" int fhe_tr_mul_r_dev(const fhe_ntt_plan *plan, const void *d_a, const
     if (!p_ev) { if ((rc = fwd(plan, dp, P, WP, batch, st)) != FHE_OK) return rc; P = WP; }
     u64 *C = out_ev ? (u64 *)d_out : WC;
     // T = 1, nc = rows: out[b][c] = A[b][c] * P[b]
-    { fhe::KernelTimer kt_("mac_rows", 0, st);
-    fhe::launch_mac_rows(dp.arith == fhe::kArStrict63, fhe_ew_grid(fhe::mac_rows_threads(batch, rows, n)), st, A, P, C, (u64)batch, (u32)n, (u32)1, (u32)rows, (u64)rows * n, plan->mod);
-    }
-    LAUNCH_OK("mac_rows_kernel");
+    if ((rc = fhe_mac_rows(dp.arith == fhe::kArStrict63, st, A, P, C, batch, (u32)n, 1, rows, (u64)rows * n, plan->mod)) != FHE_OK) return rc;
     return out_ev ? FHE_OK : inv(plan, dp, C, (u64 *)d_out, total, st);
 }
 
@@ -370,10 +335,7 @@ static int keyed_mac(const fhe_ntt_plan *plan, const fhe::DevicePlan &dp, const 
     int rc;
     if (!key_is_evals) { if ((rc = fwd(plan, dp, d_key, WK, (u64)T * nc, st)) != FHE_OK) return rc; K = WK; }
     if (!v_is_evals) { if ((rc = fwd(plan, dp, d_v, WV, batch * T, st)) != FHE_OK) return rc; V = WV; }
-    { fhe::KernelTimer kt_("mac_rows", 0, st);
-    fhe::launch_mac_rows(dp.arith == fhe::kArStrict63, fhe_ew_grid(fhe::mac_rows_threads(batch, nc, n)), st, K, V, d_out, batch, (u32)n, T, nc, (u64)0, plan->mod);
-    }
-    LAUNCH_OK("mac_rows_kernel");
+    if ((rc = fhe_mac_rows(dp.arith == fhe::kArStrict63, st, K, V, d_out, batch, (u32)n, T, nc, 0, plan->mod)) != FHE_OK) return rc;
     return out_evals ? FHE_OK : inv(plan, dp, d_out, d_out, batch * nc, st);
 }
 
@@ -481,11 +443,7 @@ extern "C" int fhe_glwe_key_switch_dev(const fhe_ntt_plan *plan, unsigned k, uns
             if (parts > 1 && (e = fhe::launch_sum_parts(PART, RHS, batch, parts, (u64)k1 * n, plan->q, st)) != hipSuccess)
                 return fhe_hip_fail(e, "sum_parts_kernel");
             if ((rc = inv(plan, dp, RHS, RHS, batch * k1, st)) != FHE_OK) return rc;
-            { fhe::KernelTimer kt_("ks_tail", 0, st);
-            hipLaunchKernelGGL(fhe::ks_tail_kernel, dim3(fhe_ew_grid(batch * k1 * n)), dim3(256), 0, st, (const u64 *)d_glwe, (const u64 *)RHS, (u64 *)d_out, (u64)batch, (u32)n, (u32)k, (u64)plan->q);
-            }
-            LAUNCH_OK("ks_tail_kernel");
-            return FHE_OK;
+            return launch("ks_tail", 0, st, fhe::ks_tail_kernel, fhe_ew_grid(batch * k1 * n), 256, d_glwe, RHS, d_out, batch, (u32)n, k, plan->q);
         }
         if (e != hipErrorNotSupported) return fhe_hip_fail(e, "digit_mac_kernel");
         (void)hipGetLastError();
@@ -504,10 +462,9 @@ extern "C" int fhe_glwe_key_switch_dev(const fhe_ntt_plan *plan, unsigned k, uns
         else (void)hipGetLastError();
     }
     if (!dec_is_evals) {
-        { fhe::KernelTimer kt_("decompose", 0, st);
-        hipLaunchKernelGGL(fhe::decompose_kernel, dim3(fhe_ew_grid(batch * k * n)), dim3(256), 0, st, (const u64 *)d_glwe, DEC, (u64)batch * k, (u32)n, (u64)plan->q, (u32)beta, (u32)l, (u32)k, (u64)k1 * n);
-        }
-        LAUNCH_OK("decompose_kernel");
+        if ((rc = launch("decompose", 0, st, fhe::decompose_kernel, fhe_ew_grid(batch * k * n), 256, d_glwe, DEC, (u64)batch * k, (u32)n, plan->q, beta, l, k,
+                         (u64)k1 * n)) != FHE_OK)
+            return rc;
     }
     // ksk viewed as [T = k*l][k1][n]; DEC as [batch][T][n]
     if (dp.wide && dp.log_n >= 8 && dp.log_n <= 12) {
@@ -518,11 +475,7 @@ extern "C" int fhe_glwe_key_switch_dev(const fhe_ntt_plan *plan, unsigned k, uns
         return fhe_hip_fail(e, "digit_tail_kernel");
     }
     if ((rc = keyed_mac(plan, dp, (const u64 *)d_ksk, flags & FHE_A_IS_EVALS, DEC, dec_is_evals, RHS, false, T, k1, batch, WS, st)) != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("ks_tail", 0, st);
-    hipLaunchKernelGGL(fhe::ks_tail_kernel, dim3(fhe_ew_grid(batch * k1 * n)), dim3(256), 0, st, (const u64 *)d_glwe, (const u64 *)RHS, (u64 *)d_out, (u64)batch, (u32)n, (u32)k, (u64)plan->q);
-    }
-    LAUNCH_OK("ks_tail_kernel");
-    return FHE_OK;
+    return launch("ks_tail", 0, st, fhe::ks_tail_kernel, fhe_ew_grid(batch * k1 * n), 256, d_glwe, RHS, d_out, batch, (u32)n, k, plan->q);
 }
 
 // Resident key-switching key: the form the product consumes, built once.  Base 2 with k = 1 at 2^8 <= n <= 2^12: the
@@ -582,32 +535,18 @@ extern "C" int fhe_tr_dot(const fhe_ntt_plan *plan, const uint64_t *a, const uin
     if (!plan) return fhe_fail(FHE_E_NULL, "fhe_tr_dot: plan is NULL");
     if (batch == 0 || k == 0) return FHE_OK;
     if (!a || !b || !c) return fhe_fail(FHE_E_NULL, "fhe_tr_dot: NULL buffer");
-    int dev, rc = fhe_current_device(&dev);
-    if (rc != FHE_OK) return rc;
     const size_t row = plan->n * 8;
-    FheHostStage hs;
-    void *da, *db, *dc;
-    if ((rc = hs.up(a, batch * k * row, &da)) != FHE_OK) return rc;
-    if ((rc = hs.up(b, batch * k * row, &db)) != FHE_OK) return rc;
-    if ((rc = hs.up(nullptr, batch * row, &dc)) != FHE_OK) return rc;
-    if ((rc = fhe_tr_dot_dev(plan, da, db, dc, k, batch, 0, hipStreamPerThread)) != FHE_OK) return rc;
-    return hs.down(c, dc, batch * row);
+    return fhe_host_call({{a, batch * k * row}, {b, batch * k * row}}, c, batch * row,
+                         [&](void *const *d) { return fhe_tr_dot_dev(plan, d[0], d[1], d[2], k, batch, 0, hipStreamPerThread); });
 }
 
 extern "C" int fhe_tr_mul_r(const fhe_ntt_plan *plan, const uint64_t *a, const uint64_t *p, uint64_t *out, unsigned rows, size_t batch) {
     if (!plan) return fhe_fail(FHE_E_NULL, "fhe_tr_mul_r: plan is NULL");
     if (batch == 0 || rows == 0) return FHE_OK;
     if (!a || !p || !out) return fhe_fail(FHE_E_NULL, "fhe_tr_mul_r: NULL buffer");
-    int dev, rc = fhe_current_device(&dev);
-    if (rc != FHE_OK) return rc;
     const size_t row = plan->n * 8;
-    FheHostStage hs;
-    void *da, *dp, *dout;
-    if ((rc = hs.up(a, batch * rows * row, &da)) != FHE_OK) return rc;
-    if ((rc = hs.up(p, batch * row, &dp)) != FHE_OK) return rc;
-    if ((rc = hs.up(nullptr, batch * rows * row, &dout)) != FHE_OK) return rc;
-    if ((rc = fhe_tr_mul_r_dev(plan, da, dp, dout, rows, batch, 0, hipStreamPerThread)) != FHE_OK) return rc;
-    return hs.down(out, dout, batch * rows * row);
+    return fhe_host_call({{a, batch * rows * row}, {p, batch * row}}, out, batch * rows * row,
+                         [&](void *const *d) { return fhe_tr_mul_r_dev(plan, d[0], d[1], d[2], rows, batch, 0, hipStreamPerThread); });
 }
 
 extern "C" int fhe_glev_mul(const fhe_ntt_plan *plan, unsigned k, unsigned l, const uint64_t *glev, const uint64_t *v, uint64_t *out, size_t batch) {
@@ -615,16 +554,9 @@ extern "C" int fhe_glev_mul(const fhe_ntt_plan *plan, unsigned k, unsigned l, co
     if (batch == 0) return FHE_OK;
     if (l == 0) return fhe_fail(FHE_E_INVALID, "fhe_glev_mul: l = 0");
     if (!glev || !v || !out) return fhe_fail(FHE_E_NULL, "fhe_glev_mul: NULL buffer");
-    int dev, rc = fhe_current_device(&dev);
-    if (rc != FHE_OK) return rc;
     const size_t row = plan->n * 8, k1 = (size_t)k + 1;
-    FheHostStage hs;
-    void *dg, *dv, *dout;
-    if ((rc = hs.up(glev, l * k1 * row, &dg)) != FHE_OK) return rc;
-    if ((rc = hs.up(v, batch * l * row, &dv)) != FHE_OK) return rc;
-    if ((rc = hs.up(nullptr, batch * k1 * row, &dout)) != FHE_OK) return rc;
-    if ((rc = fhe_glev_mul_dev(plan, k, l, dg, dv, dout, batch, 0, hipStreamPerThread)) != FHE_OK) return rc;
-    return hs.down(out, dout, batch * k1 * row);
+    return fhe_host_call({{glev, l * k1 * row}, {v, batch * l * row}}, out, batch * k1 * row,
+                         [&](void *const *d) { return fhe_glev_mul_dev(plan, k, l, d[0], d[1], d[2], batch, 0, hipStreamPerThread); });
 }
 
 extern "C" int fhe_glwe_key_switch(const fhe_ntt_plan *plan, unsigned k, unsigned beta, unsigned l, const uint64_t *glwe, const uint64_t *ksk,
@@ -633,14 +565,7 @@ extern "C" int fhe_glwe_key_switch(const fhe_ntt_plan *plan, unsigned k, unsigne
     if (batch == 0) return FHE_OK;
     if (k == 0 || l == 0 || beta < 2) return fhe_fail(FHE_E_INVALID, "fhe_glwe_key_switch: need k, l >= 1, beta >= 2");
     if (!glwe || !ksk || !out) return fhe_fail(FHE_E_NULL, "fhe_glwe_key_switch: NULL buffer");
-    int dev, rc = fhe_current_device(&dev);
-    if (rc != FHE_OK) return rc;
     const size_t row = plan->n * 8, k1 = (size_t)k + 1;
-    FheHostStage hs;
-    void *dg, *dk, *dout;
-    if ((rc = hs.up(glwe, batch * k1 * row, &dg)) != FHE_OK) return rc;
-    if ((rc = hs.up(ksk, (size_t)k * l * k1 * row, &dk)) != FHE_OK) return rc;
-    if ((rc = hs.up(nullptr, batch * k1 * row, &dout)) != FHE_OK) return rc;
-    if ((rc = fhe_glwe_key_switch_dev(plan, k, beta, l, dg, dk, dout, batch, 0, hipStreamPerThread)) != FHE_OK) return rc;
-    return hs.down(out, dout, batch * k1 * row);
+    return fhe_host_call({{glwe, batch * k1 * row}, {ksk, (size_t)k * l * k1 * row}}, out, batch * k1 * row,
+                         [&](void *const *d) { return fhe_glwe_key_switch_dev(plan, k, beta, l, d[0], d[1], d[2], batch, 0, hipStreamPerThread); });
 }

@@ -13,6 +13,7 @@
 // (zq_device.hpp).  All operands must be canonical (< q).  Q63 (2^62 <= q < 2^63, with CHUNK = kMacChunk63 = 2): the
 // strict reduction, every partial result canonical — 4q does not fit a word there.
 #pragma once
+#include "capi_internal.hpp"
 #include "zq_device.hpp"
 
 namespace fhe {
@@ -64,14 +65,14 @@ __global__ __launch_bounds__(256) void mac_rows_kernel(const u64 *__restrict__ G
     }
 }
 
-// the launch, by the plan's modulus range
-static inline void launch_mac_rows(bool q63, unsigned grid, hipStream_t st, const u64 *G, const u64 *D, u64 *out, u64 batch, u32 n, u32 T, u32 nc,
-                                   u64 gstride, const Mod &m) {
-    if (q63) hipLaunchKernelGGL((mac_rows_kernel<(int)kMacChunk63, true>), dim3(grid), dim3(256), 0, st, G, D, out, batch, n, T, nc, gstride, m);
-    else hipLaunchKernelGGL((mac_rows_kernel<>), dim3(grid), dim3(256), 0, st, G, D, out, batch, n, T, nc, gstride, m);
-}
-
 // workgroups for mac_rows_kernel over `batch` elements of nc rows of n words
 static inline u64 mac_rows_threads(u64 batch, u32 nc, u64 n) { return batch * ((nc + 1) / 2) * (n / 2); }
 
 }  // namespace fhe
+
+// the timed launch with its check (FHE_* code), by the plan's modulus range: q63 for 2^62 <= q < 2^63
+static inline int fhe_mac_rows(bool q63, hipStream_t st, const fhe::u64 *G, const fhe::u64 *D, fhe::u64 *out, fhe::u64 batch, fhe::u32 n,
+                               fhe::u32 T, fhe::u32 nc, fhe::u64 gstride, const fhe::Mod &m) {
+    return launch("mac_rows", 0, st, q63 ? fhe::mac_rows_kernel<(int)fhe::kMacChunk63, true> : fhe::mac_rows_kernel<>,
+                  fhe_ew_grid(fhe::mac_rows_threads(batch, nc, n)), 256, G, D, out, batch, n, T, nc, gstride, m);
+}

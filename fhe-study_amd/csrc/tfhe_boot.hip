@@ -45,13 +45,11 @@
 // are the negacyclic read and the shift wherever they occur.  The LWE key switch is one tile (tlwe_ks_kernel) over a digit
 // policy: BitDigit (beta = 2) and SignedDigit (§11).  extract0_word is the sample extraction at h = 0 that tfhe_cb_extract_kernel
 // and tfhe_mux_extract_kernel combine; tfhe_many_extract_kernel scatters (one read, F stores) and states the rule itself.
-// Host side: launch() is a timed launch with its check; ks_grid, bsk_bytes, ksk_bytes and overlaps_any are the limits and
-// extents every entry point uses.  A gadget bootstrap is a BootShape (a BrShape and the key switch's gadget) and three stages: check_boot, boot_workspace (slots 7, 8,
+// Host side: launch() (capi_internal.hpp) is a timed launch with its check; ks_grid, bsk_bytes, ksk_bytes and overlaps_any
+// (capi_internal.hpp) are the limits and extents every entry point uses.  A gadget bootstrap is a BootShape (a BrShape and the key switch's gadget) and three stages: check_boot, boot_workspace (slots 7, 8,
 // 5), and after the entry point's own init launch finish_boot (CMux steps, the extraction it names, key switch).
 #include <algorithm>
-#include <initializer_list>
 #include <cstdio>
-#include <type_traits>
 
 #include "capi_internal.hpp"
 #include "digit32.hpp"
@@ -603,45 +601,6 @@ __global__ __launch_bounds__(256) void tglwe_box_expand_kernel(const u64 *__rest
 namespace {
 
 bool br_ext32_on(u64 n, unsigned k, unsigned l) { return fhe_ext32_enabled() && fhe::ext32_shape_supported(n, k, l); }
-
-// does [d_out, d_out + out_bytes) intersect one of the inputs {pointer, bytes}?
-struct Extent { const void *p; u64 bytes; };
-bool overlaps_any(const void *d_out, u64 out_bytes, std::initializer_list<Extent> inputs) {
-    for (const Extent &e : inputs)
-        if (overlaps(d_out, out_bytes, e.p, e.bytes)) return true;
-    return false;
-}
-
-// a kernel argument as its parameter type: device pointers arrive as void *, and an integer may widen but not narrow
-template <class P, class A>
-P kernel_arg(A a) {
-    static_assert(!(std::is_integral<P>::value && std::is_integral<A>::value) || sizeof(A) <= sizeof(P), "narrowing kernel argument: cast it at the call");
-    return static_cast<P>(a);
-}
-// one timed launch (tag L for the timer) and its check: the FHE_* code.  A launch error names kernel_name, <label>_kernel if NULL.
-template <class... P, class... A>
-int launch_named(const char *label, const char *kernel_name, int L, hipStream_t st, void (*kernel)(P...), unsigned grid, unsigned block, A... args) {
-    {
-        fhe::KernelTimer kt_(label, L, st);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, kernel_arg<P>(args)...);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return FHE_OK;
-    char name[64];
-    snprintf(name, sizeof name, "%s_kernel", label);
-    return fhe_hip_fail(e, kernel_name ? kernel_name : name);
-}
-template <class K, class... A>
-int launch(const char *label, int L, hipStream_t st, K kernel, unsigned grid, unsigned block, A... args) {
-    return launch_named(label, nullptr, L, st, kernel, grid, block, args...);
-}
-
-int check_ring(uint64_t n, unsigned k, const char *who) {
-    if (n < 2 || (n & (n - 1)) != 0 || n > (1ull << 19))
-        return fhe_fail(FHE_E_BAD_N, "%s: n=%llu must be a power of two in [2, 2^19]", who, (unsigned long long)n);
-    if (k < 1 || k > 64) return fhe_fail(FHE_E_INVALID, "%s: need 1 <= k <= 64", who);
-    return FHE_OK;
-}
 
 int check_br(uint64_t n, unsigned k, unsigned l, unsigned n_lwe, const char *who) {
     int rc = check_ring(n, k, who);

@@ -244,20 +244,12 @@ int check_cdt(const void *d_cdt, unsigned m, unsigned log_scale, hipStream_t st,
 
 int stream_fill(const fhe::ChaChaKey &key, u32 purpose, u64 first_row, u64 row_words, u32 bits, u64 *d_out, u64 rows, hipStream_t st) {
     const u64 row_blocks = (row_words + 7) / 8;
-    { fhe::KernelTimer kt_("tfhe_stream_words", (int)purpose, st);
-    hipLaunchKernelGGL(fhe::tfhe_stream_words_kernel, dim3(fhe_ew_grid(rows * row_blocks)), dim3(256), 0, st, key, purpose, first_row, row_words,
-                       row_blocks, rows, bits, d_out);
-    }
-    LAUNCH_OK("tfhe_stream_words_kernel");
-    return FHE_OK;
+    return launch("tfhe_stream_words", (int)purpose, st, fhe::tfhe_stream_words_kernel, fhe_ew_grid(rows * row_blocks), 256, key, purpose, first_row,
+                  row_words, row_blocks, rows, bits, d_out);
 }
 
 int rows_copy(const u64 *src, u64 src_stride, u64 mask, u64 *dst, u32 L, u64 rows, hipStream_t st) {
-    { fhe::KernelTimer kt_("tn_rows_copy", (int)L, st);
-    hipLaunchKernelGGL(fhe::tn_rows_copy_kernel, dim3(fhe_ew_grid(rows << L)), dim3(256), 0, st, src, src_stride, mask, dst, L, rows);
-    }
-    LAUNCH_OK("tn_rows_copy_kernel");
-    return FHE_OK;
+    return launch("tn_rows_copy", (int)L, st, fhe::tn_rows_copy_kernel, fhe_ew_grid(rows << L), 256, src, src_stride, mask, dst, L, rows);
 }
 
 // staging of a TGLWE call: A, S (the key broadcast over a chunk as 0/1 words) and P = A S, `chunk` rows each
@@ -310,12 +302,8 @@ extern "C" int fhe_tlwe_encrypt_dev(unsigned n, const uint8_t *seed, uint64_t fi
     hipStream_t st = (hipStream_t)hip_stream;
     int rc = check_cdt(d_cdt, m, log_scale, st, who);
     if (rc != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("tlwe_encrypt", (int)std::min<u64>(n, 1u << 20), st);
-    hipLaunchKernelGGL(fhe::tlwe_encrypt_kernel, dim3((unsigned)std::min<u64>(batch, 1u << 16)), dim3(fhe::LE_TH), 0, st, seed_key(seed), first_row,
-                       (const u64 *)d_key, (const u64 *)d_mu, (const u64 *)d_cdt, m, log_scale, (u64 *)d_out, n, (u64)batch);
-    }
-    LAUNCH_OK("tlwe_encrypt_kernel");
-    return FHE_OK;
+    return launch("tlwe_encrypt", (int)std::min<u64>(n, 1u << 20), st, fhe::tlwe_encrypt_kernel, (unsigned)std::min<u64>(batch, 1u << 16), fhe::LE_TH,
+                  seed_key(seed), first_row, d_key, d_mu, d_cdt, m, log_scale, d_out, n, batch);
 }
 
 extern "C" int fhe_tlwe_phase_dev(unsigned n, const void *d_key, const void *d_in, void *d_out, size_t batch, void *hip_stream) {
@@ -329,12 +317,8 @@ extern "C" int fhe_tlwe_phase_dev(unsigned n, const void *d_key, const void *d_i
     if (overlaps(d_out, out_bytes, d_key, (u64)n * 8) || overlaps(d_out, out_bytes, d_in, (u64)batch * ((u64)n + 1) * 8))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key or the input", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    { fhe::KernelTimer kt_("tlwe_phase", (int)std::min<u64>(n, 1u << 20), st);
-    hipLaunchKernelGGL(fhe::tlwe_phase_kernel, dim3((unsigned)std::min<u64>(batch, 1u << 16)), dim3(fhe::LE_TH), 0, st, (const u64 *)d_key,
-                       (const u64 *)d_in, (u64 *)d_out, n, (u64)batch);
-    }
-    LAUNCH_OK("tlwe_phase_kernel");
-    return FHE_OK;
+    return launch("tlwe_phase", (int)std::min<u64>(n, 1u << 20), st, fhe::tlwe_phase_kernel, (unsigned)std::min<u64>(batch, 1u << 16), fhe::LE_TH, d_key,
+                  d_in, d_out, n, batch);
 }
 
 extern "C" int fhe_tglwe_encrypt_dev(uint64_t n, unsigned k, const uint8_t *seed, uint64_t first_row, const void *d_key, const void *d_msg,
@@ -367,11 +351,9 @@ extern "C" int fhe_tglwe_encrypt_dev(uint64_t n, unsigned k, const uint8_t *seed
         if ((rc = stream_fill(key, fhe::STREAM_MASK, first_row + r0, n, 0, A, cr, st)) != FHE_OK) return rc;
         if ((rc = fhe_tn_mul_dev(n, A, S, P, cr, st)) != FHE_OK) return rc;
         const u64 *msg = d_msg ? (const u64 *)d_msg + r0 * msg_stride : nullptr;
-        { fhe::KernelTimer kt_("tglwe_encrypt_epilogue", (int)L, st);
-        hipLaunchKernelGGL(fhe::tglwe_encrypt_epilogue_kernel, dim3(fhe_ew_grid(cr << (L - 3))), dim3(256), 0, st, key, first_row + r0, (const u64 *)A,
-                           (const u64 *)P, msg, (u64)msg_stride, (const u64 *)d_cdt, m, log_scale, (u64 *)d_out + r0 * 2 * n, L, cr);
-        }
-        LAUNCH_OK("tglwe_encrypt_epilogue_kernel");
+        if ((rc = launch("tglwe_encrypt_epilogue", (int)L, st, fhe::tglwe_encrypt_epilogue_kernel, fhe_ew_grid(cr << (L - 3)), 256, key, first_row + r0, A,
+                         P, msg, msg_stride, d_cdt, m, log_scale, (u64 *)d_out + r0 * 2 * n, L, cr)) != FHE_OK)
+            return rc;
     }
     return FHE_OK;
 }
@@ -396,11 +378,9 @@ extern "C" int fhe_tglwe_phase_dev(uint64_t n, unsigned k, const void *d_key, co
         const u64 *src = (const u64 *)d_in + r0 * 2 * n;
         if ((rc = rows_copy(src, 2 * n, ~0ull, A, L, cr, st)) != FHE_OK) return rc;
         if ((rc = fhe_tn_mul_dev(n, A, S, P, cr, st)) != FHE_OK) return rc;
-        { fhe::KernelTimer kt_("tglwe_phase_epilogue", (int)L, st);
-        hipLaunchKernelGGL(fhe::tglwe_phase_epilogue_kernel, dim3(fhe_ew_grid(cr << L)), dim3(256), 0, st, src, (const u64 *)P,
-                           (u64 *)d_out + r0 * n, L, cr);
-        }
-        LAUNCH_OK("tglwe_phase_epilogue_kernel");
+        if ((rc = launch("tglwe_phase_epilogue", (int)L, st, fhe::tglwe_phase_epilogue_kernel, fhe_ew_grid(cr << L), 256, src, P, (u64 *)d_out + r0 * n, L,
+                         cr)) != FHE_OK)
+            return rc;
     }
     return FHE_OK;
 }

@@ -408,10 +408,7 @@ static int z_forward_src(const ZCtx &z, int k, const u64 *src, u64 *out, u64 row
                                                   fhe_batch_tile_for(z.plan[k]), st);
     if (e == hipSuccess) return FHE_OK;
     if (e != hipErrorNotSupported) return fhe_hip_fail(e, "zring reducing forward NTT");
-    { fhe::KernelTimer kt_("zr_reduce_pad", 0, st);
-    hipLaunchKernelGGL(fhe::zr_reduce_pad_kernel, dim3(fhe_ew_grid(rows * n)), dim3(256), 0, st, src, out, rows, (u32)n_src, (u32)n, z.cc.m[k]);
-    }
-    LAUNCH_OK("zr_reduce_pad_kernel");
+    if (int rc = launch("zr_reduce_pad", 0, st, fhe::zr_reduce_pad_kernel, fhe_ew_grid(rows * n), 256, src, out, rows, (u32)n_src, (u32)n, z.cc.m[k])) return rc;
     return z_forward(z, k, out, out, rows, st);
 }
 static int z_inverse(const ZCtx &z, int k, const u64 *in, u64 *out, u64 rows, hipStream_t st) {
@@ -419,29 +416,18 @@ static int z_inverse(const ZCtx &z, int k, const u64 *in, u64 *out, u64 rows, hi
                                            fhe_batch_tile_for(z.plan[k]), st);
     return e == hipSuccess ? FHE_OK : fhe_hip_fail(e, "zring inverse NTT");
 }
-static int z_crt(const ZCtx &z, bool is_signed, const u64 *r1, const u64 *r2, const u64 *r3, u64 *out,
-                 u64 count, hipStream_t st) {
-    const unsigned g = fhe_ew_grid(count);
-    fhe::KernelTimer kt_("zr_crt", z.K, st);
-#define CRT_CASE(K_, S_) hipLaunchKernelGGL((fhe::zr_crt_kernel<K_, S_>), dim3(g), dim3(256), 0, st, r1, r2, r3, out, count, z.cc)
-    if (z.K == 1) { if (is_signed) CRT_CASE(1, true); else CRT_CASE(1, false); }
-    else if (z.K == 2) { if (is_signed) CRT_CASE(2, true); else CRT_CASE(2, false); }
-    else { if (is_signed) CRT_CASE(3, true); else CRT_CASE(3, false); }
-#undef CRT_CASE
-    LAUNCH_OK("zr_crt_kernel");
-    return FHE_OK;
+static int z_crt(const ZCtx &z, bool is_signed, const u64 *r1, const u64 *r2, const u64 *r3, void *out, u64 count, hipStream_t st) {
+    static const decltype(&fhe::zr_crt_kernel<1, false>) kernels[3][2] = {{fhe::zr_crt_kernel<1, false>, fhe::zr_crt_kernel<1, true>},
+                                                                           {fhe::zr_crt_kernel<2, false>, fhe::zr_crt_kernel<2, true>},
+                                                                           {fhe::zr_crt_kernel<3, false>, fhe::zr_crt_kernel<3, true>}};
+    return launch("zr_crt", z.K, st, kernels[z.K - 1][is_signed], fhe_ew_grid(count), 256, r1, r2, r3, out, count, z.cc);
 }
 
 // out[row][j] = (addend[row][j] +) fold(from_f64(round(num * crt(residues)[.] / den))): rows x 2n residues in
-static int z_crt_mdr(const ZCtx &z, const u64 *r1, const u64 *r2, const u64 *r3, const u64 *addend, u64 *out,
-                     u64 rows, u64 n, u64 q, u64 num, u64 den, hipStream_t st) {
-    const unsigned g = fhe_ew_grid(rows * n);
-    fhe::KernelTimer kt_("zr_crt_mdr", z.K, st);
-#define MDR_CASE(K_) hipLaunchKernelGGL((fhe::zr_crt_mdr_kernel<K_>), dim3(g), dim3(256), 0, st, r1, r2, r3, addend, out, rows, (u32)n, q, num, den, z.cc)
-    if (z.K == 1) MDR_CASE(1); else if (z.K == 2) MDR_CASE(2); else MDR_CASE(3);
-#undef MDR_CASE
-    LAUNCH_OK("zr_crt_mdr_kernel");
-    return FHE_OK;
+static int z_crt_mdr(const ZCtx &z, const u64 *r1, const u64 *r2, const u64 *r3, const void *addend, void *out, u64 rows, u64 n, u64 q, u64 num,
+                     u64 den, hipStream_t st) {
+    static const decltype(&fhe::zr_crt_mdr_kernel<1>) kernels[3] = {fhe::zr_crt_mdr_kernel<1>, fhe::zr_crt_mdr_kernel<2>, fhe::zr_crt_mdr_kernel<3>};
+    return launch("zr_crt_mdr", z.K, st, kernels[z.K - 1], fhe_ew_grid(rows * n), 256, r1, r2, r3, addend, out, rows, (u32)n, q, num, den, z.cc);
 }
 
 // inverse transform (two-pass sizes, one prime) whose last pass scales, rounds and folds: rows x 2n residues in
@@ -481,40 +467,79 @@ static hipError_t z_inverse_mdr(const ZCtx &z, u64 *r, u64 *out, u64 rows, u64 q
 static unsigned bits_of(u64 x) { unsigned b = 0; while (x) { b++; x >>= 1; } return b; }
 static unsigned ceil_log2(u64 x) { return x <= 1 ? 0 : bits_of(x - 1); }
 
-static int check_pow2_n(u64 n, const char *who) {
-    if (n < 2 || (n & (n - 1)) != 0 || n > (1ull << 19))
-        return fhe_fail(FHE_E_BAD_N, "%s: n=%llu must be a power of two in [2, 2^19]", who, (unsigned long long)n);
-    return FHE_OK;
+// One CRT-lifted product: both sources transformed modulo each of the K primes that the bound on the true coefficients
+// asks for, multiplied, transformed back and recombined by Garner's CRT into d_out (out_rows x n words mod 2^64).
+//   T = 0: out[r] = a[r] * b[r], the pointwise product fused into the inverse transform (a_rows = b_rows = out_rows)
+//   T > 0: out[i][c] = sum_{t<T} a[g_i][t][c] * b[i][t] over `batch` elements (mac_kernel.hpp: nc rows each, a shared by the
+//          batch for gstride = 0)
+//   digits > 0: b's transformed rows are the `digits` bit digits of each of its b_rows source rows (zr_digits_kernel)
+// Workspace slot 1: [a: a_rows] [digit staging, if any] [b's transforms] [K x out_rows residues], rows of n words.
+struct ZProduct {
+    const void *a, *b;
+    u64 a_rows, b_rows, out_rows;
+    u64 n_src, n;            // words per source row; the transform size (n_src zero-padded to it)
+    unsigned bits;           // |true coefficient| < 2^bits
+    bool is_signed;
+    u64 batch;               // T > 0 only, as are nc and gstride
+    u32 T, nc;
+    u64 gstride;
+    u32 digits;
+};
+static int z_product(const ZProduct &p, void *d_out, hipStream_t st) {
+    ZCtx z;
+    int rc = zctx_init(&z, p.n, primes_for_bits(p.bits, p.is_signed));
+    if (rc != FHE_OK) return rc;
+    const u64 n = p.n, b_tr = p.digits ? p.b_rows * p.digits : p.b_rows, owords = p.out_rows * n;
+    void *wsv = nullptr;
+    rc = fhe_workspace_get(1, (p.a_rows + (p.digits ? 2 : 1) * b_tr + (size_t)z.K * p.out_rows) * n * 8, st, &wsv);
+    if (rc != FHE_OK) return rc;
+    u64 *A = (u64 *)wsv, *Dg = A + p.a_rows * n, *B = p.digits ? Dg + b_tr * n : Dg, *R = B + b_tr * n;   // R: K residue arrays
+    bool digits_done = false;
+    for (int k = 0; k < z.K; k++) {
+        if ((rc = z_forward_src(z, k, (const u64 *)p.a, A, p.a_rows, p.n_src, st)) != FHE_OK) return rc;
+        if (!p.digits) {
+            if ((rc = z_forward_src(z, k, (const u64 *)p.b, B, p.b_rows, p.n_src, st)) != FHE_OK) return rc;
+        } else {
+            // B = NTT of the 0/1 digit polynomials (digits are < every prime).  Single-pass sizes
+            // extract the bit in the transform's load; larger n materialises the digits once.
+            hipError_t e = fhe::launch_ntt_forward_digits(z.dp[k], (const u64 *)p.b, B, p.b_rows, p.digits, st);
+            if (e == hipErrorNotSupported) {
+                if (!digits_done) {
+                    if ((rc = launch("zr_digits", 0, st, fhe::zr_digits_kernel, fhe_ew_grid(b_tr * n), 256, p.b, Dg, p.b_rows, (u32)n, p.digits)) != FHE_OK)
+                        return rc;
+                    digits_done = true;
+                }
+                if ((rc = z_forward(z, k, Dg, B, b_tr, st)) != FHE_OK) return rc;
+            } else if (e != hipSuccess) {
+                return fhe_hip_fail(e, "digit forward NTT");
+            }
+        }
+        u64 *Rk = R + (u64)k * owords;
+        if (p.T == 0) {
+            hipError_t e = fhe::launch_ntt_inverse(z.dp[k], A, B, nullptr, Rk, p.out_rows, fhe_batch_tile_for(z.plan[k]), st);
+            if (e != hipSuccess) return fhe_hip_fail(e, "zring inverse(A.*B)");
+            continue;
+        }
+        if ((rc = fhe_mac_rows(false, st, A, B, Rk, p.batch, (u32)n, p.T, p.nc, p.gstride, z.cc.m[k])) != FHE_OK) return rc;   // CRT primes are below 2^61
+        if ((rc = z_inverse(z, k, Rk, Rk, p.out_rows, st)) != FHE_OK) return rc;
+    }
+    return z_crt(z, p.is_signed, R, R + owords, R + 2 * owords, d_out, owords, st);
 }
 
 // ---- arith::ring_n::naive_mul ---------------------------------------------------------------
 extern "C" int fhe_r_naive_mul_dev(uint64_t n, const void *d_a, const void *d_b, void *d_out, size_t batch,
                                    unsigned a_bits, unsigned b_bits, void *hip_stream) {
-    int rc = check_pow2_n(n, "fhe_r_naive_mul_dev");
+    int rc = check_ring(n, "fhe_r_naive_mul_dev");
     if (rc != FHE_OK) return rc;
     if (batch == 0) return FHE_OK;
     if (!d_a || !d_b || !d_out) return fhe_fail(FHE_E_NULL, "fhe_r_naive_mul_dev: NULL buffer");
     REQUIRE_ALIGNED(d_a); REQUIRE_ALIGNED(d_b); REQUIRE_ALIGNED(d_out);
     if (a_bits == 0 || a_bits > 64) a_bits = 64;
     if (b_bits == 0 || b_bits > 64) b_bits = 64;
-    const u64 n2 = 2 * n;
-    ZCtx z;
-    rc = zctx_init(&z, n2, primes_for_bits(a_bits + b_bits + ceil_log2(n), false));
-    if (rc != FHE_OK) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
-    const u64 words = batch * n2;
-    void *wsv = nullptr;
-    rc = fhe_workspace_get(1, (2 + (size_t)z.K) * words * 8, st, &wsv);
-    if (rc != FHE_OK) return rc;
-    u64 *A = (u64 *)wsv, *B = A + words, *R = B + words;   // R: K residue arrays
-    for (int k = 0; k < z.K; k++) {
-        if ((rc = z_forward_src(z, k, (const u64 *)d_a, A, batch, n, st)) != FHE_OK) return rc;
-        if ((rc = z_forward_src(z, k, (const u64 *)d_b, B, batch, n, st)) != FHE_OK) return rc;
-        hipError_t e = fhe::launch_ntt_inverse(z.dp[k], A, B, nullptr, R + (u64)k * words, batch,
-                                               fhe_batch_tile_for(z.plan[k]), st);
-        if (e != hipSuccess) return fhe_hip_fail(e, "zring inverse(A.*B)");
-    }
-    return z_crt(z, false, R, R + words, R + 2 * words, (u64 *)d_out, words, st);
+    ZProduct p{};
+    p.a = d_a; p.b = d_b; p.a_rows = p.b_rows = p.out_rows = batch; p.n_src = n; p.n = 2 * n;
+    p.bits = a_bits + b_bits + ceil_log2(n);
+    return z_product(p, d_out, (hipStream_t)hip_stream);
 }
 
 // ---- arith::ring_n::mul_div_round -----------------------------------------------------------
@@ -527,12 +552,8 @@ extern "C" int fhe_mul_div_round_dev(uint64_t q, uint64_t n, const void *d_v, ui
     int dev;
     int rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("zr_mul_div_round", 0, (hipStream_t)hip_stream);
-    hipLaunchKernelGGL(fhe::zr_mul_div_round_kernel, dim3(fhe_ew_grid(batch * n)), dim3(256), 0, (hipStream_t)hip_stream,
-                       (const u64 *)d_v, (u64 *)d_out, (u64)batch, (u32)n, (u64)q, (u64)num, (u64)den);
-    }
-    LAUNCH_OK("zr_mul_div_round_kernel");
-    return FHE_OK;
+    return launch("zr_mul_div_round", 0, (hipStream_t)hip_stream, fhe::zr_mul_div_round_kernel, fhe_ew_grid(batch * n), 256, d_v, d_out, batch, (u32)n, q,
+                  num, den);
 }
 
 // ---- BFV on two / three 27-bit primes (bfv32.hip): small q, 1024 <= n <= 8192 -----------------------------------------
@@ -646,7 +667,7 @@ static int bfv32_relinearize(uint64_t q, uint64_t n, uint64_t pq, const void *d_
 // d_ab: [a0 | a1 | b0 | b1], each batch x n (mod q).  d_c: [c0 | c1 | c2], each batch x n.
 extern "C" int fhe_bfv_tensor_dev(uint64_t q, uint64_t n, uint64_t t, const void *d_ab, void *d_c, size_t batch,
                                   void *hip_stream) {
-    int rc = check_pow2_n(n, "fhe_bfv_tensor_dev");
+    int rc = check_ring(n, "fhe_bfv_tensor_dev");
     if (rc != FHE_OK) return rc;
     if (q < 2 || (q >> 63)) return fhe_fail(FHE_E_BAD_Q, "fhe_bfv_tensor_dev: q must be in [2, 2^63)");
     if (batch == 0) return FHE_OK;
@@ -667,10 +688,7 @@ extern "C" int fhe_bfv_tensor_dev(uint64_t q, uint64_t n, uint64_t t, const void
     for (int k = 0; k < z.K; k++) {
         if ((rc = z_forward_src(z, k, (const u64 *)d_ab, AB, 4 * batch, n, st)) != FHE_OK) return rc;
         u64 *Rk = R + 3 * (u64)k * words;
-        { fhe::KernelTimer kt_("zr_tensor", 0, st);
-        hipLaunchKernelGGL(fhe::zr_tensor_kernel, dim3(fhe_ew_grid(words)), dim3(256), 0, st, (const u64 *)AB, Rk, words, z.cc.m[k]);
-        }
-        LAUNCH_OK("zr_tensor_kernel");
+        if ((rc = launch("zr_tensor", 0, st, fhe::zr_tensor_kernel, fhe_ew_grid(words), 256, AB, Rk, words, z.cc.m[k])) != FHE_OK) return rc;
         if (z.K == 1) {   // one prime: scale by t/q, round, reduce and fold in the inverse's last pass
             hipError_t e = z_inverse_mdr(z, Rk, (u64 *)d_c, 3 * batch, q, t, q, st);
             if (e == hipSuccess) return FHE_OK;
@@ -680,7 +698,7 @@ extern "C" int fhe_bfv_tensor_dev(uint64_t q, uint64_t n, uint64_t t, const void
         if ((rc = z_inverse(z, k, Rk, Rk, 3 * batch, st)) != FHE_OK) return rc;
     }
     // recombine, scale by t/q, round, reduce, fold — in one kernel (the integers are never stored)
-    return z_crt_mdr(z, R, R + 3 * words, R + 6 * words, nullptr, (u64 *)d_c, 3 * batch, n, q, t, q, st);
+    return z_crt_mdr(z, R, R + 3 * words, R + 6 * words, nullptr, d_c, 3 * batch, n, q, t, q, st);
 }
 
 // The relinearisation key in the form the products consume: for each of the K CRT primes, NTT_k(rlk0 mod P_k) and
@@ -694,7 +712,7 @@ static unsigned relin_split_bits(uint64_t q, uint64_t n, uint64_t pq) {
     return (h >= 1 && bits_of(q - 1) + h + ceil_log2(n) <= 60) ? h : 0;
 }
 static int bfv_relin_ctx(ZCtx *z, unsigned *h, uint64_t q, uint64_t n, uint64_t pq, const char *who) {
-    int rc = check_pow2_n(n, who);
+    int rc = check_ring(n, who);
     if (rc != FHE_OK) return rc;
     if (q < 2 || (q >> 63) || pq < q || (pq >> 63)) return fhe_fail(FHE_E_BAD_Q, "%s: need 2 <= q <= pq < 2^63", who);
     *h = relin_split_bits(q, n, pq);
@@ -713,10 +731,7 @@ extern "C" size_t fhe_bfv_rlk_prepared_words(uint64_t q, uint64_t n, uint64_t pq
 static int bfv_rlk_prepare(const ZCtx &z, unsigned h, uint64_t n, const u64 *d_rlk, u64 *prep, u64 *scratch, hipStream_t st) {
     int rc;
     if (h) {
-        { fhe::KernelTimer kt_("zr_split_h", 0, st);
-        hipLaunchKernelGGL(fhe::zr_split_h_kernel, dim3(fhe_ew_grid(2 * n)), dim3(256), 0, st, d_rlk, scratch, (u64)2, (u32)n, (u32)h);
-        }
-        LAUNCH_OK("zr_split_h_kernel");
+        if ((rc = launch("zr_split_h", 0, st, fhe::zr_split_h_kernel, fhe_ew_grid(2 * n), 256, d_rlk, scratch, 2, (u32)n, h)) != FHE_OK) return rc;
         return z_forward_src(z, 0, scratch, prep, 4, n, st);
     }
     for (int k = 0; k < z.K; k++)
@@ -751,28 +766,19 @@ static int bfv_relinearize_with(const ZCtx &z, unsigned h, uint64_t q, uint64_t 
     const u64 *c2 = (const u64 *)d_c + 2 * bn;
     if (h) {   // one prime, key halves: rows [rlk0_lo | rlk0_hi | rlk1_lo | rlk1_hi] x batch
         if ((rc = z_forward_src(z, 0, c2, X, batch, n, st)) != FHE_OK) return rc;
-        { fhe::KernelTimer kt_("zr_mul_bcast", 0, st);
-        hipLaunchKernelGGL(fhe::zr_mul_bcast_kernel, dim3(fhe_ew_grid(words)), dim3(256), 0, st, (const u64 *)X, d_prep, R, (u64)batch, (u32)n2, (u32)4, z.cc.m[0]);
-        }
-        LAUNCH_OK("zr_mul_bcast_kernel");
+        if ((rc = launch("zr_mul_bcast", 0, st, fhe::zr_mul_bcast_kernel, fhe_ew_grid(words), 256, X, d_prep, R, batch, (u32)n2, 4, z.cc.m[0])) != FHE_OK) return rc;
         if ((rc = z_inverse(z, 0, R, R, 4 * batch, st)) != FHE_OK) return rc;
-        { fhe::KernelTimer kt_("zr_split_mdr", 0, st);
-        hipLaunchKernelGGL(fhe::zr_split_mdr_kernel, dim3(fhe_ew_grid(2 * bn)), dim3(256), 0, st, (const u64 *)R, (const u64 *)d_c, (u64 *)d_out, (u64)batch, (u32)n, (u32)h, (u64)q, (u64)1, (u64)p);
-        }
-        LAUNCH_OK("zr_split_mdr_kernel");
-        return FHE_OK;
+        return launch("zr_split_mdr", 0, st, fhe::zr_split_mdr_kernel, fhe_ew_grid(2 * bn), 256, R, d_c, d_out, batch, (u32)n, h, q, 1, p);
     }
     for (int k = 0; k < z.K; k++) {
         if ((rc = z_forward_src(z, k, c2, X, batch, n, st)) != FHE_OK) return rc;
         u64 *Rk = R + 2 * (u64)k * words;
-        { fhe::KernelTimer kt_("zr_mul_bcast", 0, st);
-        hipLaunchKernelGGL(fhe::zr_mul_bcast_kernel, dim3(fhe_ew_grid(words)), dim3(256), 0, st, (const u64 *)X, d_prep + (u64)k * 2 * n2, Rk, (u64)batch, (u32)n2, (u32)2, z.cc.m[k]);
-        }
-        LAUNCH_OK("zr_mul_bcast_kernel");
+        if ((rc = launch("zr_mul_bcast", 0, st, fhe::zr_mul_bcast_kernel, fhe_ew_grid(words), 256, X, d_prep + (u64)k * 2 * n2, Rk, batch, (u32)n2, 2, z.cc.m[k])) != FHE_OK)
+            return rc;
         if ((rc = z_inverse(z, k, Rk, Rk, 2 * batch, st)) != FHE_OK) return rc;
     }
     // (c0, c1) + mul_div_round(crt(..), 1, p): recombination, scaling, fold and the final add in one kernel
-    return z_crt_mdr(z, R, R + 2 * words, R + 4 * words, (const u64 *)d_c, (u64 *)d_out, 2 * batch, n, q, 1, p, st);
+    return z_crt_mdr(z, R, R + 2 * words, R + 4 * words, d_c, d_out, 2 * batch, n, q, 1, p, st);
 }
 
 extern "C" int fhe_bfv_relinearize_prepared_dev(uint64_t q, uint64_t n, uint64_t pq, const void *d_prepared, const void *d_c,
@@ -842,28 +848,15 @@ extern "C" int fhe_bfv_mul_prepared_dev(uint64_t q, uint64_t n, uint64_t t, uint
 // ---- TFHE: Tn x Tn -----------------------------------------------------------------------------
 extern "C" int fhe_tn_mul_dev(uint64_t n, const void *d_a, const void *d_b, void *d_out, size_t batch,
                               void *hip_stream) {
-    int rc = check_pow2_n(n, "fhe_tn_mul_dev");
+    int rc = check_ring(n, "fhe_tn_mul_dev");
     if (rc != FHE_OK) return rc;
     if (batch == 0) return FHE_OK;
     if (!d_a || !d_b || !d_out) return fhe_fail(FHE_E_NULL, "fhe_tn_mul_dev: NULL buffer");
     REQUIRE_ALIGNED(d_a); REQUIRE_ALIGNED(d_b); REQUIRE_ALIGNED(d_out);
-    ZCtx z;
-    rc = zctx_init(&z, n, primes_for_bits(128 + ceil_log2(n), true));   // |c_k| < n * 2^128
-    if (rc != FHE_OK) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
-    const u64 words = batch * n;
-    void *wsv = nullptr;
-    rc = fhe_workspace_get(1, (2 + (size_t)z.K) * words * 8, st, &wsv);
-    if (rc != FHE_OK) return rc;
-    u64 *A = (u64 *)wsv, *B = A + words, *R = B + words;
-    for (int k = 0; k < z.K; k++) {
-        if ((rc = z_forward_src(z, k, (const u64 *)d_a, A, batch, n, st)) != FHE_OK) return rc;
-        if ((rc = z_forward_src(z, k, (const u64 *)d_b, B, batch, n, st)) != FHE_OK) return rc;
-        hipError_t e = fhe::launch_ntt_inverse(z.dp[k], A, B, nullptr, R + (u64)k * words, batch,
-                                               fhe_batch_tile_for(z.plan[k]), st);
-        if (e != hipSuccess) return fhe_hip_fail(e, "zring inverse(A.*B)");
-    }
-    return z_crt(z, true, R, R + words, R + 2 * words, (u64 *)d_out, words, st);
+    ZProduct p{};
+    p.a = d_a; p.b = d_b; p.a_rows = p.b_rows = p.out_rows = batch; p.n_src = p.n = n;
+    p.bits = 128 + ceil_log2(n); p.is_signed = true;   // |c_k| < n * 2^128
+    return z_product(p, d_out, (hipStream_t)hip_stream);
 }
 
 // ---- the two-small-prime (27-bit) form of the external product (digit32.hip): per (n, device) tables ---------------------------
@@ -985,7 +978,7 @@ extern "C" size_t fhe_tggsw_prepared_words(uint64_t n, unsigned k, unsigned l) {
 }
 
 extern "C" int fhe_tggsw_prepare_dev(uint64_t n, unsigned k, unsigned l, const void *d_tggsw, void *d_prepared, void *hip_stream) {
-    int rc = check_pow2_n(n, "fhe_tggsw_prepare_dev");
+    int rc = check_ring(n, "fhe_tggsw_prepare_dev");
     if (rc != FHE_OK) return rc;
     if (l < 1 || l > 64 || k < 1 || k > 64) return fhe_fail(FHE_E_INVALID, "fhe_tggsw_prepare_dev: need 1 <= l <= 64, 1 <= k <= 64");
     if (!one_prime_form(n, k, l)) return fhe_fail(FHE_E_INVALID, "fhe_tggsw_prepare_dev: no prepared form for n=%llu, k=%u, l=%u (fhe_tggsw_prepared_words is 0)", (unsigned long long)n, k, l);
@@ -1018,16 +1011,27 @@ int fhe_tggsw_prepare_keys(uint64_t n, unsigned k, unsigned l, uint64_t keys, co
         return e == hipSuccess ? FHE_OK : fhe_hip_fail(e, "ntt32_fwd_key_kernel");
     }
     // [key][t][c][n] is [key * T + t][c][n]: the split and the transforms see one key of keys * T TGLev rows
-    { fhe::KernelTimer kt_("zr_split32", 0, st);
-    hipLaunchKernelGGL(fhe::zr_split32_kernel, dim3(fhe_ew_grid(keys * grows * n)), dim3(256), 0, st, (const u64 *)d_tggsw, (u64 *)d_prepared, keys * T, k1, (u32)n);
-    }
-    LAUNCH_OK("zr_split32_kernel");
+    if ((rc = launch("zr_split32", 0, st, fhe::zr_split32_kernel, fhe_ew_grid(keys * grows * n), 256, d_tggsw, d_prepared, keys * T, k1, (u32)n)) != FHE_OK) return rc;
     return z_forward(z1, 0, (const u64 *)d_prepared, (u64 *)d_prepared, keys * 2 * grows, st);          // halves are < 2^32 < P1
+}
+
+// The end of the one-prime external product: PART holds `parts` partial half-sums [b][half][c] in the NTT domain.  Their sum, the
+// 2(k+1) inverse transforms and the recombination of the halves are one kernel where a workgroup holds whole ciphertexts
+// (4096/n >= 2(k+1) rows); otherwise three: the sum into R (R = PART when parts = 1), the inverses, zr_combine32.
+static int torus_tail(const ZCtx &z1, u64 *PART, u32 parts, u64 *R, u32 k1, u64 n, void *d_out, u64 batch, hipStream_t st) {
+    hipError_t e = fhe::launch_digit_tail_torus(z1.dp[0], PART, parts, k1, z1.cc.half1, (u64 *)d_out, batch, st);
+    if (e == hipSuccess) return FHE_OK;
+    if (e != hipErrorNotSupported) return fhe_hip_fail(e, "digit_tail_kernel");
+    (void)hipGetLastError();
+    if (parts > 1 && (e = fhe::launch_sum_parts(PART, R, batch, parts, 2ull * k1 * n, z1.cc.m[0].q, st)) != hipSuccess)
+        return fhe_hip_fail(e, "sum_parts_kernel");
+    if (int rc = z_inverse(z1, 0, R, R, 2 * batch * k1, st)) return rc;
+    return launch("zr_combine32", 0, st, fhe::zr_combine32_kernel, fhe_ew_grid(batch * k1 * n), 256, R, d_out, batch, k1, (u32)n, z1.cc.p1, z1.cc.half1);
 }
 
 extern "C" int fhe_tggsw_external_product_prepared_dev(uint64_t n, unsigned k, unsigned l, const void *d_prepared,
                                                        const void *d_tglwe, void *d_out, size_t batch, void *hip_stream) {
-    int rc = check_pow2_n(n, "fhe_tggsw_external_product_prepared_dev");
+    int rc = check_ring(n, "fhe_tggsw_external_product_prepared_dev");
     if (rc != FHE_OK) return rc;
     if (l < 1 || l > 64 || k < 1 || k > 64) return fhe_fail(FHE_E_INVALID, "external product: need 1 <= l <= 64, 1 <= k <= 64");
     if (!one_prime_form(n, k, l)) return fhe_fail(FHE_E_INVALID, "fhe_tggsw_external_product_prepared_dev: no prepared form for this shape");
@@ -1064,22 +1068,7 @@ extern "C" int fhe_tggsw_external_product_prepared_dev(uint64_t n, unsigned k, u
         if ((rc = fhe_workspace_get(1, ((u64)parts + 1) * 2 * orows * n * 8, st, &wsv)) != FHE_OK) return rc;
         u64 *R = (u64 *)wsv, *PART = parts > 1 ? R + 2 * orows * n : R;
         hipError_t e = fhe::launch_digit_mac(z1.dp[0], fhe::SRC_DIGITS, (const u64 *)d_tglwe, (u64)k1 * n, k1, l, G2, 2 * k1, PART, parts, batch, st);
-        if (e == hipSuccess) {
-            // sum of the parts, the 2(k+1) inverse transforms and the recombination of the halves: one kernel
-            // where a workgroup holds whole ciphertexts (4096/n >= 2(k+1) rows), three otherwise
-            e = fhe::launch_digit_tail_torus(z1.dp[0], PART, parts, k1, z1.cc.half1, (u64 *)d_out, batch, st);
-            if (e == hipSuccess) return FHE_OK;
-            if (e != hipErrorNotSupported) return fhe_hip_fail(e, "digit_tail_kernel");
-            (void)hipGetLastError();
-            if (parts > 1 && (e = fhe::launch_sum_parts(PART, R, batch, parts, 2ull * k1 * n, z1.cc.m[0].q, st)) != hipSuccess)
-                return fhe_hip_fail(e, "sum_parts_kernel");
-            if ((rc = z_inverse(z1, 0, R, R, 2 * orows, st)) != FHE_OK) return rc;
-            { fhe::KernelTimer kt_("zr_combine32", 0, st);
-            hipLaunchKernelGGL(fhe::zr_combine32_kernel, dim3(fhe_ew_grid(orows * n)), dim3(256), 0, st, (const u64 *)R, (u64 *)d_out, (u64)batch, k1, (u32)n, z1.cc.p1, z1.cc.half1);
-            }
-            LAUNCH_OK("zr_combine32_kernel");
-            return FHE_OK;
-        }
+        if (e == hipSuccess) return torus_tail(z1, PART, parts, R, k1, n, d_out, batch, st);
         if (e != hipErrorNotSupported) return fhe_hip_fail(e, "digit_mac_kernel");
         (void)hipGetLastError();
     }
@@ -1088,27 +1077,15 @@ extern "C" int fhe_tggsw_external_product_prepared_dev(uint64_t n, unsigned k, u
     u64 *D = (u64 *)wsv, *R = D + drows * n;
     hipError_t e = fhe::launch_ntt_forward_digits(z1.dp[0], (const u64 *)d_tglwe, D, orows, (u32)l, st);
     if (e != hipSuccess) return fhe_hip_fail(e, "digit forward NTT");
-    { fhe::KernelTimer kt_("mac_rows", 0, st);
-    hipLaunchKernelGGL((fhe::mac_rows_kernel<>), dim3(fhe_ew_grid(fhe::mac_rows_threads(batch, 2 * k1, n))), dim3(256), 0, st, G2, (const u64 *)D, R, (u64)batch, (u32)n, (u32)T, 2 * k1, (u64)0, z1.cc.m[0]);
-    }
-    LAUNCH_OK("mac_rows_kernel");
-    e = fhe::launch_digit_tail_torus(z1.dp[0], R, 1, k1, z1.cc.half1, (u64 *)d_out, batch, st);     // inverse + recombination
-    if (e == hipSuccess) return FHE_OK;
-    if (e != hipErrorNotSupported) return fhe_hip_fail(e, "digit_tail_kernel");
-    (void)hipGetLastError();
-    if ((rc = z_inverse(z1, 0, R, R, 2 * orows, st)) != FHE_OK) return rc;
-    { fhe::KernelTimer kt_("zr_combine32", 0, st);
-    hipLaunchKernelGGL(fhe::zr_combine32_kernel, dim3(fhe_ew_grid(orows * n)), dim3(256), 0, st, (const u64 *)R, (u64 *)d_out, (u64)batch, k1, (u32)n, z1.cc.p1, z1.cc.half1);
-    }
-    LAUNCH_OK("zr_combine32_kernel");
-    return FHE_OK;
+    if ((rc = fhe_mac_rows(false, st, G2, D, R, batch, (u32)n, (u32)T, 2 * k1, 0, z1.cc.m[0])) != FHE_OK) return rc;
+    return torus_tail(z1, R, 1, R, k1, n, d_out, batch, st);     // inverse + recombination
 }
 
 
 // d_tggsw [(k+1)][l][(k+1)][n], one key for the batch; d_tglwe [batch][(k+1)][n]; d_out likewise.
 extern "C" int fhe_tggsw_external_product_dev(uint64_t n, unsigned k, unsigned l, const void *d_tggsw,
                                               const void *d_tglwe, void *d_out, size_t batch, void *hip_stream) {
-    int rc = check_pow2_n(n, "fhe_tggsw_external_product_dev");
+    int rc = check_ring(n, "fhe_tggsw_external_product_dev");
     if (rc != FHE_OK) return rc;
     if (l < 1 || l > 64 || k < 1 || k > 64) return fhe_fail(FHE_E_INVALID, "external product: need 1 <= l <= 64, 1 <= k <= 64");
     if (batch == 0) return FHE_OK;
@@ -1116,7 +1093,7 @@ extern "C" int fhe_tggsw_external_product_dev(uint64_t n, unsigned k, unsigned l
     REQUIRE_ALIGNED(d_tggsw); REQUIRE_ALIGNED(d_tglwe); REQUIRE_ALIGNED(d_out);
     const u32 k1 = k + 1;
     hipStream_t st = (hipStream_t)hip_stream;
-    const u64 grows = (u64)k1 * l * k1, drows = batch * k1 * l, orows = batch * k1;
+    const u64 grows = (u64)k1 * l * k1;
     // One-prime form (see zr_split32_kernel): the digit transforms — the dominant cost — are needed
     // for ONE prime instead of two.  Valid while each half-sum stays below P1/2: (k+1)*l*n <= 2^26.
     // Needs the bit-extracting transform (single-pass sizes); larger n takes the two-prime form.
@@ -1128,41 +1105,12 @@ extern "C" int fhe_tggsw_external_product_dev(uint64_t n, unsigned k, unsigned l
         if ((rc = fhe_tggsw_prepare_dev(n, k, l, d_tggsw, wsv, hip_stream)) != FHE_OK) return rc;
         return fhe_tggsw_external_product_prepared_dev(n, k, l, wsv, d_tglwe, d_out, batch, hip_stream);
     }
-    ZCtx z;
-    // digits are 0/1: |sum| < (k+1) * l * n * 2^64
-    rc = zctx_init(&z, n, primes_for_bits(64 + ceil_log2(n) + ceil_log2((u64)k1 * l), true));
-    if (rc != FHE_OK) return rc;
-    void *wsv = nullptr;
-    rc = fhe_workspace_get(1, (grows + 2 * drows + (size_t)z.K * orows) * n * 8, st, &wsv);
-    if (rc != FHE_OK) return rc;
-    u64 *G = (u64 *)wsv, *Dg = G + grows * n, *D = Dg + drows * n, *R = D + drows * n;
-    bool digits_done = false;
-    for (int kk = 0; kk < z.K; kk++) {
-        if ((rc = z_forward_src(z, kk, (const u64 *)d_tggsw, G, grows, n, st)) != FHE_OK) return rc;
-        // D = NTT of the 0/1 digit polynomials (digits are < every prime).  Single-pass sizes
-        // extract the bit in the transform's load; larger n materialises the digits once.
-        hipError_t e = fhe::launch_ntt_forward_digits(z.dp[kk], (const u64 *)d_tglwe, D, orows, (u32)l, st);
-        if (e == hipErrorNotSupported) {
-            if (!digits_done) {
-                { fhe::KernelTimer kt_("zr_digits", 0, st);
-                hipLaunchKernelGGL(fhe::zr_digits_kernel, dim3(fhe_ew_grid(drows * n)), dim3(256), 0, st, (const u64 *)d_tglwe, Dg, (u64)orows, (u32)n, (u32)l);
-                }
-                LAUNCH_OK("zr_digits_kernel");
-                digits_done = true;
-            }
-            if ((rc = z_forward(z, kk, Dg, D, drows, st)) != FHE_OK) return rc;
-        } else if (e != hipSuccess) {
-            return fhe_hip_fail(e, "digit forward NTT");
-        }
-        u64 *Rk = R + (u64)kk * orows * n;
-        // out[b][c] = sum_{i<k1,d<l} G[i][d][c] * D[b][i][d]  (tggsw.rs:57-59,145): T = k1*l terms, k1 rows
-        { fhe::KernelTimer kt_("mac_rows", 0, st);
-        hipLaunchKernelGGL((fhe::mac_rows_kernel<>), dim3(fhe_ew_grid(fhe::mac_rows_threads(batch, k1, n))), dim3(256), 0, st, (const u64 *)G, (const u64 *)D, Rk, (u64)batch, (u32)n, (u32)(k1 * l), (u32)k1, (u64)0, z.cc.m[kk]);
-        }
-        LAUNCH_OK("mac_rows_kernel");
-        if ((rc = z_inverse(z, kk, Rk, Rk, orows, st)) != FHE_OK) return rc;
-    }
-    return z_crt(z, true, R, R + orows * n, R + 2 * orows * n, (u64 *)d_out, orows * n, st);
+    // out[b][c] = sum_{i<k1,d<l} G[i][d][c] * D[b][i][d]  (tggsw.rs:57-59,145): T = k1*l terms, k1 rows
+    ZProduct p{};
+    p.a = d_tggsw; p.a_rows = grows; p.b = d_tglwe; p.b_rows = p.out_rows = batch * k1; p.digits = l; p.n_src = p.n = n;
+    p.bits = 64 + ceil_log2(n) + ceil_log2((u64)k1 * l); p.is_signed = true;   // digits are 0/1: |sum| < (k+1) * l * n * 2^64
+    p.batch = batch; p.T = k1 * l; p.nc = k1;
+    return z_product(p, d_out, st);
 }
 
 // ---- TFHE: TGLWE x Tn (plaintext product) and TGLev x Vec<Tn> -------------------------------------
@@ -1170,178 +1118,91 @@ extern "C" int fhe_tggsw_external_product_dev(uint64_t n, unsigned k, unsigned l
 // d_tglwe, d_out [batch][(k+1)][n]; d_p [batch][n].  Full 64 x 64-bit operands: 3 primes.
 extern "C" int fhe_tglwe_mul_tn_dev(uint64_t n, unsigned k, const void *d_tglwe, const void *d_p, void *d_out,
                                     size_t batch, void *hip_stream) {
-    int rc = check_pow2_n(n, "fhe_tglwe_mul_tn_dev");
+    int rc = check_ring(n, "fhe_tglwe_mul_tn_dev");
     if (rc != FHE_OK) return rc;
     if (k < 1 || k > 64) return fhe_fail(FHE_E_INVALID, "fhe_tglwe_mul_tn_dev: need 1 <= k <= 64");
     if (batch == 0) return FHE_OK;
     if (!d_tglwe || !d_p || !d_out) return fhe_fail(FHE_E_NULL, "fhe_tglwe_mul_tn_dev: NULL buffer");
     REQUIRE_ALIGNED(d_tglwe); REQUIRE_ALIGNED(d_p); REQUIRE_ALIGNED(d_out);
     const u32 k1 = k + 1;
-    ZCtx z;
-    rc = zctx_init(&z, n, primes_for_bits(128 + ceil_log2(n), true));   // |c_j| < n * 2^128
-    if (rc != FHE_OK) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
-    const u64 rows = batch * k1;
-    void *wsv = nullptr;
-    rc = fhe_workspace_get(1, (rows + batch + (size_t)z.K * rows) * n * 8, st, &wsv);
-    if (rc != FHE_OK) return rc;
-    u64 *A = (u64 *)wsv, *P = A + rows * n, *R = P + batch * n;
-    for (int kk = 0; kk < z.K; kk++) {
-        if ((rc = z_forward_src(z, kk, (const u64 *)d_tglwe, A, rows, n, st)) != FHE_OK) return rc;
-        if ((rc = z_forward_src(z, kk, (const u64 *)d_p, P, batch, n, st)) != FHE_OK) return rc;
-        u64 *Rk = R + (u64)kk * rows * n;
-        // T = 1 term, nc = k+1 rows, "key" = the ciphertext itself (per batch element)
-        { fhe::KernelTimer kt_("mac_rows", 0, st);
-        hipLaunchKernelGGL((fhe::mac_rows_kernel<>), dim3(fhe_ew_grid(fhe::mac_rows_threads(batch, k1, n))), dim3(256), 0, st, (const u64 *)A, (const u64 *)P, Rk, (u64)batch, (u32)n, (u32)1, k1, (u64)k1 * n, z.cc.m[kk]);
-        }
-        LAUNCH_OK("mac_rows_kernel");
-        if ((rc = z_inverse(z, kk, Rk, Rk, rows, st)) != FHE_OK) return rc;
-    }
-    return z_crt(z, true, R, R + rows * n, R + 2 * rows * n, (u64 *)d_out, rows * n, st);
+    // T = 1 term, nc = k+1 rows, "key" = the ciphertext itself (per batch element)
+    ZProduct p{};
+    p.a = d_tglwe; p.a_rows = p.out_rows = batch * k1; p.b = d_p; p.b_rows = batch; p.n_src = p.n = n;
+    p.bits = 128 + ceil_log2(n); p.is_signed = true;   // |c_j| < n * 2^128
+    p.batch = batch; p.T = 1; p.nc = k1; p.gstride = (u64)k1 * n;
+    return z_product(p, d_out, (hipStream_t)hip_stream);
 }
 
 // tfhe/src/tggsw.rs:139-149: out[b] = sum_{d<l} tglev[d] * v[b][d]  (TGLWE x Tn summed over the levels).
 // d_tglev [l][(k+1)][n] (one for the batch); d_v [batch][l][n] (any 64-bit words); d_out [batch][(k+1)][n].
 extern "C" int fhe_tglev_mul_dev(uint64_t n, unsigned k, unsigned l, const void *d_tglev, const void *d_v, void *d_out,
                                  size_t batch, void *hip_stream) {
-    int rc = check_pow2_n(n, "fhe_tglev_mul_dev");
+    int rc = check_ring(n, "fhe_tglev_mul_dev");
     if (rc != FHE_OK) return rc;
     if (l < 1 || l > 64 || k < 1 || k > 64) return fhe_fail(FHE_E_INVALID, "fhe_tglev_mul_dev: need 1 <= l <= 64, 1 <= k <= 64");
     if (batch == 0) return FHE_OK;
     if (!d_tglev || !d_v || !d_out) return fhe_fail(FHE_E_NULL, "fhe_tglev_mul_dev: NULL buffer");
     REQUIRE_ALIGNED(d_tglev); REQUIRE_ALIGNED(d_v); REQUIRE_ALIGNED(d_out);
     const u32 k1 = k + 1;
-    ZCtx z;
-    rc = zctx_init(&z, n, primes_for_bits(128 + ceil_log2(n) + ceil_log2(l), true));   // |sum| < l * n * 2^128
-    if (rc != FHE_OK) return rc;
-    hipStream_t st = (hipStream_t)hip_stream;
-    const u64 grows = (u64)l * k1, vrows = batch * l, orows = batch * k1;
-    void *wsv = nullptr;
-    rc = fhe_workspace_get(1, (grows + vrows + (size_t)z.K * orows) * n * 8, st, &wsv);
-    if (rc != FHE_OK) return rc;
-    u64 *G = (u64 *)wsv, *V = G + grows * n, *R = V + vrows * n;
-    for (int kk = 0; kk < z.K; kk++) {
-        if ((rc = z_forward_src(z, kk, (const u64 *)d_tglev, G, grows, n, st)) != FHE_OK) return rc;
-        if ((rc = z_forward_src(z, kk, (const u64 *)d_v, V, vrows, n, st)) != FHE_OK) return rc;
-        u64 *Rk = R + (u64)kk * orows * n;
-        { fhe::KernelTimer kt_("mac_rows", 0, st);
-        hipLaunchKernelGGL((fhe::mac_rows_kernel<>), dim3(fhe_ew_grid(fhe::mac_rows_threads(batch, k1, n))), dim3(256), 0, st, (const u64 *)G, (const u64 *)V, Rk, (u64)batch, (u32)n, (u32)l, k1, (u64)0, z.cc.m[kk]);
-        }
-        LAUNCH_OK("mac_rows_kernel");
-        if ((rc = z_inverse(z, kk, Rk, Rk, orows, st)) != FHE_OK) return rc;
-    }
-    return z_crt(z, true, R, R + orows * n, R + 2 * orows * n, (u64 *)d_out, orows * n, st);
+    ZProduct p{};
+    p.a = d_tglev; p.a_rows = (u64)l * k1; p.b = d_v; p.b_rows = batch * l; p.out_rows = batch * k1; p.n_src = p.n = n;
+    p.bits = 128 + ceil_log2(n) + ceil_log2(l); p.is_signed = true;   // |sum| < l * n * 2^128
+    p.batch = batch; p.T = l; p.nc = k1;
+    return z_product(p, d_out, (hipStream_t)hip_stream);
 }
 
 // ---- host-buffer wrappers (what a Rust shim binds) ------------------------------------------------
-using HostStage = FheHostStage;
-
 extern "C" int fhe_bfv_mul(uint64_t q, uint64_t n, uint64_t t, uint64_t pq, const uint64_t *rlk, const uint64_t *ab,
                            uint64_t *out, size_t batch) {
     if (batch == 0) return FHE_OK;
     if (!rlk || !ab || !out) return fhe_fail(FHE_E_NULL, "fhe_bfv_mul: NULL buffer");
-    int dev, rc = fhe_current_device(&dev);
-    if (rc != FHE_OK) return rc;
-    HostStage hs;
-    void *drlk, *dab, *dout;
-    if ((rc = hs.up(rlk, 2 * n * 8, &drlk)) != FHE_OK) return rc;
-    if ((rc = hs.up(ab, 4 * batch * n * 8, &dab)) != FHE_OK) return rc;
-    if ((rc = hs.up(nullptr, 2 * batch * n * 8, &dout)) != FHE_OK) return rc;
-    rc = fhe_bfv_mul_dev(q, n, t, pq, drlk, dab, dout, batch, hipStreamPerThread);
-    if (rc != FHE_OK) return rc;
-    return hs.down(out, dout, 2 * batch * n * 8);
+    return fhe_host_call({{rlk, 2 * n * 8}, {ab, 4 * batch * n * 8}}, out, 2 * batch * n * 8,
+                         [&](void *const *d) { return fhe_bfv_mul_dev(q, n, t, pq, d[0], d[1], d[2], batch, hipStreamPerThread); });
 }
 
 extern "C" int fhe_bfv_tensor(uint64_t q, uint64_t n, uint64_t t, const uint64_t *ab, uint64_t *c, size_t batch) {
     if (batch == 0) return FHE_OK;
     if (!ab || !c) return fhe_fail(FHE_E_NULL, "fhe_bfv_tensor: NULL buffer");
-    int dev, rc = fhe_current_device(&dev);
-    if (rc != FHE_OK) return rc;
-    HostStage hs;
-    void *dab, *dc;
-    if ((rc = hs.up(ab, 4 * batch * n * 8, &dab)) != FHE_OK) return rc;
-    if ((rc = hs.up(nullptr, 3 * batch * n * 8, &dc)) != FHE_OK) return rc;
-    rc = fhe_bfv_tensor_dev(q, n, t, dab, dc, batch, hipStreamPerThread);
-    if (rc != FHE_OK) return rc;
-    return hs.down(c, dc, 3 * batch * n * 8);
+    return fhe_host_call({{ab, 4 * batch * n * 8}}, c, 3 * batch * n * 8,
+                         [&](void *const *d) { return fhe_bfv_tensor_dev(q, n, t, d[0], d[1], batch, hipStreamPerThread); });
 }
 
 extern "C" int fhe_r_naive_mul(uint64_t n, const int64_t *a, const int64_t *b, int64_t *out, size_t batch) {
     if (batch == 0) return FHE_OK;
     if (!a || !b || !out) return fhe_fail(FHE_E_NULL, "fhe_r_naive_mul: NULL buffer");
-    int dev, rc = fhe_current_device(&dev);
-    if (rc != FHE_OK) return rc;
-    HostStage hs;
-    void *da, *db, *dout;
-    if ((rc = hs.up(a, batch * n * 8, &da)) != FHE_OK) return rc;
-    if ((rc = hs.up(b, batch * n * 8, &db)) != FHE_OK) return rc;
-    if ((rc = hs.up(nullptr, 2 * batch * n * 8, &dout)) != FHE_OK) return rc;
     // operands are read as NON-NEGATIVE 64-bit integers (Rq::to_r gives values in [0,q), ring_n.rs:72-79)
-    rc = fhe_r_naive_mul_dev(n, da, db, dout, batch, 64, 64, hipStreamPerThread);
-    if (rc != FHE_OK) return rc;
-    return hs.down(out, dout, 2 * batch * n * 8);
+    return fhe_host_call({{a, batch * n * 8}, {b, batch * n * 8}}, out, 2 * batch * n * 8,
+                         [&](void *const *d) { return fhe_r_naive_mul_dev(n, d[0], d[1], d[2], batch, 64, 64, hipStreamPerThread); });
 }
 
 extern "C" int fhe_tn_mul(uint64_t n, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t batch) {
     if (batch == 0) return FHE_OK;
     if (!a || !b || !out) return fhe_fail(FHE_E_NULL, "fhe_tn_mul: NULL buffer");
-    int dev, rc = fhe_current_device(&dev);
-    if (rc != FHE_OK) return rc;
-    HostStage hs;
-    void *da, *db, *dout;
-    if ((rc = hs.up(a, batch * n * 8, &da)) != FHE_OK) return rc;
-    if ((rc = hs.up(b, batch * n * 8, &db)) != FHE_OK) return rc;
-    if ((rc = hs.up(nullptr, batch * n * 8, &dout)) != FHE_OK) return rc;
-    rc = fhe_tn_mul_dev(n, da, db, dout, batch, hipStreamPerThread);
-    if (rc != FHE_OK) return rc;
-    return hs.down(out, dout, batch * n * 8);
+    return fhe_host_call({{a, batch * n * 8}, {b, batch * n * 8}}, out, batch * n * 8,
+                         [&](void *const *d) { return fhe_tn_mul_dev(n, d[0], d[1], d[2], batch, hipStreamPerThread); });
 }
 
 extern "C" int fhe_tggsw_external_product(uint64_t n, unsigned k, unsigned l, const uint64_t *tggsw,
                                           const uint64_t *tglwe, uint64_t *out, size_t batch) {
     if (batch == 0) return FHE_OK;
     if (!tggsw || !tglwe || !out) return fhe_fail(FHE_E_NULL, "fhe_tggsw_external_product: NULL buffer");
-    int dev, rc = fhe_current_device(&dev);
-    if (rc != FHE_OK) return rc;
-    HostStage hs;
-    void *dg, *dt, *dout;
     const size_t k1 = k + 1;
-    if ((rc = hs.up(tggsw, k1 * l * k1 * n * 8, &dg)) != FHE_OK) return rc;
-    if ((rc = hs.up(tglwe, batch * k1 * n * 8, &dt)) != FHE_OK) return rc;
-    if ((rc = hs.up(nullptr, batch * k1 * n * 8, &dout)) != FHE_OK) return rc;
-    rc = fhe_tggsw_external_product_dev(n, k, l, dg, dt, dout, batch, hipStreamPerThread);
-    if (rc != FHE_OK) return rc;
-    return hs.down(out, dout, batch * k1 * n * 8);
+    return fhe_host_call({{tggsw, k1 * l * k1 * n * 8}, {tglwe, batch * k1 * n * 8}}, out, batch * k1 * n * 8,
+                         [&](void *const *d) { return fhe_tggsw_external_product_dev(n, k, l, d[0], d[1], d[2], batch, hipStreamPerThread); });
 }
 
 extern "C" int fhe_tglwe_mul_tn(uint64_t n, unsigned k, const uint64_t *tglwe, const uint64_t *p, uint64_t *out, size_t batch) {
     if (batch == 0) return FHE_OK;
     if (!tglwe || !p || !out) return fhe_fail(FHE_E_NULL, "fhe_tglwe_mul_tn: NULL buffer");
-    int dev, rc = fhe_current_device(&dev);
-    if (rc != FHE_OK) return rc;
-    HostStage hs;
-    void *dc, *dp, *dout;
     const size_t k1 = (size_t)k + 1;
-    if ((rc = hs.up(tglwe, batch * k1 * n * 8, &dc)) != FHE_OK) return rc;
-    if ((rc = hs.up(p, batch * n * 8, &dp)) != FHE_OK) return rc;
-    if ((rc = hs.up(nullptr, batch * k1 * n * 8, &dout)) != FHE_OK) return rc;
-    rc = fhe_tglwe_mul_tn_dev(n, k, dc, dp, dout, batch, hipStreamPerThread);
-    if (rc != FHE_OK) return rc;
-    return hs.down(out, dout, batch * k1 * n * 8);
+    return fhe_host_call({{tglwe, batch * k1 * n * 8}, {p, batch * n * 8}}, out, batch * k1 * n * 8,
+                         [&](void *const *d) { return fhe_tglwe_mul_tn_dev(n, k, d[0], d[1], d[2], batch, hipStreamPerThread); });
 }
 
 extern "C" int fhe_tglev_mul(uint64_t n, unsigned k, unsigned l, const uint64_t *tglev, const uint64_t *v, uint64_t *out, size_t batch) {
     if (batch == 0) return FHE_OK;
     if (!tglev || !v || !out) return fhe_fail(FHE_E_NULL, "fhe_tglev_mul: NULL buffer");
-    int dev, rc = fhe_current_device(&dev);
-    if (rc != FHE_OK) return rc;
-    HostStage hs;
-    void *dg, *dv, *dout;
     const size_t k1 = (size_t)k + 1;
-    if ((rc = hs.up(tglev, (size_t)l * k1 * n * 8, &dg)) != FHE_OK) return rc;
-    if ((rc = hs.up(v, batch * l * n * 8, &dv)) != FHE_OK) return rc;
-    if ((rc = hs.up(nullptr, batch * k1 * n * 8, &dout)) != FHE_OK) return rc;
-    rc = fhe_tglev_mul_dev(n, k, l, dg, dv, dout, batch, hipStreamPerThread);
-    if (rc != FHE_OK) return rc;
-    return hs.down(out, dout, batch * k1 * n * 8);
+    return fhe_host_call({{tglev, (size_t)l * k1 * n * 8}, {v, batch * l * n * 8}}, out, batch * k1 * n * 8,
+                         [&](void *const *d) { return fhe_tglev_mul_dev(n, k, l, d[0], d[1], d[2], batch, hipStreamPerThread); });
 }

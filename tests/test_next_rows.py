@@ -400,3 +400,64 @@ def test_gpu_external_product_digit_load_at_every_single_pass_size(pkg, oracle, 
     tglwe = rng.integers(0, U64, (batch, k + 1, n), dtype=np.uint64)
     got = pkg.binding.tggsw_external_product(n, k, l, tggsw, tglwe).reshape(batch, k + 1, n)
     assert np.array_equal(got, oracle.external_product(n, k, l, tggsw, tglwe))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("a_bits,b_bits,K", [(1, 1, 1), (29, 28, 2), (59, 59, 3)])
+def test_gpu_naive_mul_recombines_one_two_and_three_primes(pkg, oracle, a_bits, b_bits, K):
+    """fhe_r_naive_mul_dev takes K primes for a_bits + b_bits + log2 n <= 60, <= 121, <= 182 (unsigned lift): at n = 16
+    the smallest bounds that give each K, operands at their bound, and the recombination kernel's K read back from the
+    kernel timer (label zr_crt, tag K)"""
+    import torch
+    B, L = pkg.binding, pkg.load_library()
+    n, batch = 16, 3
+    rng = np.random.default_rng(a_bits)
+    a = rng.integers(0, 1 << a_bits, (batch, n), dtype=np.int64)
+    b = rng.integers(0, 1 << b_bits, (batch, n), dtype=np.int64)
+    a[0], b[0] = (1 << a_bits) - 1, (1 << b_bits) - 1
+    da, db = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+    out = torch.empty((batch, 2 * n), dtype=torch.int64, device="cuda")
+    B.kernel_timing_reset()
+    B.kernel_timing_enable(1)
+    try:
+        B._check(L.fhe_r_naive_mul_dev(n, da.data_ptr(), db.data_ptr(), out.data_ptr(), batch, a_bits, b_bits, None))
+        torch.cuda.synchronize()
+        crt = {name: launches for name, (_, launches) in B.kernel_timing_read().items() if name.startswith("zr_crt")}
+    finally:
+        B.kernel_timing_enable(0)
+        B.kernel_timing_reset()
+    assert crt == {f"zr_crt_{K}": 1}
+    got = out.cpu().numpy()
+    assert np.array_equal(got[:, :2 * n - 1], oracle.r_naive_mul(n, a, b)) and not got[:, 2 * n - 1].any()
+
+
+@pytest.mark.gpu
+def test_gpu_external_product_unfused_61_bit_route(pkg, oracle):
+    """FHE_DIGIT_MAC_FUSED=0 with FHE_EXT32=0 (both read once per process: a fresh child) takes the one-prime external
+    product through the materialised digit transforms and mac_rows; its end is the tail kernel at n = 1024 and the inverse
+    transforms with zr_combine32 at n = 16, where there is no tail kernel.  k = 1, l = 2, batch 2, against the oracle."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (
+        "import sys, numpy as np; sys.path.insert(0, %r)\n"
+        "import fhe_study_amd as pkg\n"
+        "from oracle import load_oracle\n"
+        "O, B = load_oracle(), pkg.binding\n"
+        "for n in (16, 1024):\n"
+        "    k, l, batch = 1, 2, 2\n"
+        "    rng = np.random.default_rng(n)\n"
+        "    g = rng.integers(0, 1 << 64, (k + 1, l, k + 1, n), dtype=np.uint64)\n"
+        "    c = rng.integers(0, 1 << 64, (batch, k + 1, n), dtype=np.uint64)\n"
+        "    B.kernel_timing_reset(); B.kernel_timing_enable(1)\n"
+        "    got = B.tggsw_external_product(n, k, l, g, c).reshape(batch, k + 1, n)\n"
+        "    names = sorted(x.rsplit('_', 1)[0] for x in B.kernel_timing_read())\n"
+        "    B.kernel_timing_enable(0)\n"
+        "    assert np.array_equal(got, O.external_product(n, k, l, g, c)), n\n"
+        "    print('route', n, ' '.join(names))\n" % root)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, FHE_DIGIT_MAC_FUSED="0", FHE_EXT32="0"), capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    routes = {int(ln.split()[1]): ln.split()[2:] for ln in r.stdout.splitlines() if ln.startswith("route")}
+    assert set(routes) == {16, 1024}
+    assert "mac_rows" in routes[16] and "zr_combine32" in routes[16]
+    assert "mac_rows" in routes[1024] and "zr_combine32" not in routes[1024]
