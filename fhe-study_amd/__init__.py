@@ -4,7 +4,8 @@ Layout:
   csrc/        HIP kernels (gfx950) + the C ABI of include/fhe_ntt.h → libfhe_ntt.so
   binding.py   ctypes plumbing over the C ABI
   arith.py     host mirror of the reference's RingParam / Rq / NTT surface
-  bfv.py       RLWE::tensor / RLWE::mul (bfv/src/lib.rs) over the exact-product rows
+  bfv.py       RLWE::tensor / RLWE::mul (bfv/src/lib.rs) over the exact-product rows, and BFV's client side
+  device.py    device buffers for bfv.py and tfhe.py (torch as the allocator)
   tfhe.py      Tn x Tn and TGGSW x TGLWE (ring_torus.rs, tfhe/src/tggsw.rs)
   host/        the same mirror in C++ (arith.hpp), for compiled callers
 

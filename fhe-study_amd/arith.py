@@ -27,11 +27,15 @@ from .binding import FheError, Plan
 _plans = {}
 
 
-def _plan(param):
+def plan_of(param):
+    """the memoised Plan of a RingParam"""
     key = (param.q, param.n)
     if key not in _plans:
         _plans[key] = Plan(param.q, param.n)
     return _plans[key]
+
+
+_plan = plan_of
 
 
 @dataclass(frozen=True)

@@ -14,8 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FHE_NTT_LIB") or os.path.join(_HERE, "libfhe_ntt.so")  # env: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip", "tfhe_client.hip"]
-HEADERS = ["ntt_kernels.hpp", "ntt_rounds.hpp", "ntt_persist.hpp", "persist_sched.hpp", "digit_mac.hpp", "digit32.hpp", "bfv32.hpp", "smallq.hpp", "ntt32_rounds.hpp", "ntt32_big.hpp", "zq_device.hpp", "capi_internal.hpp", "mac_kernel.hpp", "ntt_kernels.hip",
+SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip", "tfhe_client.hip", "bfv_client.hip"]
+HEADERS = ["ntt_kernels.hpp", "ntt_rounds.hpp", "ntt_persist.hpp", "persist_sched.hpp", "digit_mac.hpp", "digit32.hpp", "bfv32.hpp", "smallq.hpp", "ntt32_rounds.hpp", "ntt32_big.hpp", "zq_device.hpp", "capi_internal.hpp", "mac_kernel.hpp", "chacha_stream.hpp", "ntt_kernels.hip",
            os.path.join("..", "..", "include", "fhe_ntt.h"), os.path.join("..", "..", "include", "fhe_ntt_experimental.h")]
 OBJ_DIR = os.path.join(_HERE, "build")
 # -ffp-contract=off: zring.hip restates the reference's f64 scale-and-round (one IEEE rounding
@@ -81,6 +81,8 @@ EXPORTS = [
     "fhe_tfhe_pksk_words", "fhe_tlwe_gadget_packing_key_switch_dev", "fhe_tglwe_box_expand_dev", "fhe_tfhe_gadget_bootstrap_rows_dev",
     # key generation, encryption and decryption: the client side (tfhe_client.hip)
     "fhe_tfhe_stream_words_dev", "fhe_tlwe_encrypt_dev", "fhe_tlwe_phase_dev", "fhe_tglwe_encrypt_dev", "fhe_tglwe_phase_dev",
+    # BFV key generation, encryption and decryption: the client side (bfv_client.hip)
+    "fhe_bfv_secret_key_dev", "fhe_bfv_public_key_dev", "fhe_bfv_relin_key_dev", "fhe_bfv_encrypt_dev", "fhe_bfv_decrypt_dev",
 ]
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
@@ -89,6 +91,7 @@ FHE_GATE_COUNT = 10
 FHE_LUT_NONE = 0xFFFFFFFF                    # include/fhe_ntt.h: the index of an operand whose scale is 0, by convention
 FHE_STREAM_MASK, FHE_STREAM_ERR, FHE_STREAM_KEY = 1, 2, 3    # include/fhe_ntt.h: the purposes of the random stream
 FHE_STREAM_BITS = 1                          # flag of fhe_tfhe_stream_words_dev: every word AND 1
+FHE_STREAM_BFV_MASK, FHE_STREAM_BFV_ERR, FHE_STREAM_BFV_KEY, FHE_STREAM_BFV_EPH = 0x11, 0x12, 0x13, 0x14    # the BFV rows of that stream
 
 
 # include/fhe_ntt_experimental.h: the persistent kernels' switches (exported, NOT part of the boundary)
@@ -276,6 +279,11 @@ def load_library():
     L.fhe_tlwe_phase_dev.argtypes = [_uint, _vp, _vp, _vp, _sz, _vp]
     L.fhe_tglwe_encrypt_dev.argtypes = [_u64, _uint, ctypes.c_char_p, _u64, _vp, _vp, _sz, _vp, _uint, _uint, _vp, _sz, _vp]
     L.fhe_tglwe_phase_dev.argtypes = [_u64, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_bfv_secret_key_dev.argtypes = [_u64, ctypes.c_char_p, _u64, _vp, _vp]
+    L.fhe_bfv_public_key_dev.argtypes = [_vp, ctypes.c_char_p, _u64, _vp, _vp, _uint, _vp, _vp]
+    L.fhe_bfv_relin_key_dev.argtypes = [_u64, _u64, _u64, ctypes.c_char_p, _u64, _vp, _vp, _uint, _vp, _vp]
+    L.fhe_bfv_encrypt_dev.argtypes = [_vp, _u64, ctypes.c_char_p, _u64, _vp, _vp, _sz, _vp, _uint, _vp, _sz, _vp]
+    L.fhe_bfv_decrypt_dev.argtypes = [_vp, _u64, _vp, _vp, _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -679,6 +687,32 @@ def tglwe_encrypt_dev(n, k, seed, first_row, d_key, d_msg, msg_stride, d_cdt, m,
 
 def tglwe_phase_dev(n, k, d_key, d_in, d_out, rows, stream=None):
     _check(load_library().fhe_tglwe_phase_dev(n, k, d_key, d_in, d_out, rows, stream))
+
+
+# ---- BFV key generation, encryption and decryption (plan: a Plan, seed: 32 bytes) ---------------------------
+def bfv_secret_key_dev(n, seed, key_row, d_s, stream=None):
+    """d_s [n]: the 0/1 words of KEY row key_row"""
+    _check(load_library().fhe_bfv_secret_key_dev(n, _seed(seed), key_row, d_s, stream))
+
+
+def bfv_public_key_dev(plan, seed, row, d_s, d_cdt, m, d_pk, stream=None):
+    """d_pk [2][n] = (-a s + e, a) mod q"""
+    _check(load_library().fhe_bfv_public_key_dev(plan.handle, _seed(seed), row, d_s, d_cdt, m, d_pk, stream))
+
+
+def bfv_relin_key_dev(q, n, pq, seed, row, d_s, d_cdt, m, d_rlk, stream=None):
+    """d_rlk [2][n] = (-(a s + e) + p s^2, a) mod pq, exactly"""
+    _check(load_library().fhe_bfv_relin_key_dev(q, n, pq, _seed(seed), row, d_s, d_cdt, m, d_rlk, stream))
+
+
+def bfv_encrypt_dev(plan, t, seed, first_row, d_pk_evals, d_msg, msg_stride, d_cdt, m, d_out, batch, stream=None):
+    """d_out [2][batch][n]; d_msg None: m = 0; msg_stride 0: one message polynomial for every row"""
+    _check(load_library().fhe_bfv_encrypt_dev(plan.handle, t, _seed(seed), first_row, d_pk_evals, d_msg, msg_stride, d_cdt, m, d_out, batch, stream))
+
+
+def bfv_decrypt_dev(plan, t, d_s_evals, d_ct, d_out, batch, stream=None):
+    """d_ct [2][batch][n] -> d_out [batch][n], words below t"""
+    _check(load_library().fhe_bfv_decrypt_dev(plan.handle, t, d_s_evals, d_ct, d_out, batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

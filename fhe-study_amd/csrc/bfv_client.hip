@@ -1,0 +1,487 @@
+// bfv_client.hip — the client side of BFV on the device (bfv/src/lib.rs:118-225): the secret key, the
+// public key, the relinearisation key, encryption and decryption.  Everything is exact and independent of launch geometry.
+//
+//   stream    the ChaCha20 stream of §17 unchanged (chacha_stream.hpp): key = the 32-byte seed, nonce = (purpose, row lo, row
+//             hi), stream word j of a block = u32 word 2j | u32 word 2j + 1 << 32.  Four purposes of their own: BFV_MASK =
+//             0x11, BFV_ERR = 0x12, BFV_KEY = 0x13, BFV_EPH = 0x14, so no BFV row shares a nonce with a TFHE row.
+//   uniform   coefficient i modulo Q (Q = q or pq, below 2^63) from MASK words w0 = 2i, w1 = 2i + 1 of the row:
+//             a_i = floor((w1 2^64 + w0) Q / 2^128) = ((u128) w1 Q + mulhi64(w0, Q)) >> 64.  No rejection: a_i depends on i only.
+//   secret    s_i = KEY word i AND 1                                   (the reference's Uniform(0, 2))
+//   u         from EPH word i: (w AND 1) - ((w >> 1) AND 1), i.e. -1, 0, 1 with probability 1/4, 1/2, 1/4 (the law of the
+//             reference's rounded Uniform(-1.0, 1.0)), stored as 0, 1 or Q - 1
+//   errors    cdt_error of §17 at log_scale 0, taken into [0, Q) as e or Q - |e|: the discrete Gaussian of §17, NOT the
+//             reference's rounded Normal(0, 3.2).  Encryption row r draws e1 from ERR row 2r and e2 from ERR row 2r + 1, a key
+//             row r draws e from ERR row 2r: hence first_row + rows <= 2^63.
+//   pk        (-a s + e, a) mod q
+//   encrypt   c0 = pk0 u + e1 + Delta (m mod q), c1 = pk1 u + e2, Delta = floor(q / t)
+//   decrypt   cs = c0 + c1 s mod q, then Zq::from_f64(q, round(t as f64 * cs as f64 / q as f64)) reduced mod t: the f64 steps
+//             of fhe_rq_mul_div_round_dev (glue.hip) on the same f64_as_i64 helper (zq_device.hpp), then fhe_rq_remodule_dev's
+//   rlk       (-(a s + e) + p s^2, a) mod pq, EXACTLY.  The reference forms a s and s^2 through `as f64` (tmp_naive_mul ->
+//             from_vec_i64), which is exact only while a coefficient of the integer product stays below 2^53; the device
+//             computes the exact value everywhere, which is the reference's wherever its route is exact.  Admitted for
+//             n pq < 2^63 only: the signed negacyclic product mod 2^64 of fhe_tn_mul_dev is then the integer product, and one
+//             reduction mod pq finishes it (p s^2 mod pq = p (s^2 mod q)).
+//
+// Encryption, the pointwise route: bfv_ephemeral_kernel writes u, the forward transform runs in place,
+// bfv_pk_pointwise_kernel multiplies u^ by both key rows (a thread keeps its two key words in registers and walks down the
+// batch: the key is read once per workgroup, never staged per row), the two inverse transforms run in place and
+// bfv_encrypt_epilogue_kernel adds e1 + Delta m and e2 on the way to the caller's buffer: one forward and two inverse
+// transforms per ciphertext, two staging rows.  The staged route, taken where fhe_rq_mul_dev is one fused kernel because it
+// measured faster there: bfv_broadcast_kernel copies both key rows over a chunk once per call and fhe_rq_mul_dev forms
+// each product as one fused 32-bit kernel (u is transformed twice); five staging rows.  The staging is bounded by processing
+// 2^21 coefficients at a time in workspace slot 10 (32 MiB, 80 MiB staged); every word is a function of its (row, index)
+// alone, so the result depends neither on the chunking nor on the route.  Decryption stages c1 the same way (pointwise).
+// The kernels make u64 accesses only and the transforms run on library workspace, so callers' buffers need 8-byte alignment.
+#include <algorithm>
+#include <cstdlib>
+#include <vector>
+
+#include "capi_internal.hpp"
+#include "chacha_stream.hpp"
+#include "smallq.hpp"
+
+using fhe::Mod;
+using fhe::u32;
+using fhe::u64;
+
+namespace fhe {
+
+constexpr u32 BFV_MASK = 0x11, BFV_ERR = 0x12, BFV_KEY = 0x13, BFV_EPH = 0x14;
+
+__device__ __forceinline__ u64 bfv_uniform(u64 w0, u64 w1, u64 Q) {
+    return (u64)(((unsigned __int128)w1 * Q + __umul64hi(w0, Q)) >> 64);
+}
+// a b mod q for canonical or arbitrary words and any q below 2^63 (uniform branch)
+__device__ __forceinline__ u64 bfv_mulmod(u64 a, u64 b, const Mod &m) { return (m.q >> 62) ? mul_mod_var63(a, b, m) : mul_mod_var(a, b, m); }
+// the signed error word e (|e| < Q) as a residue
+__device__ __forceinline__ u64 bfv_err_residue(u64 e, u64 Q) { return (long long)e < 0 ? Q + e : e; }
+// x mod Q for a signed word and any Q below 2^63
+__device__ __forceinline__ u64 bfv_smod(u64 x, u64 Q) {
+    const long long r = (long long)x % (long long)Q;
+    return r < 0 ? (u64)(r + (long long)Q) : (u64)r;
+}
+
+// A thread holds `1 << lper` (at most PER) consecutive words of the flat output, thread i the words from i << lper on; the
+// block's words leave through LDS so that every store instruction writes 256 consecutive words.  All 256 threads call it.
+template <u32 PER>
+__device__ __forceinline__ void bfv_store_block(u64 *stage, const u64 (&v)[PER], u32 lper, u64 block_first_word, u64 total_words, u64 *__restrict__ out) {
+    const u32 tid = threadIdx.x, per = 1u << lper;
+#pragma unroll
+    for (u32 j = 0; j < PER; j++)
+        if (j < per) stage[tid * (PER + 1) + j] = v[j];
+    __syncthreads();
+#pragma unroll
+    for (u32 k = 0; k < PER; k++) {
+        const u32 t = k * 256 + tid;
+        if (t < (256u << lper) && block_first_word + t < total_words) out[block_first_word + t] = stage[(t >> lper) * (PER + 1) + (t & (per - 1))];
+    }
+    __syncthreads();
+}
+
+// out [rows][n]: uniform coefficients modulo Q of MASK rows first_row ..; a thread takes a ChaCha block = 4 coefficients
+// (n = 2: the two of its row).  lper = log2 min(n, 4), row_blocks = max(n / 4, 1).
+__global__ __launch_bounds__(256) void bfv_uniform_kernel(ChaChaKey key, u64 first_row, u64 Q, u32 lper, u64 row_blocks, u64 rows, u64 *__restrict__ out) {
+    __shared__ u64 stage[256 * 5];
+    const u64 total = rows * row_blocks;
+    for (u64 base = (u64)blockIdx.x * 256; base < total; base += (u64)gridDim.x * 256) {
+        const u64 i = base + threadIdx.x;
+        u64 v[4] = {0, 0, 0, 0};
+        if (i < total) {
+            const u64 r = i / row_blocks, c = i - r * row_blocks;
+            u64 w[8];
+            chacha_block(key, (u32)c, BFV_MASK, first_row + r, w);
+#pragma unroll
+            for (u32 j = 0; j < 4; j++) v[j] = bfv_uniform(w[2 * j], w[2 * j + 1], Q);
+        }
+        bfv_store_block<4>(stage, v, lper, base << lper, total << lper, out);
+    }
+}
+
+// out [rows][n] from `purpose` rows first_row ..: key != 0: the secret-key bits w AND 1 (BFV_KEY); key = 0: the ephemeral u
+// as the residue 0, 1 or Q - 1 (BFV_EPH), ready for the forward transform.  A thread takes a block = 8 coefficients.
+__global__ __launch_bounds__(256) void bfv_ephemeral_kernel(ChaChaKey key, u32 purpose, u32 is_key, u64 first_row, u64 Q, u32 lper, u64 row_blocks, u64 rows,
+                                                            u64 *__restrict__ out) {
+    __shared__ u64 stage[256 * 9];
+    const u64 total = rows * row_blocks;
+    for (u64 base = (u64)blockIdx.x * 256; base < total; base += (u64)gridDim.x * 256) {
+        const u64 i = base + threadIdx.x;
+        u64 v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (i < total) {
+            const u64 r = i / row_blocks, c = i - r * row_blocks;
+            u64 w[8];
+            chacha_block(key, (u32)c, purpose, first_row + r, w);
+#pragma unroll
+            for (u32 j = 0; j < 8; j++) {
+                const u32 b0 = (u32)w[j] & 1u, b1 = ((u32)w[j] >> 1) & 1u;
+                v[j] = is_key ? (u64)b0 : (b0 == b1 ? 0ull : (b0 ? 1ull : Q - 1));
+            }
+        }
+        bfv_store_block<8>(stage, v, lper, base << lper, total << lper, out);
+    }
+}
+
+// KEYS = 2: out0[r] = u^[r] (.) key[0], out1[r] = u^[r] (.) key[1] (encryption; out0 may be u^ itself); KEYS = 1: out0[r] =
+// u^[r] (.) key[0] (decryption).  key [KEYS][n] is shared by the batch: a thread loads its column's key words once and walks
+// down the rows, rpb = 256 / min(n, 256) rows per pass.  Any q below 2^63: the 128-bit product with zq_device.hpp's reduction.
+template <int KEYS>
+__global__ __launch_bounds__(256) void bfv_pk_pointwise_kernel(const u64 *u, const u64 *__restrict__ key, u64 *out0, u64 *__restrict__ out1, u32 L, u64 rows,
+                                                               Mod m) {
+    const u64 n = 1ull << L;
+    const u32 lc = L < 8u ? L : 8u, rpb = 256u >> lc;                        // columns of a block = 1 << lc
+    const u64 col = ((u64)blockIdx.x << lc) + (threadIdx.x & ((1u << lc) - 1u));
+    const u64 k0 = key[col], k1 = KEYS == 2 ? key[n + col] : 0ull;
+    for (u64 r = (u64)blockIdx.y * rpb + (threadIdx.x >> lc); r < rows; r += (u64)gridDim.y * rpb) {
+        const u64 x = u[(r << L) + col];
+        out0[(r << L) + col] = bfv_mulmod(x, k0, m);
+        if (KEYS == 2) out1[(r << L) + col] = bfv_mulmod(x, k1, m);
+    }
+}
+
+// out0[r] = P0[r] + e1 + Delta (msg_r mod q), out1[r] = P1[r] + e2 (mod q, canonical) for encryption row first_row + r: e1
+// from ERR row 2 (first_row + r), e2 from the row after it; a thread takes 8 coefficients (one ChaCha block of each error
+// row), the table sits in LDS.  msg null: m = 0; msg_stride 0: one message for every row.
+__global__ __launch_bounds__(256) void bfv_encrypt_epilogue_kernel(ChaChaKey key, u64 first_row, const u64 *__restrict__ P0, const u64 *__restrict__ P1,
+                                                                   const u64 *__restrict__ msg, u64 msg_stride, const u64 *__restrict__ cdt, u32 cm,
+                                                                   u64 delta, u64 *__restrict__ out0, u64 *__restrict__ out1, u32 L, u64 rows, Mod m) {
+    __shared__ u64 scdt[CDT_MAX];
+    for (u32 i = threadIdx.x; i < cm; i += 256) scdt[i] = cdt[i];
+    __syncthreads();
+    const u32 LB = L > 3u ? L - 3u : 0u;                          // blocks per row = max(n / 8, 1)
+    const u64 n = 1ull << L, total = rows << LB, stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 r = i >> LB, c = i & ((1ull << LB) - 1u), erow = 2 * (first_row + r);
+        u64 w1[8], w2[8];
+        if (cm) {
+            chacha_block(key, (u32)c, BFV_ERR, erow, w1);
+            chacha_block(key, (u32)c, BFV_ERR, erow + 1, w2);
+        }
+        const u64 at = (r << L) + 8 * c;
+        const u64 *__restrict__ mp = msg ? msg + r * msg_stride + 8 * c : nullptr;
+#pragma unroll
+        for (u32 j = 0; j < 8; j++) {
+            if (8 * c + j < n) {
+                const u64 e1 = cm ? bfv_err_residue(cdt_error(scdt, cm, w1[j], 0), m.q) : 0ull;
+                const u64 e2 = cm ? bfv_err_residue(cdt_error(scdt, cm, w2[j], 0), m.q) : 0ull;
+                const u64 dm = mp ? bfv_mulmod(reduce_any(mp[j], m), delta, m) : 0ull;
+                out0[at + j] = add63(add63(P0[at + j], e1, m), dm, m);
+                out1[at + j] = add63(P1[at + j], e2, m);
+            }
+        }
+    }
+}
+
+// out = Zq::from_f64(q, round(t (c0 + P mod q) / q)) mod t: zq_device.hpp's zq_from_f64, the helper of the library's other
+// f64 epilogues (round of an integral value is itself, so its words are rq_mul_div_round_kernel's, glue.hip, which spells
+// the same steps out; tests/test_bfv_client_gpu.py compares the two at every residue of q = 65537), then Rq::remodule
+__global__ __launch_bounds__(256) void bfv_decrypt_epilogue_kernel(const u64 *__restrict__ c0, const u64 *__restrict__ P, u64 *__restrict__ out, u64 count,
+                                                                   u64 t, Mod m) {
+    const u64 stride = (u64)gridDim.x * 256;
+    const double nf = (double)t, df = (double)m.q;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        const u64 cs = add63(c0[i], P[i], m);
+        const u64 v = zq_from_f64(m.q, round((nf * (double)cs) / df));
+        out[i] = v >= t ? v % t : v;
+    }
+}
+
+// dst [rows][n] = src [n]: the key rows of the staged route (below), once per call
+__global__ __launch_bounds__(256) void bfv_broadcast_kernel(const u64 *__restrict__ src, u64 *__restrict__ dst, u32 L, u64 rows) {
+    const u64 total = rows << L, N = 1ull << L;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += (u64)gridDim.x * 256) dst[i] = src[i & (N - 1)];
+}
+
+// dst [n] = src[i] AND 1: a secret key as canonical 0/1 words
+__global__ __launch_bounds__(256) void bfv_key_bits_kernel(const u64 *__restrict__ src, u64 *__restrict__ dst, u64 n) {
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) dst[i] = src[i] & 1ull;
+}
+
+// pk [2][n] = (-(a s) + e, a) mod q: as = a s mod q, e from ERR row 2 row; a thread takes 8 coefficients
+__global__ __launch_bounds__(256) void bfv_pk_epilogue_kernel(ChaChaKey key, u64 row, const u64 *__restrict__ a, const u64 *__restrict__ as,
+                                                              const u64 *__restrict__ cdt, u32 cm, u64 *__restrict__ pk, u64 n, Mod m) {
+    __shared__ u64 scdt[CDT_MAX];
+    for (u32 i = threadIdx.x; i < cm; i += 256) scdt[i] = cdt[i];
+    __syncthreads();
+    const u64 blocks = (n + 7) / 8;
+    for (u64 c = (u64)blockIdx.x * 256 + threadIdx.x; c < blocks; c += (u64)gridDim.x * 256) {
+        u64 w[8];
+        if (cm) chacha_block(key, (u32)c, BFV_ERR, 2 * row, w);
+#pragma unroll
+        for (u32 j = 0; j < 8; j++) {
+            const u64 i = 8 * c + j;
+            if (i < n) {
+                const u64 e = cm ? bfv_err_residue(cdt_error(scdt, cm, w[j], 0), m.q) : 0ull;
+                pk[i] = add63(sub63(0ull, as[i], m), e, m);
+                pk[n + i] = a[i];
+            }
+        }
+    }
+}
+
+// rlk [2][n] = (-(a s + e) + p s^2, a) mod pq from the integer products as = a s and ss = s s (signed words, |.| < n pq <
+// 2^63): one reduction mod pq each; p (ss mod q) < pq is p ss mod pq
+__global__ __launch_bounds__(256) void bfv_rlk_epilogue_kernel(ChaChaKey key, u64 row, const u64 *__restrict__ a, const u64 *__restrict__ as,
+                                                               const u64 *__restrict__ ss, const u64 *__restrict__ cdt, u32 cm, u64 *__restrict__ rlk, u64 n,
+                                                               u64 q, u64 pq) {
+    __shared__ u64 scdt[CDT_MAX];
+    for (u32 i = threadIdx.x; i < cm; i += 256) scdt[i] = cdt[i];
+    __syncthreads();
+    const u64 blocks = (n + 7) / 8, p = pq / q;
+    for (u64 c = (u64)blockIdx.x * 256 + threadIdx.x; c < blocks; c += (u64)gridDim.x * 256) {
+        u64 w[8];
+        if (cm) chacha_block(key, (u32)c, BFV_ERR, 2 * row, w);
+#pragma unroll
+        for (u32 j = 0; j < 8; j++) {
+            const u64 i = 8 * c + j;
+            if (i < n) {
+                const u64 e = cm ? bfv_err_residue(cdt_error(scdt, cm, w[j], 0), pq) : 0ull;
+                u64 x = bfv_smod(as[i], pq) + e;                       // below 2 pq < 2^64
+                x = x >= pq ? x - pq : x;
+                u64 y = (x ? pq - x : 0ull) + p * bfv_smod(ss[i], q);
+                rlk[i] = y >= pq ? y - pq : y;
+                rlk[n + i] = a[i];
+            }
+        }
+    }
+}
+
+}  // namespace fhe
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kBfvClientSlot = 10;              // fhe_workspace_get slot of the staging rows (slots 0-9 are taken)
+constexpr u64 kChunkWords = 1ull << 21;         // ciphertexts are processed 2^21 coefficients at a time: 32 MiB of staging
+constexpr u64 kRowLimit = 1ull << 63;           // error rows are 2 r and 2 r + 1
+
+bool misaligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
+
+fhe::ChaChaKey seed_key(const uint8_t *seed) {
+    fhe::ChaChaKey k;
+    for (int i = 0; i < 8; i++)
+        k.w[i] = (u32)seed[4 * i] | ((u32)seed[4 * i + 1] << 8) | ((u32)seed[4 * i + 2] << 16) | ((u32)seed[4 * i + 3] << 24);
+    return k;
+}
+
+// the table's shape without a device: m <= 1024 entries, every magnitude (at most m) below the modulus
+int check_cdt_shape(const void *d_cdt, unsigned m, u64 Q, const char *who) {
+    if (m > fhe::CDT_MAX) return fhe_fail(FHE_E_INVALID, "%s: m=%u thresholds, at most %u", who, m, fhe::CDT_MAX);
+    if (m >= Q) return fhe_fail(FHE_E_INVALID, "%s: the largest error magnitude m=%u must be below the modulus %llu", who, m, (unsigned long long)Q);
+    if (m && !d_cdt) return fhe_fail(FHE_E_NULL, "%s: NULL error table with m=%u", who, m);
+    if (m && misaligned8(d_cdt)) return fhe_fail(FHE_E_INVALID, "%s: d_cdt must be 8-byte aligned", who);
+    return FHE_OK;
+}
+// its words, as §17 checks them: strictly increasing thresholds below 2^63, on a host copy (synchronises `st`)
+int check_cdt_words(const void *d_cdt, unsigned m, hipStream_t st, const char *who) {
+    if (m == 0) return FHE_OK;
+    std::vector<u64> t(m);
+    HIP_TRY(hipMemcpyAsync(t.data(), d_cdt, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (unsigned i = 0; i < m; i++)
+        if (t[i] >> 63 || (i && t[i] <= t[i - 1]))
+            return fhe_fail(FHE_E_INVALID, "%s: the error table must be strictly increasing and below 2^63 (entry %u)", who, i);
+    return FHE_OK;
+}
+
+u32 log2_of(u64 n) { return (u32)__builtin_ctzll(n); }
+
+// out [rows][n]: the uniform rows modulo Q
+int uniform_fill(const fhe::ChaChaKey &key, u64 first_row, u64 Q, u64 n, u64 *out, u64 rows, hipStream_t st) {
+    const u32 lper = std::min<u32>(log2_of(n), 2u);
+    const u64 row_blocks = n >> lper;
+    return launch("bfv_uniform", (int)log2_of(n), st, fhe::bfv_uniform_kernel, fhe_ew_grid(rows * row_blocks), 256, key, first_row, Q, lper, row_blocks, rows,
+                  out);
+}
+// out [rows][n]: secret-key bits (is_key) or the ephemeral residues modulo Q
+int small_fill(const fhe::ChaChaKey &key, u32 purpose, u32 is_key, u64 first_row, u64 Q, u64 n, u64 *out, u64 rows, hipStream_t st) {
+    const u32 lper = std::min<u32>(log2_of(n), 3u);
+    const u64 row_blocks = n >> lper;
+    return launch("bfv_ephemeral", (int)log2_of(n), st, fhe::bfv_ephemeral_kernel, fhe_ew_grid(rows * row_blocks), 256, key, purpose, is_key, first_row, Q, lper,
+                  row_blocks, rows, out);
+}
+
+template <int KEYS>
+int pointwise(const fhe_ntt_plan *plan, const u64 *u, const u64 *key, u64 *out0, u64 *out1, u64 rows, hipStream_t st) {
+    const u32 L = plan->log_n, lc = std::min<u32>(L, 8u), rpb = 256u >> lc;
+    const unsigned gx = (unsigned)(plan->n >> lc);
+    const u64 passes = (rows + rpb - 1) / rpb;
+    const unsigned gy = (unsigned)std::min<u64>(passes, std::max<u64>(1, 4096 / gx));
+    {
+        fhe::KernelTimer kt_("bfv_pk_pointwise", (int)L, st);
+        hipLaunchKernelGGL(fhe::bfv_pk_pointwise_kernel<KEYS>, dim3(gx, gy), dim3(256), 0, st, u, key, out0, out1, L, rows, plan->mod);
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FHE_OK : fhe_hip_fail(e, "bfv_pk_pointwise_kernel");
+}
+
+}  // namespace
+
+extern "C" int fhe_bfv_secret_key_dev(uint64_t n, const uint8_t *seed, uint64_t key_row, void *d_s, void *hip_stream) {
+    const char *who = "fhe_bfv_secret_key_dev";
+    int rc = check_ring(n, who);
+    if (rc != FHE_OK) return rc;
+    if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
+    if (!d_s) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_s)) return fhe_fail(FHE_E_INVALID, "%s: d_s must be 8-byte aligned", who);
+    int dev;
+    if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
+    return small_fill(seed_key(seed), fhe::BFV_KEY, 1, key_row, 0, n, (u64 *)d_s, 1, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_bfv_public_key_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t row, const void *d_s, const void *d_cdt, unsigned m,
+                                      void *d_pk, void *hip_stream) {
+    const char *who = "fhe_bfv_public_key_dev";
+    if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
+    if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
+    const u64 n = plan->n, q = plan->q;
+    int rc = check_cdt_shape(d_cdt, m, q, who);
+    if (rc != FHE_OK) return rc;
+    if (row >= kRowLimit) return fhe_fail(FHE_E_INVALID, "%s: row must be below 2^63", who);
+    if (!d_s || !d_pk) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_s) || misaligned8(d_pk)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    if (overlaps_any(d_pk, 2 * n * 8, {{d_s, n * 8}, {d_cdt, (u64)m * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_pk overlaps the key or the error table", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
+    void *w = nullptr;
+    if ((rc = fhe_workspace_get(kBfvClientSlot, 3 * n * 8, st, &w)) != FHE_OK) return rc;
+    u64 *A = (u64 *)w, *S = A + n, *P = S + n;
+    const fhe::ChaChaKey key = seed_key(seed);
+    if ((rc = uniform_fill(key, row, q, n, A, 1, st)) != FHE_OK) return rc;
+    if ((rc = launch("bfv_key_bits", 0, st, fhe::bfv_key_bits_kernel, fhe_ew_grid(n), 256, d_s, S, n)) != FHE_OK) return rc;
+    if ((rc = fhe_rq_mul_dev(plan, A, 0, S, 0, P, nullptr, nullptr, nullptr, 1, nullptr, st)) != FHE_OK) return rc;
+    return launch("bfv_pk_epilogue", (int)plan->log_n, st, fhe::bfv_pk_epilogue_kernel, fhe_ew_grid((n + 7) / 8), 256, key, row, A, P, d_cdt, m, d_pk, n,
+                  plan->mod);
+}
+
+extern "C" int fhe_bfv_relin_key_dev(uint64_t q, uint64_t n, uint64_t pq, const uint8_t *seed, uint64_t row, const void *d_s, const void *d_cdt,
+                                     unsigned m, void *d_rlk, void *hip_stream) {
+    const char *who = "fhe_bfv_relin_key_dev";
+    int rc = check_ring(n, who);
+    if (rc != FHE_OK) return rc;
+    if (q < 2 || pq < q || pq % q != 0)
+        return fhe_fail(FHE_E_INVALID, "%s: need q >= 2 and pq a multiple of q (q=%llu, pq=%llu)", who, (unsigned long long)q, (unsigned long long)pq);
+    if (!mul_fits(n, pq, kRowLimit - 1))
+        return fhe_fail(FHE_E_INVALID, "%s: need n pq < 2^63 (n=%llu, pq=%llu)", who, (unsigned long long)n, (unsigned long long)pq);
+    if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
+    if ((rc = check_cdt_shape(d_cdt, m, pq, who)) != FHE_OK) return rc;
+    if (row >= kRowLimit) return fhe_fail(FHE_E_INVALID, "%s: row must be below 2^63", who);
+    if (!d_s || !d_rlk) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_s) || misaligned8(d_rlk)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    if (overlaps_any(d_rlk, 2 * n * 8, {{d_s, n * 8}, {d_cdt, (u64)m * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_rlk overlaps the key or the error table", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
+    void *w = nullptr;
+    if ((rc = fhe_workspace_get(kBfvClientSlot, 4 * n * 8, st, &w)) != FHE_OK) return rc;
+    u64 *A = (u64 *)w, *S = A + n, *AS = S + n, *SS = AS + n;
+    const fhe::ChaChaKey key = seed_key(seed);
+    if ((rc = uniform_fill(key, row, pq, n, A, 1, st)) != FHE_OK) return rc;
+    if ((rc = launch("bfv_key_bits", 0, st, fhe::bfv_key_bits_kernel, fhe_ew_grid(n), 256, d_s, S, n)) != FHE_OK) return rc;
+    if ((rc = fhe_tn_mul_dev(n, A, S, AS, 1, st)) != FHE_OK) return rc;
+    if ((rc = fhe_tn_mul_dev(n, S, S, SS, 1, st)) != FHE_OK) return rc;
+    return launch("bfv_rlk_epilogue", (int)log2_of(n), st, fhe::bfv_rlk_epilogue_kernel, fhe_ew_grid((n + 7) / 8), 256, key, row, A, AS, SS, d_cdt, m, d_rlk, n,
+                  q, pq);
+}
+
+extern "C" int fhe_bfv_encrypt_dev(const fhe_ntt_plan *plan, uint64_t t, const uint8_t *seed, uint64_t first_row, const void *d_pk_evals,
+                                   const void *d_msg, size_t msg_stride, const void *d_cdt, unsigned m, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_bfv_encrypt_dev";
+    if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
+    if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
+    const u64 n = plan->n, q = plan->q;
+    if (t < 2 || t >= q) return fhe_fail(FHE_E_INVALID, "%s: need 2 <= t < q (t=%llu, q=%llu)", who, (unsigned long long)t, (unsigned long long)q);
+    int rc = check_cdt_shape(d_cdt, m, q, who);
+    if (rc != FHE_OK) return rc;
+    if (d_msg && msg_stride != 0 && msg_stride < n) return fhe_fail(FHE_E_INVALID, "%s: msg_stride must be 0 (one message) or at least n", who);
+    if (batch == 0) return FHE_OK;
+    if (first_row > kRowLimit || (u64)batch > kRowLimit - first_row) return fhe_fail(FHE_E_INVALID, "%s: first_row + batch passes 2^63", who);
+    if (!mul_fits((u64)batch, 2 * n, kWordLimit) || !mul_fits((u64)batch - 1, (u64)msg_stride, kWordLimit - n))
+        return fhe_fail(FHE_E_INVALID, "%s: batch or msg_stride too large", who);
+    if (!d_pk_evals || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_pk_evals) || misaligned8(d_msg) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 out_bytes = (u64)batch * 2 * n * 8, msg_bytes = d_msg ? (((u64)batch - 1) * msg_stride + n) * 8 : 0;
+    if (overlaps_any(d_out, out_bytes, {{d_pk_evals, 2 * n * 8}, {d_msg, msg_bytes}, {d_cdt, (u64)m * 8}}))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key, the messages or the error table", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
+    const u32 L = plan->log_n;
+    const u64 chunk = std::min<u64>(batch, std::max<u64>(1, kChunkWords >> L));
+    // Two routes to the two products, same words (DESIGN.md §20 has the rule and the measurements).  Where fhe_rq_mul_dev is
+    // one fused kernel (moduli with a 32-bit form, smallq.hip: q < 2^30, 2^8 <= n <= 2^18; any modulus at the single-pass
+    // sizes 2^8 <= n <= 2^13), two of them against the key rows staged over a chunk (once per call) measured faster than
+    // forward + pointwise + two inverses.  Everything else: the pointwise route.  FHE_BFV_ENCRYPT_STAGED=0 / =1 (read per
+    // call: tools/bfv_client_rate.py times both routes in one process) forces the pointwise / the staged route.
+    fhe::DevicePlan dp;
+    if ((rc = fhe_device_plan(plan, &dp)) != FHE_OK) return rc;
+    fhe::SmallQArgs sq{};
+    const char *route = getenv("FHE_BFV_ENCRYPT_STAGED");
+    const bool fused_product = fhe_smallq_args(plan, dp, &sq) || (L >= 8 && L <= 13);
+    const bool staged = route && route[0] == '1' ? true : fused_product && !(route && route[0] == '0');
+    void *w = nullptr;
+    if ((rc = fhe_workspace_get(kBfvClientSlot, (staged ? 5 : 2) * chunk * n * 8, st, &w)) != FHE_OK) return rc;
+    u64 *U = (u64 *)w, *H = U + chunk * n, *P = nullptr, *K0 = nullptr, *K1 = nullptr;
+    if (staged) {
+        P = H + chunk * n; K0 = P + chunk * n; K1 = K0 + chunk * n;
+        if ((rc = launch("bfv_broadcast", (int)L, st, fhe::bfv_broadcast_kernel, fhe_ew_grid(chunk << L), 256, d_pk_evals, K0, L, chunk)) != FHE_OK) return rc;
+        if ((rc = launch("bfv_broadcast", (int)L, st, fhe::bfv_broadcast_kernel, fhe_ew_grid(chunk << L), 256, (const u64 *)d_pk_evals + n, K1, L, chunk)) != FHE_OK)
+            return rc;
+    }
+    const fhe::ChaChaKey key = seed_key(seed);
+    const u32 LB = L > 3 ? L - 3 : 0;
+    for (u64 r0 = 0; r0 < batch; r0 += chunk) {
+        const u64 cr = std::min<u64>(chunk, batch - r0);
+        const u64 *R0 = U, *R1 = H;                               // the two products of the chunk
+        if ((rc = small_fill(key, fhe::BFV_EPH, 0, first_row + r0, q, n, U, cr, st)) != FHE_OK) return rc;
+        if (staged) {
+            if ((rc = fhe_rq_mul_dev(plan, U, 0, K0, 1, P, nullptr, nullptr, nullptr, cr, nullptr, st)) != FHE_OK) return rc;
+            if ((rc = fhe_rq_mul_dev(plan, U, 0, K1, 1, H, nullptr, nullptr, nullptr, cr, nullptr, st)) != FHE_OK) return rc;
+            R0 = P;
+        } else {
+            if ((rc = fhe_ntt_forward_dev(plan, U, U, cr, st)) != FHE_OK) return rc;
+            if ((rc = pointwise<2>(plan, U, (const u64 *)d_pk_evals, U, H, cr, st)) != FHE_OK) return rc;
+            if ((rc = fhe_ntt_inverse_dev(plan, U, U, cr, st)) != FHE_OK) return rc;
+            if ((rc = fhe_ntt_inverse_dev(plan, H, H, cr, st)) != FHE_OK) return rc;
+        }
+        const u64 *msg = d_msg ? (const u64 *)d_msg + r0 * msg_stride : nullptr;
+        u64 *o0 = (u64 *)d_out + r0 * n, *o1 = (u64 *)d_out + ((u64)batch + r0) * n;
+        if ((rc = launch("bfv_encrypt_epilogue", (int)L, st, fhe::bfv_encrypt_epilogue_kernel, fhe_ew_grid(cr << LB), 256, key, first_row + r0, R0, R1, msg,
+                         msg_stride, d_cdt, m, q / t, o0, o1, L, cr, plan->mod)) != FHE_OK)
+            return rc;
+    }
+    return FHE_OK;
+}
+
+extern "C" int fhe_bfv_decrypt_dev(const fhe_ntt_plan *plan, uint64_t t, const void *d_s_evals, const void *d_ct, void *d_out, size_t batch,
+                                   void *hip_stream) {
+    const char *who = "fhe_bfv_decrypt_dev";
+    if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
+    const u64 n = plan->n, q = plan->q;
+    if (t < 2 || t >= q) return fhe_fail(FHE_E_INVALID, "%s: need 2 <= t < q (t=%llu, q=%llu)", who, (unsigned long long)t, (unsigned long long)q);
+    if (batch == 0) return FHE_OK;
+    if (!mul_fits((u64)batch, 2 * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_s_evals || !d_ct || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_s_evals) || misaligned8(d_ct) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 out_bytes = (u64)batch * n * 8;
+    if (overlaps_any(d_out, out_bytes, {{d_s_evals, n * 8}, {d_ct, 2 * out_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key or the ciphertexts", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const u32 L = plan->log_n;
+    const u64 chunk = std::min<u64>(batch, std::max<u64>(1, kChunkWords >> L));
+    void *w = nullptr;
+    int rc = fhe_workspace_get(kBfvClientSlot, chunk * n * 8, st, &w);
+    if (rc != FHE_OK) return rc;
+    u64 *W = (u64 *)w;
+    for (u64 r0 = 0; r0 < batch; r0 += chunk) {
+        const u64 cr = std::min<u64>(chunk, batch - r0);
+        const u64 *c0 = (const u64 *)d_ct + r0 * n, *c1 = (const u64 *)d_ct + ((u64)batch + r0) * n;
+        const u64 *src = c1;
+        if (fhe_misaligned(c1)) {                                 // the transforms take 16-byte aligned rows
+            HIP_TRY(hipMemcpyAsync(W, c1, cr * n * 8, hipMemcpyDeviceToDevice, st));
+            src = W;
+        }
+        if ((rc = fhe_ntt_forward_dev(plan, src, W, cr, st)) != FHE_OK) return rc;
+        if ((rc = pointwise<1>(plan, W, (const u64 *)d_s_evals, W, nullptr, cr, st)) != FHE_OK) return rc;
+        if ((rc = fhe_ntt_inverse_dev(plan, W, W, cr, st)) != FHE_OK) return rc;
+        if ((rc = launch("bfv_decrypt_epilogue", (int)L, st, fhe::bfv_decrypt_epilogue_kernel, fhe_ew_grid(cr * n), 256, c0, W, (u64 *)d_out + r0 * n, cr * n,
+                         t, plan->mod)) != FHE_OK)
+            return rc;
+    }
+    return FHE_OK;
+}

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "chacha_stream.hpp"   // ChaChaKey, chacha_block, cdt_error, CDT_MAX: shared with bfv_client.hip
 
 using fhe::u32;
 using fhe::u64;
@@ -34,49 +35,6 @@ using fhe::u64;
 namespace fhe {
 
 constexpr u32 STREAM_MASK = 1, STREAM_ERR = 2, STREAM_KEY = 3;
-constexpr u32 CDT_MAX = 1024;
-
-struct ChaChaKey { u32 w[8]; };   // by value: the seed sits in SGPRs
-
-__device__ __forceinline__ u32 rotl32(u32 x, u32 r) { return (x << r) | (x >> (32u - r)); }
-__device__ __forceinline__ void chacha_qr(u32 &a, u32 &b, u32 &c, u32 &d) {
-    a += b; d ^= a; d = rotl32(d, 16);
-    c += d; b ^= c; b = rotl32(b, 12);
-    a += b; d ^= a; d = rotl32(d, 8);
-    c += d; b ^= c; b = rotl32(b, 7);
-}
-// block `counter` of row `row` under `purpose` -> the 8 stream words of the block
-__device__ __forceinline__ void chacha_block(const ChaChaKey &key, u32 counter, u32 purpose, u64 row, u64 (&out)[8]) {
-    const u32 in[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key.w[0], key.w[1], key.w[2], key.w[3],
-                        key.w[4], key.w[5], key.w[6], key.w[7], counter, purpose, (u32)row, (u32)(row >> 32)};
-    u32 x0 = in[0], x1 = in[1], x2 = in[2], x3 = in[3], x4 = in[4], x5 = in[5], x6 = in[6], x7 = in[7], x8 = in[8], x9 = in[9], x10 = in[10],
-        x11 = in[11], x12 = in[12], x13 = in[13], x14 = in[14], x15 = in[15];
-    for (int r = 0; r < 10; r++) {
-        chacha_qr(x0, x4, x8, x12); chacha_qr(x1, x5, x9, x13); chacha_qr(x2, x6, x10, x14); chacha_qr(x3, x7, x11, x15);
-        chacha_qr(x0, x5, x10, x15); chacha_qr(x1, x6, x11, x12); chacha_qr(x2, x7, x8, x13); chacha_qr(x3, x4, x9, x14);
-    }
-    out[0] = (u64)(x0 + in[0]) | ((u64)(x1 + in[1]) << 32);
-    out[1] = (u64)(x2 + in[2]) | ((u64)(x3 + in[3]) << 32);
-    out[2] = (u64)(x4 + in[4]) | ((u64)(x5 + in[5]) << 32);
-    out[3] = (u64)(x6 + in[6]) | ((u64)(x7 + in[7]) << 32);
-    out[4] = (u64)(x8 + in[8]) | ((u64)(x9 + in[9]) << 32);
-    out[5] = (u64)(x10 + in[10]) | ((u64)(x11 + in[11]) << 32);
-    out[6] = (u64)(x12 + in[12]) | ((u64)(x13 + in[13]) << 32);
-    out[7] = (u64)(x14 + in[14]) | ((u64)(x15 + in[15]) << 32);
-}
-
-// the error word of stream word u: magnitude #{i < m : cdt[i] <= u >> 1} (the table is strictly increasing: a binary search),
-// negative when u & 1, shifted left by log_scale
-__device__ __forceinline__ u64 cdt_error(const u64 *cdt, u32 m, u64 u, u32 log_scale) {
-    const u64 r = u >> 1;
-    u32 lo = 0, hi = m;
-    while (lo < hi) {
-        const u32 mid = (lo + hi) >> 1;
-        if (cdt[mid] <= r) lo = mid + 1; else hi = mid;
-    }
-    const u64 mag = lo;
-    return ((u & 1u) ? 0ull - mag : mag) << log_scale;
-}
 
 // out [rows][row_words]: stream word i of row first_row + r under `purpose`; bits: every word AND 1.  A thread takes a block.
 __global__ __launch_bounds__(256) void tfhe_stream_words_kernel(ChaChaKey key, u32 purpose, u64 first_row, u64 row_words, u64 row_blocks, u64 rows,

@@ -132,18 +132,7 @@ class TGGSW:
 
 
 # ---- TFHE bootstrapping (tfhe/src/tlwe.rs) ----------------------------------------------------------------------
-def _torch():
-    import torch
-
-    return torch
-
-
-def _to_dev(x):
-    return _torch().from_numpy(np.ascontiguousarray(x, dtype=np.uint64).view(np.int64)).cuda()
-
-
-def _from_dev(t):
-    return t.cpu().numpy().view(np.uint64)
+from .device import from_dev as _from_dev, to_dev as _to_dev, torch as _torch  # noqa: E402  (shared with bfv.py)
 
 
 class TLWE:

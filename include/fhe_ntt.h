@@ -539,6 +539,47 @@ int fhe_tglwe_encrypt_dev(uint64_t n, unsigned k, const uint8_t *seed, uint64_t 
 int fhe_tglwe_phase_dev(uint64_t n, unsigned k, const void *d_key, const void *d_in, void *d_out, size_t rows,
                         void *hip_stream);
 
+/* ---- BFV key generation, encryption and decryption: the client side (bfv/src/lib.rs:118-225) ----
+ * Exact and independent of launch geometry.  The stream is the one above, unchanged (`seed`: a HOST pointer to 32 bytes, the
+ * whole secret), under four purposes of its own, so no BFV row shares a nonce with a TFHE row (fhe_tfhe_stream_words_dev
+ * does not serve them): FHE_STREAM_BFV_MASK, _ERR, _KEY, _EPH.  A row is one polynomial.
+ *   uniform  coefficient i modulo Q (Q = q or pq < 2^63) from MASK words w0 = 2i, w1 = 2i + 1 of the row:
+ *            floor((w1 2^64 + w0) Q / 2^128); no rejection, bias below 2^-65
+ *   secret   s_i = KEY word i AND 1; where a key is read, only bit 0 of a word counts
+ *   u        EPH word w of coefficient i: (w AND 1) - ((w >> 1) AND 1), as the residue 0, 1 or q - 1
+ *   errors   the table-inversion sampler above at log_scale 0 (d_cdt [m], m <= 1024), as the residue e or Q - |e|: a discrete
+ *            Gaussian, not the reference's rounded Normal(0, 3.2).  Encryption row r takes e1 from ERR row 2r and e2 from ERR
+ *            row 2r + 1, key row r takes e from ERR row 2r, so row indices stay below 2^63.  The table is checked on a host
+ *            copy (synchronises hip_stream), and its largest magnitude m must be below the modulus.
+ *   fhe_bfv_secret_key_dev   d_s [n] = the 0/1 words of KEY row key_row
+ *   fhe_bfv_public_key_dev   d_pk = [pk0 | pk1] = (-a s + e, a) mod q, n words each; a = the uniform MASK row `row`
+ *   fhe_bfv_relin_key_dev    d_rlk = [rlk0 | rlk1] = (-(a s + e) + p s^2, a) mod pq, p = pq / q, in the layout of
+ *            fhe_bfv_relinearize_dev / fhe_bfv_rlk_prepare_dev.  EXACT: the reference routes a s and s^2 through f64
+ *            (tmp_naive_mul -> from_vec_i64), exact while a coefficient of the integer product stays below 2^53; these are the
+ *            reference's words wherever that route is exact.  Needs pq a multiple of q and n pq < 2^63.
+ *   fhe_bfv_encrypt_dev      d_out = [c0 | c1], each batch x n: row r is encryption row first_row + r, c0 = pk0 u + e1 +
+ *            floor(q / t) (m_r mod q), c1 = pk1 u + e2.  d_pk_evals [2][n] = fhe_ntt_forward_dev of d_pk, made once per key.
+ *            m_r = d_msg + r msg_stride (msg_stride = 0: one message for every row, otherwise >= n; d_msg NULL: m = 0).
+ *   fhe_bfv_decrypt_dev      d_out [batch][n] = (round(t (c0 + c1 s mod q) / q) mod q) mod t with the f64 steps of
+ *            fhe_rq_mul_div_round_dev; d_s_evals [n] = fhe_ntt_forward_dev of the secret; d_ct = [c0 | c1]
+ * Device buffers need 8-byte alignment.  t < 2 or t >= q, m > 1024 or a table §17 rejects or whose magnitudes reach the
+ * modulus, first_row + rows past 2^63, n pq >= 2^63 or pq not a multiple of q, an output that overlaps an input and extents
+ * past 2^60 words are FHE_E_INVALID and write nothing; batch = 0 is a no-op.  A plan fixes (q, n). */
+#define FHE_STREAM_BFV_MASK 0x11u
+#define FHE_STREAM_BFV_ERR 0x12u
+#define FHE_STREAM_BFV_KEY 0x13u
+#define FHE_STREAM_BFV_EPH 0x14u
+int fhe_bfv_secret_key_dev(uint64_t n, const uint8_t *seed, uint64_t key_row, void *d_s, void *hip_stream);
+int fhe_bfv_public_key_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t row, const void *d_s, const void *d_cdt,
+                           unsigned m, void *d_pk, void *hip_stream);
+int fhe_bfv_relin_key_dev(uint64_t q, uint64_t n, uint64_t pq, const uint8_t *seed, uint64_t row, const void *d_s,
+                          const void *d_cdt, unsigned m, void *d_rlk, void *hip_stream);
+int fhe_bfv_encrypt_dev(const fhe_ntt_plan *plan, uint64_t t, const uint8_t *seed, uint64_t first_row,
+                        const void *d_pk_evals, const void *d_msg, size_t msg_stride, const void *d_cdt, unsigned m,
+                        void *d_out, size_t batch, void *hip_stream);
+int fhe_bfv_decrypt_dev(const fhe_ntt_plan *plan, uint64_t t, const void *d_s_evals, const void *d_ct, void *d_out,
+                        size_t batch, void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
