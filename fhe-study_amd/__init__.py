@@ -5,7 +5,8 @@ Layout:
   binding.py   ctypes plumbing over the C ABI
   arith.py     host mirror of the reference's RingParam / Rq / NTT surface
   bfv.py       RLWE::tensor / RLWE::mul (bfv/src/lib.rs) over the exact-product rows, and BFV's client side
-  device.py    device buffers for bfv.py and tfhe.py (torch as the allocator)
+  ckks.py      the CKKS encoder (a double-precision FFT), keys, encryption and decryption (ckks/src)
+  device.py    device buffers for bfv.py, ckks.py and tfhe.py (torch as the allocator)
   tfhe.py      Tn x Tn and TGGSW x TGLWE (ring_torus.rs, tfhe/src/tggsw.rs)
   host/        the same mirror in C++ (arith.hpp), for compiled callers
 
@@ -19,7 +20,7 @@ from .arith import NTT, RingParam, Rq, mul, mul_mut  # noqa: F401
 
 def __getattr__(name):
     # `sharding` needs torch.distributed; keep it off the import path of torch-free users
-    if name in ("sharding", "bfv", "tfhe"):
+    if name in ("sharding", "bfv", "ckks", "tfhe"):
         import importlib
 
         return importlib.import_module(__name__ + "." + name)

@@ -14,8 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FHE_NTT_LIB") or os.path.join(_HERE, "libfhe_ntt.so")  # env: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip", "tfhe_client.hip", "bfv_client.hip"]
-HEADERS = ["ntt_kernels.hpp", "ntt_rounds.hpp", "ntt_persist.hpp", "persist_sched.hpp", "digit_mac.hpp", "digit32.hpp", "bfv32.hpp", "smallq.hpp", "ntt32_rounds.hpp", "ntt32_big.hpp", "zq_device.hpp", "capi_internal.hpp", "mac_kernel.hpp", "chacha_stream.hpp", "ntt_kernels.hip",
+SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip", "tfhe_client.hip", "bfv_client.hip", "ckks_client.hip"]
+HEADERS = ["ntt_kernels.hpp", "ntt_rounds.hpp", "ntt_persist.hpp", "persist_sched.hpp", "digit_mac.hpp", "digit32.hpp", "bfv32.hpp", "smallq.hpp", "ntt32_rounds.hpp", "ntt32_big.hpp", "zq_device.hpp", "capi_internal.hpp", "mac_kernel.hpp", "chacha_stream.hpp", "bfv_client_kernels.hpp", "ntt_kernels.hip",
            os.path.join("..", "..", "include", "fhe_ntt.h"), os.path.join("..", "..", "include", "fhe_ntt_experimental.h")]
 OBJ_DIR = os.path.join(_HERE, "build")
 # -ffp-contract=off: zring.hip restates the reference's f64 scale-and-round (one IEEE rounding
@@ -83,6 +83,9 @@ EXPORTS = [
     "fhe_tfhe_stream_words_dev", "fhe_tlwe_encrypt_dev", "fhe_tlwe_phase_dev", "fhe_tglwe_encrypt_dev", "fhe_tglwe_phase_dev",
     # BFV key generation, encryption and decryption: the client side (bfv_client.hip)
     "fhe_bfv_secret_key_dev", "fhe_bfv_public_key_dev", "fhe_bfv_relin_key_dev", "fhe_bfv_encrypt_dev", "fhe_bfv_decrypt_dev",
+    # CKKS: the FFT encoder, key generation, encryption and decryption (ckks_client.hip)
+    "fhe_ckks_twiddles", "fhe_ckks_encode_dev", "fhe_ckks_decode_dev", "fhe_ckks_secret_key_dev", "fhe_ckks_public_key_dev", "fhe_ckks_encrypt_dev",
+    "fhe_ckks_decrypt_dev",
 ]
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
@@ -92,6 +95,7 @@ FHE_LUT_NONE = 0xFFFFFFFF                    # include/fhe_ntt.h: the index of a
 FHE_STREAM_MASK, FHE_STREAM_ERR, FHE_STREAM_KEY = 1, 2, 3    # include/fhe_ntt.h: the purposes of the random stream
 FHE_STREAM_BITS = 1                          # flag of fhe_tfhe_stream_words_dev: every word AND 1
 FHE_STREAM_BFV_MASK, FHE_STREAM_BFV_ERR, FHE_STREAM_BFV_KEY, FHE_STREAM_BFV_EPH = 0x11, 0x12, 0x13, 0x14    # the BFV rows of that stream
+FHE_STREAM_CKKS_MASK, FHE_STREAM_CKKS_ERR, FHE_STREAM_CKKS_KEY, FHE_STREAM_CKKS_EPH = 0x21, 0x22, 0x23, 0x24    # the CKKS rows
 
 
 # include/fhe_ntt_experimental.h: the persistent kernels' switches (exported, NOT part of the boundary)
@@ -284,6 +288,14 @@ def load_library():
     L.fhe_bfv_relin_key_dev.argtypes = [_u64, _u64, _u64, ctypes.c_char_p, _u64, _vp, _vp, _uint, _vp, _vp]
     L.fhe_bfv_encrypt_dev.argtypes = [_vp, _u64, ctypes.c_char_p, _u64, _vp, _vp, _sz, _vp, _uint, _vp, _sz, _vp]
     L.fhe_bfv_decrypt_dev.argtypes = [_vp, _u64, _vp, _vp, _vp, _sz, _vp]
+    _f64 = ctypes.c_double
+    L.fhe_ckks_twiddles.argtypes = [_u64, _vp]
+    L.fhe_ckks_encode_dev.argtypes = [_u64, _f64, _vp, _vp, _sz, _vp, _sz, _vp]
+    L.fhe_ckks_decode_dev.argtypes = [_u64, _f64, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_secret_key_dev.argtypes = [_vp, ctypes.c_char_p, _u64, _vp, _vp]
+    L.fhe_ckks_public_key_dev.argtypes = [_vp, ctypes.c_char_p, _u64, _vp, _vp, _uint, _vp, _vp]
+    L.fhe_ckks_encrypt_dev.argtypes = [_vp, ctypes.c_char_p, _u64, _vp, _vp, _sz, _vp, _uint, _vp, _sz, _vp]
+    L.fhe_ckks_decrypt_dev.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -713,6 +725,44 @@ def bfv_encrypt_dev(plan, t, seed, first_row, d_pk_evals, d_msg, msg_stride, d_c
 def bfv_decrypt_dev(plan, t, d_s_evals, d_ct, d_out, batch, stream=None):
     """d_ct [2][batch][n] -> d_out [batch][n], words below t"""
     _check(load_library().fhe_bfv_decrypt_dev(plan.handle, t, d_s_evals, d_ct, d_out, batch, stream))
+
+
+# ---- CKKS: the encoder and the client side (DESIGN.md §21; complex values are interleaved float64 pairs) ---------------------
+def ckks_twiddles(n):
+    """[n] complex128: exp(i pi k / n), k < n, the table the encoder kernels read (host only, no device)"""
+    out = np.empty(n, dtype=np.complex128)
+    _check(load_library().fhe_ckks_twiddles(n, out.ctypes.data_as(_vp)))
+    return out
+
+
+def ckks_encode_dev(n, delta, d_tw, d_z, z_stride, d_out, batch, stream=None):
+    """d_z [batch][n/2] complex (z_stride in complex values; 0: one vector) -> d_out [batch][n] int64"""
+    _check(load_library().fhe_ckks_encode_dev(n, delta, d_tw, d_z, z_stride, d_out, batch, stream))
+
+
+def ckks_decode_dev(n, delta, d_tw, d_p, d_out, batch, stream=None):
+    """d_p [batch][n] int64 -> d_out [batch][n/2] complex"""
+    _check(load_library().fhe_ckks_decode_dev(n, delta, d_tw, d_p, d_out, batch, stream))
+
+
+def ckks_secret_key_dev(plan, seed, key_row, d_s, stream=None):
+    """d_s [n]: the ternary secret of KEY row key_row as residues 0, 1, q - 1"""
+    _check(load_library().fhe_ckks_secret_key_dev(plan.handle, _seed(seed), key_row, d_s, stream))
+
+
+def ckks_public_key_dev(plan, seed, row, d_s, d_cdt, m, d_pk, stream=None):
+    """d_pk [2][n] = (-a s + e, a) mod q"""
+    _check(load_library().fhe_ckks_public_key_dev(plan.handle, _seed(seed), row, d_s, d_cdt, m, d_pk, stream))
+
+
+def ckks_encrypt_dev(plan, seed, first_row, d_pk_evals, d_msg, msg_stride, d_cdt, m, d_out, batch, stream=None):
+    """d_out [2][batch][n]; d_msg int64 rows (None: m = 0; msg_stride 0: one message polynomial for every row)"""
+    _check(load_library().fhe_ckks_encrypt_dev(plan.handle, _seed(seed), first_row, d_pk_evals, d_msg, msg_stride, d_cdt, m, d_out, batch, stream))
+
+
+def ckks_decrypt_dev(plan, d_s_evals, d_ct, d_out, batch, stream=None):
+    """d_ct [2][batch][n] -> d_out [batch][n] int64, centred"""
+    _check(load_library().fhe_ckks_decrypt_dev(plan.handle, d_s_evals, d_ct, d_out, batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

@@ -1,0 +1,194 @@
+"""Host mirror of the reference's CKKS surface (ckks/src/encoder.rs, ckks/src/lib.rs) over the C ABI, on the device
+(DESIGN.md §21): the canonical embedding as a double-precision FFT, keys, encryption, decryption, and the additions.
+
+    reference (Rust)                          here
+    Param { ring, t }             lib.rs:20   Param(ring)                       (t only sizes the reference's test inputs)
+    Encoder::new(n, scale)   encoder.rs:30    Encoder(n, delta)                 (holds the device twiddle table)
+    Encoder::encode / decode encoder.rs:57    Encoder.encode(z) / .decode(p, scale=None)
+    CKKS::new_key(rng)            lib.rs:46   ClientKey.generate(seed, param, delta), .public_key(slot)
+    CKKS::encrypt / decrypt       lib.rs:66   ClientKey.encrypt(pk, m) / .decrypt(ct)
+    encode_and_encrypt            lib.rs:96   ClientKey.encode_and_encrypt(pk, z)
+    decrypt_and_decode            lib.rs:107  ClientKey.decrypt_and_decode(ct, scale=None)
+    CKKS::add / sub               lib.rs:113  Ciphertext.__add__ / __sub__     (sub subtracts both components)
+    -                                         mul_plain(ct, m): decode with scale = delta^2
+
+Departures, all recorded in §21: the mask a is uniform modulo q (the reference draws it from the secret's distribution),
+`sub` subtracts both components (lib.rs:117 adds the second), the errors are §17's discrete Gaussian, and the encoder
+is an O(N log N) transform whose roundings are not MKL's.
+"""
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import binding
+from .arith import RingParam, plan_of as _plan
+from .device import from_dev as _from_dev, to_dev as _to_dev, torch as _torch
+from .tfhe import cdt_table
+
+
+@dataclass(frozen=True)
+class Param:
+    """lib.rs:20-23: the ciphertext ring"""
+    ring: RingParam
+
+
+class Encoder:
+    """encoder.rs: slot i < n/2 of a polynomial is its value at exp(i pi (2i+1) / n).  Holds fhe_ckks_twiddles(n) on the device."""
+
+    def __init__(self, n, delta):
+        self.n, self.delta = int(n), float(delta)
+        self.d_tw = _torch().from_numpy(binding.ckks_twiddles(self.n).view(np.float64)).cuda()
+
+    def encode_dev(self, d_z, batch, z_stride=None):
+        """device complex128 [batch][n/2] -> device int64 [batch][n]"""
+        torch = _torch()
+        out = torch.empty((batch, self.n), dtype=torch.int64, device="cuda")
+        binding.ckks_encode_dev(self.n, self.delta, self.d_tw.data_ptr(), d_z.data_ptr(), self.n // 2 if z_stride is None else z_stride, out.data_ptr(), batch)
+        return out
+
+    def encode(self, z):
+        """complex slots (n/2,) or (batch, n/2) -> int64 coefficients of the same leading shape"""
+        z = np.ascontiguousarray(z, dtype=np.complex128)
+        rows = z.reshape(-1, self.n // 2)
+        out = self.encode_dev(_torch().from_numpy(rows.view(np.float64)).cuda(), rows.shape[0])
+        return out.cpu().numpy().reshape(z.shape[:-1] + (self.n,))
+
+    def decode_dev(self, d_p, batch, scale=None):
+        torch = _torch()
+        out = torch.empty((batch, self.n // 2, 2), dtype=torch.float64, device="cuda")
+        binding.ckks_decode_dev(self.n, self.delta if scale is None else float(scale), self.d_tw.data_ptr(), d_p.data_ptr(), out.data_ptr(), batch)
+        return out
+
+    def decode(self, p, scale=None):
+        """int64 coefficients (n,) or (batch, n) -> complex128 slots; scale: the divisor when it is not delta (delta^2 after mul_plain)"""
+        p = np.ascontiguousarray(p, dtype=np.int64)
+        rows = p.reshape(-1, self.n)
+        out = self.decode_dev(_torch().from_numpy(rows).cuda(), rows.shape[0], scale)
+        return out.cpu().numpy().view(np.complex128).reshape(p.shape[:-1] + (self.n // 2,))
+
+
+class PublicKey:
+    """(pk0, pk1) mod q as coefficients (numpy) and, resident on the device, both halves as evals [2][n]"""
+
+    def __init__(self, param, coeffs, d_evals):
+        self.param, self.coeffs, self.d_evals = param, coeffs, d_evals
+
+
+class Ciphertext:
+    """(c0, c1) mod q, u64 words of shape (n,) or (batch, n)"""
+
+    def __init__(self, ring, c0, c1):
+        self.ring, self.c0, self.c1 = ring, c0, c1
+
+    def _rows(self, rhs, fn):
+        if rhs.ring != self.ring or rhs.c0.shape != self.c0.shape:
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "operands differ in RingParam or shape")
+        a, b = _to_dev(np.stack([self.c0, self.c1])), _to_dev(np.stack([rhs.c0, rhs.c1]))
+        c = _torch().empty_like(a)
+        binding._check(fn(_plan(self.ring).handle, a.data_ptr(), b.data_ptr(), c.data_ptr(), a.numel() // self.ring.n, None))
+        out = _from_dev(c)
+        return Ciphertext(self.ring, out[0], out[1])
+
+    def __add__(self, rhs):
+        """lib.rs:113-115 with fhe_rq_add_dev"""
+        return self._rows(rhs, binding.load_library().fhe_rq_add_dev)
+
+    def __sub__(self, rhs):
+        """(c0 - c0', c1 - c1') with fhe_rq_sub_dev: both components, unlike lib.rs:117"""
+        return self._rows(rhs, binding.load_library().fhe_rq_sub_dev)
+
+
+def mul_plain(ct, m):
+    """both components times the encoded plaintext m (int64 coefficients, (n,) or the ciphertext's shape) through
+    fhe_rq_mul_dev: the one multiplication a single modulus carries; decode the result with scale = delta^2"""
+    ring = ct.ring
+    plan = _plan(ring)
+    mm = np.mod(np.broadcast_to(np.asarray(m, dtype=np.int64), ct.c0.shape), np.int64(ring.q)).astype(np.uint64)
+    a, b = _to_dev(np.stack([ct.c0, ct.c1])), _to_dev(np.stack([mm, mm]))
+    c = _torch().empty_like(a)
+    plan.rq_mul_dev(a.data_ptr(), b.data_ptr(), c.data_ptr(), a.numel() // ring.n)
+    out = _from_dev(c)
+    return Ciphertext(ring, out[0], out[1])
+
+
+class ClientKey:
+    """The CKKS secret, resident on the device with its evals, an Encoder, and what is made from them.  The
+    32-byte seed is the whole secret; rows never repeat within a seed, as for bfv.ClientKey:
+        [0, 2^56)          fresh encryptions, in the order of the encrypt calls
+        1 2^56 + slot      public_key(slot)
+    and a builder refuses a slot (0 <= slot < 2^16) it has used.  The secret is KEY row 0."""
+
+    ENCRYPT_ROWS = 1 << 56
+    PK_BASE = 1 << 56
+
+    def __init__(self, seed, param, delta, d_s, d_s_evals, sigma):
+        self.seed, self.param, self.d_s, self.d_s_evals = bytes(seed), param, d_s, d_s_evals
+        self.encoder = Encoder(param.ring.n, delta)
+        self._next_row, self._slots = 0, set()
+        tab = cdt_table(sigma)
+        self._cdt, self._m = (_to_dev(tab) if len(tab) else None), len(tab)
+
+    @classmethod
+    def generate(cls, seed, param, delta, sigma=3.2):
+        torch = _torch()
+        n, plan = param.ring.n, _plan(param.ring)
+        d_s = torch.empty(n, dtype=torch.int64, device="cuda")
+        d_e = torch.empty(n, dtype=torch.int64, device="cuda")
+        binding.ckks_secret_key_dev(plan, seed, 0, d_s.data_ptr())
+        plan.forward_dev(d_s.data_ptr(), d_e.data_ptr(), 1)
+        torch.cuda.synchronize()
+        return cls(seed, param, delta, d_s, d_e, sigma)
+
+    def _cdt_ptr(self):
+        return self._cdt.data_ptr() if self._m else None
+
+    def public_key(self, slot=0):
+        """CKKS::new_key's pk = (-a s + e, a), lib.rs:61, with a uniform modulo q"""
+        torch = _torch()
+        ring = self.param.ring
+        if not 0 <= int(slot) < 1 << 16:
+            raise ValueError("public_key: slot must be in [0, 2^16)")
+        if int(slot) in self._slots:
+            raise ValueError(f"public_key: slot {slot} of this seed is already used; a second key needs a slot of its own")
+        self._slots.add(int(slot))
+        pk = torch.empty((2, ring.n), dtype=torch.int64, device="cuda")
+        ev = torch.empty_like(pk)
+        binding.ckks_public_key_dev(_plan(ring), self.seed, self.PK_BASE + int(slot), self.d_s.data_ptr(), self._cdt_ptr(), self._m, pk.data_ptr())
+        _plan(ring).forward_dev(pk.data_ptr(), ev.data_ptr(), 2)
+        return PublicKey(self.param, _from_dev(pk), ev)
+
+    def encrypt(self, pk, m):
+        """CKKS::encrypt, lib.rs:66-85: m int64 coefficients (n,) or (batch, n) -> Ciphertext on fresh rows"""
+        torch = _torch()
+        ring = self.param.ring
+        m = np.ascontiguousarray(m, dtype=np.int64)
+        msg = m.reshape(-1, ring.n)
+        batch = msg.shape[0]
+        if self._next_row + batch > self.ENCRYPT_ROWS:
+            raise ValueError("encrypt: this seed's 2^56 encryption rows are used up")
+        d_m = torch.from_numpy(msg).cuda()
+        out = torch.empty((2, batch, ring.n), dtype=torch.int64, device="cuda")
+        binding.ckks_encrypt_dev(_plan(ring), self.seed, self._next_row, pk.d_evals.data_ptr(), d_m.data_ptr(), ring.n, self._cdt_ptr(), self._m,
+                                 out.data_ptr(), batch)
+        self._next_row += batch
+        w = _from_dev(out)
+        return Ciphertext(ring, w[0].reshape(m.shape), w[1].reshape(m.shape))
+
+    def decrypt(self, ct):
+        """CKKS::decrypt, lib.rs:87-94 -> int64 coefficients, centred"""
+        torch = _torch()
+        ring = self.param.ring
+        if ct.ring != ring:
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the ciphertext is not in this key's ring")
+        shape = ct.c0.shape
+        d_ct = _to_dev(np.stack([ct.c0.reshape(-1, ring.n), ct.c1.reshape(-1, ring.n)]))
+        batch = d_ct.shape[1]
+        out = torch.empty((batch, ring.n), dtype=torch.int64, device="cuda")
+        binding.ckks_decrypt_dev(_plan(ring), self.d_s_evals.data_ptr(), d_ct.data_ptr(), out.data_ptr(), batch)
+        return out.cpu().numpy().reshape(shape)
+
+    def encode_and_encrypt(self, pk, z):
+        return self.encrypt(pk, self.encoder.encode(z))
+
+    def decrypt_and_decode(self, ct, scale=None):
+        return self.encoder.decode(self.decrypt(ct), scale)

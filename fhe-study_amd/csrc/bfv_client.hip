@@ -32,13 +32,8 @@
 // 2^21 coefficients at a time in workspace slot 10 (32 MiB, 80 MiB staged); every word is a function of its (row, index)
 // alone, so the result depends neither on the chunking nor on the route.  Decryption stages c1 the same way (pointwise).
 // The kernels make u64 accesses only and the transforms run on library workspace, so callers' buffers need 8-byte alignment.
-#include <algorithm>
-#include <cstdlib>
-#include <vector>
-
-#include "capi_internal.hpp"
-#include "chacha_stream.hpp"
-#include "smallq.hpp"
+// The sampling kernels, the pointwise product and the key broadcast live in bfv_client_kernels.hpp, which ckks_client.hip shares.
+#include "bfv_client_kernels.hpp"
 
 using fhe::Mod;
 using fhe::u32;
@@ -48,94 +43,12 @@ namespace fhe {
 
 constexpr u32 BFV_MASK = 0x11, BFV_ERR = 0x12, BFV_KEY = 0x13, BFV_EPH = 0x14;
 
-__device__ __forceinline__ u64 bfv_uniform(u64 w0, u64 w1, u64 Q) {
-    return (u64)(((unsigned __int128)w1 * Q + __umul64hi(w0, Q)) >> 64);
-}
-// a b mod q for canonical or arbitrary words and any q below 2^63 (uniform branch)
-__device__ __forceinline__ u64 bfv_mulmod(u64 a, u64 b, const Mod &m) { return (m.q >> 62) ? mul_mod_var63(a, b, m) : mul_mod_var(a, b, m); }
-// the signed error word e (|e| < Q) as a residue
-__device__ __forceinline__ u64 bfv_err_residue(u64 e, u64 Q) { return (long long)e < 0 ? Q + e : e; }
 // x mod Q for a signed word and any Q below 2^63
 __device__ __forceinline__ u64 bfv_smod(u64 x, u64 Q) {
     const long long r = (long long)x % (long long)Q;
     return r < 0 ? (u64)(r + (long long)Q) : (u64)r;
 }
 
-// A thread holds `1 << lper` (at most PER) consecutive words of the flat output, thread i the words from i << lper on; the
-// block's words leave through LDS so that every store instruction writes 256 consecutive words.  All 256 threads call it.
-template <u32 PER>
-__device__ __forceinline__ void bfv_store_block(u64 *stage, const u64 (&v)[PER], u32 lper, u64 block_first_word, u64 total_words, u64 *__restrict__ out) {
-    const u32 tid = threadIdx.x, per = 1u << lper;
-#pragma unroll
-    for (u32 j = 0; j < PER; j++)
-        if (j < per) stage[tid * (PER + 1) + j] = v[j];
-    __syncthreads();
-#pragma unroll
-    for (u32 k = 0; k < PER; k++) {
-        const u32 t = k * 256 + tid;
-        if (t < (256u << lper) && block_first_word + t < total_words) out[block_first_word + t] = stage[(t >> lper) * (PER + 1) + (t & (per - 1))];
-    }
-    __syncthreads();
-}
-
-// out [rows][n]: uniform coefficients modulo Q of MASK rows first_row ..; a thread takes a ChaCha block = 4 coefficients
-// (n = 2: the two of its row).  lper = log2 min(n, 4), row_blocks = max(n / 4, 1).
-__global__ __launch_bounds__(256) void bfv_uniform_kernel(ChaChaKey key, u64 first_row, u64 Q, u32 lper, u64 row_blocks, u64 rows, u64 *__restrict__ out) {
-    __shared__ u64 stage[256 * 5];
-    const u64 total = rows * row_blocks;
-    for (u64 base = (u64)blockIdx.x * 256; base < total; base += (u64)gridDim.x * 256) {
-        const u64 i = base + threadIdx.x;
-        u64 v[4] = {0, 0, 0, 0};
-        if (i < total) {
-            const u64 r = i / row_blocks, c = i - r * row_blocks;
-            u64 w[8];
-            chacha_block(key, (u32)c, BFV_MASK, first_row + r, w);
-#pragma unroll
-            for (u32 j = 0; j < 4; j++) v[j] = bfv_uniform(w[2 * j], w[2 * j + 1], Q);
-        }
-        bfv_store_block<4>(stage, v, lper, base << lper, total << lper, out);
-    }
-}
-
-// out [rows][n] from `purpose` rows first_row ..: key != 0: the secret-key bits w AND 1 (BFV_KEY); key = 0: the ephemeral u
-// as the residue 0, 1 or Q - 1 (BFV_EPH), ready for the forward transform.  A thread takes a block = 8 coefficients.
-__global__ __launch_bounds__(256) void bfv_ephemeral_kernel(ChaChaKey key, u32 purpose, u32 is_key, u64 first_row, u64 Q, u32 lper, u64 row_blocks, u64 rows,
-                                                            u64 *__restrict__ out) {
-    __shared__ u64 stage[256 * 9];
-    const u64 total = rows * row_blocks;
-    for (u64 base = (u64)blockIdx.x * 256; base < total; base += (u64)gridDim.x * 256) {
-        const u64 i = base + threadIdx.x;
-        u64 v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (i < total) {
-            const u64 r = i / row_blocks, c = i - r * row_blocks;
-            u64 w[8];
-            chacha_block(key, (u32)c, purpose, first_row + r, w);
-#pragma unroll
-            for (u32 j = 0; j < 8; j++) {
-                const u32 b0 = (u32)w[j] & 1u, b1 = ((u32)w[j] >> 1) & 1u;
-                v[j] = is_key ? (u64)b0 : (b0 == b1 ? 0ull : (b0 ? 1ull : Q - 1));
-            }
-        }
-        bfv_store_block<8>(stage, v, lper, base << lper, total << lper, out);
-    }
-}
-
-// KEYS = 2: out0[r] = u^[r] (.) key[0], out1[r] = u^[r] (.) key[1] (encryption; out0 may be u^ itself); KEYS = 1: out0[r] =
-// u^[r] (.) key[0] (decryption).  key [KEYS][n] is shared by the batch: a thread loads its column's key words once and walks
-// down the rows, rpb = 256 / min(n, 256) rows per pass.  Any q below 2^63: the 128-bit product with zq_device.hpp's reduction.
-template <int KEYS>
-__global__ __launch_bounds__(256) void bfv_pk_pointwise_kernel(const u64 *u, const u64 *__restrict__ key, u64 *out0, u64 *__restrict__ out1, u32 L, u64 rows,
-                                                               Mod m) {
-    const u64 n = 1ull << L;
-    const u32 lc = L < 8u ? L : 8u, rpb = 256u >> lc;                        // columns of a block = 1 << lc
-    const u64 col = ((u64)blockIdx.x << lc) + (threadIdx.x & ((1u << lc) - 1u));
-    const u64 k0 = key[col], k1 = KEYS == 2 ? key[n + col] : 0ull;
-    for (u64 r = (u64)blockIdx.y * rpb + (threadIdx.x >> lc); r < rows; r += (u64)gridDim.y * rpb) {
-        const u64 x = u[(r << L) + col];
-        out0[(r << L) + col] = bfv_mulmod(x, k0, m);
-        if (KEYS == 2) out1[(r << L) + col] = bfv_mulmod(x, k1, m);
-    }
-}
 
 // out0[r] = P0[r] + e1 + Delta (msg_r mod q), out1[r] = P1[r] + e2 (mod q, canonical) for encryption row first_row + r: e1
 // from ERR row 2 (first_row + r), e2 from the row after it; a thread takes 8 coefficients (one ChaCha block of each error
@@ -182,12 +95,6 @@ __global__ __launch_bounds__(256) void bfv_decrypt_epilogue_kernel(const u64 *__
         const u64 v = zq_from_f64(m.q, round((nf * (double)cs) / df));
         out[i] = v >= t ? v % t : v;
     }
-}
-
-// dst [rows][n] = src [n]: the key rows of the staged route (below), once per call
-__global__ __launch_bounds__(256) void bfv_broadcast_kernel(const u64 *__restrict__ src, u64 *__restrict__ dst, u32 L, u64 rows) {
-    const u64 total = rows << L, N = 1ull << L;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += (u64)gridDim.x * 256) dst[i] = src[i & (N - 1)];
 }
 
 // dst [n] = src[i] AND 1: a secret key as canonical 0/1 words
@@ -250,68 +157,6 @@ __global__ __launch_bounds__(256) void bfv_rlk_epilogue_kernel(ChaChaKey key, u6
 namespace {
 
 constexpr int kBfvClientSlot = 10;              // fhe_workspace_get slot of the staging rows (slots 0-9 are taken)
-constexpr u64 kChunkWords = 1ull << 21;         // ciphertexts are processed 2^21 coefficients at a time: 32 MiB of staging
-constexpr u64 kRowLimit = 1ull << 63;           // error rows are 2 r and 2 r + 1
-
-bool misaligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
-
-fhe::ChaChaKey seed_key(const uint8_t *seed) {
-    fhe::ChaChaKey k;
-    for (int i = 0; i < 8; i++)
-        k.w[i] = (u32)seed[4 * i] | ((u32)seed[4 * i + 1] << 8) | ((u32)seed[4 * i + 2] << 16) | ((u32)seed[4 * i + 3] << 24);
-    return k;
-}
-
-// the table's shape without a device: m <= 1024 entries, every magnitude (at most m) below the modulus
-int check_cdt_shape(const void *d_cdt, unsigned m, u64 Q, const char *who) {
-    if (m > fhe::CDT_MAX) return fhe_fail(FHE_E_INVALID, "%s: m=%u thresholds, at most %u", who, m, fhe::CDT_MAX);
-    if (m >= Q) return fhe_fail(FHE_E_INVALID, "%s: the largest error magnitude m=%u must be below the modulus %llu", who, m, (unsigned long long)Q);
-    if (m && !d_cdt) return fhe_fail(FHE_E_NULL, "%s: NULL error table with m=%u", who, m);
-    if (m && misaligned8(d_cdt)) return fhe_fail(FHE_E_INVALID, "%s: d_cdt must be 8-byte aligned", who);
-    return FHE_OK;
-}
-// its words, as §17 checks them: strictly increasing thresholds below 2^63, on a host copy (synchronises `st`)
-int check_cdt_words(const void *d_cdt, unsigned m, hipStream_t st, const char *who) {
-    if (m == 0) return FHE_OK;
-    std::vector<u64> t(m);
-    HIP_TRY(hipMemcpyAsync(t.data(), d_cdt, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (unsigned i = 0; i < m; i++)
-        if (t[i] >> 63 || (i && t[i] <= t[i - 1]))
-            return fhe_fail(FHE_E_INVALID, "%s: the error table must be strictly increasing and below 2^63 (entry %u)", who, i);
-    return FHE_OK;
-}
-
-u32 log2_of(u64 n) { return (u32)__builtin_ctzll(n); }
-
-// out [rows][n]: the uniform rows modulo Q
-int uniform_fill(const fhe::ChaChaKey &key, u64 first_row, u64 Q, u64 n, u64 *out, u64 rows, hipStream_t st) {
-    const u32 lper = std::min<u32>(log2_of(n), 2u);
-    const u64 row_blocks = n >> lper;
-    return launch("bfv_uniform", (int)log2_of(n), st, fhe::bfv_uniform_kernel, fhe_ew_grid(rows * row_blocks), 256, key, first_row, Q, lper, row_blocks, rows,
-                  out);
-}
-// out [rows][n]: secret-key bits (is_key) or the ephemeral residues modulo Q
-int small_fill(const fhe::ChaChaKey &key, u32 purpose, u32 is_key, u64 first_row, u64 Q, u64 n, u64 *out, u64 rows, hipStream_t st) {
-    const u32 lper = std::min<u32>(log2_of(n), 3u);
-    const u64 row_blocks = n >> lper;
-    return launch("bfv_ephemeral", (int)log2_of(n), st, fhe::bfv_ephemeral_kernel, fhe_ew_grid(rows * row_blocks), 256, key, purpose, is_key, first_row, Q, lper,
-                  row_blocks, rows, out);
-}
-
-template <int KEYS>
-int pointwise(const fhe_ntt_plan *plan, const u64 *u, const u64 *key, u64 *out0, u64 *out1, u64 rows, hipStream_t st) {
-    const u32 L = plan->log_n, lc = std::min<u32>(L, 8u), rpb = 256u >> lc;
-    const unsigned gx = (unsigned)(plan->n >> lc);
-    const u64 passes = (rows + rpb - 1) / rpb;
-    const unsigned gy = (unsigned)std::min<u64>(passes, std::max<u64>(1, 4096 / gx));
-    {
-        fhe::KernelTimer kt_("bfv_pk_pointwise", (int)L, st);
-        hipLaunchKernelGGL(fhe::bfv_pk_pointwise_kernel<KEYS>, dim3(gx, gy), dim3(256), 0, st, u, key, out0, out1, L, rows, plan->mod);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? FHE_OK : fhe_hip_fail(e, "bfv_pk_pointwise_kernel");
-}
 
 }  // namespace
 
@@ -345,7 +190,7 @@ extern "C" int fhe_bfv_public_key_dev(const fhe_ntt_plan *plan, const uint8_t *s
     if ((rc = fhe_workspace_get(kBfvClientSlot, 3 * n * 8, st, &w)) != FHE_OK) return rc;
     u64 *A = (u64 *)w, *S = A + n, *P = S + n;
     const fhe::ChaChaKey key = seed_key(seed);
-    if ((rc = uniform_fill(key, row, q, n, A, 1, st)) != FHE_OK) return rc;
+    if ((rc = uniform_fill(key, fhe::BFV_MASK, row, q, n, A, 1, st)) != FHE_OK) return rc;
     if ((rc = launch("bfv_key_bits", 0, st, fhe::bfv_key_bits_kernel, fhe_ew_grid(n), 256, d_s, S, n)) != FHE_OK) return rc;
     if ((rc = fhe_rq_mul_dev(plan, A, 0, S, 0, P, nullptr, nullptr, nullptr, 1, nullptr, st)) != FHE_OK) return rc;
     return launch("bfv_pk_epilogue", (int)plan->log_n, st, fhe::bfv_pk_epilogue_kernel, fhe_ew_grid((n + 7) / 8), 256, key, row, A, P, d_cdt, m, d_pk, n,
@@ -373,7 +218,7 @@ extern "C" int fhe_bfv_relin_key_dev(uint64_t q, uint64_t n, uint64_t pq, const 
     if ((rc = fhe_workspace_get(kBfvClientSlot, 4 * n * 8, st, &w)) != FHE_OK) return rc;
     u64 *A = (u64 *)w, *S = A + n, *AS = S + n, *SS = AS + n;
     const fhe::ChaChaKey key = seed_key(seed);
-    if ((rc = uniform_fill(key, row, pq, n, A, 1, st)) != FHE_OK) return rc;
+    if ((rc = uniform_fill(key, fhe::BFV_MASK, row, pq, n, A, 1, st)) != FHE_OK) return rc;
     if ((rc = launch("bfv_key_bits", 0, st, fhe::bfv_key_bits_kernel, fhe_ew_grid(n), 256, d_s, S, n)) != FHE_OK) return rc;
     if ((rc = fhe_tn_mul_dev(n, A, S, AS, 1, st)) != FHE_OK) return rc;
     if ((rc = fhe_tn_mul_dev(n, S, S, SS, 1, st)) != FHE_OK) return rc;
@@ -409,12 +254,8 @@ extern "C" int fhe_bfv_encrypt_dev(const fhe_ntt_plan *plan, uint64_t t, const u
     // sizes 2^8 <= n <= 2^13), two of them against the key rows staged over a chunk (once per call) measured faster than
     // forward + pointwise + two inverses.  Everything else: the pointwise route.  FHE_BFV_ENCRYPT_STAGED=0 / =1 (read per
     // call: tools/bfv_client_rate.py times both routes in one process) forces the pointwise / the staged route.
-    fhe::DevicePlan dp;
-    if ((rc = fhe_device_plan(plan, &dp)) != FHE_OK) return rc;
-    fhe::SmallQArgs sq{};
-    const char *route = getenv("FHE_BFV_ENCRYPT_STAGED");
-    const bool fused_product = fhe_smallq_args(plan, dp, &sq) || (L >= 8 && L <= 13);
-    const bool staged = route && route[0] == '1' ? true : fused_product && !(route && route[0] == '0');
+    bool staged = false;
+    if ((rc = encrypt_route_staged(plan, "FHE_BFV_ENCRYPT_STAGED", &staged)) != FHE_OK) return rc;
     void *w = nullptr;
     if ((rc = fhe_workspace_get(kBfvClientSlot, (staged ? 5 : 2) * chunk * n * 8, st, &w)) != FHE_OK) return rc;
     u64 *U = (u64 *)w, *H = U + chunk * n, *P = nullptr, *K0 = nullptr, *K1 = nullptr;

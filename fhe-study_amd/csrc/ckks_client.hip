@@ -1,0 +1,532 @@
+// ckks_client.hip — the client side of CKKS on the device (ckks/src/encoder.rs, ckks/src/lib.rs:46-118): the
+// canonical embedding as a double-precision FFT (encode, decode), the secret key, the public key, encryption and decryption.
+//
+//   embedding  w = exp(i pi / N); slot i of N/2 is the polynomial at w^(2i+1), i < N/2 (the reference's order); slots
+//              N-1-i are the conjugates and are never stored
+//   decode     z_i = (1/Delta) sum_j p_j w^((2i+1) j), p signed 64-bit words taken to f64 first
+//   encode     a_j = (1/N) Re(w^-j sum_i h_i w^(-2ij)) over the Hermitian extension h of Delta z; coefficient j =
+//              f64_as_i64(round(a_j)), round half away from zero
+//   the fold   with M = N/2 and x_j = (p_j + i p_(j+M)) w^j, F_k = sum_j x_j exp(2 pi i jk / M) is the polynomial at
+//              w^(4k+1): slot 2k = F_k / Delta, slot 2k+1 = conj(F_(M-1-k)) / Delta.  Decode is this M-point transform of
+//              the folded, twisted coefficients; encode is its inverse (conjugate twiddles, untwist, 1/M) on F built
+//              from the slots.  One transform of M = N/2 complex points in 8 N bytes of LDS serves a polynomial.
+//   twiddles   d_tw [N] interleaved (cos, sin)(pi k / N), k < N, from fhe_ckks_twiddles: the twist w^j (j < M) and the
+//              butterfly factors exp(2 pi i k / (2^s Ns)) = w^(k N / (2^(s-1) Ns)), all below w^N.  No sincos in a kernel.
+//   stream     §17's ChaCha20 stream under CKKS_MASK = 0x21, CKKS_ERR = 0x22, CKKS_KEY = 0x23, CKKS_EPH = 0x24
+//   secret     ternary from KEY word w: (w AND 1) - ((w >> 1) AND 1) as the residue 0, 1 or q - 1; v the same on EPH words
+//   mask       uniform modulo q by §20's 128-bit map (NOT the reference's rounded Uniform(-1, 1), which hides nothing)
+//   errors     cdt_error at log_scale 0; encryption row r: ERR rows 2r and 2r + 1, key row r: ERR row 2r
+//   pk         (-a s + e, a);  c0 = v pk0 + e0 + (m mod q), c1 = v pk1 + e1, m signed words
+//   decrypt    d = c0 + c1 s mod q, centred: d - q where d > floor(q / 2), as signed words
+//
+// The transform: Stockham autosort, radix-8 rounds (three radix-2 stages in registers, three table twiddles per thread and
+// round) and a last round of radix 2^(log2 M mod 3); a thread owns 8 points, a polynomial M/8 threads, small rings share a
+// workgroup.  Between rounds the points cross LDS as two planes of doubles (re, im) with the index swizzle `swz`:
+// reads are unit-stride over a wave (ds_read_b64: 32-lane groups, 32 double banks: lanes l .. l+31 read a .. a+31, and swz
+// is a bijection on each aligned run of 32).  Writes are ds_write_b64: 16-lane groups over 16 double banks (bits 0-3 of
+// the index).  Round Ns = 1 writes index 8j + r: a group's lanes vary bits 3-6; round Ns = 8 writes 64 (j / 8) + j mod 8 +
+// 8r: lanes vary bits 0-2 and 6; rounds Ns >= 64 write runs of 16.  swz XORs bit 4 into bit 0, bit 5 into bit 1 and bit 6
+// into bits 2 and 3: the bank bits of the three patterns are (b3, b4, b5, b6 ^ b3) -> 16 values, (b0, b1, b2, b6) -> 16
+// values, and the identity: conflict-free in every round for M >= 128 (smaller rings pack several polynomials into a
+// group and may meet 2-way conflicts; they are not the sizes that matter).
+#include <cmath>
+
+#include "bfv_client_kernels.hpp"
+
+using fhe::Mod;
+using fhe::u32;
+using fhe::u64;
+
+namespace fhe {
+
+constexpr u32 CKKS_MASK = 0x21, CKKS_ERR = 0x22, CKKS_KEY = 0x23, CKKS_EPH = 0x24;
+
+struct cplx { double re, im; };
+__device__ __forceinline__ cplx cadd(cplx a, cplx b) { return {a.re + b.re, a.im + b.im}; }
+__device__ __forceinline__ cplx csub(cplx a, cplx b) { return {a.re - b.re, a.im - b.im}; }
+__device__ __forceinline__ cplx cmul(cplx a, cplx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+// a times S i and a times exp(S i pi / 4)
+template <int S> __device__ __forceinline__ cplx mul_i(cplx a) { return S > 0 ? cplx{-a.im, a.re} : cplx{a.im, -a.re}; }
+template <int S> __device__ __forceinline__ cplx mul_z8(cplx a) {
+    constexpr double h = 0.70710678118654752440;
+    return S > 0 ? cplx{(a.re - a.im) * h, (a.im + a.re) * h} : cplx{(a.re + a.im) * h, (a.im - a.re) * h};
+}
+// table entry k (w^k), conjugated for the inverse direction
+template <int S> __device__ __forceinline__ cplx tw_at(const double *__restrict__ tw, u32 k) { return {tw[2 * k], S > 0 ? tw[2 * k + 1] : -tw[2 * k + 1]}; }
+
+__host__ __device__ constexpr u32 brev(u32 p, int L) {
+    u32 r = 0;
+    for (int i = 0; i < L; i++) r |= ((p >> i) & 1u) << (L - 1 - i);
+    return r;
+}
+
+// The 2^L-point transform with exponent sign S of v[r] w^(r k) in place (w = exp(S 2 pi i / (2^L Ns)), the Stockham input
+// twiddle): stage s multiplies by tws[s] = exp(S 2 pi i k / (2^(s+1) Ns)); ONE: k = 0, every twiddle is 1.  Output q sits
+// in v[brev(q)].
+template <int L, int S, bool ONE>
+__device__ __forceinline__ void bfly(cplx *v, const cplx *tws) {
+    auto tm = [&](int s, cplx x) { return ONE ? x : cmul(tws[s], x); };
+    if constexpr (L == 1) {
+        const cplx t = tm(0, v[1]);
+        v[1] = csub(v[0], t); v[0] = cadd(v[0], t);
+    } else if constexpr (L == 2) {
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            const cplx t = tm(0, v[r + 2]);
+            v[r + 2] = csub(v[r], t); v[r] = cadd(v[r], t);
+        }
+        cplx t = tm(1, v[1]);
+        v[1] = csub(v[0], t); v[0] = cadd(v[0], t);
+        t = mul_i<S>(tm(1, v[3]));
+        v[3] = csub(v[2], t); v[2] = cadd(v[2], t);
+    } else if constexpr (L == 3) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const cplx t = tm(0, v[r + 4]);
+            v[r + 4] = csub(v[r], t); v[r] = cadd(v[r], t);
+        }
+#pragma unroll
+        for (int q0 = 0; q0 < 2; q0++)
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                cplx t = tm(1, v[r + 2 + 4 * q0]);
+                if (q0) t = mul_i<S>(t);
+                v[r + 2 + 4 * q0] = csub(v[r + 4 * q0], t); v[r + 4 * q0] = cadd(v[r + 4 * q0], t);
+            }
+#pragma unroll
+        for (int q0 = 0; q0 < 2; q0++)
+#pragma unroll
+            for (int q1 = 0; q1 < 2; q1++) {
+                const int o = 2 * q1 + 4 * q0;
+                cplx t = tm(2, v[o + 1]);
+                if (q0) t = mul_z8<S>(t);
+                if (q1) t = mul_i<S>(t);
+                v[o + 1] = csub(v[o], t); v[o] = cadd(v[o], t);
+            }
+    }
+}
+
+template <int LM>
+struct CkksShape {
+    static constexpr int M = 1 << LM, LE = LM < 3 ? LM : 3, E = 1 << LE, TP = M / E;   // points, points and threads of a polynomial
+    static constexpr int BT = TP > 256 ? TP : 256, PB = BT / TP;                       // threads and polynomials of a workgroup
+    static constexpr int NR8 = LM / 3, LR = LM % 3;                                    // radix-8 rounds, log2 of the last radix
+    static constexpr int LDS = LM > 3 ? PB * 2 * M : 1;                                // doubles
+};
+
+__device__ __forceinline__ u32 swz(u32 a) { return a ^ (((a >> 4) & 3u) | (((a >> 6) & 1u) * 12u)); }
+
+// One polynomial: X_k = sum_j x_j exp(S 2 pi i jk / M), x_j = in(j), X_k to out(k, .); thread t of the polynomial's TP.
+// Every thread of the workgroup calls it (the rounds meet at barriers).
+template <int LM, int S, class In, class Out>
+__device__ __forceinline__ void ckks_fft(double *sre, double *sim, u32 t, const double *__restrict__ tw, In in, Out out) {
+    using Sh = CkksShape<LM>;
+    constexpr int E = Sh::E, TP = Sh::TP, NR8 = Sh::NR8, LR = Sh::LR;
+    cplx v[E];
+#pragma unroll
+    for (int e = 0; e < E; e++) v[e] = in(t + e * TP);
+    if constexpr (LM <= 3) {
+        bfly<LM, S, true>(v, nullptr);
+#pragma unroll
+        for (int p = 0; p < E; p++) out(brev(p, LM), v[p]);
+    } else {
+#pragma unroll
+        for (int rd = 0; rd < NR8; rd++) {
+            const int LNS = 3 * rd;
+            const u32 k = t & ((1u << LNS) - 1u);
+            if (rd == 0) {
+                bfly<3, S, true>(v, nullptr);
+            } else {
+                __syncthreads();
+#pragma unroll
+                for (int r = 0; r < 8; r++) v[r] = {sre[swz(t + r * TP)], sim[swz(t + r * TP)]};
+                cplx tws[3];
+#pragma unroll
+                for (int s = 0; s < 3; s++) tws[s] = tw_at<S>(tw, k << (LM + 1 - s - LNS));
+                bfly<3, S, false>(v, tws);
+            }
+            if (rd == NR8 - 1 && LR == 0) {
+#pragma unroll
+                for (int p = 0; p < 8; p++) out(t + brev(p, 3) * TP, v[p]);
+            } else {
+                if (rd > 0) __syncthreads();
+                const u32 j0 = ((t >> LNS) << (LNS + 3)) + k;
+#pragma unroll
+                for (int p = 0; p < 8; p++) {
+                    const u32 a = swz(j0 + (brev(p, 3) << LNS));
+                    sre[a] = v[p].re; sim[a] = v[p].im;
+                }
+            }
+        }
+        if constexpr (LR > 0) {
+            constexpr int R = 1 << LR, LNS = LM - LR;
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < 8 / R; u++) {
+                const u32 j = t + u * TP;
+                cplx x[R], tws[LR];
+#pragma unroll
+                for (int r = 0; r < R; r++) x[r] = {sre[swz(j + (r << LNS))], sim[swz(j + (r << LNS))]};
+#pragma unroll
+                for (int s = 0; s < LR; s++) tws[s] = tw_at<S>(tw, j << (LR + 1 - s));
+                bfly<LR, S, false>(x, tws);
+#pragma unroll
+                for (int p = 0; p < R; p++) out(j + (brev(p, LR) << LNS), x[p]);
+            }
+        }
+    }
+}
+
+// z [batch][N/2] interleaved = decode of p [batch][N] signed words: the i64 -> f64 conversion, the fold and the twist on the
+// load, the slot order and the division by Delta on the store
+template <int LM>
+__global__ __launch_bounds__(CkksShape<LM>::BT) void ckks_decode_kernel(const double *__restrict__ tw, const long long *__restrict__ p, double *__restrict__ z,
+                                                                        double delta, u64 batch) {
+    using Sh = CkksShape<LM>;
+    constexpr u32 M = Sh::M;
+    __shared__ double lds[Sh::LDS];
+    const u32 pl = threadIdx.x / Sh::TP, t = threadIdx.x % Sh::TP;
+    const u64 poly = (u64)blockIdx.x * Sh::PB + pl;
+    const bool valid = poly < batch;
+    const long long *pp = p + (valid ? poly : 0) * (2 * M);
+    double *zz = z + (valid ? poly : 0) * (2 * M);
+    auto in = [&](u32 j) -> cplx {
+        if (!valid) return {0.0, 0.0};
+        const cplx c = {(double)pp[j], (double)pp[j + M]};
+        return cmul(c, tw_at<1>(tw, j));
+    };
+    auto out = [&](u32 k, cplx F) {
+        if (!valid) return;
+        const bool lo = 2 * k < M;
+        const u32 slot = lo ? 2 * k : 2 * M - 1 - 2 * k;
+        zz[2 * slot] = F.re / delta;
+        zz[2 * slot + 1] = (lo ? F.im : -F.im) / delta;
+    };
+    ckks_fft<LM, 1>(lds + pl * 2 * M, lds + pl * 2 * M + M, t, tw, in, out);
+}
+
+// out [batch][N] signed words = encode of z [batch][N/2] (row r at z + 2 r z_stride doubles; z_stride 0: one vector): Delta
+// and the Hermitian extension on the load; the untwist, 1/M, the rounding and the i64 conversion on the store
+template <int LM>
+__global__ __launch_bounds__(CkksShape<LM>::BT) void ckks_encode_kernel(const double *__restrict__ tw, const double *__restrict__ z, u64 z_stride,
+                                                                        long long *__restrict__ o, double delta, u64 batch) {
+    using Sh = CkksShape<LM>;
+    constexpr u32 M = Sh::M;
+    __shared__ double lds[Sh::LDS];
+    const u32 pl = threadIdx.x / Sh::TP, t = threadIdx.x % Sh::TP;
+    const u64 poly = (u64)blockIdx.x * Sh::PB + pl;
+    const bool valid = poly < batch;
+    const double *zz = z + (valid ? poly : 0) * z_stride * 2;
+    long long *oo = o + (valid ? poly : 0) * (2 * M);
+    constexpr double inv_m = 1.0 / (double)M;
+    auto in = [&](u32 k) -> cplx {
+        if (!valid) return {0.0, 0.0};
+        const bool lo = 2 * k < M;
+        const u32 slot = lo ? 2 * k : 2 * M - 1 - 2 * k;
+        const double re = delta * zz[2 * slot], im = delta * zz[2 * slot + 1];
+        return {re, lo ? im : -im};
+    };
+    auto out = [&](u32 j, cplx X) {
+        if (!valid) return;
+        const cplx c = cmul(X, tw_at<-1>(tw, j));
+        oo[j] = f64_as_i64(round(c.re * inv_m));
+        oo[j + M] = f64_as_i64(round(c.im * inv_m));
+    };
+    ckks_fft<LM, -1>(lds + pl * 2 * M, lds + pl * 2 * M + M, t, tw, in, out);
+}
+
+// x mod q for a signed word and any q below 2^63, by the multiplication of reduce_any
+__device__ __forceinline__ u64 ckks_smod(u64 x, const Mod &m) {
+    const bool neg = (long long)x < 0;
+    const u64 r = reduce_any(neg ? 0ull - x : x, m);
+    return (neg && r) ? m.q - r : r;
+}
+
+// out0[r] = P0[r] + e0 + (msg_r mod q), out1[r] = P1[r] + e1 (mod q, canonical) for encryption row first_row + r: e0 from
+// ERR row 2 (first_row + r), e1 from the row after it; bfv_encrypt_epilogue_kernel with a signed message and no Delta
+__global__ __launch_bounds__(256) void ckks_encrypt_epilogue_kernel(ChaChaKey key, u64 first_row, const u64 *__restrict__ P0, const u64 *__restrict__ P1,
+                                                                    const u64 *__restrict__ msg, u64 msg_stride, const u64 *__restrict__ cdt, u32 cm,
+                                                                    u64 *__restrict__ out0, u64 *__restrict__ out1, u32 L, u64 rows, Mod m) {
+    __shared__ u64 scdt[CDT_MAX];
+    for (u32 i = threadIdx.x; i < cm; i += 256) scdt[i] = cdt[i];
+    __syncthreads();
+    const u32 LB = L > 3u ? L - 3u : 0u;                          // blocks per row = max(n / 8, 1)
+    const u64 n = 1ull << L, total = rows << LB, stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const u64 r = i >> LB, c = i & ((1ull << LB) - 1u), erow = 2 * (first_row + r);
+        u64 w1[8], w2[8];
+        if (cm) {
+            chacha_block(key, (u32)c, CKKS_ERR, erow, w1);
+            chacha_block(key, (u32)c, CKKS_ERR, erow + 1, w2);
+        }
+        const u64 at = (r << L) + 8 * c;
+        const u64 *__restrict__ mp = msg ? msg + r * msg_stride + 8 * c : nullptr;
+#pragma unroll
+        for (u32 j = 0; j < 8; j++) {
+            if (8 * c + j < n) {
+                const u64 e1 = cm ? bfv_err_residue(cdt_error(scdt, cm, w1[j], 0), m.q) : 0ull;
+                const u64 e2 = cm ? bfv_err_residue(cdt_error(scdt, cm, w2[j], 0), m.q) : 0ull;
+                const u64 dm = mp ? ckks_smod(mp[j], m) : 0ull;
+                out0[at + j] = add63(add63(P0[at + j], e1, m), dm, m);
+                out1[at + j] = add63(P1[at + j], e2, m);
+            }
+        }
+    }
+}
+
+// out = c0 + P mod q, centred as ring_n.rs:113-127: d - q where d > floor(q / 2), a signed word
+__global__ __launch_bounds__(256) void ckks_decrypt_epilogue_kernel(const u64 *__restrict__ c0, const u64 *__restrict__ P, u64 *__restrict__ out, u64 count,
+                                                                    Mod m) {
+    const u64 stride = (u64)gridDim.x * 256, half = m.q >> 1;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        const u64 d = add63(c0[i], P[i], m);
+        out[i] = d > half ? d - m.q : d;
+    }
+}
+
+// pk [2][n] = (-(a s) + e, a) mod q: as = a s mod q, e from ERR row 2 row; a thread takes 8 coefficients
+__global__ __launch_bounds__(256) void ckks_pk_epilogue_kernel(ChaChaKey key, u64 row, const u64 *__restrict__ a, const u64 *__restrict__ as,
+                                                               const u64 *__restrict__ cdt, u32 cm, u64 *__restrict__ pk, u64 n, Mod m) {
+    __shared__ u64 scdt[CDT_MAX];
+    for (u32 i = threadIdx.x; i < cm; i += 256) scdt[i] = cdt[i];
+    __syncthreads();
+    const u64 blocks = (n + 7) / 8;
+    for (u64 c = (u64)blockIdx.x * 256 + threadIdx.x; c < blocks; c += (u64)gridDim.x * 256) {
+        u64 w[8];
+        if (cm) chacha_block(key, (u32)c, CKKS_ERR, 2 * row, w);
+#pragma unroll
+        for (u32 j = 0; j < 8; j++) {
+            const u64 i = 8 * c + j;
+            if (i < n) {
+                const u64 e = cm ? bfv_err_residue(cdt_error(scdt, cm, w[j], 0), m.q) : 0ull;
+                pk[i] = add63(sub63(0ull, as[i], m), e, m);
+                pk[n + i] = a[i];
+            }
+        }
+    }
+}
+
+}  // namespace fhe
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kCkksClientSlot = 11;             // fhe_workspace_get slot of the staging rows (slot 10 is BFV's)
+constexpr u64 kCkksMaxN = 1ull << 13;           // M = N/2 = 2^12 complex points fill 64 KiB of LDS
+
+int check_encoder(uint64_t n, double delta, const char *who) {
+    if (n < 2 || (n & (n - 1)) != 0 || n > kCkksMaxN)
+        return fhe_fail(FHE_E_INVALID, "%s: n=%llu must be a power of two in [2, 2^13]", who, (unsigned long long)n);
+    if (!(delta > 0.0) || !std::isfinite(delta)) return fhe_fail(FHE_E_INVALID, "%s: the scale must be finite and positive", who);
+    return FHE_OK;
+}
+
+template <int LM>
+int launch_decode(const double *tw, const long long *p, double *z, double delta, u64 batch, hipStream_t st) {
+    using Sh = fhe::CkksShape<LM>;
+    return launch("ckks_decode", LM + 1, st, fhe::ckks_decode_kernel<LM>, (unsigned)((batch + Sh::PB - 1) / Sh::PB), Sh::BT, tw, p, z, delta, batch);
+}
+template <int LM>
+int launch_encode(const double *tw, const double *z, u64 z_stride, long long *o, double delta, u64 batch, hipStream_t st) {
+    using Sh = fhe::CkksShape<LM>;
+    return launch("ckks_encode", LM + 1, st, fhe::ckks_encode_kernel<LM>, (unsigned)((batch + Sh::PB - 1) / Sh::PB), Sh::BT, tw, z, z_stride, o, delta, batch);
+}
+#define CKKS_BY_SIZE(LM, CALL)                                                                                      \
+    switch (LM) {                                                                                                   \
+        case 0: return CALL(0); case 1: return CALL(1); case 2: return CALL(2); case 3: return CALL(3);             \
+        case 4: return CALL(4); case 5: return CALL(5); case 6: return CALL(6); case 7: return CALL(7);             \
+        case 8: return CALL(8); case 9: return CALL(9); case 10: return CALL(10); case 11: return CALL(11);         \
+        default: return CALL(12);                                                                                   \
+    }
+
+}  // namespace
+
+extern "C" int fhe_ckks_twiddles(uint64_t n, double *out) {
+    const char *who = "fhe_ckks_twiddles";
+    if (n < 2 || (n & (n - 1)) != 0 || n > kCkksMaxN) return fhe_fail(FHE_E_INVALID, "%s: n=%llu must be a power of two in [2, 2^13]", who, (unsigned long long)n);
+    if (!out) return fhe_fail(FHE_E_NULL, "%s: NULL table", who);
+    const long double pi = 3.141592653589793238462643383279502884L;
+    for (uint64_t k = 0; k < n; k++) {
+        // octant symmetry: the argument handed to cosl / sinl never passes pi / 4
+        const uint64_t kk = 2 * k <= n ? k : n - k;             // pi kk / n in [0, pi / 2]; cos changes sign past pi / 2
+        long double c, s;
+        if (4 * kk <= n) {
+            const long double a = pi * (long double)kk / (long double)n;
+            c = cosl(a); s = sinl(a);
+        } else {
+            const long double a = pi * (long double)(n - 2 * kk) / (long double)(2 * n);
+            c = sinl(a); s = cosl(a);
+        }
+        out[2 * k] = (double)(2 * k <= n ? c : -c);
+        out[2 * k + 1] = (double)s;
+    }
+    return FHE_OK;
+}
+
+extern "C" int fhe_ckks_encode_dev(uint64_t n, double delta, const void *d_tw, const void *d_z, size_t z_stride, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_encode_dev";
+    int rc = check_encoder(n, delta, who);
+    if (rc != FHE_OK) return rc;
+    if (z_stride != 0 && z_stride < n / 2) return fhe_fail(FHE_E_INVALID, "%s: z_stride must be 0 (one vector) or at least n / 2", who);
+    if (batch == 0) return FHE_OK;
+    if (!mul_fits((u64)batch, n, kWordLimit) || !mul_fits((u64)batch - 1, (u64)z_stride, (kWordLimit - n) / 2))
+        return fhe_fail(FHE_E_INVALID, "%s: batch or z_stride too large", who);
+    if (!d_tw || !d_z || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_tw) || misaligned8(d_z) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 z_bytes = (((u64)batch - 1) * z_stride + n / 2) * 16;
+    if (overlaps_any(d_out, (u64)batch * n * 8, {{d_z, z_bytes}, {d_tw, n * 16}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the slots or the twiddle table", who);
+    int dev;
+    if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+#define CKKS_ENC(LM) launch_encode<LM>((const double *)d_tw, (const double *)d_z, (u64)z_stride, (long long *)d_out, delta, (u64)batch, st)
+    CKKS_BY_SIZE(log2_of(n) - 1, CKKS_ENC)
+#undef CKKS_ENC
+}
+
+extern "C" int fhe_ckks_decode_dev(uint64_t n, double delta, const void *d_tw, const void *d_p, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_decode_dev";
+    int rc = check_encoder(n, delta, who);
+    if (rc != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    if (!mul_fits((u64)batch, n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_tw || !d_p || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_tw) || misaligned8(d_p) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    if (overlaps_any(d_out, (u64)batch * n * 8, {{d_p, (u64)batch * n * 8}, {d_tw, n * 16}}))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the polynomials or the twiddle table", who);
+    int dev;
+    if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+#define CKKS_DEC(LM) launch_decode<LM>((const double *)d_tw, (const long long *)d_p, (double *)d_out, delta, (u64)batch, st)
+    CKKS_BY_SIZE(log2_of(n) - 1, CKKS_DEC)
+#undef CKKS_DEC
+}
+
+extern "C" int fhe_ckks_secret_key_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t key_row, void *d_s, void *hip_stream) {
+    const char *who = "fhe_ckks_secret_key_dev";
+    if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
+    if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
+    if (!d_s) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_s)) return fhe_fail(FHE_E_INVALID, "%s: d_s must be 8-byte aligned", who);
+    int dev, rc;
+    if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
+    return small_fill(seed_key(seed), fhe::CKKS_KEY, 0, key_row, plan->q, plan->n, (u64 *)d_s, 1, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_ckks_public_key_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t row, const void *d_s, const void *d_cdt, unsigned m,
+                                       void *d_pk, void *hip_stream) {
+    const char *who = "fhe_ckks_public_key_dev";
+    if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
+    if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
+    const u64 n = plan->n, q = plan->q;
+    int rc = check_cdt_shape(d_cdt, m, q, who);
+    if (rc != FHE_OK) return rc;
+    if (row >= kRowLimit) return fhe_fail(FHE_E_INVALID, "%s: row must be below 2^63", who);
+    if (!d_s || !d_pk) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_s) || misaligned8(d_pk)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    if (overlaps_any(d_pk, 2 * n * 8, {{d_s, n * 8}, {d_cdt, (u64)m * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_pk overlaps the key or the error table", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
+    void *w = nullptr;
+    if ((rc = fhe_workspace_get(kCkksClientSlot, 3 * n * 8, st, &w)) != FHE_OK) return rc;
+    u64 *A = (u64 *)w, *S = A + n, *P = S + n;
+    const fhe::ChaChaKey key = seed_key(seed);
+    if ((rc = uniform_fill(key, fhe::CKKS_MASK, row, q, n, A, 1, st)) != FHE_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(S, d_s, n * 8, hipMemcpyDeviceToDevice, st));      // the product takes 16-byte aligned rows
+    if ((rc = fhe_rq_mul_dev(plan, A, 0, S, 0, P, nullptr, nullptr, nullptr, 1, nullptr, st)) != FHE_OK) return rc;
+    return launch("ckks_pk_epilogue", (int)plan->log_n, st, fhe::ckks_pk_epilogue_kernel, fhe_ew_grid((n + 7) / 8), 256, key, row, A, P, d_cdt, m, d_pk, n,
+                  plan->mod);
+}
+
+extern "C" int fhe_ckks_encrypt_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t first_row, const void *d_pk_evals, const void *d_msg,
+                                    size_t msg_stride, const void *d_cdt, unsigned m, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_encrypt_dev";
+    if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
+    if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
+    const u64 n = plan->n, q = plan->q;
+    int rc = check_cdt_shape(d_cdt, m, q, who);
+    if (rc != FHE_OK) return rc;
+    if (d_msg && msg_stride != 0 && msg_stride < n) return fhe_fail(FHE_E_INVALID, "%s: msg_stride must be 0 (one message) or at least n", who);
+    if (batch == 0) return FHE_OK;
+    if (first_row > kRowLimit || (u64)batch > kRowLimit - first_row) return fhe_fail(FHE_E_INVALID, "%s: first_row + batch passes 2^63", who);
+    if (!mul_fits((u64)batch, 2 * n, kWordLimit) || !mul_fits((u64)batch - 1, (u64)msg_stride, kWordLimit - n))
+        return fhe_fail(FHE_E_INVALID, "%s: batch or msg_stride too large", who);
+    if (!d_pk_evals || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_pk_evals) || misaligned8(d_msg) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 out_bytes = (u64)batch * 2 * n * 8, msg_bytes = d_msg ? (((u64)batch - 1) * msg_stride + n) * 8 : 0;
+    if (overlaps_any(d_out, out_bytes, {{d_pk_evals, 2 * n * 8}, {d_msg, msg_bytes}, {d_cdt, (u64)m * 8}}))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key, the messages or the error table", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
+    const u32 L = plan->log_n;
+    const u64 chunk = std::min<u64>(batch, std::max<u64>(1, kChunkWords >> L));
+    // BFV's two routes and its rule; FHE_CKKS_ENCRYPT_STAGED=0 / =1, read per call, forces one
+    bool staged = false;
+    if ((rc = encrypt_route_staged(plan, "FHE_CKKS_ENCRYPT_STAGED", &staged)) != FHE_OK) return rc;
+    void *w = nullptr;
+    if ((rc = fhe_workspace_get(kCkksClientSlot, (staged ? 5 : 2) * chunk * n * 8, st, &w)) != FHE_OK) return rc;
+    u64 *U = (u64 *)w, *H = U + chunk * n, *P = nullptr, *K0 = nullptr, *K1 = nullptr;
+    if (staged) {
+        P = H + chunk * n; K0 = P + chunk * n; K1 = K0 + chunk * n;
+        if ((rc = launch("bfv_broadcast", (int)L, st, fhe::bfv_broadcast_kernel, fhe_ew_grid(chunk << L), 256, d_pk_evals, K0, L, chunk)) != FHE_OK) return rc;
+        if ((rc = launch("bfv_broadcast", (int)L, st, fhe::bfv_broadcast_kernel, fhe_ew_grid(chunk << L), 256, (const u64 *)d_pk_evals + n, K1, L, chunk)) != FHE_OK)
+            return rc;
+    }
+    const fhe::ChaChaKey key = seed_key(seed);
+    const u32 LB = L > 3 ? L - 3 : 0;
+    for (u64 r0 = 0; r0 < batch; r0 += chunk) {
+        const u64 cr = std::min<u64>(chunk, batch - r0);
+        const u64 *R0 = U, *R1 = H;                               // the two products of the chunk
+        if ((rc = small_fill(key, fhe::CKKS_EPH, 0, first_row + r0, q, n, U, cr, st)) != FHE_OK) return rc;
+        if (staged) {
+            if ((rc = fhe_rq_mul_dev(plan, U, 0, K0, 1, P, nullptr, nullptr, nullptr, cr, nullptr, st)) != FHE_OK) return rc;
+            if ((rc = fhe_rq_mul_dev(plan, U, 0, K1, 1, H, nullptr, nullptr, nullptr, cr, nullptr, st)) != FHE_OK) return rc;
+            R0 = P;
+        } else {
+            if ((rc = fhe_ntt_forward_dev(plan, U, U, cr, st)) != FHE_OK) return rc;
+            if ((rc = pointwise<2>(plan, U, (const u64 *)d_pk_evals, U, H, cr, st)) != FHE_OK) return rc;
+            if ((rc = fhe_ntt_inverse_dev(plan, U, U, cr, st)) != FHE_OK) return rc;
+            if ((rc = fhe_ntt_inverse_dev(plan, H, H, cr, st)) != FHE_OK) return rc;
+        }
+        const u64 *msg = d_msg ? (const u64 *)d_msg + r0 * msg_stride : nullptr;
+        u64 *o0 = (u64 *)d_out + r0 * n, *o1 = (u64 *)d_out + ((u64)batch + r0) * n;
+        if ((rc = launch("ckks_encrypt_epilogue", (int)L, st, fhe::ckks_encrypt_epilogue_kernel, fhe_ew_grid(cr << LB), 256, key, first_row + r0, R0, R1, msg,
+                         msg_stride, d_cdt, m, o0, o1, L, cr, plan->mod)) != FHE_OK)
+            return rc;
+    }
+    return FHE_OK;
+}
+
+extern "C" int fhe_ckks_decrypt_dev(const fhe_ntt_plan *plan, const void *d_s_evals, const void *d_ct, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_decrypt_dev";
+    if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
+    const u64 n = plan->n;
+    if (batch == 0) return FHE_OK;
+    if (!mul_fits((u64)batch, 2 * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_s_evals || !d_ct || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_s_evals) || misaligned8(d_ct) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 out_bytes = (u64)batch * n * 8;
+    if (overlaps_any(d_out, out_bytes, {{d_s_evals, n * 8}, {d_ct, 2 * out_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key or the ciphertexts", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const u32 L = plan->log_n;
+    const u64 chunk = std::min<u64>(batch, std::max<u64>(1, kChunkWords >> L));
+    void *w = nullptr;
+    int rc = fhe_workspace_get(kCkksClientSlot, chunk * n * 8, st, &w);
+    if (rc != FHE_OK) return rc;
+    u64 *W = (u64 *)w;
+    for (u64 r0 = 0; r0 < batch; r0 += chunk) {
+        const u64 cr = std::min<u64>(chunk, batch - r0);
+        const u64 *c0 = (const u64 *)d_ct + r0 * n, *c1 = (const u64 *)d_ct + ((u64)batch + r0) * n;
+        const u64 *src = c1;
+        if (fhe_misaligned(c1)) {                                 // the transforms take 16-byte aligned rows
+            HIP_TRY(hipMemcpyAsync(W, c1, cr * n * 8, hipMemcpyDeviceToDevice, st));
+            src = W;
+        }
+        if ((rc = fhe_ntt_forward_dev(plan, src, W, cr, st)) != FHE_OK) return rc;
+        if ((rc = pointwise<1>(plan, W, (const u64 *)d_s_evals, W, nullptr, cr, st)) != FHE_OK) return rc;
+        if ((rc = fhe_ntt_inverse_dev(plan, W, W, cr, st)) != FHE_OK) return rc;
+        if ((rc = launch("ckks_decrypt_epilogue", (int)L, st, fhe::ckks_decrypt_epilogue_kernel, fhe_ew_grid(cr * n), 256, c0, W, (u64 *)d_out + r0 * n, cr * n,
+                         plan->mod)) != FHE_OK)
+            return rc;
+    }
+    return FHE_OK;
+}

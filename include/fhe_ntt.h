@@ -580,6 +580,49 @@ int fhe_bfv_encrypt_dev(const fhe_ntt_plan *plan, uint64_t t, const uint8_t *see
 int fhe_bfv_decrypt_dev(const fhe_ntt_plan *plan, uint64_t t, const void *d_s_evals, const void *d_ct, void *d_out,
                         size_t batch, void *hip_stream);
 
+/* ---- CKKS: the encoder, key generation, encryption and decryption (ckks/src/encoder.rs, ckks/src/lib.rs:46-118;
+ * DESIGN.md §21) ----
+ * The embedding: w = exp(i pi / n); slot i of n/2 is the value of the polynomial at w^(2i+1), i < n/2 (the reference's
+ * order, not the 5^j order); the conjugate slots n-1-i are never stored.  Complex values are interleaved double pairs.
+ *   fhe_ckks_twiddles    HOST only, needs no device: out [n] pairs (cos, sin)(pi k / n), k < n, each within 1 ulp (long
+ *            double, arguments reduced to [0, pi/4]).  The caller uploads the table and passes it as d_tw.
+ *   fhe_ckks_encode_dev  d_out [batch][n] signed 64-bit words: coefficient j = f64_as_i64(round(a_j)), round half away from
+ *            zero, a_j = (1/n) Re(w^-j sum_i h_i w^(-2ij)) over the Hermitian extension h of delta z as the device's f64
+ *            transform computes it (error bound in §21; not bit-compatible with the reference's MKL solve).  Row r of d_z
+ *            starts at complex value r z_stride (z_stride = 0: one vector for every row, otherwise >= n/2).
+ *   fhe_ckks_decode_dev  d_out [batch][n/2] complex: z_i = (1/delta) sum_j p_j w^((2i+1) j), d_p [batch][n] signed words
+ *            converted to f64 first.
+ * The encoder takes 2 <= n <= 2^13 (one workgroup's LDS holds a polynomial) and a finite, positive delta.
+ * The scheme runs on the stream above under FHE_STREAM_CKKS_MASK, _ERR, _KEY, _EPH (fhe_tfhe_stream_words_dev does not
+ * serve them); a row is one polynomial; samples, row numbering and the error table are those of the BFV block, except:
+ *   secret   ternary: s_i = (w AND 1) - ((w >> 1) AND 1) of KEY word i, as the residue 0, 1 or q - 1; the ephemeral v the
+ *            same on EPH words
+ *   mask     uniform modulo q (the reference draws it from the secret's distribution, which hides nothing: not followed)
+ *   fhe_ckks_secret_key_dev  d_s [n] residues 0, 1, q - 1 of KEY row key_row
+ *   fhe_ckks_public_key_dev  d_pk = [pk0 | pk1] = (-a s + e, a) mod q; d_s as written by fhe_ckks_secret_key_dev
+ *   fhe_ckks_encrypt_dev     d_out = [c0 | c1], each batch x n: c0 = v pk0 + e0 + (m_r mod q), c1 = v pk1 + e1; the message
+ *            rows are SIGNED words (d_msg NULL: m = 0; msg_stride 0: one message); d_pk_evals as for BFV
+ *   fhe_ckks_decrypt_dev     d_out [batch][n] signed words: d = c0 + c1 s mod q, then d - q where d > floor(q / 2)
+ * Device buffers need 8-byte alignment.  Rejections are those of the BFV block (table, row range, overlap, extents):
+ * FHE_E_INVALID, nothing written; batch = 0 is a no-op. */
+#define FHE_STREAM_CKKS_MASK 0x21u
+#define FHE_STREAM_CKKS_ERR 0x22u
+#define FHE_STREAM_CKKS_KEY 0x23u
+#define FHE_STREAM_CKKS_EPH 0x24u
+int fhe_ckks_twiddles(uint64_t n, double *out);
+int fhe_ckks_encode_dev(uint64_t n, double delta, const void *d_tw, const void *d_z, size_t z_stride, void *d_out,
+                        size_t batch, void *hip_stream);
+int fhe_ckks_decode_dev(uint64_t n, double delta, const void *d_tw, const void *d_p, void *d_out, size_t batch,
+                        void *hip_stream);
+int fhe_ckks_secret_key_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t key_row, void *d_s, void *hip_stream);
+int fhe_ckks_public_key_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t row, const void *d_s, const void *d_cdt,
+                            unsigned m, void *d_pk, void *hip_stream);
+int fhe_ckks_encrypt_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t first_row, const void *d_pk_evals,
+                         const void *d_msg, size_t msg_stride, const void *d_cdt, unsigned m, void *d_out, size_t batch,
+                         void *hip_stream);
+int fhe_ckks_decrypt_dev(const fhe_ntt_plan *plan, const void *d_s_evals, const void *d_ct, void *d_out, size_t batch,
+                         void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
