@@ -5,7 +5,8 @@ Layout:
   binding.py   ctypes plumbing over the C ABI
   arith.py     host mirror of the reference's RingParam / Rq / NTT surface
   bfv.py       RLWE::tensor / RLWE::mul (bfv/src/lib.rs) over the exact-product rows, and BFV's client side
-  ckks.py      the CKKS encoder (a double-precision FFT), keys, encryption and decryption (ckks/src)
+  ckks.py      the CKKS encoder (a double-precision FFT), keys, encryption and decryption (ckks/src), and the evaluator on an
+               RNS modulus chain: ct x ct, relinearisation, rescaling
   device.py    device buffers for bfv.py, ckks.py and tfhe.py (torch as the allocator)
   tfhe.py      Tn x Tn and TGGSW x TGLWE (ring_torus.rs, tfhe/src/tggsw.rs)
   host/        the same mirror in C++ (arith.hpp), for compiled callers

@@ -14,7 +14,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FHE_NTT_LIB") or os.path.join(_HERE, "libfhe_ntt.so")  # env: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip", "tfhe_client.hip", "bfv_client.hip", "ckks_client.hip"]
+SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip", "tfhe_client.hip", "bfv_client.hip", "ckks_client.hip", "ckks_eval.hip"]
 HEADERS = ["ntt_kernels.hpp", "ntt_rounds.hpp", "ntt_persist.hpp", "persist_sched.hpp", "digit_mac.hpp", "digit32.hpp", "bfv32.hpp", "smallq.hpp", "ntt32_rounds.hpp", "ntt32_big.hpp", "zq_device.hpp", "capi_internal.hpp", "mac_kernel.hpp", "chacha_stream.hpp", "bfv_client_kernels.hpp", "ntt_kernels.hip",
            os.path.join("..", "..", "include", "fhe_ntt.h"), os.path.join("..", "..", "include", "fhe_ntt_experimental.h")]
 OBJ_DIR = os.path.join(_HERE, "build")
@@ -86,6 +86,9 @@ EXPORTS = [
     # CKKS: the FFT encoder, key generation, encryption and decryption (ckks_client.hip)
     "fhe_ckks_twiddles", "fhe_ckks_encode_dev", "fhe_ckks_decode_dev", "fhe_ckks_secret_key_dev", "fhe_ckks_public_key_dev", "fhe_ckks_encrypt_dev",
     "fhe_ckks_decrypt_dev",
+    # CKKS on an RNS modulus chain: ct x ct, relinearisation, rescaling (ckks_eval.hip)
+    "fhe_ckks_rns_from_i64_dev", "fhe_ckks_rns_relin_key_dev", "fhe_ckks_rns_tensor_dev", "fhe_ckks_rns_relinearize_dev", "fhe_ckks_rns_mul_dev",
+    "fhe_ckks_rns_rescale_dev", "fhe_ckks_rns_workspace_bytes",
 ]
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
@@ -296,6 +299,15 @@ def load_library():
     L.fhe_ckks_public_key_dev.argtypes = [_vp, ctypes.c_char_p, _u64, _vp, _vp, _uint, _vp, _vp]
     L.fhe_ckks_encrypt_dev.argtypes = [_vp, ctypes.c_char_p, _u64, _vp, _vp, _sz, _vp, _uint, _vp, _sz, _vp]
     L.fhe_ckks_decrypt_dev.argtypes = [_vp, _vp, _vp, _vp, _sz, _vp]
+    _pp = ctypes.POINTER(_vp)
+    L.fhe_ckks_rns_from_i64_dev.argtypes = [_pp, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_rns_relin_key_dev.argtypes = [_pp, _uint, _vp, ctypes.c_char_p, _u64, _vp, _vp, _uint, _vp, _vp]
+    L.fhe_ckks_rns_tensor_dev.argtypes = [_pp, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_rns_relinearize_dev.argtypes = [_pp, _uint, _vp, _vp, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_rns_mul_dev.argtypes = [_pp, _uint, _vp, _vp, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_rns_rescale_dev.argtypes = [_pp, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_rns_workspace_bytes.argtypes = [_u64, _uint, _sz]
+    L.fhe_ckks_rns_workspace_bytes.restype = _sz
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -763,6 +775,52 @@ def ckks_encrypt_dev(plan, seed, first_row, d_pk_evals, d_msg, msg_stride, d_cdt
 def ckks_decrypt_dev(plan, d_s_evals, d_ct, d_out, batch, stream=None):
     """d_ct [2][batch][n] -> d_out [batch][n] int64, centred"""
     _check(load_library().fhe_ckks_decrypt_dev(plan.handle, d_s_evals, d_ct, d_out, batch, stream))
+
+
+def _plan_array(plans):
+    """a host array of plan handles; a None entry is passed as NULL"""
+    return (_vp * max(len(plans), 1))(*[None if p is None else getattr(p, "handle", p) for p in plans])
+
+
+def _handle(plan):
+    return None if plan is None else getattr(plan, "handle", plan)
+
+
+def ckks_rns_from_i64_dev(plans, d_in, d_out, batch, stream=None, limbs=None):
+    """fhe_ckks_rns_from_i64_dev: signed rows [batch][n] -> evals [limbs][batch][n]"""
+    _check(load_library().fhe_ckks_rns_from_i64_dev(_plan_array(plans), len(plans) if limbs is None else limbs, d_in, d_out, batch, stream))
+
+
+def ckks_rns_relin_key_dev(plans, special, seed, first_row, d_s, d_cdt, m, d_rlk, stream=None, limbs=None):
+    """fhe_ckks_rns_relin_key_dev: d_rlk [limbs][limbs + 1][2][n] evals from d_s [limbs + 1][n]"""
+    _check(load_library().fhe_ckks_rns_relin_key_dev(_plan_array(plans), len(plans) if limbs is None else limbs, _handle(special), _seed(seed), first_row, d_s, d_cdt,
+                                                     m, d_rlk, stream))
+
+
+def ckks_rns_tensor_dev(plans, d_a, d_b, d_out, batch, stream=None, limbs=None):
+    """fhe_ckks_rns_tensor_dev: [limbs][2][batch][n] x 2 -> [limbs][3][batch][n]"""
+    _check(load_library().fhe_ckks_rns_tensor_dev(_plan_array(plans), len(plans) if limbs is None else limbs, d_a, d_b, d_out, batch, stream))
+
+
+def ckks_rns_relinearize_dev(plans, special, d_rlk, key_limbs, d_d, d_out, batch, stream=None, limbs=None):
+    """fhe_ckks_rns_relinearize_dev: [limbs][3][batch][n] -> [limbs][2][batch][n]"""
+    _check(load_library().fhe_ckks_rns_relinearize_dev(_plan_array(plans), len(plans) if limbs is None else limbs, _handle(special), d_rlk, key_limbs, d_d, d_out,
+                                                       batch, stream))
+
+
+def ckks_rns_mul_dev(plans, special, d_rlk, key_limbs, d_a, d_b, d_out, batch, stream=None, limbs=None):
+    """fhe_ckks_rns_mul_dev: the tensor and its relinearisation in one call"""
+    _check(load_library().fhe_ckks_rns_mul_dev(_plan_array(plans), len(plans) if limbs is None else limbs, _handle(special), d_rlk, key_limbs, d_a, d_b, d_out, batch,
+                                               stream))
+
+
+def ckks_rns_rescale_dev(plans, d_in, d_out, batch, stream=None, limbs=None):
+    """fhe_ckks_rns_rescale_dev: [limbs][2][batch][n] -> [limbs - 1][2][batch][n]"""
+    _check(load_library().fhe_ckks_rns_rescale_dev(_plan_array(plans), len(plans) if limbs is None else limbs, d_in, d_out, batch, stream))
+
+
+def ckks_rns_workspace_bytes(n, limbs, batch):
+    return int(load_library().fhe_ckks_rns_workspace_bytes(n, limbs, batch))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

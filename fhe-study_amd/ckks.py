@@ -192,3 +192,234 @@ class ClientKey:
 
     def decrypt_and_decode(self, ct, scale=None):
         return self.encoder.decode(self.decrypt(ct), scale)
+
+
+# ---- the RNS modulus chain: ct x ct, relinearisation, rescaling (ckks_eval.hip) ---------------------------------
+@dataclass(frozen=True)
+class RnsParam:
+    """n, the chain primes q_0 .. q_L and the special prime P >= max q_i of the relinearisation key; level l = limbs 0 .. l"""
+    n: int
+    moduli: tuple
+    special: int
+
+    def __post_init__(self):
+        object.__setattr__(self, "moduli", tuple(int(q) for q in self.moduli))
+        object.__setattr__(self, "special", int(self.special))
+        if not 1 <= len(self.moduli) <= 8:
+            raise ValueError("RnsParam: the chain has 1 to 8 primes")
+        if len(set(self.moduli + (self.special,))) != len(self.moduli) + 1:
+            raise ValueError("RnsParam: the primes of the chain and the special prime must be distinct")
+        if self.special < max(self.moduli):
+            raise ValueError("RnsParam: the special prime must not be below a chain prime")
+
+    @property
+    def max_level(self):
+        return len(self.moduli) - 1
+
+    def plans(self, level=None):
+        """the plans of limbs 0 .. level (default: all)"""
+        k = len(self.moduli) if level is None else level + 1
+        return [_plan(RingParam(q, self.n)) for q in self.moduli[:k]]
+
+    def special_plan(self):
+        return _plan(RingParam(self.special, self.n))
+
+
+class RnsRelinKey:
+    """rlk [j][i][2][n] evals on the device, j <= L, i in {0 .. L, P}"""
+
+    def __init__(self, param, d_rlk):
+        self.param, self.d_rlk = param, d_rlk
+
+
+class RnsPublicKey:
+    """per limb (pk0, pk1) mod q_i as evals [limbs][2][n] on the device"""
+
+    def __init__(self, param, d_evals):
+        self.param, self.d_evals = param, d_evals
+
+
+SCALE_TOLERANCE = 2.0 ** -20
+
+
+class RnsCiphertext:
+    """A device tensor [level + 1][2][batch][n] of evals with its level and float64 scale"""
+
+    def __init__(self, param, d, level, scale):
+        self.param, self.d, self.level, self.scale = param, d, int(level), float(scale)
+
+    @property
+    def batch(self):
+        return self.d.shape[2]
+
+    def at_level(self, level):
+        """dropping top limbs is truncation"""
+        if not 0 <= level <= self.level:
+            raise ValueError(f"at_level: level {level} is not in [0, {self.level}]")
+        return RnsCiphertext(self.param, self.d[:level + 1].contiguous(), level, self.scale)
+
+    def _pair(self, rhs):
+        if rhs.param != self.param or rhs.batch != self.batch:
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "operands differ in RnsParam or batch")
+        level = min(self.level, rhs.level)
+        return self.at_level(level), rhs.at_level(level), level
+
+    def _rows(self, rhs, fn):
+        if abs(rhs.scale - self.scale) > SCALE_TOLERANCE * self.scale:
+            raise ValueError(f"the scales {self.scale} and {rhs.scale} differ by more than a relative 2^-20")
+        a, b, level = self._pair(rhs)
+        out = _torch().empty_like(a.d)
+        for i, plan in enumerate(self.param.plans(level)):
+            binding._check(fn(plan.handle, a.d[i].data_ptr(), b.d[i].data_ptr(), out[i].data_ptr(), 2 * self.batch, None))
+        return RnsCiphertext(self.param, out, level, self.scale)
+
+    def __add__(self, rhs):
+        return self._rows(rhs, binding.load_library().fhe_rq_add_dev)
+
+    def __sub__(self, rhs):
+        return self._rows(rhs, binding.load_library().fhe_rq_sub_dev)
+
+    def mul(self, rhs, rlk):
+        """ct x ct and relinearisation (fhe_ckks_rns_mul_dev); the scale multiplies and the result is NOT rescaled"""
+        if rlk.param != self.param:
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the relinearisation key is not of this ciphertext's chain")
+        a, b, level = self._pair(rhs)
+        out = _torch().empty_like(a.d)
+        binding.ckks_rns_mul_dev(self.param.plans(level), self.param.special_plan(), rlk.d_rlk.data_ptr(), len(self.param.moduli), a.d.data_ptr(), b.d.data_ptr(),
+                                 out.data_ptr(), self.batch)
+        return RnsCiphertext(self.param, out, level, self.scale * rhs.scale)
+
+    def rescale(self):
+        """divide and round by the top prime: level - 1, scale / q_level; refused at level 0"""
+        if self.level == 0:
+            raise binding.FheError(binding.FHE_E_INVALID, "rescale: a ciphertext at level 0 cannot be rescaled")
+        torch = _torch()
+        out = torch.empty((self.level, 2, self.batch, self.param.n), dtype=torch.int64, device="cuda")
+        binding.ckks_rns_rescale_dev(self.param.plans(self.level), self.d.data_ptr(), out.data_ptr(), self.batch)
+        return RnsCiphertext(self.param, out, self.level - 1, self.scale / self.param.moduli[self.level])
+
+    def _plain(self, m):
+        """signed rows (n,) or (batch, n) -> evals [level + 1][batch][n]"""
+        torch = _torch()
+        n = self.param.n
+        rows = np.array(np.broadcast_to(np.asarray(m, dtype=np.int64), (self.batch, n)))   # a writable copy
+        out = torch.empty((self.level + 1, self.batch, n), dtype=torch.int64, device="cuda")
+        d_rows = torch.from_numpy(rows).cuda()
+        binding.ckks_rns_from_i64_dev(self.param.plans(self.level), d_rows.data_ptr(), out.data_ptr(), self.batch)
+        return out
+
+    def add_plain(self, m):
+        """c0 + m for an encoded plaintext at this ciphertext's scale"""
+        pt, out = self._plain(m), self.d.clone()
+        for i, plan in enumerate(self.param.plans(self.level)):
+            binding._check(binding.load_library().fhe_rq_add_dev(plan.handle, self.d[i, 0].data_ptr(), pt[i].data_ptr(), out[i, 0].data_ptr(), self.batch, None))
+        return RnsCiphertext(self.param, out, self.level, self.scale)
+
+    def mul_plain(self, m, scale):
+        """both components times an encoded plaintext of scale `scale`; the scale multiplies"""
+        pt, out = self._plain(m), _torch().empty_like(self.d)
+        for i, plan in enumerate(self.param.plans(self.level)):
+            for c in range(2):
+                plan.pointwise_mul_dev(self.d[i, c].data_ptr(), pt[i].data_ptr(), out[i, c].data_ptr(), self.batch)
+        return RnsCiphertext(self.param, out, self.level, self.scale * float(scale))
+
+
+class RnsClientKey:
+    """The CKKS secret under every prime of an RnsParam: the same ternary row (KEY row 0) as residues and evals per limb, the
+    special prime's last.  Rows of a seed, as ClientKey and disjoint from its rows:
+        [0, 2^56)                    fresh encryptions
+        1 2^56 + slot                public_key(slot)
+        2 2^56 + 64 slot + j         digit j of relin_key(slot)
+    A builder refuses a slot (0 <= slot < 2^16) it has used."""
+
+    ENCRYPT_ROWS = 1 << 56
+    PK_BASE = 1 << 56
+    RLK_BASE = 2 << 56
+
+    def __init__(self, seed, param, delta, d_s, d_s_evals, sigma):
+        self.seed, self.param, self.delta, self.d_s, self.d_s_evals = bytes(seed), param, float(delta), d_s, d_s_evals
+        self.encoder = Encoder(param.n, delta)
+        self._next_row, self._pk_slots, self._rlk_slots = 0, set(), set()
+        tab = cdt_table(sigma)
+        self._cdt, self._m = (_to_dev(tab) if len(tab) else None), len(tab)
+
+    def _all_plans(self):
+        return self.param.plans() + [self.param.special_plan()]
+
+    @classmethod
+    def generate(cls, seed, param, delta, sigma=3.2):
+        torch = _torch()
+        plans = param.plans() + [param.special_plan()]
+        d_s = torch.empty((len(plans), param.n), dtype=torch.int64, device="cuda")
+        d_e = torch.empty_like(d_s)
+        for i, plan in enumerate(plans):
+            binding.ckks_secret_key_dev(plan, seed, 0, d_s[i].data_ptr())
+            plan.forward_dev(d_s[i].data_ptr(), d_e[i].data_ptr(), 1)
+        torch.cuda.synchronize()
+        return cls(seed, param, delta, d_s, d_e, sigma)
+
+    def _cdt_ptr(self):
+        return self._cdt.data_ptr() if self._m else None
+
+    @staticmethod
+    def _take(slots, slot, who):
+        if not 0 <= int(slot) < 1 << 16:
+            raise ValueError(f"{who}: slot must be in [0, 2^16)")
+        if int(slot) in slots:
+            raise ValueError(f"{who}: slot {slot} of this seed is already used; a second key needs a slot of its own")
+        slots.add(int(slot))
+
+    def public_key(self, slot=0):
+        """fhe_ckks_public_key_dev per limb with one row: the residues of one key (-a s + e, a) modulo Q"""
+        torch = _torch()
+        self._take(self._pk_slots, slot, "public_key")
+        plans = self.param.plans()
+        pk = torch.empty((len(plans), 2, self.param.n), dtype=torch.int64, device="cuda")
+        for i, plan in enumerate(plans):
+            binding.ckks_public_key_dev(plan, self.seed, self.PK_BASE + int(slot), self.d_s[i].data_ptr(), self._cdt_ptr(), self._m, pk[i].data_ptr())
+            plan.forward_dev(pk[i].data_ptr(), pk[i].data_ptr(), 2)
+        return RnsPublicKey(self.param, pk)
+
+    def relin_key(self, slot=0):
+        torch = _torch()
+        self._take(self._rlk_slots, slot, "relin_key")
+        k = len(self.param.moduli)
+        rlk = torch.empty((k, k + 1, 2, self.param.n), dtype=torch.int64, device="cuda")
+        binding.ckks_rns_relin_key_dev(self.param.plans(), self.param.special_plan(), self.seed, self.RLK_BASE + 64 * int(slot), self.d_s.data_ptr(), self._cdt_ptr(),
+                                       self._m, rlk.data_ptr())
+        return RnsRelinKey(self.param, rlk)
+
+    def encrypt(self, pk, m, scale=None):
+        """m int64 coefficients (n,) or (batch, n) -> RnsCiphertext at the top level: fhe_ckks_encrypt_dev per limb on the same rows"""
+        torch = _torch()
+        n = self.param.n
+        msg = np.ascontiguousarray(m, dtype=np.int64).reshape(-1, n)
+        batch = msg.shape[0]
+        if self._next_row + batch > self.ENCRYPT_ROWS:
+            raise ValueError("encrypt: this seed's 2^56 encryption rows are used up")
+        d_m = torch.from_numpy(msg).cuda()
+        plans = self.param.plans()
+        out = torch.empty((len(plans), 2, batch, n), dtype=torch.int64, device="cuda")
+        for i, plan in enumerate(plans):
+            binding.ckks_encrypt_dev(plan, self.seed, self._next_row, pk.d_evals[i].data_ptr(), d_m.data_ptr(), n, self._cdt_ptr(), self._m, out[i].data_ptr(), batch)
+            plan.forward_dev(out[i].data_ptr(), out[i].data_ptr(), 2 * batch)
+        self._next_row += batch
+        return RnsCiphertext(self.param, out, self.param.max_level, self.delta if scale is None else scale)
+
+    def decrypt(self, ct):
+        """limb 0 only: exact while |m + e| < q_0 / 2 -> int64 coefficients [batch][n]"""
+        torch = _torch()
+        if ct.param != self.param:
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the ciphertext is not in this key's chain")
+        plan = self.param.plans(0)[0]
+        coef = torch.empty_like(ct.d[0])
+        plan.inverse_dev(ct.d[0].data_ptr(), coef.data_ptr(), 2 * ct.batch)
+        out = torch.empty((ct.batch, self.param.n), dtype=torch.int64, device="cuda")
+        binding.ckks_decrypt_dev(plan, self.d_s_evals[0].data_ptr(), coef.data_ptr(), out.data_ptr(), ct.batch)
+        return out.cpu().numpy()
+
+    def encode_and_encrypt(self, pk, z):
+        return self.encrypt(pk, self.encoder.encode(z))
+
+    def decrypt_and_decode(self, ct):
+        return self.encoder.decode(self.decrypt(ct), ct.scale)

@@ -1,0 +1,465 @@
+// ckks_eval.hip — the CKKS evaluator on an RNS modulus chain: the eval-domain tensor, the basis lift between
+// limbs, the key-switch accumulation against a hybrid relinearisation key with one special prime, and the divide-and-round
+// that drops a limb (the special prime after a key switch, the top limb in a rescale).
+//
+//   chain      primes q_0 .. q_L (1 <= L + 1 <= 8) and one special prime P >= max q_i, all distinct, one plan each, same n
+//   ciphertext [limb][2][batch][n] evals (the engine's bit-reversed order), canonical; level l = limbs 0 .. l, k = l + 1
+//   tensor     per limb: d0 = a0 b0, d1 = a0 b1 + a1 b0 (one reduction of the 128-bit sum), d2 = a1 b1: [limb][3][batch][n]
+//   lift       a coefficient-domain residue x mod q_j, centred (x - q_j where x > floor(q_j / 2)), reduced modulo q_i
+//   rlk        [j][i][2][n] evals, j <= L, i in {0 .. L, P}: (-a_ji s + e_j + [i = j] (P mod q_j) s^2, a_ji) mod q_i
+//   relin      inverse d2 per limb; lift digit j to every limb i != j of {0 .. l, P}; forward; t_i = sum_j D_ji (.) rlk[j][i];
+//              r_i = (t_i - lift(t_P)) P^-1 mod q_i; out = (d0 + r0, d1 + r1)
+//   rescale    c'_i = (c_i - lift(c_l)) q_l^-1 mod q_i for i < l, both components
+//
+// All kernels are grid-stride and element-wise on fhe_ew_grid, bounds-checked against their element count, plain C++ with
+// vector stores and no scratch.  The transforms are fhe_ntt_forward_dev / fhe_ntt_inverse_dev on the workspace (slot 12),
+// one call per limb and direction over everything of that limb that is ready; a chunk is 2^21 / (n k^2) ciphertexts
+// (2^21 / (n k) for a rescale, which stages 2k slabs a ciphertext).
+#include "bfv_client_kernels.hpp"
+
+using fhe::Mod;
+using fhe::u32;
+using fhe::u64;
+
+namespace fhe {
+
+constexpr u32 kRnsMaxLimbs = 8, kRnsMaxTargets = kRnsMaxLimbs + 1;
+
+// what reduce_any needs of every target of a lift, by value: indexed by unrolled constants only, so it stays in SGPRs
+struct LiftArgs {
+    u64 q[kRnsMaxTargets], onep[kRnsMaxTargets];
+    u64 off[kRnsMaxTargets];   // first word of target t's residues in dst
+    u32 targets;
+};
+
+// dst[off[t] + i] = lift of src[i] modulo q[t] for every target t, the source read once.  SIGNED: src holds signed 64-bit
+// words (a plaintext row); otherwise canonical residues modulo qs, centred first.  The magnitude is reduced by
+// reduce_any's multiplication (x - mulhi(x, floor(2^64 / q)) q lies in [0, 2q) for any 64-bit x), then negated.
+template <bool SIGNED>
+__global__ __launch_bounds__(256) void ckks_rns_lift_kernel(const u64 *__restrict__ src, u64 *__restrict__ dst, u64 count, u64 qs, LiftArgs a) {
+    const u64 stride = (u64)gridDim.x * 256, half = qs >> 1;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        const u64 x = src[i];
+        const bool neg = SIGNED ? (long long)x < 0 : x > half;
+        const u64 mag = SIGNED ? (neg ? 0ull - x : x) : (neg ? qs - x : x);
+#pragma unroll
+        for (u32 t = 0; t < kRnsMaxTargets; t++) {
+            if (t < a.targets) {
+                const u64 q = a.q[t];
+                u64 r = mag - __umul64hi(mag, a.onep[t]) * q;
+                r = r >= q ? r - q : r;
+                dst[a.off[t] + i] = (neg && r) ? q - r : r;
+            }
+        }
+    }
+}
+
+// one limb of the tensor: a, b two components `*_cs` words apart, out three components o_cs apart, `count` words each
+__global__ __launch_bounds__(256) void ckks_rns_tensor_kernel(const u64 *__restrict__ a, u64 a_cs, const u64 *__restrict__ b, u64 b_cs, u64 *__restrict__ out,
+                                                              u64 o_cs, u64 count, Mod m) {
+    const u64 stride = (u64)gridDim.x * 256;
+    const bool wide = (m.q >> 62) != 0;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        const u64 a0 = a[i], a1 = a[a_cs + i], b0 = b[i], b1 = b[b_cs + i];
+        const u128 s = (u128)a0 * b1 + (u128)a1 * b0;                 // two terms below q^2 < 2^126: below 2^127
+        out[i] = bfv_mulmod(a0, b0, m);
+        out[o_cs + i] = wide ? reduce128_63((u64)(s >> 64), (u64)s, m) : reduce128((u64)(s >> 64), (u64)s, m);
+        out[2 * o_cs + i] = bfv_mulmod(a1, b1, m);
+    }
+}
+
+// One target limb of the key switch: out[c][i] = sum_{j < k} D_j[i] key[j][c][i mod n], c = 0, 1, `count` words a component.
+// Digit j is `own` for j = own_j (the limb's own d2 evals, never lifted) and dig + (j - (j > own_j)) dig_stride otherwise; the
+// key row of digit j is key + j key_stride, [2][n], shared by the batch.
+// Overflow: operands are canonical, so a term is below q^2.  q < 2^62: k <= 8 terms below 2^124 sum to less than 2^127 and
+// the accumulators fold once, at the end.  q >= 2^62: a term is below 2^126, so the accumulators fold before every term of
+// even index j >= 2 (kMacChunk63 = 2): a canonical carry-over below 2^63 and two terms stay below 2^127 + 2^63 < 2^128.
+__global__ __launch_bounds__(256) void ckks_rns_keymac_kernel(const u64 *__restrict__ dig, u64 dig_stride, const u64 *__restrict__ own, u32 own_j,
+                                                              const u64 *__restrict__ key, u64 key_stride, u64 *__restrict__ out, u32 k, u32 L, u64 count,
+                                                              Mod m) {
+    const u64 stride = (u64)gridDim.x * 256, n = 1ull << L;
+    const bool wide = (m.q >> 62) != 0;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        const u64 x = i & (n - 1);
+        MacAcc a0, a1;
+        for (u32 j = 0; j < k; j++) {
+            if (wide && j && (j % kMacChunk63) == 0) {
+                a0.fold63(m);
+                a1.fold63(m);
+            }
+            const u64 d = j == own_j ? own[i] : dig[(u64)(j - (j > own_j ? 1u : 0u)) * dig_stride + i];
+            const u64 *__restrict__ kp = key + (u64)j * key_stride + x;
+            a0.mac(d, kp[0]);
+            a1.mac(d, kp[n]);
+        }
+        out[i] = wide ? a0.fold63(m) : a0.fold(m);
+        out[count + i] = wide ? a1.fold63(m) : a1.fold(m);
+    }
+}
+
+// out = (x - t) inv (+ add) mod q over two components of `count` words, each operand's components `*_cs` words apart
+__global__ __launch_bounds__(256) void ckks_rns_divround_kernel(const u64 *__restrict__ x, u64 x_cs, const u64 *__restrict__ t, u64 t_cs,
+                                                                const u64 *__restrict__ add, u64 add_cs, u64 *__restrict__ out, u64 out_cs, u64 count, u64 inv,
+                                                                Mod m) {
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < 2 * count; i += stride) {
+        const u64 c = i >= count ? 1u : 0u, e = i - c * count;
+        u64 v = bfv_mulmod(sub63(x[c * x_cs + e], t[c * t_cs + e], m), inv, m);
+        if (add) v = add63(v, add[c * add_cs + e], m);
+        out[c * out_cs + e] = v;
+    }
+}
+
+// the diagonal term of the relinearisation key, in evals: pk0 += c s^2 (c = P mod q_j)
+__global__ __launch_bounds__(256) void ckks_rns_keyterm_kernel(u64 *__restrict__ pk0, const u64 *__restrict__ s_evals, u64 c, u64 n, Mod m) {
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+        const u64 s = s_evals[i];
+        pk0[i] = add63(pk0[i], bfv_mulmod(c, bfv_mulmod(s, s, m), m), m);
+    }
+}
+
+}  // namespace fhe
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kCkksEvalSlot = 12;   // fhe_workspace_get slot (11 is the CKKS client's)
+
+struct Chain {
+    unsigned k = 0;                                  // limbs in use
+    u64 n = 0;
+    u32 L = 0;
+    const fhe_ntt_plan *p[fhe::kRnsMaxTargets] = {};   // p[k] is the special prime's plan where the call has one
+};
+
+u64 pow_mod(u64 b, u64 e, u64 q) {
+    u64 r = 1;
+    for (b %= q; e; e >>= 1) {
+        if (e & 1) r = (u64)((unsigned __int128)r * b % q);
+        b = (u64)((unsigned __int128)b * b % q);
+    }
+    return r;
+}
+u64 inv_mod(u64 a, u64 q) { return pow_mod(a % q, q - 2, q); }   // q prime, a not a multiple of q
+
+// plans[0 .. limbs) and, where the entry point takes one, the special prime: FHE_E_NULL, then the limb count, the ring, the
+// repeated moduli, P >= max q_i
+int check_chain(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, bool want_special, Chain *c, const char *who) {
+    if (!plans) return fhe_fail(FHE_E_NULL, "%s: plans is NULL", who);
+    if (limbs < 1 || limbs > fhe::kRnsMaxLimbs) return fhe_fail(FHE_E_INVALID, "%s: limbs=%u must be in [1, 8]", who, limbs);
+    for (unsigned i = 0; i < limbs; i++)
+        if (!plans[i]) return fhe_fail(FHE_E_NULL, "%s: plan %u is NULL", who, i);
+    if (want_special && !special) return fhe_fail(FHE_E_NULL, "%s: the special prime's plan is NULL", who);
+    c->k = limbs;
+    c->n = plans[0]->n;
+    c->L = plans[0]->log_n;
+    for (unsigned i = 0; i < limbs; i++) c->p[i] = plans[i];
+    const unsigned all = limbs + (want_special ? 1u : 0u);
+    if (want_special) c->p[limbs] = special;
+    for (unsigned i = 1; i < all; i++)
+        if (c->p[i]->n != c->n) return fhe_fail(FHE_E_PARAM_MISMATCH, "%s: plan %u has n=%llu, plan 0 n=%llu", who, i, (unsigned long long)c->p[i]->n, (unsigned long long)c->n);
+    if (c->n < 2) return fhe_fail(FHE_E_BAD_N, "%s: n must be at least 2", who);
+    for (unsigned i = 0; i < all; i++)
+        for (unsigned j = 0; j < i; j++)
+            if (c->p[i]->q == c->p[j]->q) return fhe_fail(FHE_E_INVALID, "%s: modulus %llu is repeated in the chain", who, (unsigned long long)c->p[i]->q);
+    if (want_special)
+        for (unsigned i = 0; i < limbs; i++)
+            if (special->q < c->p[i]->q) return fhe_fail(FHE_E_INVALID, "%s: the special prime must not be below a chain prime", who);
+    return FHE_OK;
+}
+
+// ciphertexts of a chunk: 2^21 / (n k^2), at least one
+u64 chunk_rows(const Chain &c, u64 batch) { return std::min<u64>(batch, std::max<u64>(1, (kChunkWords >> c.L) / ((u64)c.k * c.k))); }
+// a rescale stages 2k slabs a ciphertext, not k^2 + 8k + 2: its chunk is 2^21 / (n k) ciphertexts, at least one
+u64 rescale_chunk_rows(const Chain &c, u64 batch) { return std::min<u64>(batch, std::max<u64>(1, (kChunkWords >> c.L) / (u64)c.k)); }
+// words of workspace per ciphertext of a chunk: tensor 3k, digits k, lifted digits k^2, t 2(k + 1), lifted t_P 2k
+u64 words_per_row(const Chain &c) { return ((u64)c.k * c.k + 8ull * c.k + 2) * c.n; }
+
+int lift_launch(bool is_signed, const u64 *src, u64 *dst, u64 count, u64 qs, const fhe::LiftArgs &a, u32 L, hipStream_t st) {
+    if (a.targets == 0) return FHE_OK;
+    return is_signed ? launch_named("ckks_rns_lift", "ckks_rns_lift_kernel", (int)L, st, fhe::ckks_rns_lift_kernel<true>, fhe_ew_grid(count), 256, src, dst, count, qs, a)
+                     : launch_named("ckks_rns_lift", "ckks_rns_lift_kernel", (int)L, st, fhe::ckks_rns_lift_kernel<false>, fhe_ew_grid(count), 256, src, dst, count, qs, a);
+}
+void lift_target(fhe::LiftArgs *a, const fhe_ntt_plan *p, u64 off) {
+    a->q[a->targets] = p->q;
+    a->onep[a->targets] = p->mod.onep;
+    a->off[a->targets] = off;
+    a->targets++;
+}
+
+// the transforms take 16-byte aligned rows and the ABI promises 8: a misaligned source is copied into the workspace first
+int inverse_into(const fhe_ntt_plan *p, const u64 *src, u64 *dst, u64 polys, hipStream_t st) {
+    if (fhe_misaligned(src)) {
+        HIP_TRY(hipMemcpyAsync(dst, src, polys * p->n * 8, hipMemcpyDeviceToDevice, st));
+        src = dst;
+    }
+    return fhe_ntt_inverse_dev(p, src, dst, polys, st);
+}
+
+int tensor_rows(const Chain &c, const u64 *a, const u64 *b, u64 batch, u64 r0, u64 *out, u64 o_rows, u64 o_r0, u64 cr, hipStream_t st) {
+    const u64 n = c.n;
+    for (unsigned i = 0; i < c.k; i++) {
+        const int rc = launch("ckks_rns_tensor", (int)c.L, st, fhe::ckks_rns_tensor_kernel, fhe_ew_grid(cr * n), 256, a + ((u64)i * 2 * batch + r0) * n, batch * n,
+                              b + ((u64)i * 2 * batch + r0) * n, batch * n, out + ((u64)i * 3 * o_rows + o_r0) * n, o_rows * n, cr * n, c.p[i]->mod);
+        if (rc != FHE_OK) return rc;
+    }
+    return FHE_OK;
+}
+
+// rows d_r0 .. d_r0 + cr of d [k][3][d_rows][n] -> rows o_r0 .. of out [k][2][o_rows][n]; W holds (k^2 + 5k + 2) cr n words
+int relin_rows(const Chain &c, const u64 *rlk, unsigned key_limbs, const u64 *pinv, const u64 *d, u64 d_rows, u64 d_r0, u64 *out, u64 o_rows, u64 o_r0, u64 cr,
+               u64 *W, hipStream_t st) {
+    const u64 n = c.n, slab = cr * n;
+    const unsigned k = c.k;
+    u64 *C = W, *D = C + k * slab, *T = D + (u64)k * k * slab, *E = T + 2ull * (k + 1) * slab;
+    auto d_at = [&](unsigned limb, unsigned comp) { return d + (((u64)limb * 3 + comp) * d_rows + d_r0) * n; };
+    auto D_of = [&](unsigned i) { return D + (u64)i * (k - 1) * slab; };             // limb i < k holds k - 1 lifted digits, P all k
+    int rc;
+    for (unsigned j = 0; j < k; j++)
+        if ((rc = inverse_into(c.p[j], d_at(j, 2), C + j * slab, cr, st)) != FHE_OK) return rc;
+    for (unsigned j = 0; j < k; j++) {
+        fhe::LiftArgs a{};
+        for (unsigned i = 0; i <= k; i++)
+            if (i != j) lift_target(&a, c.p[i], (u64)(D_of(i) - D) + (u64)(i < k && j > i ? j - 1 : j) * slab);
+        if ((rc = lift_launch(false, C + j * slab, D, slab, c.p[j]->q, a, c.L, st)) != FHE_OK) return rc;
+    }
+    for (unsigned i = 0; i <= k; i++) {
+        const u64 polys = (u64)(i < k ? k - 1 : k) * cr;
+        if (polys && (rc = fhe_ntt_forward_dev(c.p[i], D_of(i), D_of(i), polys, st)) != FHE_OK) return rc;
+    }
+    for (unsigned i = 0; i <= k; i++) {
+        const u64 *key = rlk + (u64)(i < k ? i : key_limbs) * 2 * n;
+        if ((rc = launch("ckks_rns_keymac", (int)c.L, st, fhe::ckks_rns_keymac_kernel, fhe_ew_grid(slab), 256, D_of(i), slab, i < k ? d_at(i, 2) : nullptr, i, key,
+                         (u64)(key_limbs + 1) * 2 * n, T + 2ull * i * slab, k, c.L, slab, c.p[i]->mod)) != FHE_OK)
+            return rc;
+    }
+    u64 *TP = T + 2ull * k * slab;
+    if ((rc = fhe_ntt_inverse_dev(c.p[k], TP, TP, 2 * cr, st)) != FHE_OK) return rc;
+    fhe::LiftArgs a{};
+    for (unsigned i = 0; i < k; i++) lift_target(&a, c.p[i], 2ull * i * slab);
+    if ((rc = lift_launch(false, TP, E, 2 * slab, c.p[k]->q, a, c.L, st)) != FHE_OK) return rc;
+    for (unsigned i = 0; i < k; i++)
+        if ((rc = fhe_ntt_forward_dev(c.p[i], E + 2ull * i * slab, E + 2ull * i * slab, 2 * cr, st)) != FHE_OK) return rc;
+    for (unsigned i = 0; i < k; i++)
+        if ((rc = launch("ckks_rns_divround", (int)c.L, st, fhe::ckks_rns_divround_kernel, fhe_ew_grid(2 * slab), 256, T + 2ull * i * slab, slab, E + 2ull * i * slab,
+                         slab, d_at(i, 0), d_rows * n, out + ((u64)i * 2 * o_rows + o_r0) * n, o_rows * n, slab, pinv[i], c.p[i]->mod)) != FHE_OK)
+            return rc;
+    return FHE_OK;
+}
+
+int check_key_limbs(const Chain &c, unsigned key_limbs, const char *who) {
+    if (key_limbs < c.k || key_limbs > fhe::kRnsMaxLimbs)
+        return fhe_fail(FHE_E_INVALID, "%s: key_limbs=%u must be at least limbs=%u and at most 8", who, key_limbs, c.k);
+    return FHE_OK;
+}
+
+void special_inverses(const Chain &c, u64 *pinv) {
+    for (unsigned i = 0; i < c.k; i++) pinv[i] = inv_mod(c.p[c.k]->q, c.p[i]->q);
+}
+
+}  // namespace
+
+extern "C" size_t fhe_ckks_rns_workspace_bytes(uint64_t n, unsigned limbs, size_t batch) {
+    if (n < 2 || (n & (n - 1)) != 0 || n > (1ull << 19) || limbs < 1 || limbs > fhe::kRnsMaxLimbs || batch == 0) return 0;
+    Chain c;
+    c.k = limbs;
+    c.n = n;
+    c.L = log2_of(n);
+    return (size_t)(std::max<u64>(words_per_row(c) * chunk_rows(c, batch), 2ull * limbs * n * rescale_chunk_rows(c, batch)) * 8);
+}
+
+extern "C" int fhe_ckks_rns_from_i64_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *d_in, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_rns_from_i64_dev";
+    Chain c;
+    int rc = check_chain(plans, limbs, nullptr, false, &c, who);
+    if (rc != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, (u64)c.k * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_in) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    if (overlaps_any(d_out, (u64)c.k * batch * n * 8, {{d_in, (u64)batch * n * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the rows", who);
+    int dev;
+    if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    u64 *out = (u64 *)d_out;
+    const bool direct = !fhe_misaligned(d_out);                      // residues land in d_out and are transformed in place
+    const u64 cb = direct ? (u64)batch : chunk_rows(c, batch);
+    u64 *W = nullptr;
+    if (!direct) {
+        void *w = nullptr;
+        if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)((u64)c.k * cb * n * 8), st, &w)) != FHE_OK) return rc;
+        W = (u64 *)w;
+    }
+    for (u64 r0 = 0; r0 < batch; r0 += cb) {
+        const u64 cr = std::min<u64>(cb, batch - r0);
+        fhe::LiftArgs a{};
+        for (unsigned i = 0; i < c.k; i++) lift_target(&a, c.p[i], direct ? (u64)i * batch * n : (u64)i * cr * n);
+        u64 *dst = direct ? out : W;
+        if ((rc = lift_launch(true, (const u64 *)d_in + r0 * n, dst, cr * n, 0, a, c.L, st)) != FHE_OK) return rc;
+        for (unsigned i = 0; i < c.k; i++) {
+            u64 *row = dst + a.off[i];
+            if ((rc = fhe_ntt_forward_dev(c.p[i], row, row, cr, st)) != FHE_OK) return rc;
+            if (!direct) HIP_TRY(hipMemcpyAsync(out + ((u64)i * batch + r0) * n, row, cr * n * 8, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    return FHE_OK;
+}
+
+extern "C" int fhe_ckks_rns_relin_key_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const uint8_t *seed, uint64_t first_row,
+                                          const void *d_s, const void *d_cdt, unsigned m, void *d_rlk, void *hip_stream) {
+    const char *who = "fhe_ckks_rns_relin_key_dev";
+    Chain c;
+    int rc = check_chain(plans, limbs, special, true, &c, who);
+    if (rc != FHE_OK) return rc;
+    if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
+    const u64 n = c.n;
+    const unsigned k = c.k, cols = k + 1;
+    u64 qmin = c.p[0]->q;
+    for (unsigned i = 1; i < k; i++) qmin = std::min<u64>(qmin, c.p[i]->q);
+    if ((rc = check_cdt_shape(d_cdt, m, qmin, who)) != FHE_OK) return rc;
+    if (first_row >= kRowLimit - k) return fhe_fail(FHE_E_INVALID, "%s: first_row + limbs passes 2^63", who);
+    if (!d_s || !d_rlk) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_s) || misaligned8(d_rlk)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 rlk_words = (u64)k * cols * 2 * n;
+    if (overlaps_any(d_rlk, rlk_words * 8, {{d_s, (u64)cols * n * 8}, {d_cdt, (u64)m * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_rlk overlaps the key or the error table", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
+    void *w = nullptr;
+    if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(4 * n * 8), st, &w)) != FHE_OK) return rc;
+    u64 *PK = (u64 *)w, *S = PK + 2 * n, *SE = S + n;            // one key row, the limb's secret (16-byte aligned) and its evals
+    for (unsigned j = 0; j < k; j++) {
+        for (unsigned i = 0; i < cols; i++) {
+            const fhe_ntt_plan *p = c.p[i];
+            HIP_TRY(hipMemcpyAsync(S, (const u64 *)d_s + (u64)i * n, n * 8, hipMemcpyDeviceToDevice, st));
+            if ((rc = fhe_ckks_public_key_dev(p, seed, first_row + j, S, d_cdt, m, PK, st)) != FHE_OK) return rc;
+            if ((rc = fhe_ntt_forward_dev(p, PK, PK, 2, st)) != FHE_OK) return rc;
+            if (i == j) {
+                if ((rc = fhe_ntt_forward_dev(p, S, SE, 1, st)) != FHE_OK) return rc;
+                if ((rc = launch("ckks_rns_keyterm", (int)c.L, st, fhe::ckks_rns_keyterm_kernel, fhe_ew_grid(n), 256, PK, SE, special->q % p->q, n, p->mod)) != FHE_OK)
+                    return rc;
+            }
+            HIP_TRY(hipMemcpyAsync((u64 *)d_rlk + ((u64)j * cols + i) * 2 * n, PK, 2 * n * 8, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    return FHE_OK;
+}
+
+extern "C" int fhe_ckks_rns_tensor_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *d_a, const void *d_b, void *d_out, size_t batch,
+                                       void *hip_stream) {
+    const char *who = "fhe_ckks_rns_tensor_dev";
+    Chain c;
+    int rc = check_chain(plans, limbs, nullptr, false, &c, who);
+    if (rc != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, 3ull * c.k * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_a || !d_b || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_a) || misaligned8(d_b) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 in_bytes = 2ull * c.k * batch * n * 8;
+    if (overlaps_any(d_out, 3ull * c.k * batch * n * 8, {{d_a, in_bytes}, {d_b, in_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an operand", who);
+    int dev;
+    if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
+    return tensor_rows(c, (const u64 *)d_a, (const u64 *)d_b, batch, 0, (u64 *)d_out, batch, 0, batch, (hipStream_t)hip_stream);
+}
+
+extern "C" int fhe_ckks_rns_relinearize_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *d_rlk, unsigned key_limbs,
+                                            const void *d_d, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_rns_relinearize_dev";
+    Chain c;
+    int rc = check_chain(plans, limbs, special, true, &c, who);
+    if (rc != FHE_OK) return rc;
+    if ((rc = check_key_limbs(c, key_limbs, who)) != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, 3ull * c.k * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_rlk || !d_d || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_rlk) || misaligned8(d_d) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 rlk_bytes = (u64)key_limbs * (key_limbs + 1) * 2 * n * 8;
+    if (overlaps_any(d_out, 2ull * c.k * batch * n * 8, {{d_d, 3ull * c.k * batch * n * 8}, {d_rlk, rlk_bytes}}))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the tensor or the key", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const u64 cb = chunk_rows(c, batch);
+    void *w = nullptr;
+    if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(words_per_row(c) * cb * 8), st, &w)) != FHE_OK) return rc;
+    u64 pinv[fhe::kRnsMaxLimbs];
+    special_inverses(c, pinv);
+    for (u64 r0 = 0; r0 < batch; r0 += cb) {
+        const u64 cr = std::min<u64>(cb, batch - r0);
+        if ((rc = relin_rows(c, (const u64 *)d_rlk, key_limbs, pinv, (const u64 *)d_d, batch, r0, (u64 *)d_out, batch, r0, cr, (u64 *)w, st)) != FHE_OK) return rc;
+    }
+    return FHE_OK;
+}
+
+extern "C" int fhe_ckks_rns_mul_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *d_rlk, unsigned key_limbs,
+                                    const void *d_a, const void *d_b, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_rns_mul_dev";
+    Chain c;
+    int rc = check_chain(plans, limbs, special, true, &c, who);
+    if (rc != FHE_OK) return rc;
+    if ((rc = check_key_limbs(c, key_limbs, who)) != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, 3ull * c.k * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_rlk || !d_a || !d_b || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_rlk) || misaligned8(d_a) || misaligned8(d_b) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 ct_bytes = 2ull * c.k * batch * n * 8, rlk_bytes = (u64)key_limbs * (key_limbs + 1) * 2 * n * 8;
+    if (overlaps_any(d_out, ct_bytes, {{d_a, ct_bytes}, {d_b, ct_bytes}, {d_rlk, rlk_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an operand or the key", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const u64 cb = chunk_rows(c, batch);
+    void *w = nullptr;
+    if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(words_per_row(c) * cb * 8), st, &w)) != FHE_OK) return rc;
+    u64 pinv[fhe::kRnsMaxLimbs];
+    special_inverses(c, pinv);
+    for (u64 r0 = 0; r0 < batch; r0 += cb) {
+        const u64 cr = std::min<u64>(cb, batch - r0);
+        u64 *Dt = (u64 *)w, *W = Dt + 3ull * c.k * cr * n;           // the chunk's tensor, then relin_rows' buffers
+        if ((rc = tensor_rows(c, (const u64 *)d_a, (const u64 *)d_b, batch, r0, Dt, cr, 0, cr, st)) != FHE_OK) return rc;
+        if ((rc = relin_rows(c, (const u64 *)d_rlk, key_limbs, pinv, Dt, cr, 0, (u64 *)d_out, batch, r0, cr, W, st)) != FHE_OK) return rc;
+    }
+    return FHE_OK;
+}
+
+extern "C" int fhe_ckks_rns_rescale_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *d_in, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_rns_rescale_dev";
+    Chain c;
+    int rc = check_chain(plans, limbs, nullptr, false, &c, who);
+    if (rc != FHE_OK) return rc;
+    if (limbs < 2) return fhe_fail(FHE_E_INVALID, "%s: a ciphertext of one limb cannot be rescaled", who);
+    if (batch == 0) return FHE_OK;
+    const u64 n = c.n;
+    const unsigned k = c.k, top = k - 1;
+    if (!mul_fits((u64)batch, 2ull * k * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_in) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    if (overlaps_any(d_out, 2ull * top * batch * n * 8, {{d_in, 2ull * k * batch * n * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the ciphertexts", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const u64 cb = rescale_chunk_rows(c, batch);
+    void *w = nullptr;
+    if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(2ull * k * cb * n * 8), st, &w)) != FHE_OK) return rc;
+    u64 qinv[fhe::kRnsMaxLimbs];
+    for (unsigned i = 0; i < top; i++) qinv[i] = inv_mod(c.p[top]->q, c.p[i]->q);
+    const u64 *in = (const u64 *)d_in;
+    u64 *out = (u64 *)d_out;
+    for (u64 r0 = 0; r0 < batch; r0 += cb) {
+        const u64 cr = std::min<u64>(cb, batch - r0), slab = cr * n;
+        u64 *C = (u64 *)w, *E = C + 2 * slab;
+        const u64 *t0 = in + ((u64)top * 2 * batch + r0) * n;         // the top limb's two components, batch n apart
+        if (cr == batch) {
+            if ((rc = inverse_into(c.p[top], t0, C, 2 * cr, st)) != FHE_OK) return rc;
+        } else {
+            if ((rc = inverse_into(c.p[top], t0, C, cr, st)) != FHE_OK) return rc;
+            if ((rc = inverse_into(c.p[top], t0 + batch * n, C + slab, cr, st)) != FHE_OK) return rc;
+        }
+        fhe::LiftArgs a{};
+        for (unsigned i = 0; i < top; i++) lift_target(&a, c.p[i], 2ull * i * slab);
+        if ((rc = lift_launch(false, C, E, 2 * slab, c.p[top]->q, a, c.L, st)) != FHE_OK) return rc;
+        for (unsigned i = 0; i < top; i++)
+            if ((rc = fhe_ntt_forward_dev(c.p[i], E + 2ull * i * slab, E + 2ull * i * slab, 2 * cr, st)) != FHE_OK) return rc;
+        for (unsigned i = 0; i < top; i++)
+            if ((rc = launch("ckks_rns_divround", (int)c.L, st, fhe::ckks_rns_divround_kernel, fhe_ew_grid(2 * slab), 256, in + ((u64)i * 2 * batch + r0) * n, batch * n,
+                             E + 2ull * i * slab, slab, nullptr, 0, out + ((u64)i * 2 * batch + r0) * n, batch * n, slab, qinv[i], c.p[i]->mod)) != FHE_OK)
+                return rc;
+    }
+    return FHE_OK;
+}

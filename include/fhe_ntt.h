@@ -623,6 +623,45 @@ int fhe_ckks_encrypt_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t
 int fhe_ckks_decrypt_dev(const fhe_ntt_plan *plan, const void *d_s_evals, const void *d_ct, void *d_out, size_t batch,
                          void *hip_stream);
 
+/* ---- CKKS on an RNS modulus chain: ct x ct, relinearisation, rescaling (ckks_eval.hip) ----
+ * A chain is `limbs` plans (1 <= limbs <= 8) of distinct primes q_0 .. and the same n, passed as a HOST array `plans`; the
+ * entry points that switch keys also take the plan of one special prime P >= max q_i, distinct from all of them.  A
+ * ciphertext at `limbs` limbs is d [limbs][2][batch][n]: evaluation domain (the order of fhe_ntt_forward_dev), canonical
+ * residues; dropping the top limb is truncation.  lift(x mod q_j -> q_i): x centred (x - q_j where x > floor(q_j / 2)),
+ * reduced modulo q_i.
+ *   fhe_ckks_rns_from_i64_dev     d_out [limbs][batch][n] = evals of the signed 64-bit rows d_in [batch][n] modulo each prime
+ *   fhe_ckks_rns_relin_key_dev    d_rlk [limbs][limbs + 1][2][n] evals, column i < limbs modulo q_i, column `limbs` modulo P:
+ *            rlk[j][i] = (-a_ji s + e_j + [i = j] (P mod q_j) s^2, a_ji) = fhe_ckks_public_key_dev on plan i with row
+ *            first_row + j, plus the diagonal term.  d_s [limbs + 1][n]: fhe_ckks_secret_key_dev of one (seed, key_row) under
+ *            every plan, the special prime's last.
+ *   fhe_ckks_rns_tensor_dev       d_out [limbs][3][batch][n]: d0 = a0 b0, d1 = a0 b1 + a1 b0, d2 = a1 b1 per limb
+ *   fhe_ckks_rns_relinearize_dev  d_out [limbs][2][batch][n] from a tensor d_d: digit j = d2 modulo q_j in coefficients,
+ *            lifted to every limb of {0 .. limbs - 1, P}; t_i = sum_j D_ji rlk[j][i]; r_i = (t_i - lift(t_P)) P^-1 mod q_i;
+ *            out = (d0 + r0, d1 + r1).  d_rlk was made for key_limbs >= limbs limbs: its digits j < limbs and columns
+ *            {0 .. limbs - 1, key_limbs} are read, so one key serves every level.
+ *   fhe_ckks_rns_mul_dev          the two above in one call, the tensor kept in the library workspace
+ *   fhe_ckks_rns_rescale_dev      d_out [limbs - 1][2][batch][n]: c'_i = (c_i - lift(c_top)) q_top^-1 mod q_i, top = limbs - 1
+ *   fhe_ckks_rns_workspace_bytes  the most library workspace one of these calls takes at (n, limbs, batch); 0 for a shape they refuse
+ * Device buffers need 8-byte alignment.  FHE_E_NULL for a NULL pointer (a plan included); FHE_E_PARAM_MISMATCH for plans
+ * whose n differ; FHE_E_INVALID for limbs outside [1, 8], a repeated modulus, P < max q_i, key_limbs < limbs or > 8, an
+ * output that overlaps an input, a rescale at one limb, and the table and row-range conditions of the BFV block.  Nothing
+ * is written on rejection; batch = 0 is a no-op. */
+int fhe_ckks_rns_from_i64_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *d_in, void *d_out, size_t batch,
+                              void *hip_stream);
+int fhe_ckks_rns_relin_key_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special,
+                               const uint8_t *seed, uint64_t first_row, const void *d_s, const void *d_cdt, unsigned m,
+                               void *d_rlk, void *hip_stream);
+int fhe_ckks_rns_tensor_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *d_a, const void *d_b, void *d_out,
+                            size_t batch, void *hip_stream);
+int fhe_ckks_rns_relinearize_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special,
+                                 const void *d_rlk, unsigned key_limbs, const void *d_d, void *d_out, size_t batch,
+                                 void *hip_stream);
+int fhe_ckks_rns_mul_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *d_rlk,
+                         unsigned key_limbs, const void *d_a, const void *d_b, void *d_out, size_t batch, void *hip_stream);
+int fhe_ckks_rns_rescale_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *d_in, void *d_out, size_t batch,
+                             void *hip_stream);
+size_t fhe_ckks_rns_workspace_bytes(uint64_t n, unsigned limbs, size_t batch);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
