@@ -89,7 +89,10 @@ EXPORTS = [
     # CKKS on an RNS modulus chain: ct x ct, relinearisation, rescaling (ckks_eval.hip)
     "fhe_ckks_rns_from_i64_dev", "fhe_ckks_rns_relin_key_dev", "fhe_ckks_rns_tensor_dev", "fhe_ckks_rns_relinearize_dev", "fhe_ckks_rns_mul_dev",
     "fhe_ckks_rns_rescale_dev", "fhe_ckks_rns_workspace_bytes",
+    # CKKS on the RNS chain: slot rotations and conjugation with Galois keys (ckks_eval.hip)
+    "fhe_ckks_galois_evals_dev", "fhe_ckks_rns_galois_key_dev", "fhe_ckks_rns_galois_dev", "fhe_ckks_rns_galois_workspace_bytes",
 ]
+FHE_CKKS_GALOIS_MAX_COUNT = 256              # include/fhe_ntt.h: the most Galois elements of one fhe_ckks_rns_galois_dev call
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
 GATES = {"AND": 0, "NAND": 1, "OR": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -308,6 +311,11 @@ def load_library():
     L.fhe_ckks_rns_rescale_dev.argtypes = [_pp, _uint, _vp, _vp, _sz, _vp]
     L.fhe_ckks_rns_workspace_bytes.argtypes = [_u64, _uint, _sz]
     L.fhe_ckks_rns_workspace_bytes.restype = _sz
+    L.fhe_ckks_galois_evals_dev.argtypes = [_vp, _u64, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_rns_galois_key_dev.argtypes = [_pp, _uint, _vp, ctypes.c_char_p, _u64, _u64, _vp, _vp, _uint, _vp, _vp]
+    L.fhe_ckks_rns_galois_dev.argtypes = [_pp, _uint, _vp, _pp, ctypes.POINTER(_u64), _uint, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_rns_galois_workspace_bytes.argtypes = [_u64, _uint, _sz, _uint]
+    L.fhe_ckks_rns_galois_workspace_bytes.restype = _sz
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -821,6 +829,30 @@ def ckks_rns_rescale_dev(plans, d_in, d_out, batch, stream=None, limbs=None):
 
 def ckks_rns_workspace_bytes(n, limbs, batch):
     return int(load_library().fhe_ckks_rns_workspace_bytes(n, limbs, batch))
+
+
+def ckks_galois_evals_dev(plan, g, d_in, d_out, polys, stream=None):
+    """fhe_ckks_galois_evals_dev: rows [polys][n] of evals under sigma_g, out[x] = in[pi_g(x)]"""
+    _check(load_library().fhe_ckks_galois_evals_dev(_handle(plan), g, d_in, d_out, polys, stream))
+
+
+def ckks_rns_galois_key_dev(plans, special, seed, first_row, g, d_s, d_cdt, m, d_gk, stream=None, limbs=None):
+    """fhe_ckks_rns_galois_key_dev: d_gk [limbs][limbs + 1][2][n] evals from d_s [limbs + 1][n], the diagonal term on sigma_g(s)"""
+    _check(load_library().fhe_ckks_rns_galois_key_dev(_plan_array(plans), len(plans) if limbs is None else limbs, _handle(special), _seed(seed), first_row, g, d_s,
+                                                      d_cdt, m, d_gk, stream))
+
+
+def ckks_rns_galois_dev(plans, special, d_gks, gs, key_limbs, d_in, d_out, batch, stream=None, limbs=None, count=None):
+    """fhe_ckks_rns_galois_dev: [limbs][2][batch][n] -> [count][limbs][2][batch][n], one hoisted digit decomposition for all of
+    gs; d_gks a list of device key pointers (None is passed as NULL, as is a None list)"""
+    keys = None if d_gks is None else (_vp * max(len(d_gks), 1))(*d_gks)
+    els = None if gs is None else (_u64 * max(len(gs), 1))(*gs)
+    _check(load_library().fhe_ckks_rns_galois_dev(_plan_array(plans), len(plans) if limbs is None else limbs, _handle(special), keys, els,
+                                                  len(gs) if count is None else count, key_limbs, d_in, d_out, batch, stream))
+
+
+def ckks_rns_galois_workspace_bytes(n, limbs, batch, count):
+    return int(load_library().fhe_ckks_rns_galois_workspace_bytes(n, limbs, batch, count))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

@@ -242,6 +242,59 @@ class RnsPublicKey:
 SCALE_TOLERANCE = 2.0 ** -20
 
 
+# ---- Galois automorphisms: slot rotations and conjugation ---------------------------------------------------------
+def galois_element(n, step):
+    """the Galois element of a rotation of the n/2 slots by `step` (in the rotation order): 5^(step mod n/2) mod 2n"""
+    return pow(5, int(step) % max(n // 2, 1), 2 * n)
+
+
+def conjugation_element(n):
+    return 2 * n - 1
+
+
+def rotation_order(n):
+    """-> (index, conj): entry t of the rotation order is slot index[t] of the encoder's order, conjugated where conj[t]:
+    u_t = 5^t mod 2n is the exponent of the root at which entry t evaluates, slot i sits at exponent 2i + 1, and an
+    exponent u >= n is the conjugate of 2n - u"""
+    u = np.array([pow(5, t, 2 * n) for t in range(n // 2)], dtype=np.int64)
+    conj = u >= n
+    return np.where(conj, (2 * n - u - 1) // 2, (u - 1) // 2), conj
+
+
+def to_rotation_order(z):
+    """slots [..][n/2] in the encoder's order -> the order in which rotation by `step` is np.roll(w, -step)"""
+    z = np.asarray(z, dtype=np.complex128)
+    idx, conj = rotation_order(2 * z.shape[-1])
+    return np.where(conj, np.conj(z[..., idx]), z[..., idx])
+
+
+def from_rotation_order(w):
+    w = np.asarray(w, dtype=np.complex128)
+    idx, conj = rotation_order(2 * w.shape[-1])
+    z = np.empty_like(w)
+    z[..., idx] = np.where(conj, np.conj(w), w)
+    return z
+
+
+class RnsGaloisKey:
+    """gk_g [j][i][2][n] evals on the device, the shape of a relinearisation key, for the Galois element g"""
+
+    def __init__(self, param, g, d_gk):
+        g = int(g)
+        if g % 2 == 0 or not 0 < g < 2 * param.n:
+            raise ValueError(f"RnsGaloisKey: g={g} must be odd and in [1, 2n)")
+        self.param, self.g, self.d_gk = param, g, d_gk
+
+    @property
+    def is_conjugation(self):
+        return self.g == 2 * self.param.n - 1
+
+    @property
+    def is_rotation(self):
+        """the powers of 5 modulo 2n are the g = 1 (mod 4)"""
+        return self.g % 4 == 1
+
+
 class RnsCiphertext:
     """A device tensor [level + 1][2][batch][n] of evals with its level and float64 scale"""
 
@@ -298,6 +351,34 @@ class RnsCiphertext:
         binding.ckks_rns_rescale_dev(self.param.plans(self.level), self.d.data_ptr(), out.data_ptr(), self.batch)
         return RnsCiphertext(self.param, out, self.level - 1, self.scale / self.param.moduli[self.level])
 
+    def rotate_many(self, gks):
+        """sigma_g of this ciphertext for every key of `gks` from one call (fhe_ckks_rns_galois_dev): the digit decomposition
+        of c1 is shared.  Level and scale are unchanged."""
+        torch = _torch()
+        gks = list(gks)
+        if any(gk.param != self.param for gk in gks):
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "a Galois key is not of this ciphertext's chain")
+        out = torch.empty((len(gks),) + tuple(self.d.shape), dtype=torch.int64, device="cuda")
+        binding.ckks_rns_galois_dev(self.param.plans(self.level), self.param.special_plan(), [gk.d_gk.data_ptr() for gk in gks], [gk.g for gk in gks],
+                                    len(self.param.moduli), self.d.data_ptr(), out.data_ptr(), self.batch)
+        return [RnsCiphertext(self.param, out[r], self.level, self.scale) for r in range(len(gks))]
+
+    def apply_galois(self, gk):
+        """sigma_g with the key's g: (pi_g(c0) + r0, r1), (r0, r1) the key switch of pi_g(c1)"""
+        return self.rotate_many([gk])[0]
+
+    def rotate(self, gk):
+        """the slots, in the rotation order, moved by the key's step; a key that is no rotation key is refused"""
+        if not gk.is_rotation:
+            raise ValueError(f"rotate: g={gk.g} is no power of 5 modulo 2n")
+        return self.apply_galois(gk)
+
+    def conjugate(self, gk):
+        """every slot conjugated; a key of another element is refused"""
+        if not gk.is_conjugation:
+            raise ValueError(f"conjugate: g={gk.g} is not 2n - 1")
+        return self.apply_galois(gk)
+
     def _plain(self, m):
         """signed rows (n,) or (batch, n) -> evals [level + 1][batch][n]"""
         torch = _torch()
@@ -330,16 +411,19 @@ class RnsClientKey:
         [0, 2^56)                    fresh encryptions
         1 2^56 + slot                public_key(slot)
         2 2^56 + 64 slot + j         digit j of relin_key(slot)
+        3 2^56 + 64 slot + j         digit j of galois_key(g, slot)
     A builder refuses a slot (0 <= slot < 2^16) it has used."""
 
     ENCRYPT_ROWS = 1 << 56
     PK_BASE = 1 << 56
     RLK_BASE = 2 << 56
+    GK_BASE = 3 << 56
 
     def __init__(self, seed, param, delta, d_s, d_s_evals, sigma):
         self.seed, self.param, self.delta, self.d_s, self.d_s_evals = bytes(seed), param, float(delta), d_s, d_s_evals
         self.encoder = Encoder(param.n, delta)
         self._next_row, self._pk_slots, self._rlk_slots = 0, set(), set()
+        self._gk_slots = set()
         tab = cdt_table(sigma)
         self._cdt, self._m = (_to_dev(tab) if len(tab) else None), len(tab)
 
@@ -388,6 +472,25 @@ class RnsClientKey:
         binding.ckks_rns_relin_key_dev(self.param.plans(), self.param.special_plan(), self.seed, self.RLK_BASE + 64 * int(slot), self.d_s.data_ptr(), self._cdt_ptr(),
                                        self._m, rlk.data_ptr())
         return RnsRelinKey(self.param, rlk)
+
+    def galois_key(self, g, slot):
+        """the key of sigma_g from rows GK_BASE + 64 slot + j; one slot per key, whatever its g"""
+        torch = _torch()
+        g = int(g)
+        if g % 2 == 0 or not 0 < g < 2 * self.param.n:
+            raise ValueError(f"galois_key: g={g} must be odd and in [1, 2n)")
+        self._take(self._gk_slots, slot, "galois_key")
+        k = len(self.param.moduli)
+        gk = torch.empty((k, k + 1, 2, self.param.n), dtype=torch.int64, device="cuda")
+        binding.ckks_rns_galois_key_dev(self.param.plans(), self.param.special_plan(), self.seed, self.GK_BASE + 64 * int(slot), g, self.d_s.data_ptr(),
+                                        self._cdt_ptr(), self._m, gk.data_ptr())
+        return RnsGaloisKey(self.param, g, gk)
+
+    def rotation_key(self, step, slot):
+        return self.galois_key(galois_element(self.param.n, step), slot)
+
+    def conjugation_key(self, slot):
+        return self.galois_key(conjugation_element(self.param.n), slot)
 
     def encrypt(self, pk, m, scale=None):
         """m int64 coefficients (n,) or (batch, n) -> RnsCiphertext at the top level: fhe_ckks_encrypt_dev per limb on the same rows"""

@@ -10,6 +10,10 @@
 //   relin      inverse d2 per limb; lift digit j to every limb i != j of {0 .. l, P}; forward; t_i = sum_j D_ji (.) rlk[j][i];
 //              r_i = (t_i - lift(t_P)) P^-1 mod q_i; out = (d0 + r0, d1 + r1)
 //   rescale    c'_i = (c_i - lift(c_l)) q_l^-1 mod q_i for i < l, both components
+//   galois      sigma_g: a(X) -> a(X^g), g odd; in evals an index permutation, sigma_g(a)^[x] = a^[pi_g(x)].  gk_g is
+//              rlk with sigma_g(s) for s^2; apply = the key switch of pi_g(c1) plus pi_g(c0).  The digits are those of the
+//              unpermuted c1, computed once for any number of g (the automorphism commutes with the transforms and the odd,
+//              coefficient-wise lift), and pi_g is folded into the key sums' and the divide-and-round's reads
 //
 // All kernels are grid-stride and element-wise on fhe_ew_grid, bounds-checked against their element count, plain C++ with
 // vector stores and no scratch.  The transforms are fhe_ntt_forward_dev / fhe_ntt_inverse_dev on the workspace (slot 12),
@@ -54,6 +58,23 @@ __global__ __launch_bounds__(256) void ckks_rns_lift_kernel(const u64 *__restric
     }
 }
 
+// pi_g(x) of DESIGN.md §23: index x of the engine's order holds the value at psi^(2 brv_L(x) + 1), so sigma_g(a)^[x] = a^[pi_g(x)]
+// with pi_g(x) = brv_L((((2 brv_L(x) + 1) g mod 2n) - 1) / 2).  2n divides 2^32, so the 32-bit product may wrap; L >= 1, so
+// the shifts by 32 - L are defined.  pi_g maps an aligned block of 2^t indices onto an aligned block of 2^t indices.
+__device__ __forceinline__ u32 galois_index(u32 x, u32 g, u32 L) {
+    const u32 e = (2u * (__brev(x) >> (32u - L)) + 1u) * g;
+    return __brev((e & ((2u << L) - 1u)) >> 1) >> (32u - L);
+}
+
+// the bare automorphism on `count` words of rows of n = 2^L evals: out[r n + x] = in[r n + pi_g(x)]; count is a multiple of n
+__global__ __launch_bounds__(256) void ckks_rns_galois_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, u64 count, u32 g, u32 L) {
+    const u64 stride = (u64)gridDim.x * 256, n = 1ull << L;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        const u64 x = i & (n - 1);
+        out[i] = in[i - x + galois_index((u32)x, g, L)];
+    }
+}
+
 // one limb of the tensor: a, b two components `*_cs` words apart, out three components o_cs apart, `count` words each
 __global__ __launch_bounds__(256) void ckks_rns_tensor_kernel(const u64 *__restrict__ a, u64 a_cs, const u64 *__restrict__ b, u64 b_cs, u64 *__restrict__ out,
                                                               u64 o_cs, u64 count, Mod m) {
@@ -74,20 +95,23 @@ __global__ __launch_bounds__(256) void ckks_rns_tensor_kernel(const u64 *__restr
 // Overflow: operands are canonical, so a term is below q^2.  q < 2^62: k <= 8 terms below 2^124 sum to less than 2^127 and
 // the accumulators fold once, at the end.  q >= 2^62: a term is below 2^126, so the accumulators fold before every term of
 // even index j >= 2 (kMacChunk63 = 2): a canonical carry-over below 2^63 and two terms stay below 2^127 + 2^63 < 2^128.
+// GATHER (a Galois key switch, §23): the digits and `own` are read at pi_g of the index within the row, the key row at the
+// index itself; g is not read otherwise.
+template <bool GATHER>
 __global__ __launch_bounds__(256) void ckks_rns_keymac_kernel(const u64 *__restrict__ dig, u64 dig_stride, const u64 *__restrict__ own, u32 own_j,
                                                               const u64 *__restrict__ key, u64 key_stride, u64 *__restrict__ out, u32 k, u32 L, u64 count,
-                                                              Mod m) {
+                                                              u32 g, Mod m) {
     const u64 stride = (u64)gridDim.x * 256, n = 1ull << L;
     const bool wide = (m.q >> 62) != 0;
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
-        const u64 x = i & (n - 1);
+        const u64 x = i & (n - 1), s = GATHER ? i - x + galois_index((u32)x, g, L) : i;
         MacAcc a0, a1;
         for (u32 j = 0; j < k; j++) {
             if (wide && j && (j % kMacChunk63) == 0) {
                 a0.fold63(m);
                 a1.fold63(m);
             }
-            const u64 d = j == own_j ? own[i] : dig[(u64)(j - (j > own_j ? 1u : 0u)) * dig_stride + i];
+            const u64 d = j == own_j ? own[s] : dig[(u64)(j - (j > own_j ? 1u : 0u)) * dig_stride + s];
             const u64 *__restrict__ kp = key + (u64)j * key_stride + x;
             a0.mac(d, kp[0]);
             a1.mac(d, kp[n]);
@@ -110,12 +134,36 @@ __global__ __launch_bounds__(256) void ckks_rns_divround_kernel(const u64 *__res
     }
 }
 
+// the divide-and-round of a Galois key switch: out = (x - t) inv mod q over two components of `count` words (rows of n = 2^L),
+// and the addend pi_g(c0) of the first component gathered from the input ciphertext here
+__global__ __launch_bounds__(256) void ckks_rns_divround_galois_kernel(const u64 *__restrict__ x, u64 x_cs, const u64 *__restrict__ t, u64 t_cs,
+                                                                       const u64 *__restrict__ c0, u64 *__restrict__ out, u64 out_cs, u64 count, u64 inv,
+                                                                       u32 g, u32 L, Mod m) {
+    const u64 stride = (u64)gridDim.x * 256, n = 1ull << L;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < 2 * count; i += stride) {
+        const u64 c = i >= count ? 1u : 0u, e = i - c * count;
+        u64 v = bfv_mulmod(sub63(x[c * x_cs + e], t[c * t_cs + e], m), inv, m);
+        if (c == 0) {
+            const u64 xx = e & (n - 1);
+            v = add63(v, c0[e - xx + galois_index((u32)xx, g, L)], m);
+        }
+        out[c * out_cs + e] = v;
+    }
+}
+
 // the diagonal term of the relinearisation key, in evals: pk0 += c s^2 (c = P mod q_j)
 __global__ __launch_bounds__(256) void ckks_rns_keyterm_kernel(u64 *__restrict__ pk0, const u64 *__restrict__ s_evals, u64 c, u64 n, Mod m) {
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
         const u64 s = s_evals[i];
         pk0[i] = add63(pk0[i], bfv_mulmod(c, bfv_mulmod(s, s, m), m), m);
     }
+}
+
+// the diagonal term of a Galois key, in evals: pk0 += c sigma_g(s)^, the secret's evals gathered by pi_g (n = 2^L)
+__global__ __launch_bounds__(256) void ckks_rns_keyterm_galois_kernel(u64 *__restrict__ pk0, const u64 *__restrict__ s_evals, u64 c, u32 g, u32 L, Mod m) {
+    const u64 n = 1ull << L;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
+        pk0[i] = add63(pk0[i], bfv_mulmod(c, s_evals[galois_index((u32)i, g, L)], m), m);
 }
 
 }  // namespace fhe
@@ -174,6 +222,8 @@ u64 chunk_rows(const Chain &c, u64 batch) { return std::min<u64>(batch, std::max
 u64 rescale_chunk_rows(const Chain &c, u64 batch) { return std::min<u64>(batch, std::max<u64>(1, (kChunkWords >> c.L) / (u64)c.k)); }
 // words of workspace per ciphertext of a chunk: tensor 3k, digits k, lifted digits k^2, t 2(k + 1), lifted t_P 2k
 u64 words_per_row(const Chain &c) { return ((u64)c.k * c.k + 8ull * c.k + 2) * c.n; }
+// a Galois key switch has no tensor: digits k, lifted digits k^2, t 2(k + 1), lifted t_P 2k, whatever the number of elements
+u64 galois_words_per_row(const Chain &c) { return ((u64)c.k * c.k + 5ull * c.k + 2) * c.n; }
 
 int lift_launch(bool is_signed, const u64 *src, u64 *dst, u64 count, u64 qs, const fhe::LiftArgs &a, u32 L, hipStream_t st) {
     if (a.targets == 0) return FHE_OK;
@@ -206,44 +256,107 @@ int tensor_rows(const Chain &c, const u64 *a, const u64 *b, u64 batch, u64 r0, u
     return FHE_OK;
 }
 
+// The workspace of one key switch over cr ciphertexts (slab = cr n words): C the k digits in coefficients, D their lifts as
+// evals (limb i < k holds the k - 1 digits j != i, P all k), T the k + 1 key sums of two components, E the lifted t_P
+struct SwitchBufs {
+    u64 *C, *D, *T, *E;
+    u64 slab;
+    unsigned k;
+    SwitchBufs(u64 *W, unsigned k_, u64 slab_) : C(W), D(C + k_ * slab_), T(D + (u64)k_ * k_ * slab_), E(T + 2ull * (k_ + 1) * slab_), slab(slab_), k(k_) {}
+    u64 *D_of(unsigned i) const { return D + (u64)i * (k - 1) * slab; }
+    u64 *TP() const { return T + 2ull * k * slab; }
+};
+
+// steps (1)-(3) of §22: digit j = src(j) (cr rows of evals modulo q_j) in coefficients, lifted to every limb i != j of
+// {0 .. k - 1, P} and transformed
+template <class Src>
+int digit_rows(const Chain &c, Src src, const SwitchBufs &b, u64 cr, hipStream_t st) {
+    const unsigned k = c.k;
+    int rc;
+    for (unsigned j = 0; j < k; j++)
+        if ((rc = inverse_into(c.p[j], src(j), b.C + j * b.slab, cr, st)) != FHE_OK) return rc;
+    for (unsigned j = 0; j < k; j++) {
+        fhe::LiftArgs a{};
+        for (unsigned i = 0; i <= k; i++)
+            if (i != j) lift_target(&a, c.p[i], (u64)(b.D_of(i) - b.D) + (u64)(i < k && j > i ? j - 1 : j) * b.slab);
+        if ((rc = lift_launch(false, b.C + j * b.slab, b.D, b.slab, c.p[j]->q, a, c.L, st)) != FHE_OK) return rc;
+    }
+    for (unsigned i = 0; i <= k; i++) {
+        const u64 polys = (u64)(i < k ? k - 1 : k) * cr;
+        if (polys && (rc = fhe_ntt_forward_dev(c.p[i], b.D_of(i), b.D_of(i), polys, st)) != FHE_OK) return rc;
+    }
+    return FHE_OK;
+}
+
+// step (4): t_i = sum_j D_ji (.) key[j][i], i in {0 .. k - 1, P}; own(i) is limb i's own digit in evals.  GATHER: a Galois key
+// switch, the digits read at pi_g
+template <bool GATHER, class Own>
+int keymac_rows(const Chain &c, const u64 *key, unsigned key_limbs, Own own, const SwitchBufs &b, u32 g, hipStream_t st) {
+    const unsigned k = c.k;
+    const u64 n = c.n;
+    for (unsigned i = 0; i <= k; i++) {
+        const u64 *col = key + (u64)(i < k ? i : key_limbs) * 2 * n;
+        const int rc = launch(GATHER ? "ckks_rns_keymac_galois" : "ckks_rns_keymac", (int)c.L, st, fhe::ckks_rns_keymac_kernel<GATHER>, fhe_ew_grid(b.slab), 256, b.D_of(i),
+                              b.slab, i < k ? own(i) : nullptr, i, col, (u64)(key_limbs + 1) * 2 * n, b.T + 2ull * i * b.slab, k, c.L, b.slab, g, c.p[i]->mod);
+        if (rc != FHE_OK) return rc;
+    }
+    return FHE_OK;
+}
+
+// the first half of step (5): t_P in coefficients, lifted to every limb and transformed -> E
+int special_rows(const Chain &c, const SwitchBufs &b, u64 cr, hipStream_t st) {
+    const unsigned k = c.k;
+    int rc;
+    if ((rc = fhe_ntt_inverse_dev(c.p[k], b.TP(), b.TP(), 2 * cr, st)) != FHE_OK) return rc;
+    fhe::LiftArgs a{};
+    for (unsigned i = 0; i < k; i++) lift_target(&a, c.p[i], 2ull * i * b.slab);
+    if ((rc = lift_launch(false, b.TP(), b.E, 2 * b.slab, c.p[k]->q, a, c.L, st)) != FHE_OK) return rc;
+    for (unsigned i = 0; i < k; i++)
+        if ((rc = fhe_ntt_forward_dev(c.p[i], b.E + 2ull * i * b.slab, b.E + 2ull * i * b.slab, 2 * cr, st)) != FHE_OK) return rc;
+    return FHE_OK;
+}
+
 // rows d_r0 .. d_r0 + cr of d [k][3][d_rows][n] -> rows o_r0 .. of out [k][2][o_rows][n]; W holds (k^2 + 5k + 2) cr n words
 int relin_rows(const Chain &c, const u64 *rlk, unsigned key_limbs, const u64 *pinv, const u64 *d, u64 d_rows, u64 d_r0, u64 *out, u64 o_rows, u64 o_r0, u64 cr,
                u64 *W, hipStream_t st) {
     const u64 n = c.n, slab = cr * n;
     const unsigned k = c.k;
-    u64 *C = W, *D = C + k * slab, *T = D + (u64)k * k * slab, *E = T + 2ull * (k + 1) * slab;
+    const SwitchBufs b(W, k, slab);
     auto d_at = [&](unsigned limb, unsigned comp) { return d + (((u64)limb * 3 + comp) * d_rows + d_r0) * n; };
-    auto D_of = [&](unsigned i) { return D + (u64)i * (k - 1) * slab; };             // limb i < k holds k - 1 lifted digits, P all k
+    auto d2 = [&](unsigned limb) { return d_at(limb, 2); };
     int rc;
-    for (unsigned j = 0; j < k; j++)
-        if ((rc = inverse_into(c.p[j], d_at(j, 2), C + j * slab, cr, st)) != FHE_OK) return rc;
-    for (unsigned j = 0; j < k; j++) {
-        fhe::LiftArgs a{};
-        for (unsigned i = 0; i <= k; i++)
-            if (i != j) lift_target(&a, c.p[i], (u64)(D_of(i) - D) + (u64)(i < k && j > i ? j - 1 : j) * slab);
-        if ((rc = lift_launch(false, C + j * slab, D, slab, c.p[j]->q, a, c.L, st)) != FHE_OK) return rc;
-    }
-    for (unsigned i = 0; i <= k; i++) {
-        const u64 polys = (u64)(i < k ? k - 1 : k) * cr;
-        if (polys && (rc = fhe_ntt_forward_dev(c.p[i], D_of(i), D_of(i), polys, st)) != FHE_OK) return rc;
-    }
-    for (unsigned i = 0; i <= k; i++) {
-        const u64 *key = rlk + (u64)(i < k ? i : key_limbs) * 2 * n;
-        if ((rc = launch("ckks_rns_keymac", (int)c.L, st, fhe::ckks_rns_keymac_kernel, fhe_ew_grid(slab), 256, D_of(i), slab, i < k ? d_at(i, 2) : nullptr, i, key,
-                         (u64)(key_limbs + 1) * 2 * n, T + 2ull * i * slab, k, c.L, slab, c.p[i]->mod)) != FHE_OK)
-            return rc;
-    }
-    u64 *TP = T + 2ull * k * slab;
-    if ((rc = fhe_ntt_inverse_dev(c.p[k], TP, TP, 2 * cr, st)) != FHE_OK) return rc;
-    fhe::LiftArgs a{};
-    for (unsigned i = 0; i < k; i++) lift_target(&a, c.p[i], 2ull * i * slab);
-    if ((rc = lift_launch(false, TP, E, 2 * slab, c.p[k]->q, a, c.L, st)) != FHE_OK) return rc;
+    if ((rc = digit_rows(c, d2, b, cr, st)) != FHE_OK) return rc;
+    if ((rc = keymac_rows<false>(c, rlk, key_limbs, d2, b, 0u, st)) != FHE_OK) return rc;
+    if ((rc = special_rows(c, b, cr, st)) != FHE_OK) return rc;
     for (unsigned i = 0; i < k; i++)
-        if ((rc = fhe_ntt_forward_dev(c.p[i], E + 2ull * i * slab, E + 2ull * i * slab, 2 * cr, st)) != FHE_OK) return rc;
-    for (unsigned i = 0; i < k; i++)
-        if ((rc = launch("ckks_rns_divround", (int)c.L, st, fhe::ckks_rns_divround_kernel, fhe_ew_grid(2 * slab), 256, T + 2ull * i * slab, slab, E + 2ull * i * slab,
+        if ((rc = launch("ckks_rns_divround", (int)c.L, st, fhe::ckks_rns_divround_kernel, fhe_ew_grid(2 * slab), 256, b.T + 2ull * i * slab, slab, b.E + 2ull * i * slab,
                          slab, d_at(i, 0), d_rows * n, out + ((u64)i * 2 * o_rows + o_r0) * n, o_rows * n, slab, pinv[i], c.p[i]->mod)) != FHE_OK)
             return rc;
+    return FHE_OK;
+}
+
+// §23: rows r0 .. r0 + cr of in [k][2][batch][n] under each of `count` Galois elements -> the same rows of out
+// [count][k][2][batch][n].  The digits are those of the unpermuted c1, made once; every g then takes its key sums with the
+// digits read at pi_g, the divide-and-round by P, and pi_g(c0) gathered in that last kernel.  W as for relin_rows.
+int galois_rows(const Chain &c, const u64 *const *gks, const uint64_t *gs, unsigned count, unsigned key_limbs, const u64 *pinv, const u64 *in, u64 *out, u64 batch,
+                u64 r0, u64 cr, u64 *W, hipStream_t st) {
+    const u64 n = c.n, slab = cr * n;
+    const unsigned k = c.k;
+    const SwitchBufs b(W, k, slab);
+    auto in_at = [&](unsigned limb, unsigned comp) { return in + (((u64)limb * 2 + comp) * batch + r0) * n; };
+    auto c1 = [&](unsigned limb) { return in_at(limb, 1); };
+    int rc;
+    if ((rc = digit_rows(c, c1, b, cr, st)) != FHE_OK) return rc;
+    for (unsigned r = 0; r < count; r++) {
+        const u32 g = (u32)gs[r];
+        u64 *o = out + (u64)r * k * 2 * batch * n;
+        if ((rc = keymac_rows<true>(c, gks[r], key_limbs, c1, b, g, st)) != FHE_OK) return rc;
+        if ((rc = special_rows(c, b, cr, st)) != FHE_OK) return rc;
+        for (unsigned i = 0; i < k; i++)
+            if ((rc = launch("ckks_rns_divround_galois", (int)c.L, st, fhe::ckks_rns_divround_galois_kernel, fhe_ew_grid(2 * slab), 256, b.T + 2ull * i * slab, slab,
+                             b.E + 2ull * i * slab, slab, in_at(i, 0), o + ((u64)i * 2 * batch + r0) * n, batch * n, slab, pinv[i], g, c.L, c.p[i]->mod)) != FHE_OK)
+                return rc;
+    }
     return FHE_OK;
 }
 
@@ -306,23 +419,27 @@ extern "C" int fhe_ckks_rns_from_i64_dev(const fhe_ntt_plan *const *plans, unsig
     return FHE_OK;
 }
 
-extern "C" int fhe_ckks_rns_relin_key_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const uint8_t *seed, uint64_t first_row,
-                                          const void *d_s, const void *d_cdt, unsigned m, void *d_rlk, void *hip_stream) {
-    const char *who = "fhe_ckks_rns_relin_key_dev";
+namespace {
+
+// a hybrid switching key [limbs][limbs + 1][2][n]: the public key of row first_row + j under every prime plus the diagonal
+// term (P mod q_j) x, x = s^2 for the relinearisation key (g = 0) and sigma_g(s) for a Galois key
+int switch_key(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const uint8_t *seed, uint64_t first_row, uint64_t g, bool galois,
+               const void *d_s, const void *d_cdt, unsigned m, void *d_key, void *hip_stream, const char *who) {
     Chain c;
     int rc = check_chain(plans, limbs, special, true, &c, who);
     if (rc != FHE_OK) return rc;
     if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
     const u64 n = c.n;
     const unsigned k = c.k, cols = k + 1;
+    if (galois && ((g & 1) == 0 || g >= 2 * n)) return fhe_fail(FHE_E_INVALID, "%s: g=%llu must be odd and below 2n", who, (unsigned long long)g);
     u64 qmin = c.p[0]->q;
     for (unsigned i = 1; i < k; i++) qmin = std::min<u64>(qmin, c.p[i]->q);
     if ((rc = check_cdt_shape(d_cdt, m, qmin, who)) != FHE_OK) return rc;
     if (first_row >= kRowLimit - k) return fhe_fail(FHE_E_INVALID, "%s: first_row + limbs passes 2^63", who);
-    if (!d_s || !d_rlk) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
-    if (misaligned8(d_s) || misaligned8(d_rlk)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
-    const u64 rlk_words = (u64)k * cols * 2 * n;
-    if (overlaps_any(d_rlk, rlk_words * 8, {{d_s, (u64)cols * n * 8}, {d_cdt, (u64)m * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_rlk overlaps the key or the error table", who);
+    if (!d_s || !d_key) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_s) || misaligned8(d_key)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 key_words = (u64)k * cols * 2 * n;
+    if (overlaps_any(d_key, key_words * 8, {{d_s, (u64)cols * n * 8}, {d_cdt, (u64)m * 8}})) return fhe_fail(FHE_E_INVALID, "%s: the key overlaps the secret or the error table", who);
     hipStream_t st = (hipStream_t)hip_stream;
     if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
     void *w = nullptr;
@@ -336,13 +453,27 @@ extern "C" int fhe_ckks_rns_relin_key_dev(const fhe_ntt_plan *const *plans, unsi
             if ((rc = fhe_ntt_forward_dev(p, PK, PK, 2, st)) != FHE_OK) return rc;
             if (i == j) {
                 if ((rc = fhe_ntt_forward_dev(p, S, SE, 1, st)) != FHE_OK) return rc;
-                if ((rc = launch("ckks_rns_keyterm", (int)c.L, st, fhe::ckks_rns_keyterm_kernel, fhe_ew_grid(n), 256, PK, SE, special->q % p->q, n, p->mod)) != FHE_OK)
-                    return rc;
+                rc = galois ? launch("ckks_rns_keyterm_galois", (int)c.L, st, fhe::ckks_rns_keyterm_galois_kernel, fhe_ew_grid(n), 256, PK, SE, special->q % p->q, (u32)g, c.L,
+                                     p->mod)
+                            : launch("ckks_rns_keyterm", (int)c.L, st, fhe::ckks_rns_keyterm_kernel, fhe_ew_grid(n), 256, PK, SE, special->q % p->q, n, p->mod);
+                if (rc != FHE_OK) return rc;
             }
-            HIP_TRY(hipMemcpyAsync((u64 *)d_rlk + ((u64)j * cols + i) * 2 * n, PK, 2 * n * 8, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync((u64 *)d_key + ((u64)j * cols + i) * 2 * n, PK, 2 * n * 8, hipMemcpyDeviceToDevice, st));
         }
     }
     return FHE_OK;
+}
+
+}  // namespace
+
+extern "C" int fhe_ckks_rns_relin_key_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const uint8_t *seed, uint64_t first_row,
+                                          const void *d_s, const void *d_cdt, unsigned m, void *d_rlk, void *hip_stream) {
+    return switch_key(plans, limbs, special, seed, first_row, 0, false, d_s, d_cdt, m, d_rlk, hip_stream, "fhe_ckks_rns_relin_key_dev");
+}
+
+extern "C" int fhe_ckks_rns_galois_key_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const uint8_t *seed, uint64_t first_row,
+                                           uint64_t g, const void *d_s, const void *d_cdt, unsigned m, void *d_gk, void *hip_stream) {
+    return switch_key(plans, limbs, special, seed, first_row, g, true, d_s, d_cdt, m, d_gk, hip_stream, "fhe_ckks_rns_galois_key_dev");
 }
 
 extern "C" int fhe_ckks_rns_tensor_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *d_a, const void *d_b, void *d_out, size_t batch,
@@ -460,6 +591,69 @@ extern "C" int fhe_ckks_rns_rescale_dev(const fhe_ntt_plan *const *plans, unsign
             if ((rc = launch("ckks_rns_divround", (int)c.L, st, fhe::ckks_rns_divround_kernel, fhe_ew_grid(2 * slab), 256, in + ((u64)i * 2 * batch + r0) * n, batch * n,
                              E + 2ull * i * slab, slab, nullptr, 0, out + ((u64)i * 2 * batch + r0) * n, batch * n, slab, qinv[i], c.p[i]->mod)) != FHE_OK)
                 return rc;
+    }
+    return FHE_OK;
+}
+
+// ---- Galois automorphisms: slot rotations and conjugation ---------------------------------------------------------
+extern "C" int fhe_ckks_galois_evals_dev(const fhe_ntt_plan *plan, uint64_t g, const void *d_in, void *d_out, size_t polys, void *hip_stream) {
+    const char *who = "fhe_ckks_galois_evals_dev";
+    if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
+    const u64 n = plan->n;
+    if (n < 2) return fhe_fail(FHE_E_BAD_N, "%s: n must be at least 2", who);
+    if ((g & 1) == 0 || g >= 2 * n) return fhe_fail(FHE_E_INVALID, "%s: g=%llu must be odd and below 2n", who, (unsigned long long)g);
+    if (polys == 0) return FHE_OK;
+    if (!mul_fits((u64)polys, n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: polys too large", who);
+    if (!d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_in) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 words = (u64)polys * n;
+    if (overlaps_any(d_out, words * 8, {{d_in, words * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps d_in (the permutation is not in place)", who);
+    int dev, rc;
+    if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
+    return launch("ckks_rns_galois", (int)plan->log_n, (hipStream_t)hip_stream, fhe::ckks_rns_galois_kernel, fhe_ew_grid(words), 256, (const u64 *)d_in, (u64 *)d_out, words,
+                  (u32)g, plan->log_n);
+}
+
+extern "C" size_t fhe_ckks_rns_galois_workspace_bytes(uint64_t n, unsigned limbs, size_t batch, unsigned count) {
+    if (n < 2 || (n & (n - 1)) != 0 || n > (1ull << 19) || limbs < 1 || limbs > fhe::kRnsMaxLimbs || batch == 0 || count == 0 || count > FHE_CKKS_GALOIS_MAX_COUNT)
+        return 0;
+    Chain c;
+    c.k = limbs;
+    c.n = n;
+    c.L = log2_of(n);
+    return (size_t)(galois_words_per_row(c) * chunk_rows(c, batch) * 8);       // the digits are shared: count does not enter
+}
+
+extern "C" int fhe_ckks_rns_galois_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *const *d_gks, const uint64_t *gs,
+                                       unsigned count, unsigned key_limbs, const void *d_in, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_rns_galois_dev";
+    Chain c;
+    int rc = check_chain(plans, limbs, special, true, &c, who);
+    if (rc != FHE_OK) return rc;
+    if ((rc = check_key_limbs(c, key_limbs, who)) != FHE_OK) return rc;
+    if (count > FHE_CKKS_GALOIS_MAX_COUNT) return fhe_fail(FHE_E_INVALID, "%s: count=%u passes %d", who, count, FHE_CKKS_GALOIS_MAX_COUNT);
+    if (batch == 0 || count == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, 2ull * c.k * n * count, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_gks || !gs || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_in) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 ct_bytes = 2ull * c.k * batch * n * 8, gk_bytes = (u64)key_limbs * (key_limbs + 1) * 2 * n * 8;
+    for (unsigned r = 0; r < count; r++) {
+        if (!d_gks[r]) return fhe_fail(FHE_E_NULL, "%s: key %u is NULL", who, r);
+        if (misaligned8(d_gks[r])) return fhe_fail(FHE_E_INVALID, "%s: key %u must be 8-byte aligned", who, r);
+        if ((gs[r] & 1) == 0 || gs[r] >= 2 * n) return fhe_fail(FHE_E_INVALID, "%s: g[%u]=%llu must be odd and below 2n", who, r, (unsigned long long)gs[r]);
+        if (overlaps_any(d_out, ct_bytes * count, {{d_gks[r], gk_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps key %u", who, r);
+    }
+    if (overlaps_any(d_out, ct_bytes * count, {{d_in, ct_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the ciphertexts", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const u64 cb = chunk_rows(c, batch);
+    void *w = nullptr;
+    if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(galois_words_per_row(c) * cb * 8), st, &w)) != FHE_OK) return rc;
+    u64 pinv[fhe::kRnsMaxLimbs];
+    special_inverses(c, pinv);
+    for (u64 r0 = 0; r0 < batch; r0 += cb) {
+        const u64 cr = std::min<u64>(cb, batch - r0);
+        if ((rc = galois_rows(c, (const u64 *const *)d_gks, gs, count, key_limbs, pinv, (const u64 *)d_in, (u64 *)d_out, batch, r0, cr, (u64 *)w, st)) != FHE_OK) return rc;
     }
     return FHE_OK;
 }

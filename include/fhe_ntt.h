@@ -662,6 +662,31 @@ int fhe_ckks_rns_rescale_dev(const fhe_ntt_plan *const *plans, unsigned limbs, c
                              void *hip_stream);
 size_t fhe_ckks_rns_workspace_bytes(uint64_t n, unsigned limbs, size_t batch);
 
+/* ---- CKKS on the RNS chain: slot rotations and conjugation with Galois keys (ckks_eval.hip) ----
+ * sigma_g: a(X) -> a(X^g) in Z[X]/(X^n + 1) for g odd, 1 <= g < 2n; a rotation of the slots by `step` is g = 5^step mod 2n,
+ * the conjugation g = 2n - 1.  On evals in the engine's order sigma_g is an index permutation that does not depend on q:
+ * sigma_g(a)[x] = a[pi_g(x)], pi_g(x) = brv((((2 brv(x) + 1) g mod 2n) - 1) / 2), brv the reversal of log2 n bits.
+ *   fhe_ckks_galois_evals_dev     d_out [polys][n] = the rows d_in [polys][n] of evals under sigma_g (plaintexts, keys, tests)
+ *   fhe_ckks_rns_galois_key_dev   d_gk, the shape and columns of d_rlk above: gk[j][i] = (-a_ji s + e_j + [i = j] (P mod q_j)
+ *            sigma_g(s), a_ji) from rows first_row + j
+ *   fhe_ckks_rns_galois_dev       d_out [count][limbs][2][batch][n]: d_in [limbs][2][batch][n] under sigma_gs[r] for every
+ *            r < count, each (pi_g(c0) + r0, r1) with (r0, r1) the key switch of pi_g(c1) against d_gks[r] (relinearisation's
+ *            steps with d2 = pi_g(c1)); level and scale are unchanged.  d_gks and gs are HOST arrays of `count` device key
+ *            pointers and Galois elements; the digit decomposition of c1 runs once per chunk whatever `count` is.
+ *   fhe_ckks_rns_galois_workspace_bytes  the library workspace that call takes; 0 for a shape it refuses
+ * As the block above, and: FHE_E_INVALID for g even or >= 2n, count > FHE_CKKS_GALOIS_MAX_COUNT, an output that overlaps the
+ * input or a key; FHE_E_NULL for a NULL entry of d_gks; batch = 0 or count = 0 is a no-op. */
+#define FHE_CKKS_GALOIS_MAX_COUNT 256
+int fhe_ckks_galois_evals_dev(const fhe_ntt_plan *plan, uint64_t g, const void *d_in, void *d_out, size_t polys,
+                              void *hip_stream);
+int fhe_ckks_rns_galois_key_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special,
+                                const uint8_t *seed, uint64_t first_row, uint64_t g, const void *d_s, const void *d_cdt,
+                                unsigned m, void *d_gk, void *hip_stream);
+int fhe_ckks_rns_galois_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special,
+                            const void *const *d_gks, const uint64_t *gs, unsigned count, unsigned key_limbs,
+                            const void *d_in, void *d_out, size_t batch, void *hip_stream);
+size_t fhe_ckks_rns_galois_workspace_bytes(uint64_t n, unsigned limbs, size_t batch, unsigned count);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
