@@ -7,6 +7,7 @@ Layout:
   bfv.py       RLWE::tensor / RLWE::mul (bfv/src/lib.rs) over the exact-product rows, and BFV's client side
   ckks.py      the CKKS encoder (a double-precision FFT), keys, encryption and decryption (ckks/src), and the evaluator on an
                RNS modulus chain: ct x ct, relinearisation, rescaling
+  rlwe_client.py  what the client keys of bfv.py and ckks.py share: seed, error table, row bookkeeping, PublicKey
   device.py    device buffers for bfv.py, ckks.py and tfhe.py (torch as the allocator)
   tfhe.py      Tn x Tn and TGGSW x TGLWE (ring_torus.rs, tfhe/src/tggsw.rs)
   host/        the same mirror in C++ (arith.hpp), for compiled callers

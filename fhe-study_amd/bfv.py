@@ -20,7 +20,7 @@ import numpy as np
 from . import binding
 from .arith import RingParam, Rq, plan_of as _plan
 from .device import from_dev as _from_dev, to_dev as _to_dev, torch as _torch
-from .tfhe import cdt_table
+from .rlwe_client import ClientKeyBase, PublicKey  # noqa: F401  (PublicKey: lib.rs:39, exported from here)
 
 
 @dataclass
@@ -89,13 +89,6 @@ class Param:
         return RingParam(self.t, self.ring.n)
 
 
-class PublicKey:
-    """lib.rs:39: (pk0, pk1) mod q as coefficients (numpy) and, resident on the device, both halves as evals [2][n]"""
-
-    def __init__(self, param, coeffs, d_evals):
-        self.param, self.coeffs, self.d_evals = param, coeffs, d_evals
-
-
 def _delta_m(ring, t, m, shape):
     """Delta (m mod q) on the device: fhe_rq_remodule_dev then fhe_rq_mul_by_u64_dev, as lib.rs:185-187 -> u64 words of `shape`"""
     L = binding.load_library()
@@ -123,7 +116,7 @@ def mul_const(rlk, ct, m):
     return RLWE.mul(t, rlk, ct, md)
 
 
-class ClientKey:
+class ClientKey(ClientKeyBase):
     """The BFV secret, resident on the device with its evals, and what is made from it: public keys, relinearisation keys,
     ciphertexts and plaintexts.  The 32-byte seed is the whole secret: every key bit, mask coefficient,
     ephemeral u and error is a word of the ChaCha20 stream it keys, addressed by (purpose, row).  Row indices never repeat
@@ -135,14 +128,11 @@ class ClientKey:
     same seed starts its counters again: do not encrypt fresh data under both.  sigma: the deviation of the discrete Gaussian
     errors (tfhe.cdt_table)."""
 
-    ENCRYPT_ROWS = 1 << 56
-    PK_BASE, RLK_BASE = 1 << 56, 2 << 56
+    RLK_BASE = 2 << 56
 
     def __init__(self, seed, param, d_s, d_s_evals, sigma):
-        self.seed, self.param, self.d_s, self.d_s_evals = bytes(seed), param, d_s, d_s_evals
-        self._next_row, self._slots = 0, set()
-        tab = cdt_table(sigma)
-        self._cdt, self._m = (_to_dev(tab) if len(tab) else None), len(tab)
+        super().__init__(seed, sigma)
+        self.param, self.d_s, self.d_s_evals = param, d_s, d_s_evals
 
     @classmethod
     def generate(cls, seed, param, sigma=3.2):
@@ -155,27 +145,9 @@ class ClientKey:
         torch.cuda.synchronize()
         return cls(seed, param, d_s, d_e, sigma)
 
-    def _cdt_ptr(self):
-        return self._cdt.data_ptr() if self._m else None
-
-    def _take_slot(self, kind, base, slot):
-        if not 0 <= int(slot) < 1 << 16:
-            raise ValueError(f"{kind}: slot must be in [0, 2^16)")
-        if (kind, int(slot)) in self._slots:
-            raise ValueError(f"{kind}: slot {slot} of this seed is already used; a second key needs a slot of its own")
-        self._slots.add((kind, int(slot)))
-        return base + int(slot)
-
     def public_key(self, slot=0):
         """BFV::new_key's pk = (-a s + e, a), lib.rs:134-137"""
-        torch = _torch()
-        ring = self.param.ring
-        row = self._take_slot("public_key", self.PK_BASE, slot)
-        pk = torch.empty((2, ring.n), dtype=torch.int64, device="cuda")
-        ev = torch.empty_like(pk)
-        binding.bfv_public_key_dev(_plan(ring), self.seed, row, self.d_s.data_ptr(), self._cdt_ptr(), self._m, pk.data_ptr())
-        _plan(ring).forward_dev(pk.data_ptr(), ev.data_ptr(), 2)
-        return PublicKey(self.param, _from_dev(pk), ev)
+        return self._public_key(binding.bfv_public_key_dev, self.param.ring, slot)
 
     def relin_key(self, slot=0):
         """BFV::rlk_key, lib.rs:202-225, exactly (n p q < 2^63) -> RLK"""
@@ -197,13 +169,10 @@ class ClientKey:
             raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the message is not in the plaintext ring")
         msg = m.coeffs.reshape(-1, ring.n)
         batch = msg.shape[0]
-        if self._next_row + batch > self.ENCRYPT_ROWS:
-            raise ValueError("encrypt: this seed's 2^56 encryption rows are used up")
         d_m = _to_dev(msg)
         out = torch.empty((2, batch, ring.n), dtype=torch.int64, device="cuda")
-        binding.bfv_encrypt_dev(_plan(ring), self.param.t, self.seed, self._next_row, pk.d_evals.data_ptr(), d_m.data_ptr(), ring.n, self._cdt_ptr(),
-                                self._m, out.data_ptr(), batch)
-        self._next_row += batch
+        self._on_fresh_rows(batch, lambda row: binding.bfv_encrypt_dev(_plan(ring), self.param.t, self.seed, row, pk.d_evals.data_ptr(), d_m.data_ptr(), ring.n,
+                                                                        self._cdt_ptr(), self._m, out.data_ptr(), batch))
         w = _from_dev(out)
         return RLWE(Rq(ring, w[0].reshape(m.coeffs.shape)), Rq(ring, w[1].reshape(m.coeffs.shape)))
 

@@ -23,7 +23,7 @@ import numpy as np
 from . import binding
 from .arith import RingParam, plan_of as _plan
 from .device import from_dev as _from_dev, to_dev as _to_dev, torch as _torch
-from .tfhe import cdt_table
+from .rlwe_client import ClientKeyBase, PublicKey  # noqa: F401  (PublicKey: exported from here too)
 
 
 @dataclass(frozen=True)
@@ -67,13 +67,6 @@ class Encoder:
         return out.cpu().numpy().view(np.complex128).reshape(p.shape[:-1] + (self.n // 2,))
 
 
-class PublicKey:
-    """(pk0, pk1) mod q as coefficients (numpy) and, resident on the device, both halves as evals [2][n]"""
-
-    def __init__(self, param, coeffs, d_evals):
-        self.param, self.coeffs, self.d_evals = param, coeffs, d_evals
-
-
 class Ciphertext:
     """(c0, c1) mod q, u64 words of shape (n,) or (batch, n)"""
 
@@ -111,22 +104,17 @@ def mul_plain(ct, m):
     return Ciphertext(ring, out[0], out[1])
 
 
-class ClientKey:
+class ClientKey(ClientKeyBase):
     """The CKKS secret, resident on the device with its evals, an Encoder, and what is made from them.  The
     32-byte seed is the whole secret; rows never repeat within a seed, as for bfv.ClientKey:
         [0, 2^56)          fresh encryptions, in the order of the encrypt calls
         1 2^56 + slot      public_key(slot)
     and a builder refuses a slot (0 <= slot < 2^16) it has used.  The secret is KEY row 0."""
 
-    ENCRYPT_ROWS = 1 << 56
-    PK_BASE = 1 << 56
-
     def __init__(self, seed, param, delta, d_s, d_s_evals, sigma):
-        self.seed, self.param, self.d_s, self.d_s_evals = bytes(seed), param, d_s, d_s_evals
+        super().__init__(seed, sigma)
+        self.param, self.d_s, self.d_s_evals = param, d_s, d_s_evals
         self.encoder = Encoder(param.ring.n, delta)
-        self._next_row, self._slots = 0, set()
-        tab = cdt_table(sigma)
-        self._cdt, self._m = (_to_dev(tab) if len(tab) else None), len(tab)
 
     @classmethod
     def generate(cls, seed, param, delta, sigma=3.2):
@@ -139,23 +127,9 @@ class ClientKey:
         torch.cuda.synchronize()
         return cls(seed, param, delta, d_s, d_e, sigma)
 
-    def _cdt_ptr(self):
-        return self._cdt.data_ptr() if self._m else None
-
     def public_key(self, slot=0):
         """CKKS::new_key's pk = (-a s + e, a), lib.rs:61, with a uniform modulo q"""
-        torch = _torch()
-        ring = self.param.ring
-        if not 0 <= int(slot) < 1 << 16:
-            raise ValueError("public_key: slot must be in [0, 2^16)")
-        if int(slot) in self._slots:
-            raise ValueError(f"public_key: slot {slot} of this seed is already used; a second key needs a slot of its own")
-        self._slots.add(int(slot))
-        pk = torch.empty((2, ring.n), dtype=torch.int64, device="cuda")
-        ev = torch.empty_like(pk)
-        binding.ckks_public_key_dev(_plan(ring), self.seed, self.PK_BASE + int(slot), self.d_s.data_ptr(), self._cdt_ptr(), self._m, pk.data_ptr())
-        _plan(ring).forward_dev(pk.data_ptr(), ev.data_ptr(), 2)
-        return PublicKey(self.param, _from_dev(pk), ev)
+        return self._public_key(binding.ckks_public_key_dev, self.param.ring, slot)
 
     def encrypt(self, pk, m):
         """CKKS::encrypt, lib.rs:66-85: m int64 coefficients (n,) or (batch, n) -> Ciphertext on fresh rows"""
@@ -164,13 +138,10 @@ class ClientKey:
         m = np.ascontiguousarray(m, dtype=np.int64)
         msg = m.reshape(-1, ring.n)
         batch = msg.shape[0]
-        if self._next_row + batch > self.ENCRYPT_ROWS:
-            raise ValueError("encrypt: this seed's 2^56 encryption rows are used up")
         d_m = torch.from_numpy(msg).cuda()
         out = torch.empty((2, batch, ring.n), dtype=torch.int64, device="cuda")
-        binding.ckks_encrypt_dev(_plan(ring), self.seed, self._next_row, pk.d_evals.data_ptr(), d_m.data_ptr(), ring.n, self._cdt_ptr(), self._m,
-                                 out.data_ptr(), batch)
-        self._next_row += batch
+        self._on_fresh_rows(batch, lambda row: binding.ckks_encrypt_dev(_plan(ring), self.seed, row, pk.d_evals.data_ptr(), d_m.data_ptr(), ring.n, self._cdt_ptr(),
+                                                                         self._m, out.data_ptr(), batch))
         w = _from_dev(out)
         return Ciphertext(ring, w[0].reshape(m.shape), w[1].reshape(m.shape))
 
@@ -405,7 +376,7 @@ class RnsCiphertext:
         return RnsCiphertext(self.param, out, self.level, self.scale * float(scale))
 
 
-class RnsClientKey:
+class RnsClientKey(ClientKeyBase):
     """The CKKS secret under every prime of an RnsParam: the same ternary row (KEY row 0) as residues and evals per limb, the
     special prime's last.  Rows of a seed, as ClientKey and disjoint from its rows:
         [0, 2^56)                    fresh encryptions
@@ -414,18 +385,12 @@ class RnsClientKey:
         3 2^56 + 64 slot + j         digit j of galois_key(g, slot)
     A builder refuses a slot (0 <= slot < 2^16) it has used."""
 
-    ENCRYPT_ROWS = 1 << 56
-    PK_BASE = 1 << 56
-    RLK_BASE = 2 << 56
-    GK_BASE = 3 << 56
+    RLK_BASE, GK_BASE = 2 << 56, 3 << 56
 
     def __init__(self, seed, param, delta, d_s, d_s_evals, sigma):
-        self.seed, self.param, self.delta, self.d_s, self.d_s_evals = bytes(seed), param, float(delta), d_s, d_s_evals
+        super().__init__(seed, sigma)
+        self.param, self.delta, self.d_s, self.d_s_evals = param, float(delta), d_s, d_s_evals
         self.encoder = Encoder(param.n, delta)
-        self._next_row, self._pk_slots, self._rlk_slots = 0, set(), set()
-        self._gk_slots = set()
-        tab = cdt_table(sigma)
-        self._cdt, self._m = (_to_dev(tab) if len(tab) else None), len(tab)
 
     def _all_plans(self):
         return self.param.plans() + [self.param.special_plan()]
@@ -442,34 +407,23 @@ class RnsClientKey:
         torch.cuda.synchronize()
         return cls(seed, param, delta, d_s, d_e, sigma)
 
-    def _cdt_ptr(self):
-        return self._cdt.data_ptr() if self._m else None
-
-    @staticmethod
-    def _take(slots, slot, who):
-        if not 0 <= int(slot) < 1 << 16:
-            raise ValueError(f"{who}: slot must be in [0, 2^16)")
-        if int(slot) in slots:
-            raise ValueError(f"{who}: slot {slot} of this seed is already used; a second key needs a slot of its own")
-        slots.add(int(slot))
-
     def public_key(self, slot=0):
         """fhe_ckks_public_key_dev per limb with one row: the residues of one key (-a s + e, a) modulo Q"""
         torch = _torch()
-        self._take(self._pk_slots, slot, "public_key")
+        row = self._take_slot("public_key", self.PK_BASE, slot)
         plans = self.param.plans()
         pk = torch.empty((len(plans), 2, self.param.n), dtype=torch.int64, device="cuda")
         for i, plan in enumerate(plans):
-            binding.ckks_public_key_dev(plan, self.seed, self.PK_BASE + int(slot), self.d_s[i].data_ptr(), self._cdt_ptr(), self._m, pk[i].data_ptr())
+            binding.ckks_public_key_dev(plan, self.seed, row, self.d_s[i].data_ptr(), self._cdt_ptr(), self._m, pk[i].data_ptr())
             plan.forward_dev(pk[i].data_ptr(), pk[i].data_ptr(), 2)
         return RnsPublicKey(self.param, pk)
 
     def relin_key(self, slot=0):
         torch = _torch()
-        self._take(self._rlk_slots, slot, "relin_key")
+        row = self._take_slot("relin_key", self.RLK_BASE, slot, rows=64)
         k = len(self.param.moduli)
         rlk = torch.empty((k, k + 1, 2, self.param.n), dtype=torch.int64, device="cuda")
-        binding.ckks_rns_relin_key_dev(self.param.plans(), self.param.special_plan(), self.seed, self.RLK_BASE + 64 * int(slot), self.d_s.data_ptr(), self._cdt_ptr(),
+        binding.ckks_rns_relin_key_dev(self.param.plans(), self.param.special_plan(), self.seed, row, self.d_s.data_ptr(), self._cdt_ptr(),
                                        self._m, rlk.data_ptr())
         return RnsRelinKey(self.param, rlk)
 
@@ -479,10 +433,10 @@ class RnsClientKey:
         g = int(g)
         if g % 2 == 0 or not 0 < g < 2 * self.param.n:
             raise ValueError(f"galois_key: g={g} must be odd and in [1, 2n)")
-        self._take(self._gk_slots, slot, "galois_key")
+        row = self._take_slot("galois_key", self.GK_BASE, slot, rows=64)
         k = len(self.param.moduli)
         gk = torch.empty((k, k + 1, 2, self.param.n), dtype=torch.int64, device="cuda")
-        binding.ckks_rns_galois_key_dev(self.param.plans(), self.param.special_plan(), self.seed, self.GK_BASE + 64 * int(slot), g, self.d_s.data_ptr(),
+        binding.ckks_rns_galois_key_dev(self.param.plans(), self.param.special_plan(), self.seed, row, g, self.d_s.data_ptr(),
                                         self._cdt_ptr(), self._m, gk.data_ptr())
         return RnsGaloisKey(self.param, g, gk)
 
@@ -498,15 +452,16 @@ class RnsClientKey:
         n = self.param.n
         msg = np.ascontiguousarray(m, dtype=np.int64).reshape(-1, n)
         batch = msg.shape[0]
-        if self._next_row + batch > self.ENCRYPT_ROWS:
-            raise ValueError("encrypt: this seed's 2^56 encryption rows are used up")
         d_m = torch.from_numpy(msg).cuda()
         plans = self.param.plans()
         out = torch.empty((len(plans), 2, batch, n), dtype=torch.int64, device="cuda")
-        for i, plan in enumerate(plans):
-            binding.ckks_encrypt_dev(plan, self.seed, self._next_row, pk.d_evals[i].data_ptr(), d_m.data_ptr(), n, self._cdt_ptr(), self._m, out[i].data_ptr(), batch)
-            plan.forward_dev(out[i].data_ptr(), out[i].data_ptr(), 2 * batch)
-        self._next_row += batch
+
+        def limbs(row):
+            for i, plan in enumerate(plans):
+                binding.ckks_encrypt_dev(plan, self.seed, row, pk.d_evals[i].data_ptr(), d_m.data_ptr(), n, self._cdt_ptr(), self._m, out[i].data_ptr(), batch)
+                plan.forward_dev(out[i].data_ptr(), out[i].data_ptr(), 2 * batch)
+
+        self._on_fresh_rows(batch, limbs)
         return RnsCiphertext(self.param, out, self.param.max_level, self.delta if scale is None else scale)
 
     def decrypt(self, ct):

@@ -25,14 +25,16 @@
 // Encryption, the pointwise route: bfv_ephemeral_kernel writes u, the forward transform runs in place,
 // bfv_pk_pointwise_kernel multiplies u^ by both key rows (a thread keeps its two key words in registers and walks down the
 // batch: the key is read once per workgroup, never staged per row), the two inverse transforms run in place and
-// bfv_encrypt_epilogue_kernel adds e1 + Delta m and e2 on the way to the caller's buffer: one forward and two inverse
+// rlwe_encrypt_epilogue_kernel adds e1 + Delta m and e2 on the way to the caller's buffer: one forward and two inverse
 // transforms per ciphertext, two staging rows.  The staged route, taken where fhe_rq_mul_dev is one fused kernel because it
 // measured faster there: bfv_broadcast_kernel copies both key rows over a chunk once per call and fhe_rq_mul_dev forms
 // each product as one fused 32-bit kernel (u is transformed twice); five staging rows.  The staging is bounded by processing
 // 2^21 coefficients at a time in workspace slot 10 (32 MiB, 80 MiB staged); every word is a function of its (row, index)
 // alone, so the result depends neither on the chunking nor on the route.  Decryption stages c1 the same way (pointwise).
 // The kernels make u64 accesses only and the transforms run on library workspace, so callers' buffers need 8-byte alignment.
-// The sampling kernels, the pointwise product and the key broadcast live in bfv_client_kernels.hpp, which ckks_client.hip shares.
+// The sampling kernels, the pointwise product, the key broadcast, the public-key and encryption epilogues and the host paths of
+// public key, encryption and decryption live in bfv_client_kernels.hpp, which ckks_client.hip shares: here are BFV's description
+// (`Bfv`), its own kernels and its checks.
 #include "bfv_client_kernels.hpp"
 
 using fhe::Mod;
@@ -41,46 +43,20 @@ using fhe::u64;
 
 namespace fhe {
 
-constexpr u32 BFV_MASK = 0x11, BFV_ERR = 0x12, BFV_KEY = 0x13, BFV_EPH = 0x14;
+// BFV as bfv_client_kernels.hpp's paths take a scheme: its rows of the stream, the unsigned message times Delta, workspace
+// slot 10 (slots 0-9 are taken)
+struct Bfv {
+    static constexpr u32 MASK = 0x11, ERR = 0x12, KEY = 0x13, EPH = 0x14;
+    static constexpr bool SIGNED_MSG = false;
+    static constexpr int slot = 10;
+    static constexpr const char *route_env = "FHE_BFV_ENCRYPT_STAGED", *pk_label = "bfv_pk_epilogue", *encrypt_label = "bfv_encrypt_epilogue",
+                                *decrypt_label = "bfv_decrypt_epilogue";
+};
 
 // x mod Q for a signed word and any Q below 2^63
 __device__ __forceinline__ u64 bfv_smod(u64 x, u64 Q) {
     const long long r = (long long)x % (long long)Q;
     return r < 0 ? (u64)(r + (long long)Q) : (u64)r;
-}
-
-
-// out0[r] = P0[r] + e1 + Delta (msg_r mod q), out1[r] = P1[r] + e2 (mod q, canonical) for encryption row first_row + r: e1
-// from ERR row 2 (first_row + r), e2 from the row after it; a thread takes 8 coefficients (one ChaCha block of each error
-// row), the table sits in LDS.  msg null: m = 0; msg_stride 0: one message for every row.
-__global__ __launch_bounds__(256) void bfv_encrypt_epilogue_kernel(ChaChaKey key, u64 first_row, const u64 *__restrict__ P0, const u64 *__restrict__ P1,
-                                                                   const u64 *__restrict__ msg, u64 msg_stride, const u64 *__restrict__ cdt, u32 cm,
-                                                                   u64 delta, u64 *__restrict__ out0, u64 *__restrict__ out1, u32 L, u64 rows, Mod m) {
-    __shared__ u64 scdt[CDT_MAX];
-    for (u32 i = threadIdx.x; i < cm; i += 256) scdt[i] = cdt[i];
-    __syncthreads();
-    const u32 LB = L > 3u ? L - 3u : 0u;                          // blocks per row = max(n / 8, 1)
-    const u64 n = 1ull << L, total = rows << LB, stride = (u64)gridDim.x * 256;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-        const u64 r = i >> LB, c = i & ((1ull << LB) - 1u), erow = 2 * (first_row + r);
-        u64 w1[8], w2[8];
-        if (cm) {
-            chacha_block(key, (u32)c, BFV_ERR, erow, w1);
-            chacha_block(key, (u32)c, BFV_ERR, erow + 1, w2);
-        }
-        const u64 at = (r << L) + 8 * c;
-        const u64 *__restrict__ mp = msg ? msg + r * msg_stride + 8 * c : nullptr;
-#pragma unroll
-        for (u32 j = 0; j < 8; j++) {
-            if (8 * c + j < n) {
-                const u64 e1 = cm ? bfv_err_residue(cdt_error(scdt, cm, w1[j], 0), m.q) : 0ull;
-                const u64 e2 = cm ? bfv_err_residue(cdt_error(scdt, cm, w2[j], 0), m.q) : 0ull;
-                const u64 dm = mp ? bfv_mulmod(reduce_any(mp[j], m), delta, m) : 0ull;
-                out0[at + j] = add63(add63(P0[at + j], e1, m), dm, m);
-                out1[at + j] = add63(P1[at + j], e2, m);
-            }
-        }
-    }
 }
 
 // out = Zq::from_f64(q, round(t (c0 + P mod q) / q)) mod t: zq_device.hpp's zq_from_f64, the helper of the library's other
@@ -102,28 +78,6 @@ __global__ __launch_bounds__(256) void bfv_key_bits_kernel(const u64 *__restrict
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) dst[i] = src[i] & 1ull;
 }
 
-// pk [2][n] = (-(a s) + e, a) mod q: as = a s mod q, e from ERR row 2 row; a thread takes 8 coefficients
-__global__ __launch_bounds__(256) void bfv_pk_epilogue_kernel(ChaChaKey key, u64 row, const u64 *__restrict__ a, const u64 *__restrict__ as,
-                                                              const u64 *__restrict__ cdt, u32 cm, u64 *__restrict__ pk, u64 n, Mod m) {
-    __shared__ u64 scdt[CDT_MAX];
-    for (u32 i = threadIdx.x; i < cm; i += 256) scdt[i] = cdt[i];
-    __syncthreads();
-    const u64 blocks = (n + 7) / 8;
-    for (u64 c = (u64)blockIdx.x * 256 + threadIdx.x; c < blocks; c += (u64)gridDim.x * 256) {
-        u64 w[8];
-        if (cm) chacha_block(key, (u32)c, BFV_ERR, 2 * row, w);
-#pragma unroll
-        for (u32 j = 0; j < 8; j++) {
-            const u64 i = 8 * c + j;
-            if (i < n) {
-                const u64 e = cm ? bfv_err_residue(cdt_error(scdt, cm, w[j], 0), m.q) : 0ull;
-                pk[i] = add63(sub63(0ull, as[i], m), e, m);
-                pk[n + i] = a[i];
-            }
-        }
-    }
-}
-
 // rlk [2][n] = (-(a s + e) + p s^2, a) mod pq from the integer products as = a s and ss = s s (signed words, |.| < n pq <
 // 2^63): one reduction mod pq each; p (ss mod q) < pq is p ss mod pq
 __global__ __launch_bounds__(256) void bfv_rlk_epilogue_kernel(ChaChaKey key, u64 row, const u64 *__restrict__ a, const u64 *__restrict__ as,
@@ -135,7 +89,7 @@ __global__ __launch_bounds__(256) void bfv_rlk_epilogue_kernel(ChaChaKey key, u6
     const u64 blocks = (n + 7) / 8, p = pq / q;
     for (u64 c = (u64)blockIdx.x * 256 + threadIdx.x; c < blocks; c += (u64)gridDim.x * 256) {
         u64 w[8];
-        if (cm) chacha_block(key, (u32)c, BFV_ERR, 2 * row, w);
+        if (cm) chacha_block(key, (u32)c, Bfv::ERR, 2 * row, w);
 #pragma unroll
         for (u32 j = 0; j < 8; j++) {
             const u64 i = 8 * c + j;
@@ -154,12 +108,6 @@ __global__ __launch_bounds__(256) void bfv_rlk_epilogue_kernel(ChaChaKey key, u6
 }  // namespace fhe
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-namespace {
-
-constexpr int kBfvClientSlot = 10;              // fhe_workspace_get slot of the staging rows (slots 0-9 are taken)
-
-}  // namespace
-
 extern "C" int fhe_bfv_secret_key_dev(uint64_t n, const uint8_t *seed, uint64_t key_row, void *d_s, void *hip_stream) {
     const char *who = "fhe_bfv_secret_key_dev";
     int rc = check_ring(n, who);
@@ -169,7 +117,7 @@ extern "C" int fhe_bfv_secret_key_dev(uint64_t n, const uint8_t *seed, uint64_t 
     if (misaligned8(d_s)) return fhe_fail(FHE_E_INVALID, "%s: d_s must be 8-byte aligned", who);
     int dev;
     if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
-    return small_fill(seed_key(seed), fhe::BFV_KEY, 1, key_row, 0, n, (u64 *)d_s, 1, (hipStream_t)hip_stream);
+    return small_fill(seed_key(seed), fhe::Bfv::KEY, 1, key_row, 0, n, (u64 *)d_s, 1, (hipStream_t)hip_stream);
 }
 
 extern "C" int fhe_bfv_public_key_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t row, const void *d_s, const void *d_cdt, unsigned m,
@@ -177,24 +125,10 @@ extern "C" int fhe_bfv_public_key_dev(const fhe_ntt_plan *plan, const uint8_t *s
     const char *who = "fhe_bfv_public_key_dev";
     if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
     if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
-    const u64 n = plan->n, q = plan->q;
-    int rc = check_cdt_shape(d_cdt, m, q, who);
-    if (rc != FHE_OK) return rc;
-    if (row >= kRowLimit) return fhe_fail(FHE_E_INVALID, "%s: row must be below 2^63", who);
-    if (!d_s || !d_pk) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
-    if (misaligned8(d_s) || misaligned8(d_pk)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
-    if (overlaps_any(d_pk, 2 * n * 8, {{d_s, n * 8}, {d_cdt, (u64)m * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_pk overlaps the key or the error table", who);
-    hipStream_t st = (hipStream_t)hip_stream;
-    if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
-    void *w = nullptr;
-    if ((rc = fhe_workspace_get(kBfvClientSlot, 3 * n * 8, st, &w)) != FHE_OK) return rc;
-    u64 *A = (u64 *)w, *S = A + n, *P = S + n;
-    const fhe::ChaChaKey key = seed_key(seed);
-    if ((rc = uniform_fill(key, fhe::BFV_MASK, row, q, n, A, 1, st)) != FHE_OK) return rc;
-    if ((rc = launch("bfv_key_bits", 0, st, fhe::bfv_key_bits_kernel, fhe_ew_grid(n), 256, d_s, S, n)) != FHE_OK) return rc;
-    if ((rc = fhe_rq_mul_dev(plan, A, 0, S, 0, P, nullptr, nullptr, nullptr, 1, nullptr, st)) != FHE_OK) return rc;
-    return launch("bfv_pk_epilogue", (int)plan->log_n, st, fhe::bfv_pk_epilogue_kernel, fhe_ew_grid((n + 7) / 8), 256, key, row, A, P, d_cdt, m, d_pk, n,
-                  plan->mod);
+    const u64 n = plan->n;
+    return rlwe_public_key<fhe::Bfv>(who, plan, seed, row, d_s, d_cdt, m, d_pk, (hipStream_t)hip_stream, [&](u64 *S, hipStream_t st) {
+        return launch("bfv_key_bits", 0, st, fhe::bfv_key_bits_kernel, fhe_ew_grid(n), 256, d_s, S, n);
+    });
 }
 
 extern "C" int fhe_bfv_relin_key_dev(uint64_t q, uint64_t n, uint64_t pq, const uint8_t *seed, uint64_t row, const void *d_s, const void *d_cdt,
@@ -215,10 +149,10 @@ extern "C" int fhe_bfv_relin_key_dev(uint64_t q, uint64_t n, uint64_t pq, const 
     hipStream_t st = (hipStream_t)hip_stream;
     if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
     void *w = nullptr;
-    if ((rc = fhe_workspace_get(kBfvClientSlot, 4 * n * 8, st, &w)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(fhe::Bfv::slot, 4 * n * 8, st, &w)) != FHE_OK) return rc;
     u64 *A = (u64 *)w, *S = A + n, *AS = S + n, *SS = AS + n;
     const fhe::ChaChaKey key = seed_key(seed);
-    if ((rc = uniform_fill(key, fhe::BFV_MASK, row, pq, n, A, 1, st)) != FHE_OK) return rc;
+    if ((rc = uniform_fill(key, fhe::Bfv::MASK, row, pq, n, A, 1, st)) != FHE_OK) return rc;
     if ((rc = launch("bfv_key_bits", 0, st, fhe::bfv_key_bits_kernel, fhe_ew_grid(n), 256, d_s, S, n)) != FHE_OK) return rc;
     if ((rc = fhe_tn_mul_dev(n, A, S, AS, 1, st)) != FHE_OK) return rc;
     if ((rc = fhe_tn_mul_dev(n, S, S, SS, 1, st)) != FHE_OK) return rc;
@@ -231,98 +165,19 @@ extern "C" int fhe_bfv_encrypt_dev(const fhe_ntt_plan *plan, uint64_t t, const u
     const char *who = "fhe_bfv_encrypt_dev";
     if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
     if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
-    const u64 n = plan->n, q = plan->q;
+    const u64 q = plan->q;
     if (t < 2 || t >= q) return fhe_fail(FHE_E_INVALID, "%s: need 2 <= t < q (t=%llu, q=%llu)", who, (unsigned long long)t, (unsigned long long)q);
-    int rc = check_cdt_shape(d_cdt, m, q, who);
-    if (rc != FHE_OK) return rc;
-    if (d_msg && msg_stride != 0 && msg_stride < n) return fhe_fail(FHE_E_INVALID, "%s: msg_stride must be 0 (one message) or at least n", who);
-    if (batch == 0) return FHE_OK;
-    if (first_row > kRowLimit || (u64)batch > kRowLimit - first_row) return fhe_fail(FHE_E_INVALID, "%s: first_row + batch passes 2^63", who);
-    if (!mul_fits((u64)batch, 2 * n, kWordLimit) || !mul_fits((u64)batch - 1, (u64)msg_stride, kWordLimit - n))
-        return fhe_fail(FHE_E_INVALID, "%s: batch or msg_stride too large", who);
-    if (!d_pk_evals || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
-    if (misaligned8(d_pk_evals) || misaligned8(d_msg) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
-    const u64 out_bytes = (u64)batch * 2 * n * 8, msg_bytes = d_msg ? (((u64)batch - 1) * msg_stride + n) * 8 : 0;
-    if (overlaps_any(d_out, out_bytes, {{d_pk_evals, 2 * n * 8}, {d_msg, msg_bytes}, {d_cdt, (u64)m * 8}}))
-        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key, the messages or the error table", who);
-    hipStream_t st = (hipStream_t)hip_stream;
-    if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
-    const u32 L = plan->log_n;
-    const u64 chunk = std::min<u64>(batch, std::max<u64>(1, kChunkWords >> L));
-    // Two routes to the two products, same words (DESIGN.md §20 has the rule and the measurements).  Where fhe_rq_mul_dev is
-    // one fused kernel (moduli with a 32-bit form, smallq.hip: q < 2^30, 2^8 <= n <= 2^18; any modulus at the single-pass
-    // sizes 2^8 <= n <= 2^13), two of them against the key rows staged over a chunk (once per call) measured faster than
-    // forward + pointwise + two inverses.  Everything else: the pointwise route.  FHE_BFV_ENCRYPT_STAGED=0 / =1 (read per
-    // call: tools/bfv_client_rate.py times both routes in one process) forces the pointwise / the staged route.
-    bool staged = false;
-    if ((rc = encrypt_route_staged(plan, "FHE_BFV_ENCRYPT_STAGED", &staged)) != FHE_OK) return rc;
-    void *w = nullptr;
-    if ((rc = fhe_workspace_get(kBfvClientSlot, (staged ? 5 : 2) * chunk * n * 8, st, &w)) != FHE_OK) return rc;
-    u64 *U = (u64 *)w, *H = U + chunk * n, *P = nullptr, *K0 = nullptr, *K1 = nullptr;
-    if (staged) {
-        P = H + chunk * n; K0 = P + chunk * n; K1 = K0 + chunk * n;
-        if ((rc = launch("bfv_broadcast", (int)L, st, fhe::bfv_broadcast_kernel, fhe_ew_grid(chunk << L), 256, d_pk_evals, K0, L, chunk)) != FHE_OK) return rc;
-        if ((rc = launch("bfv_broadcast", (int)L, st, fhe::bfv_broadcast_kernel, fhe_ew_grid(chunk << L), 256, (const u64 *)d_pk_evals + n, K1, L, chunk)) != FHE_OK)
-            return rc;
-    }
-    const fhe::ChaChaKey key = seed_key(seed);
-    const u32 LB = L > 3 ? L - 3 : 0;
-    for (u64 r0 = 0; r0 < batch; r0 += chunk) {
-        const u64 cr = std::min<u64>(chunk, batch - r0);
-        const u64 *R0 = U, *R1 = H;                               // the two products of the chunk
-        if ((rc = small_fill(key, fhe::BFV_EPH, 0, first_row + r0, q, n, U, cr, st)) != FHE_OK) return rc;
-        if (staged) {
-            if ((rc = fhe_rq_mul_dev(plan, U, 0, K0, 1, P, nullptr, nullptr, nullptr, cr, nullptr, st)) != FHE_OK) return rc;
-            if ((rc = fhe_rq_mul_dev(plan, U, 0, K1, 1, H, nullptr, nullptr, nullptr, cr, nullptr, st)) != FHE_OK) return rc;
-            R0 = P;
-        } else {
-            if ((rc = fhe_ntt_forward_dev(plan, U, U, cr, st)) != FHE_OK) return rc;
-            if ((rc = pointwise<2>(plan, U, (const u64 *)d_pk_evals, U, H, cr, st)) != FHE_OK) return rc;
-            if ((rc = fhe_ntt_inverse_dev(plan, U, U, cr, st)) != FHE_OK) return rc;
-            if ((rc = fhe_ntt_inverse_dev(plan, H, H, cr, st)) != FHE_OK) return rc;
-        }
-        const u64 *msg = d_msg ? (const u64 *)d_msg + r0 * msg_stride : nullptr;
-        u64 *o0 = (u64 *)d_out + r0 * n, *o1 = (u64 *)d_out + ((u64)batch + r0) * n;
-        if ((rc = launch("bfv_encrypt_epilogue", (int)L, st, fhe::bfv_encrypt_epilogue_kernel, fhe_ew_grid(cr << LB), 256, key, first_row + r0, R0, R1, msg,
-                         msg_stride, d_cdt, m, q / t, o0, o1, L, cr, plan->mod)) != FHE_OK)
-            return rc;
-    }
-    return FHE_OK;
+    return rlwe_encrypt<fhe::Bfv>(who, plan, q / t, seed, first_row, d_pk_evals, d_msg, msg_stride, d_cdt, m, d_out, batch, (hipStream_t)hip_stream);
 }
 
 extern "C" int fhe_bfv_decrypt_dev(const fhe_ntt_plan *plan, uint64_t t, const void *d_s_evals, const void *d_ct, void *d_out, size_t batch,
                                    void *hip_stream) {
     const char *who = "fhe_bfv_decrypt_dev";
     if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
-    const u64 n = plan->n, q = plan->q;
+    const u64 q = plan->q;
     if (t < 2 || t >= q) return fhe_fail(FHE_E_INVALID, "%s: need 2 <= t < q (t=%llu, q=%llu)", who, (unsigned long long)t, (unsigned long long)q);
-    if (batch == 0) return FHE_OK;
-    if (!mul_fits((u64)batch, 2 * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
-    if (!d_s_evals || !d_ct || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
-    if (misaligned8(d_s_evals) || misaligned8(d_ct) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
-    const u64 out_bytes = (u64)batch * n * 8;
-    if (overlaps_any(d_out, out_bytes, {{d_s_evals, n * 8}, {d_ct, 2 * out_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key or the ciphertexts", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    const u32 L = plan->log_n;
-    const u64 chunk = std::min<u64>(batch, std::max<u64>(1, kChunkWords >> L));
-    void *w = nullptr;
-    int rc = fhe_workspace_get(kBfvClientSlot, chunk * n * 8, st, &w);
-    if (rc != FHE_OK) return rc;
-    u64 *W = (u64 *)w;
-    for (u64 r0 = 0; r0 < batch; r0 += chunk) {
-        const u64 cr = std::min<u64>(chunk, batch - r0);
-        const u64 *c0 = (const u64 *)d_ct + r0 * n, *c1 = (const u64 *)d_ct + ((u64)batch + r0) * n;
-        const u64 *src = c1;
-        if (fhe_misaligned(c1)) {                                 // the transforms take 16-byte aligned rows
-            HIP_TRY(hipMemcpyAsync(W, c1, cr * n * 8, hipMemcpyDeviceToDevice, st));
-            src = W;
-        }
-        if ((rc = fhe_ntt_forward_dev(plan, src, W, cr, st)) != FHE_OK) return rc;
-        if ((rc = pointwise<1>(plan, W, (const u64 *)d_s_evals, W, nullptr, cr, st)) != FHE_OK) return rc;
-        if ((rc = fhe_ntt_inverse_dev(plan, W, W, cr, st)) != FHE_OK) return rc;
-        if ((rc = launch("bfv_decrypt_epilogue", (int)L, st, fhe::bfv_decrypt_epilogue_kernel, fhe_ew_grid(cr * n), 256, c0, W, (u64 *)d_out + r0 * n, cr * n,
-                         t, plan->mod)) != FHE_OK)
-            return rc;
-    }
-    return FHE_OK;
+    return rlwe_decrypt<fhe::Bfv>(who, plan, d_s_evals, d_ct, d_out, batch, st, [&](const char *label, const u64 *c0, const u64 *P, u64 *out, u64 count) {
+        return launch(label, (int)plan->log_n, st, fhe::bfv_decrypt_epilogue_kernel, fhe_ew_grid(count), 256, c0, P, out, count, t, plan->mod);
+    });
 }

@@ -1,7 +1,10 @@
 // chacha_stream.hpp — the random stream and the error sampler that the client-side units share (tfhe_client.hip, DESIGN.md
 // §17; bfv_client.hip, §20): the ChaCha20 block function (RFC 8439) keyed by the caller's 32-byte seed with the nonce
-// (purpose, row lo, row hi), and the table-inversion error sampler.  Device code only; the words are defined in §17.
+// (purpose, row lo, row hi), and the table-inversion error sampler; the words are defined in §17.  And the two host helpers
+// every client entry point starts with: the seed as a key, and the 8-byte alignment the client ABI promises.
 #pragma once
+#include <cstdint>
+
 #include "zq_device.hpp"
 
 namespace fhe {
@@ -51,3 +54,18 @@ __device__ __forceinline__ u64 cdt_error(const u64 *cdt, u32 m, u64 u, u32 log_s
 }
 
 }  // namespace fhe
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+namespace {
+
+// the caller's 32 bytes as the key's little-endian words
+inline fhe::ChaChaKey seed_key(const uint8_t *seed) {
+    fhe::ChaChaKey k;
+    for (int i = 0; i < 8; i++)
+        k.w[i] = (fhe::u32)seed[4 * i] | ((fhe::u32)seed[4 * i + 1] << 8) | ((fhe::u32)seed[4 * i + 2] << 16) | ((fhe::u32)seed[4 * i + 3] << 24);
+    return k;
+}
+// the client kernels make u64 accesses only
+inline bool misaligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
+
+}  // namespace

@@ -39,7 +39,15 @@ using fhe::u64;
 
 namespace fhe {
 
-constexpr u32 CKKS_MASK = 0x21, CKKS_ERR = 0x22, CKKS_KEY = 0x23, CKKS_EPH = 0x24;
+// CKKS as bfv_client_kernels.hpp's paths take a scheme: its rows of the stream, the signed message without a factor,
+// workspace slot 11 (slot 10 is BFV's)
+struct Ckks {
+    static constexpr u32 MASK = 0x21, ERR = 0x22, KEY = 0x23, EPH = 0x24;
+    static constexpr bool SIGNED_MSG = true;
+    static constexpr int slot = 11;
+    static constexpr const char *route_env = "FHE_CKKS_ENCRYPT_STAGED", *pk_label = "ckks_pk_epilogue", *encrypt_label = "ckks_encrypt_epilogue",
+                                *decrypt_label = "ckks_decrypt_epilogue";
+};
 
 struct cplx { double re, im; };
 __device__ __forceinline__ cplx cadd(cplx a, cplx b) { return {a.re + b.re, a.im + b.im}; }
@@ -235,45 +243,6 @@ __global__ __launch_bounds__(CkksShape<LM>::BT) void ckks_encode_kernel(const do
     ckks_fft<LM, -1>(lds + pl * 2 * M, lds + pl * 2 * M + M, t, tw, in, out);
 }
 
-// x mod q for a signed word and any q below 2^63, by the multiplication of reduce_any
-__device__ __forceinline__ u64 ckks_smod(u64 x, const Mod &m) {
-    const bool neg = (long long)x < 0;
-    const u64 r = reduce_any(neg ? 0ull - x : x, m);
-    return (neg && r) ? m.q - r : r;
-}
-
-// out0[r] = P0[r] + e0 + (msg_r mod q), out1[r] = P1[r] + e1 (mod q, canonical) for encryption row first_row + r: e0 from
-// ERR row 2 (first_row + r), e1 from the row after it; bfv_encrypt_epilogue_kernel with a signed message and no Delta
-__global__ __launch_bounds__(256) void ckks_encrypt_epilogue_kernel(ChaChaKey key, u64 first_row, const u64 *__restrict__ P0, const u64 *__restrict__ P1,
-                                                                    const u64 *__restrict__ msg, u64 msg_stride, const u64 *__restrict__ cdt, u32 cm,
-                                                                    u64 *__restrict__ out0, u64 *__restrict__ out1, u32 L, u64 rows, Mod m) {
-    __shared__ u64 scdt[CDT_MAX];
-    for (u32 i = threadIdx.x; i < cm; i += 256) scdt[i] = cdt[i];
-    __syncthreads();
-    const u32 LB = L > 3u ? L - 3u : 0u;                          // blocks per row = max(n / 8, 1)
-    const u64 n = 1ull << L, total = rows << LB, stride = (u64)gridDim.x * 256;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-        const u64 r = i >> LB, c = i & ((1ull << LB) - 1u), erow = 2 * (first_row + r);
-        u64 w1[8], w2[8];
-        if (cm) {
-            chacha_block(key, (u32)c, CKKS_ERR, erow, w1);
-            chacha_block(key, (u32)c, CKKS_ERR, erow + 1, w2);
-        }
-        const u64 at = (r << L) + 8 * c;
-        const u64 *__restrict__ mp = msg ? msg + r * msg_stride + 8 * c : nullptr;
-#pragma unroll
-        for (u32 j = 0; j < 8; j++) {
-            if (8 * c + j < n) {
-                const u64 e1 = cm ? bfv_err_residue(cdt_error(scdt, cm, w1[j], 0), m.q) : 0ull;
-                const u64 e2 = cm ? bfv_err_residue(cdt_error(scdt, cm, w2[j], 0), m.q) : 0ull;
-                const u64 dm = mp ? ckks_smod(mp[j], m) : 0ull;
-                out0[at + j] = add63(add63(P0[at + j], e1, m), dm, m);
-                out1[at + j] = add63(P1[at + j], e2, m);
-            }
-        }
-    }
-}
-
 // out = c0 + P mod q, centred as ring_n.rs:113-127: d - q where d > floor(q / 2), a signed word
 __global__ __launch_bounds__(256) void ckks_decrypt_epilogue_kernel(const u64 *__restrict__ c0, const u64 *__restrict__ P, u64 *__restrict__ out, u64 count,
                                                                     Mod m) {
@@ -284,34 +253,11 @@ __global__ __launch_bounds__(256) void ckks_decrypt_epilogue_kernel(const u64 *_
     }
 }
 
-// pk [2][n] = (-(a s) + e, a) mod q: as = a s mod q, e from ERR row 2 row; a thread takes 8 coefficients
-__global__ __launch_bounds__(256) void ckks_pk_epilogue_kernel(ChaChaKey key, u64 row, const u64 *__restrict__ a, const u64 *__restrict__ as,
-                                                               const u64 *__restrict__ cdt, u32 cm, u64 *__restrict__ pk, u64 n, Mod m) {
-    __shared__ u64 scdt[CDT_MAX];
-    for (u32 i = threadIdx.x; i < cm; i += 256) scdt[i] = cdt[i];
-    __syncthreads();
-    const u64 blocks = (n + 7) / 8;
-    for (u64 c = (u64)blockIdx.x * 256 + threadIdx.x; c < blocks; c += (u64)gridDim.x * 256) {
-        u64 w[8];
-        if (cm) chacha_block(key, (u32)c, CKKS_ERR, 2 * row, w);
-#pragma unroll
-        for (u32 j = 0; j < 8; j++) {
-            const u64 i = 8 * c + j;
-            if (i < n) {
-                const u64 e = cm ? bfv_err_residue(cdt_error(scdt, cm, w[j], 0), m.q) : 0ull;
-                pk[i] = add63(sub63(0ull, as[i], m), e, m);
-                pk[n + i] = a[i];
-            }
-        }
-    }
-}
-
 }  // namespace fhe
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 namespace {
 
-constexpr int kCkksClientSlot = 11;             // fhe_workspace_get slot of the staging rows (slot 10 is BFV's)
 constexpr u64 kCkksMaxN = 1ull << 13;           // M = N/2 = 2^12 complex points fill 64 KiB of LDS
 
 int check_encoder(uint64_t n, double delta, const char *who) {
@@ -409,7 +355,7 @@ extern "C" int fhe_ckks_secret_key_dev(const fhe_ntt_plan *plan, const uint8_t *
     if (misaligned8(d_s)) return fhe_fail(FHE_E_INVALID, "%s: d_s must be 8-byte aligned", who);
     int dev, rc;
     if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
-    return small_fill(seed_key(seed), fhe::CKKS_KEY, 0, key_row, plan->q, plan->n, (u64 *)d_s, 1, (hipStream_t)hip_stream);
+    return small_fill(seed_key(seed), fhe::Ckks::KEY, 0, key_row, plan->q, plan->n, (u64 *)d_s, 1, (hipStream_t)hip_stream);
 }
 
 extern "C" int fhe_ckks_public_key_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t row, const void *d_s, const void *d_cdt, unsigned m,
@@ -417,24 +363,10 @@ extern "C" int fhe_ckks_public_key_dev(const fhe_ntt_plan *plan, const uint8_t *
     const char *who = "fhe_ckks_public_key_dev";
     if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
     if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
-    const u64 n = plan->n, q = plan->q;
-    int rc = check_cdt_shape(d_cdt, m, q, who);
-    if (rc != FHE_OK) return rc;
-    if (row >= kRowLimit) return fhe_fail(FHE_E_INVALID, "%s: row must be below 2^63", who);
-    if (!d_s || !d_pk) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
-    if (misaligned8(d_s) || misaligned8(d_pk)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
-    if (overlaps_any(d_pk, 2 * n * 8, {{d_s, n * 8}, {d_cdt, (u64)m * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_pk overlaps the key or the error table", who);
-    hipStream_t st = (hipStream_t)hip_stream;
-    if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
-    void *w = nullptr;
-    if ((rc = fhe_workspace_get(kCkksClientSlot, 3 * n * 8, st, &w)) != FHE_OK) return rc;
-    u64 *A = (u64 *)w, *S = A + n, *P = S + n;
-    const fhe::ChaChaKey key = seed_key(seed);
-    if ((rc = uniform_fill(key, fhe::CKKS_MASK, row, q, n, A, 1, st)) != FHE_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(S, d_s, n * 8, hipMemcpyDeviceToDevice, st));      // the product takes 16-byte aligned rows
-    if ((rc = fhe_rq_mul_dev(plan, A, 0, S, 0, P, nullptr, nullptr, nullptr, 1, nullptr, st)) != FHE_OK) return rc;
-    return launch("ckks_pk_epilogue", (int)plan->log_n, st, fhe::ckks_pk_epilogue_kernel, fhe_ew_grid((n + 7) / 8), 256, key, row, A, P, d_cdt, m, d_pk, n,
-                  plan->mod);
+    return rlwe_public_key<fhe::Ckks>(who, plan, seed, row, d_s, d_cdt, m, d_pk, (hipStream_t)hip_stream, [&](u64 *S, hipStream_t st) -> int {
+        HIP_TRY(hipMemcpyAsync(S, d_s, plan->n * 8, hipMemcpyDeviceToDevice, st));      // the product takes 16-byte aligned rows
+        return FHE_OK;
+    });
 }
 
 extern "C" int fhe_ckks_encrypt_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t first_row, const void *d_pk_evals, const void *d_msg,
@@ -442,91 +374,14 @@ extern "C" int fhe_ckks_encrypt_dev(const fhe_ntt_plan *plan, const uint8_t *see
     const char *who = "fhe_ckks_encrypt_dev";
     if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
     if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
-    const u64 n = plan->n, q = plan->q;
-    int rc = check_cdt_shape(d_cdt, m, q, who);
-    if (rc != FHE_OK) return rc;
-    if (d_msg && msg_stride != 0 && msg_stride < n) return fhe_fail(FHE_E_INVALID, "%s: msg_stride must be 0 (one message) or at least n", who);
-    if (batch == 0) return FHE_OK;
-    if (first_row > kRowLimit || (u64)batch > kRowLimit - first_row) return fhe_fail(FHE_E_INVALID, "%s: first_row + batch passes 2^63", who);
-    if (!mul_fits((u64)batch, 2 * n, kWordLimit) || !mul_fits((u64)batch - 1, (u64)msg_stride, kWordLimit - n))
-        return fhe_fail(FHE_E_INVALID, "%s: batch or msg_stride too large", who);
-    if (!d_pk_evals || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
-    if (misaligned8(d_pk_evals) || misaligned8(d_msg) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
-    const u64 out_bytes = (u64)batch * 2 * n * 8, msg_bytes = d_msg ? (((u64)batch - 1) * msg_stride + n) * 8 : 0;
-    if (overlaps_any(d_out, out_bytes, {{d_pk_evals, 2 * n * 8}, {d_msg, msg_bytes}, {d_cdt, (u64)m * 8}}))
-        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key, the messages or the error table", who);
-    hipStream_t st = (hipStream_t)hip_stream;
-    if ((rc = check_cdt_words(d_cdt, m, st, who)) != FHE_OK) return rc;
-    const u32 L = plan->log_n;
-    const u64 chunk = std::min<u64>(batch, std::max<u64>(1, kChunkWords >> L));
-    // BFV's two routes and its rule; FHE_CKKS_ENCRYPT_STAGED=0 / =1, read per call, forces one
-    bool staged = false;
-    if ((rc = encrypt_route_staged(plan, "FHE_CKKS_ENCRYPT_STAGED", &staged)) != FHE_OK) return rc;
-    void *w = nullptr;
-    if ((rc = fhe_workspace_get(kCkksClientSlot, (staged ? 5 : 2) * chunk * n * 8, st, &w)) != FHE_OK) return rc;
-    u64 *U = (u64 *)w, *H = U + chunk * n, *P = nullptr, *K0 = nullptr, *K1 = nullptr;
-    if (staged) {
-        P = H + chunk * n; K0 = P + chunk * n; K1 = K0 + chunk * n;
-        if ((rc = launch("bfv_broadcast", (int)L, st, fhe::bfv_broadcast_kernel, fhe_ew_grid(chunk << L), 256, d_pk_evals, K0, L, chunk)) != FHE_OK) return rc;
-        if ((rc = launch("bfv_broadcast", (int)L, st, fhe::bfv_broadcast_kernel, fhe_ew_grid(chunk << L), 256, (const u64 *)d_pk_evals + n, K1, L, chunk)) != FHE_OK)
-            return rc;
-    }
-    const fhe::ChaChaKey key = seed_key(seed);
-    const u32 LB = L > 3 ? L - 3 : 0;
-    for (u64 r0 = 0; r0 < batch; r0 += chunk) {
-        const u64 cr = std::min<u64>(chunk, batch - r0);
-        const u64 *R0 = U, *R1 = H;                               // the two products of the chunk
-        if ((rc = small_fill(key, fhe::CKKS_EPH, 0, first_row + r0, q, n, U, cr, st)) != FHE_OK) return rc;
-        if (staged) {
-            if ((rc = fhe_rq_mul_dev(plan, U, 0, K0, 1, P, nullptr, nullptr, nullptr, cr, nullptr, st)) != FHE_OK) return rc;
-            if ((rc = fhe_rq_mul_dev(plan, U, 0, K1, 1, H, nullptr, nullptr, nullptr, cr, nullptr, st)) != FHE_OK) return rc;
-            R0 = P;
-        } else {
-            if ((rc = fhe_ntt_forward_dev(plan, U, U, cr, st)) != FHE_OK) return rc;
-            if ((rc = pointwise<2>(plan, U, (const u64 *)d_pk_evals, U, H, cr, st)) != FHE_OK) return rc;
-            if ((rc = fhe_ntt_inverse_dev(plan, U, U, cr, st)) != FHE_OK) return rc;
-            if ((rc = fhe_ntt_inverse_dev(plan, H, H, cr, st)) != FHE_OK) return rc;
-        }
-        const u64 *msg = d_msg ? (const u64 *)d_msg + r0 * msg_stride : nullptr;
-        u64 *o0 = (u64 *)d_out + r0 * n, *o1 = (u64 *)d_out + ((u64)batch + r0) * n;
-        if ((rc = launch("ckks_encrypt_epilogue", (int)L, st, fhe::ckks_encrypt_epilogue_kernel, fhe_ew_grid(cr << LB), 256, key, first_row + r0, R0, R1, msg,
-                         msg_stride, d_cdt, m, o0, o1, L, cr, plan->mod)) != FHE_OK)
-            return rc;
-    }
-    return FHE_OK;
+    return rlwe_encrypt<fhe::Ckks>(who, plan, 0, seed, first_row, d_pk_evals, d_msg, msg_stride, d_cdt, m, d_out, batch, (hipStream_t)hip_stream);
 }
 
 extern "C" int fhe_ckks_decrypt_dev(const fhe_ntt_plan *plan, const void *d_s_evals, const void *d_ct, void *d_out, size_t batch, void *hip_stream) {
     const char *who = "fhe_ckks_decrypt_dev";
     if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
-    const u64 n = plan->n;
-    if (batch == 0) return FHE_OK;
-    if (!mul_fits((u64)batch, 2 * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
-    if (!d_s_evals || !d_ct || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
-    if (misaligned8(d_s_evals) || misaligned8(d_ct) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
-    const u64 out_bytes = (u64)batch * n * 8;
-    if (overlaps_any(d_out, out_bytes, {{d_s_evals, n * 8}, {d_ct, 2 * out_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key or the ciphertexts", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    const u32 L = plan->log_n;
-    const u64 chunk = std::min<u64>(batch, std::max<u64>(1, kChunkWords >> L));
-    void *w = nullptr;
-    int rc = fhe_workspace_get(kCkksClientSlot, chunk * n * 8, st, &w);
-    if (rc != FHE_OK) return rc;
-    u64 *W = (u64 *)w;
-    for (u64 r0 = 0; r0 < batch; r0 += chunk) {
-        const u64 cr = std::min<u64>(chunk, batch - r0);
-        const u64 *c0 = (const u64 *)d_ct + r0 * n, *c1 = (const u64 *)d_ct + ((u64)batch + r0) * n;
-        const u64 *src = c1;
-        if (fhe_misaligned(c1)) {                                 // the transforms take 16-byte aligned rows
-            HIP_TRY(hipMemcpyAsync(W, c1, cr * n * 8, hipMemcpyDeviceToDevice, st));
-            src = W;
-        }
-        if ((rc = fhe_ntt_forward_dev(plan, src, W, cr, st)) != FHE_OK) return rc;
-        if ((rc = pointwise<1>(plan, W, (const u64 *)d_s_evals, W, nullptr, cr, st)) != FHE_OK) return rc;
-        if ((rc = fhe_ntt_inverse_dev(plan, W, W, cr, st)) != FHE_OK) return rc;
-        if ((rc = launch("ckks_decrypt_epilogue", (int)L, st, fhe::ckks_decrypt_epilogue_kernel, fhe_ew_grid(cr * n), 256, c0, W, (u64 *)d_out + r0 * n, cr * n,
-                         plan->mod)) != FHE_OK)
-            return rc;
-    }
-    return FHE_OK;
+    return rlwe_decrypt<fhe::Ckks>(who, plan, d_s_evals, d_ct, d_out, batch, st, [&](const char *label, const u64 *c0, const u64 *P, u64 *out, u64 count) {
+        return launch(label, (int)plan->log_n, st, fhe::ckks_decrypt_epilogue_kernel, fhe_ew_grid(count), 256, c0, P, out, count, plan->mod);
+    });
 }

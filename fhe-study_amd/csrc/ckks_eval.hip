@@ -237,13 +237,10 @@ void lift_target(fhe::LiftArgs *a, const fhe_ntt_plan *p, u64 off) {
     a->targets++;
 }
 
-// the transforms take 16-byte aligned rows and the ABI promises 8: a misaligned source is copied into the workspace first
+// `polys` rows of evals, which the ABI aligns to 8 bytes, as coefficients in the workspace rows dst
 int inverse_into(const fhe_ntt_plan *p, const u64 *src, u64 *dst, u64 polys, hipStream_t st) {
-    if (fhe_misaligned(src)) {
-        HIP_TRY(hipMemcpyAsync(dst, src, polys * p->n * 8, hipMemcpyDeviceToDevice, st));
-        src = dst;
-    }
-    return fhe_ntt_inverse_dev(p, src, dst, polys, st);
+    const int rc = aligned_rows(src, dst, polys * p->n, st, &src);
+    return rc != FHE_OK ? rc : fhe_ntt_inverse_dev(p, src, dst, polys, st);
 }
 
 int tensor_rows(const Chain &c, const u64 *a, const u64 *b, u64 batch, u64 r0, u64 *out, u64 o_rows, u64 o_r0, u64 cr, hipStream_t st) {

@@ -27,7 +27,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
-#include "chacha_stream.hpp"   // ChaChaKey, chacha_block, cdt_error, CDT_MAX: shared with bfv_client.hip
+#include "chacha_stream.hpp"   // ChaChaKey, seed_key, misaligned8, chacha_block, cdt_error, CDT_MAX: shared with bfv_client.hip
 
 using fhe::u32;
 using fhe::u64;
@@ -164,15 +164,6 @@ namespace {
 
 constexpr int kClientSlot = 9;                  // fhe_workspace_get slot of the TGLWE staging rows (fhe_tn_mul_dev takes slot 1)
 constexpr u64 kChunkWords = 1ull << 21;         // TGLWE rows are processed 2^21 coefficients at a time: 48 MiB of staging
-
-bool misaligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
-
-fhe::ChaChaKey seed_key(const uint8_t *seed) {
-    fhe::ChaChaKey k;
-    for (int i = 0; i < 8; i++)
-        k.w[i] = (u32)seed[4 * i] | ((u32)seed[4 * i + 1] << 8) | ((u32)seed[4 * i + 2] << 16) | ((u32)seed[4 * i + 3] << 24);
-    return k;
-}
 
 // rows first_row .. first_row + rows - 1 must not wrap past 2^64
 bool rows_wrap(u64 first_row, u64 rows) { return rows && first_row + (rows - 1) < first_row; }
