@@ -91,8 +91,11 @@ EXPORTS = [
     "fhe_ckks_rns_rescale_dev", "fhe_ckks_rns_workspace_bytes",
     # CKKS on the RNS chain: slot rotations and conjugation with Galois keys (ckks_eval.hip)
     "fhe_ckks_galois_evals_dev", "fhe_ckks_rns_galois_key_dev", "fhe_ckks_rns_galois_dev", "fhe_ckks_rns_galois_workspace_bytes",
+    # CKKS on the RNS chain: plaintext linear transforms, the double-hoisted diagonal sum (ckks_eval.hip)
+    "fhe_ckks_rns_diag_sum_dev", "fhe_ckks_rns_diag_workspace_bytes",
 ]
 FHE_CKKS_GALOIS_MAX_COUNT = 256              # include/fhe_ntt.h: the most Galois elements of one fhe_ckks_rns_galois_dev call
+FHE_CKKS_DIAG_MAX_OUTPUTS = 64               # include/fhe_ntt.h: the most outputs of one fhe_ckks_rns_diag_sum_dev call
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
 GATES = {"AND": 0, "NAND": 1, "OR": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -316,6 +319,9 @@ def load_library():
     L.fhe_ckks_rns_galois_dev.argtypes = [_pp, _uint, _vp, _pp, ctypes.POINTER(_u64), _uint, _uint, _vp, _vp, _sz, _vp]
     L.fhe_ckks_rns_galois_workspace_bytes.argtypes = [_u64, _uint, _sz, _uint]
     L.fhe_ckks_rns_galois_workspace_bytes.restype = _sz
+    L.fhe_ckks_rns_diag_sum_dev.argtypes = [_pp, _uint, _vp, _pp, ctypes.POINTER(_u64), _uint, _uint, _vp, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_rns_diag_workspace_bytes.argtypes = [_u64, _uint, _sz, _uint, _uint]
+    L.fhe_ckks_rns_diag_workspace_bytes.restype = _sz
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -853,6 +859,19 @@ def ckks_rns_galois_dev(plans, special, d_gks, gs, key_limbs, d_in, d_out, batch
 
 def ckks_rns_galois_workspace_bytes(n, limbs, batch, count):
     return int(load_library().fhe_ckks_rns_galois_workspace_bytes(n, limbs, batch, count))
+
+
+def ckks_rns_diag_sum_dev(plans, special, d_gks, gs, key_limbs, d_pts, outputs, d_in, d_out, batch, stream=None, limbs=None, count=None):
+    """fhe_ckks_rns_diag_sum_dev: [limbs][2][batch][n] -> [outputs][limbs][2][batch][n], out_o = sum_r m_{o,r} (.)
+    sigma_{gs[r]}(in) with d_pts [outputs][count][limbs + 1][n]; d_gks a list of device key pointers, None (NULL) where gs[r] = 1"""
+    keys = None if d_gks is None else (_vp * max(len(d_gks), 1))(*d_gks)
+    els = None if gs is None else (_u64 * max(len(gs), 1))(*gs)
+    _check(load_library().fhe_ckks_rns_diag_sum_dev(_plan_array(plans), len(plans) if limbs is None else limbs, _handle(special), keys, els,
+                                                    len(gs) if count is None else count, key_limbs, d_pts, outputs, d_in, d_out, batch, stream))
+
+
+def ckks_rns_diag_workspace_bytes(n, limbs, batch, count, outputs):
+    return int(load_library().fhe_ckks_rns_diag_workspace_bytes(n, limbs, batch, count, outputs))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

@@ -266,6 +266,104 @@ class RnsGaloisKey:
         return self.g % 4 == 1
 
 
+# ---- plaintext linear transforms: diagonal sums and baby-step giant-step -------------------------------------------
+class RnsPlaintextSet:
+    """The plaintexts of one diagonal sum, d_pts [outputs][count][level + 2][n] canonical evals on the device (the chain limbs
+    0 .. level, then the special prime), their scale, and the Galois element gs[r] that column r multiplies"""
+
+    def __init__(self, param, level, d_pts, scale, gs):
+        gs = [int(g) for g in gs]
+        for g in gs:
+            if g % 2 == 0 or not 0 < g < 2 * param.n:
+                raise ValueError(f"RnsPlaintextSet: g={g} must be odd and in [1, 2n)")
+        if d_pts is not None and (d_pts.dim() != 4 or d_pts.shape[1] != len(gs) or d_pts.shape[2] != level + 2 or d_pts.shape[3] != param.n):
+            raise ValueError("RnsPlaintextSet: d_pts is not [outputs][count][level + 2][n]")
+        self.param, self.level, self.d_pts, self.scale, self.gs = param, int(level), d_pts, float(scale), gs
+
+    @property
+    def outputs(self):
+        return self.d_pts.shape[0]
+
+
+def encode_diagonals(param, encoder, rows, steps, level, scale):
+    """rows complex [outputs][count][n/2] (or [count][n/2]: one output), slots in the rotation order; column r multiplies the
+    ciphertext rotated by steps[r].  from_rotation_order and Encoder.encode at `scale`, then fhe_ckks_rns_from_i64_dev over the
+    chain limbs 0 .. level and once more over the special prime -> RnsPlaintextSet"""
+    torch = _torch()
+    n = param.n
+    rows = np.asarray(rows, dtype=np.complex128)
+    if rows.ndim == 2:
+        rows = rows[None]
+    steps = [int(st) for st in steps]
+    if rows.ndim != 3 or rows.shape[1] != len(steps) or rows.shape[2] != n // 2 or rows.shape[0] < 1:
+        raise ValueError("encode_diagonals: rows must be [outputs][len(steps)][n/2]")
+    if not 0 <= level <= param.max_level:
+        raise ValueError(f"encode_diagonals: level {level} is not in [0, {param.max_level}]")
+    outputs, count = rows.shape[:2]
+    coef = encoder.encode(from_rotation_order(rows.reshape(outputs * count, n // 2)) * (float(scale) / encoder.delta))
+    d_rows = torch.from_numpy(np.ascontiguousarray(coef)).cuda()
+    d_pts = torch.empty((outputs * count, level + 2, n), dtype=torch.int64, device="cuda")
+    for plans, lo in ((param.plans(level), 0), ([param.special_plan()], level + 1)):
+        ev = torch.empty((len(plans), outputs * count, n), dtype=torch.int64, device="cuda")
+        binding.ckks_rns_from_i64_dev(plans, d_rows.data_ptr(), ev.data_ptr(), outputs * count)
+        d_pts[:, lo:lo + len(plans)] = ev.permute(1, 0, 2)
+    return RnsPlaintextSet(param, level, d_pts.reshape(outputs, count, level + 2, n), scale, [galois_element(n, st) for st in steps])
+
+
+def bsgs_diagonals(M, n1=None):
+    """The baby-step giant-step form of w' = M w for a square complex matrix on the rotation order (N = n/2 slots).  Diagonal t
+    is d_t[s] = M[s][(s + t) mod N]; only non-zero diagonals are kept; t = n1 j + i.  -> (n1, baby, giant, rows): the sorted
+    baby steps i and giant steps j that occur, and rows [len(giant)][len(baby)][N] with rows[a][b] = roll(d_{n1 giant[a] + baby[b]},
+    +n1 giant[a]) (zero where that diagonal is), so that
+        M w = sum_a roll(sum_b rows[a][b] * roll(w, -baby[b]), -n1 giant[a]).
+    n1 defaults to the ceiling of the square root of the number of diagonals kept."""
+    M = np.asarray(M, dtype=np.complex128)
+    N = M.shape[0]
+    if M.ndim != 2 or M.shape[1] != N or N < 1:
+        raise ValueError("bsgs_diagonals: M must be square")
+    s = np.arange(N)
+    diag = {t: M[s, (s + t) % N] for t in range(N)}
+    kept = [t for t in range(N) if np.any(diag[t] != 0)] or [0]
+    if n1 is None:
+        n1 = int(np.ceil(np.sqrt(len(kept))))
+    n1 = int(n1)
+    if not 1 <= n1 <= N:
+        raise ValueError(f"bsgs_diagonals: n1={n1} must be in [1, {N}]")
+    baby, giant = sorted({t % n1 for t in kept}), sorted({t // n1 for t in kept})
+    rows = np.zeros((len(giant), len(baby), N), dtype=np.complex128)
+    for t in kept:
+        rows[giant.index(t // n1), baby.index(t % n1)] = np.roll(diag[t], n1 * (t // n1))
+    return n1, baby, giant, rows
+
+
+class LinearTransform:
+    """w' = M w on the rotation order, encoded for RnsCiphertext.linear_transform: one RnsPlaintextSet whose outputs are the
+    giant steps and whose columns the baby steps of bsgs_diagonals"""
+
+    def __init__(self, param, n1, baby, giant, pts):
+        self.param, self.n1, self.baby, self.giant, self.pts = param, n1, list(baby), list(giant), pts
+
+    @classmethod
+    def from_matrix(cls, param, encoder, M, level, scale, n1=None):
+        M = np.asarray(M, dtype=np.complex128)
+        if M.shape != (param.n // 2, param.n // 2):
+            raise ValueError(f"LinearTransform: M must be {param.n // 2} x {param.n // 2}")
+        n1, baby, giant, rows = bsgs_diagonals(M, n1)
+        return cls(param, n1, baby, giant, encode_diagonals(param, encoder, rows, baby, level, scale))
+
+    @property
+    def level(self):
+        return self.pts.level
+
+    @property
+    def scale(self):
+        return self.pts.scale
+
+    def required_steps(self):
+        """the rotation steps whose keys linear_transform needs: the non-zero baby steps and n1 times the non-zero giant steps"""
+        return sorted({i for i in self.baby if i} | {self.n1 * j for j in self.giant if j})
+
+
 class RnsCiphertext:
     """A device tensor [level + 1][2][batch][n] of evals with its level and float64 scale"""
 
@@ -349,6 +447,42 @@ class RnsCiphertext:
         if not gk.is_conjugation:
             raise ValueError(f"conjugate: g={gk.g} is not 2n - 1")
         return self.apply_galois(gk)
+
+    def diag_sum(self, pts, gks):
+        """-> [sum_r m_{o,r} (.) sigma_{g_r}(self) for each output o] from one call (fhe_ckks_rns_diag_sum_dev): one digit
+        decomposition for all elements and outputs, one division by P an output.  gks[r] is the key of pts.gs[r]; where
+        pts.gs[r] = 1 it is not read and may be None.  Level unchanged; the scale multiplies; the caller rescales."""
+        torch = _torch()
+        gks = list(gks)
+        if pts.param != self.param or any(gk is not None and gk.param != self.param for gk in gks):
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the plaintexts or a Galois key are not of this ciphertext's chain")
+        if pts.level != self.level:
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, f"the plaintexts are at level {pts.level}, the ciphertext at {self.level}")
+        if len(gks) != len(pts.gs):
+            raise ValueError(f"diag_sum: {len(gks)} keys for {len(pts.gs)} elements")
+        for r, (g, gk) in enumerate(zip(pts.gs, gks)):
+            if g != 1 and gk is None:
+                raise ValueError(f"diag_sum: element {r} (g={g}) has no key")
+            if g != 1 and gk.g != g:
+                raise ValueError(f"diag_sum: key {r} is of g={gk.g}, the plaintexts' element is {g}")
+        out = torch.empty((pts.outputs,) + tuple(self.d.shape), dtype=torch.int64, device="cuda")
+        binding.ckks_rns_diag_sum_dev(self.param.plans(self.level), self.param.special_plan(),
+                                      [None if g == 1 else gk.d_gk.data_ptr() for g, gk in zip(pts.gs, gks)], pts.gs, len(self.param.moduli),
+                                      pts.d_pts.data_ptr(), pts.outputs, self.d.data_ptr(), out.data_ptr(), self.batch)
+        return [RnsCiphertext(self.param, out[o], self.level, self.scale * pts.scale) for o in range(pts.outputs)]
+
+    def linear_transform(self, lt, keys):
+        """M w for a LinearTransform: one diag_sum whose outputs are the giant steps' inner sums, then rotate by n1 j and add
+        for j > 0.  keys: step -> RnsGaloisKey for every step of lt.required_steps(); a missing one raises KeyError(step)."""
+        missing = [st for st in lt.required_steps() if st not in keys]
+        if missing:
+            raise KeyError(missing[0])
+        inner = self.diag_sum(lt.pts, [keys[i] if i else None for i in lt.baby])
+        acc = None
+        for j, part in zip(lt.giant, inner):
+            part = part.rotate(keys[lt.n1 * j]) if j else part
+            acc = part if acc is None else acc + part
+        return acc
 
     def _plain(self, m):
         """signed rows (n,) or (batch, n) -> evals [level + 1][batch][n]"""
@@ -445,6 +579,10 @@ class RnsClientKey(ClientKeyBase):
 
     def conjugation_key(self, slot):
         return self.galois_key(conjugation_element(self.param.n), slot)
+
+    def encode_diagonals(self, rows, steps, level, scale):
+        """encode_diagonals with this key's encoder"""
+        return encode_diagonals(self.param, self.encoder, rows, steps, level, scale)
 
     def encrypt(self, pk, m, scale=None):
         """m int64 coefficients (n,) or (batch, n) -> RnsCiphertext at the top level: fhe_ckks_encrypt_dev per limb on the same rows"""

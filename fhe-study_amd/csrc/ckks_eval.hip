@@ -14,6 +14,8 @@
 //              rlk with sigma_g(s) for s^2; apply = the key switch of pi_g(c1) plus pi_g(c0).  The digits are those of the
 //              unpermuted c1, computed once for any number of g (the automorphism commutes with the transforms and the odd,
 //              coefficient-wise lift), and pi_g is folded into the key sums' and the divide-and-round's reads
+//   diag sum    out_o = sum_r m_{o,r} (.) sigma_{g_r}(ct) for plaintexts known modulo P as well: the key sums of all
+//              elements are weighted and added in the basis Q P by one fused kernel, and each output takes one division by P
 //
 // All kernels are grid-stride and element-wise on fhe_ew_grid, bounds-checked against their element count, plain C++ with
 // vector stores and no scratch.  The transforms are fhe_ntt_forward_dev / fhe_ntt_inverse_dev on the workspace (slot 12),
@@ -148,6 +150,98 @@ __global__ __launch_bounds__(256) void ckks_rns_divround_galois_kernel(const u64
             v = add63(v, c0[e - xx + galois_index((u32)xx, g, L)], m);
         }
         out[c * out_cs + e] = v;
+    }
+}
+
+// ---- plaintext linear transforms: the double-hoisted diagonal sum -------------------------------------------
+constexpr u32 kDiagGroup = 16;     // elements of one launch, passed by value
+constexpr u32 kDiagOutputs = 2;    // outputs whose accumulators one launch keeps in registers: 8 waves a SIMD still (§24)
+
+// The elements of one launch for one target limb.  Indexed by the loop counter, which is uniform: the reads are scalar loads
+// from the kernel-argument segment, not scratch.
+struct DiagGroup {
+    const u64 *key[kDiagGroup];    // element r's key rows of this target: digit j at + j key_stride, [2][n]; not read where g = 1
+    const u64 *pt[kDiagGroup];     // m_{o, r, i} [n] of the launch's first output; output o at + o pt_os
+    u32 g[kDiagGroup];
+    u32 count;
+};
+
+// One target limb i of out_o = sum_r m_{o,r} (.) sigma_{g_r}(ct) in the extended basis, for NOUT outputs and the elements of
+// `grp`, over `count` words a component (rows of n = 2^L):
+//   u_o[c][e] (+)= sum_r m_{o,r,i}[x] (t^(r)_c[e] + pmod ct_c[pi_{g_r}(e)] [c = 0 or g_r = 1]),  x = e mod n
+// t^(r) is ckks_rns_keymac_kernel<true>'s key sum for g_r (zero for g_r = 1: the identity takes no key).  `ct` is limb i's two
+// components, ct_cs words apart, and NULL for the special prime, where the addend vanishes; limb i's own digit is ct's
+// second component.  With pmod = P mod q_i the addend rides through the division by P: (u + P a - E) P^-1 = (u - E) P^-1 + a.
+// With pmod = 1 and no element but the identity, u is the finished sum and `out` the output ciphertext.
+// CARRY: u starts from the canonical words a former group left in `out`; otherwise from zero.
+// Overflow.  Operands are canonical, so a term is below q^2.  Key sum: the addend's term, then the k <= 8 digits.  q < 2^62:
+// nine terms below 2^124 stay below 2^128; one fold, at the end.  q >= 2^62: the accumulators fold before every digit of odd
+// index j: they then hold a canonical carry-over below 2^63 and two terms below 2^126, less than 2^127 + 2^63 < 2^128.
+// Outer sum: u_o takes one term m t < q^2 an element; it folds before element r > 0 of the group where r is a multiple of
+// kMacChunk (q < 2^62: a carry-over below 2^62 and eight terms below 2^124, less than 2^127 + 2^62) or of kMacChunk63
+// (q >= 2^62: a carry-over below 2^63 and two terms below 2^126).  The carry-over is the last fold or the word CARRY read,
+// both canonical; an element that is skipped (the identity modulo P) adds no term.  So any count holds: 256 elements are
+// 16 groups, each folded to canonical words before it is stored.
+template <u32 NOUT, bool CARRY>
+__global__ __launch_bounds__(256) void ckks_rns_diagmac_kernel(const u64 *__restrict__ dig, u64 dig_stride, const u64 *__restrict__ ct, u64 ct_cs, u32 own_j,
+                                                               u64 key_stride, u64 pt_os, u64 *__restrict__ out, u64 out_cs, u64 out_os, u32 k, u32 L, u64 count,
+                                                               u64 pmod, DiagGroup grp, Mod m) {
+    const u64 stride = (u64)gridDim.x * 256, n = 1ull << L;
+    const bool wide = (m.q >> 62) != 0;
+    const u32 chunk = wide ? kMacChunk63 : kMacChunk;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        const u64 x = i & (n - 1);
+        MacAcc u[NOUT][2];
+        if (CARRY) {
+#pragma unroll
+            for (u32 o = 0; o < NOUT; o++) {
+                u[o][0].v = out[o * out_os + i];
+                u[o][1].v = out[o * out_os + out_cs + i];
+            }
+        }
+        for (u32 r = 0; r < grp.count; r++) {
+            if (r && r % chunk == 0) {
+#pragma unroll
+                for (u32 o = 0; o < NOUT; o++) {
+                    if (wide) u[o][0].fold63(m), u[o][1].fold63(m);
+                    else u[o][0].fold(m), u[o][1].fold(m);
+                }
+            }
+            const u32 g = grp.g[r];
+            if (g == 1 && !ct) continue;                             // the identity contributes nothing modulo P
+            const u64 s = i - x + galois_index((u32)x, g, L);
+            MacAcc a0, a1;
+            if (ct) {
+                a0.mac(ct[s], pmod);
+                if (g == 1) a1.mac(ct[ct_cs + s], pmod);
+            }
+            if (g != 1) {
+                const u64 *__restrict__ kr = grp.key[r] + x;
+                for (u32 j = 0; j < k; j++) {
+                    if (wide && (j & 1)) {
+                        a0.fold63(m);
+                        a1.fold63(m);
+                    }
+                    const u64 d = j == own_j ? ct[ct_cs + s] : dig[(u64)(j - (j > own_j ? 1u : 0u)) * dig_stride + s];
+                    const u64 *__restrict__ kp = kr + (u64)j * key_stride;
+                    a0.mac(d, kp[0]);
+                    a1.mac(d, kp[n]);
+                }
+            }
+            const u64 t0 = wide ? a0.fold63(m) : a0.fold(m), t1 = wide ? a1.fold63(m) : a1.fold(m);
+            const u64 *__restrict__ pr = grp.pt[r] + x;
+#pragma unroll
+            for (u32 o = 0; o < NOUT; o++) {
+                const u64 w = pr[o * pt_os];
+                u[o][0].mac(w, t0);
+                u[o][1].mac(w, t1);
+            }
+        }
+#pragma unroll
+        for (u32 o = 0; o < NOUT; o++) {
+            out[o * out_os + i] = wide ? u[o][0].fold63(m) : u[o][0].fold(m);
+            out[o * out_os + out_cs + i] = wide ? u[o][1].fold63(m) : u[o][1].fold(m);
+        }
     }
 }
 
@@ -651,6 +745,135 @@ extern "C" int fhe_ckks_rns_galois_dev(const fhe_ntt_plan *const *plans, unsigne
     for (u64 r0 = 0; r0 < batch; r0 += cb) {
         const u64 cr = std::min<u64>(cb, batch - r0);
         if ((rc = galois_rows(c, (const u64 *const *)d_gks, gs, count, key_limbs, pinv, (const u64 *)d_in, (u64 *)d_out, batch, r0, cr, (u64 *)w, st)) != FHE_OK) return rc;
+    }
+    return FHE_OK;
+}
+
+// ---- plaintext linear transforms: the double-hoisted diagonal sum ---------------------------------------------------
+namespace {
+
+// words of workspace per ciphertext of a chunk: digits k, lifted digits k^2, lifted U_P 2k, then U, 2 (k + 1) an output of a launch
+u64 diag_words_per_row(const Chain &c, unsigned outputs) {
+    return ((u64)c.k * c.k + 3ull * c.k + 2ull * (c.k + 1) * std::min<unsigned>(outputs, fhe::kDiagOutputs)) * c.n;
+}
+
+template <class... A>
+int diagmac_launch(unsigned nout, bool carry, int L, hipStream_t st, unsigned grid, A... a) {
+    const char *lab = "ckks_rns_diagmac";
+#define FHE_DIAG_CASE(N) \
+    case N: return carry ? launch(lab, L, st, fhe::ckks_rns_diagmac_kernel<N, true>, grid, 256, a...) : launch(lab, L, st, fhe::ckks_rns_diagmac_kernel<N, false>, grid, 256, a...)
+    switch (nout) {
+        FHE_DIAG_CASE(1);
+        FHE_DIAG_CASE(2);
+    }
+#undef FHE_DIAG_CASE
+    static_assert(fhe::kDiagOutputs == 2, "one case per accumulator count");
+    return fhe_fail(FHE_E_INVALID, "ckks_rns_diagmac: %u outputs in one launch", nout);
+}
+
+// §24: rows r0 .. r0 + cr of in [k][2][batch][n] -> the same rows of out [outputs][k][2][batch][n], out_o = sum_r m_{o,r} (.)
+// sigma_{g_r}(in).  `switched` (some g != 1): the digits of c1 once; per launch of up to kDiagOutputs outputs, U over the k + 1
+// targets in groups of kDiagGroup elements; per output one modulus-down of U.  Otherwise the sums land in `out` and W is not used.
+int diag_rows(const Chain &c, const u64 *const *gks, const uint64_t *gs, unsigned count, unsigned key_limbs, const u64 *pts, unsigned outputs, bool switched,
+              const u64 *pinv, const u64 *in, u64 *out, u64 batch, u64 r0, u64 cr, u64 *W, hipStream_t st) {
+    const u64 n = c.n, slab = cr * n;
+    const unsigned k = c.k;
+    SwitchBufs b(W, k, slab);
+    b.E = b.T;                                                       // E first: the U of a launch's outputs lie 2 (k + 1) slabs apart
+    b.T = b.E + 2ull * k * slab;
+    const u64 u_os = 2ull * (k + 1) * slab, o_words = 2ull * k * batch * n, pt_os = (u64)count * (k + 1) * n;
+    auto in_at = [&](unsigned limb, unsigned comp) { return in + (((u64)limb * 2 + comp) * batch + r0) * n; };
+    auto out_at = [&](unsigned o, unsigned limb) { return out + (u64)o * o_words + ((u64)limb * 2 * batch + r0) * n; };
+    int rc;
+    if (switched && (rc = digit_rows(c, [&](unsigned limb) { return in_at(limb, 1); }, b, cr, st)) != FHE_OK) return rc;
+    for (unsigned o0 = 0; o0 < outputs; o0 += fhe::kDiagOutputs) {
+        const unsigned nout = std::min<unsigned>(fhe::kDiagOutputs, outputs - o0);
+        for (unsigned i = 0; i < (switched ? k + 1 : k); i++) {
+            for (unsigned e0 = 0; e0 < count; e0 += fhe::kDiagGroup) {
+                fhe::DiagGroup grp{};
+                grp.count = std::min<unsigned>(fhe::kDiagGroup, count - e0);
+                for (unsigned r = 0; r < grp.count; r++) {
+                    grp.g[r] = (u32)gs[e0 + r];
+                    grp.key[r] = grp.g[r] == 1 ? nullptr : gks[e0 + r] + (u64)(i < k ? i : key_limbs) * 2 * n;
+                    grp.pt[r] = pts + (((u64)o0 * count + e0 + r) * (k + 1) + i) * n;
+                }
+                u64 *dst = switched ? b.T + 2ull * i * slab : out_at(o0, i);
+                const u64 pmod = !switched ? 1 : i < k ? c.p[k]->q % c.p[i]->q : 0;
+                if ((rc = diagmac_launch(nout, e0 > 0, (int)c.L, st, fhe_ew_grid(slab), switched ? b.D_of(i) : nullptr, slab, i < k ? in_at(i, 0) : nullptr, batch * n, i,
+                                         (u64)(key_limbs + 1) * 2 * n, pt_os, dst, switched ? slab : batch * n, switched ? u_os : o_words, k, c.L, slab, pmod, grp,
+                                         c.p[i]->mod)) != FHE_OK)
+                    return rc;
+            }
+        }
+        for (unsigned o = 0; switched && o < nout; o++) {
+            SwitchBufs bo = b;
+            bo.T = b.T + (u64)o * u_os;
+            if ((rc = special_rows(c, bo, cr, st)) != FHE_OK) return rc;
+            for (unsigned i = 0; i < k; i++)
+                if ((rc = launch("ckks_rns_divround", (int)c.L, st, fhe::ckks_rns_divround_kernel, fhe_ew_grid(2 * slab), 256, bo.T + 2ull * i * slab, slab,
+                                 bo.E + 2ull * i * slab, slab, nullptr, 0, out_at(o0 + o, i), batch * n, slab, pinv[i], c.p[i]->mod)) != FHE_OK)
+                    return rc;
+        }
+    }
+    return FHE_OK;
+}
+
+}  // namespace
+
+extern "C" size_t fhe_ckks_rns_diag_workspace_bytes(uint64_t n, unsigned limbs, size_t batch, unsigned count, unsigned outputs) {
+    if (n < 2 || (n & (n - 1)) != 0 || n > (1ull << 19) || limbs < 1 || limbs > fhe::kRnsMaxLimbs || batch == 0 || count == 0 || count > FHE_CKKS_GALOIS_MAX_COUNT ||
+        outputs == 0 || outputs > FHE_CKKS_DIAG_MAX_OUTPUTS)
+        return 0;
+    Chain c;
+    c.k = limbs;
+    c.n = n;
+    c.L = log2_of(n);
+    return (size_t)(diag_words_per_row(c, outputs) * chunk_rows(c, batch) * 8);   // the digits are shared and the elements summed in registers: count does not enter
+}
+
+extern "C" int fhe_ckks_rns_diag_sum_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *const *d_gks, const uint64_t *gs,
+                                         unsigned count, unsigned key_limbs, const void *d_pts, unsigned outputs, const void *d_in, void *d_out, size_t batch,
+                                         void *hip_stream) {
+    const char *who = "fhe_ckks_rns_diag_sum_dev";
+    Chain c;
+    int rc = check_chain(plans, limbs, special, true, &c, who);
+    if (rc != FHE_OK) return rc;
+    if ((rc = check_key_limbs(c, key_limbs, who)) != FHE_OK) return rc;
+    if (count > FHE_CKKS_GALOIS_MAX_COUNT) return fhe_fail(FHE_E_INVALID, "%s: count=%u passes %d", who, count, FHE_CKKS_GALOIS_MAX_COUNT);
+    if (outputs < 1 || outputs > FHE_CKKS_DIAG_MAX_OUTPUTS) return fhe_fail(FHE_E_INVALID, "%s: outputs=%u must be in [1, %d]", who, outputs, FHE_CKKS_DIAG_MAX_OUTPUTS);
+    if (batch == 0 || count == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, 2ull * c.k * n * outputs, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!gs || !d_pts || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_pts) || misaligned8(d_in) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 ct_bytes = 2ull * c.k * batch * n * 8, gk_bytes = (u64)key_limbs * (key_limbs + 1) * 2 * n * 8, out_bytes = ct_bytes * outputs;
+    bool switched = false;
+    for (unsigned r = 0; r < count; r++) {
+        if ((gs[r] & 1) == 0 || gs[r] >= 2 * n) return fhe_fail(FHE_E_INVALID, "%s: g[%u]=%llu must be odd and below 2n", who, r, (unsigned long long)gs[r]);
+        if (gs[r] == 1) continue;                                    // the identity takes no key: its entry is not read
+        switched = true;
+        if (!d_gks || !d_gks[r]) return fhe_fail(FHE_E_NULL, "%s: key %u is NULL", who, r);
+        if (misaligned8(d_gks[r])) return fhe_fail(FHE_E_INVALID, "%s: key %u must be 8-byte aligned", who, r);
+        if (overlaps_any(d_out, out_bytes, {{d_gks[r], gk_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps key %u", who, r);
+    }
+    if (overlaps_any(d_out, out_bytes, {{d_in, ct_bytes}, {d_pts, (u64)outputs * count * (c.k + 1) * n * 8}}))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the ciphertexts or the plaintexts", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const u64 cb = chunk_rows(c, batch);
+    void *w = nullptr;
+    if (switched) {
+        if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(diag_words_per_row(c, outputs) * cb * 8), st, &w)) != FHE_OK) return rc;
+    } else {
+        int dev;
+        if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
+    }
+    u64 pinv[fhe::kRnsMaxLimbs];
+    special_inverses(c, pinv);
+    for (u64 r0 = 0; r0 < batch; r0 += cb) {
+        const u64 cr = std::min<u64>(cb, batch - r0);
+        if ((rc = diag_rows(c, (const u64 *const *)d_gks, gs, count, key_limbs, (const u64 *)d_pts, outputs, switched, pinv, (const u64 *)d_in, (u64 *)d_out, batch, r0,
+                            cr, (u64 *)w, st)) != FHE_OK)
+            return rc;
     }
     return FHE_OK;
 }

@@ -687,6 +687,27 @@ int fhe_ckks_rns_galois_dev(const fhe_ntt_plan *const *plans, unsigned limbs, co
                             const void *d_in, void *d_out, size_t batch, void *hip_stream);
 size_t fhe_ckks_rns_galois_workspace_bytes(uint64_t n, unsigned limbs, size_t batch, unsigned count);
 
+/* ---- CKKS on the RNS chain: plaintext linear transforms, the double-hoisted diagonal sum (ckks_eval.hip) ----
+ *   fhe_ckks_rns_diag_sum_dev     d_out [outputs][limbs][2][batch][n]: out_o = sum_{r < count} m_{o,r} (.) sigma_{gs[r]}(d_in) for
+ *            d_in [limbs][2][batch][n] and the plaintexts d_pts [outputs][count][limbs + 1][n], canonical evals under the chain
+ *            primes and, as limb `limbs`, under P, shared by the batch.  The digit decomposition of c1 runs once per chunk;
+ *            the key sums of all elements are weighted and added in the basis Q P, and each output takes ONE division by P.
+ *            An element gs[r] = 1 is the identity: it takes no key, d_gks[r] is not read and may be NULL (d_gks itself may be
+ *            NULL where every element is 1; then nothing is transformed and no key switch runs).  Elements may repeat.
+ *            Level is unchanged; the scale is the ciphertext's times the plaintexts'.  The words are those of the formula
+ *            in §24 whatever the order of accumulation: every sum is exact modulo q_i.
+ *   fhe_ckks_rns_diag_workspace_bytes  the library workspace that call takes at most; 0 for a shape it refuses
+ * d_gks and gs are HOST arrays, as for fhe_ckks_rns_galois_dev, and the conditions are that block's, and: FHE_E_INVALID for
+ * outputs = 0 or > FHE_CKKS_DIAG_MAX_OUTPUTS and for an output that overlaps the plaintexts; FHE_E_NULL for a NULL key of an
+ * element other than 1.  A plaintext word must be below its modulus: like the ciphertext's canonicity this is the caller's
+ * contract and is not checked on the device.  batch = 0 or count = 0 is a no-op (count = 0 writes nothing, not zeros). */
+#define FHE_CKKS_DIAG_MAX_OUTPUTS 64
+int fhe_ckks_rns_diag_sum_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special,
+                              const void *const *d_gks, const uint64_t *gs, unsigned count, unsigned key_limbs,
+                              const void *d_pts, unsigned outputs, const void *d_in, void *d_out, size_t batch,
+                              void *hip_stream);
+size_t fhe_ckks_rns_diag_workspace_bytes(uint64_t n, unsigned limbs, size_t batch, unsigned count, unsigned outputs);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
