@@ -48,7 +48,7 @@ int fhe_hip_fail(hipError_t e, const char *what) {
 static inline u64 mulmod(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
 
 // ntt.rs:164-179 const_exp_mod
-static u64 exp_mod(u64 q, u64 x, u64 k) {
+u64 fhe_exp_mod(u64 q, u64 x, u64 k) {
     u64 r = 1;
     x %= q;
     while (k > 0) {
@@ -59,7 +59,7 @@ static u64 exp_mod(u64 q, u64 x, u64 k) {
     return r;
 }
 // ntt.rs:182-185 const_inv_mod (Fermat; q assumed prime as in the reference)
-static u64 inv_mod(u64 q, u64 x) { return exp_mod(q, x, q - 2); }
+u64 fhe_inv_mod(u64 q, u64 x) { return fhe_exp_mod(q, x, q - 2); }
 
 static inline u64 shoup(u64 w, u64 q) { return (u64)((((u128)w) << 64) / q); }
 
@@ -94,13 +94,13 @@ static int build_plan(u64 q, u64 n, fhe_ntt_plan *p) {
     // first k = 1,2,.. with w = k^((q-1)/2n), w^n != 1   (ntt.rs:120-129)
     u64 psi = 0;
     for (u64 k = 1; k < q; k++) {
-        u64 w = exp_mod(q, k, (q - 1) / (2 * n));
-        if (exp_mod(q, w, n) != 1) { psi = w; break; }
+        u64 w = fhe_exp_mod(q, k, (q - 1) / (2 * n));
+        if (fhe_exp_mod(q, w, n) != 1) { psi = w; break; }
     }
     if (psi == 0) return fail(FHE_E_NO_ROOT, "No primitive root of unity (ntt.rs:130)");
 
     p->q = q; p->n = n; p->log_n = log_n; p->psi = psi;
-    p->n_inv = inv_mod(q, n);  // ntt.rs:27-30
+    p->n_inv = fhe_inv_mod(q, n);  // ntt.rs:27-30
     p->roots.resize(n);
     p->roots_inv.resize(n);
     // roots[i] = psi^bitrev(i) (ntt.rs:133-147): running powers, then bit-reverse
@@ -114,7 +114,7 @@ static int build_plan(u64 q, u64 n, fhe_ntt_plan *p) {
     }
     // roots_inv[i] = roots[i]^(q-2) (ntt.rs:149-161) — kept as the reference's
     // Fermat power so that the tables agree even if q is not prime.
-    for (u64 i = 0; i < n; i++) p->roots_inv[i] = inv_mod(q, p->roots[i]);
+    for (u64 i = 0; i < n; i++) p->roots_inv[i] = fhe_inv_mod(q, p->roots[i]);
 
     p->mod.q = q;
     p->mod.q2 = 2 * q;

@@ -51,6 +51,9 @@ int fhe_hip_fail(hipError_t e, const char *what);
     } while (0)
 
 int fhe_current_device(int *dev);
+// host number theory (capi.hip): x^k mod q, and x^-1 mod q for a prime q that does not divide x
+fhe::u64 fhe_exp_mod(fhe::u64 q, fhe::u64 x, fhe::u64 k);
+fhe::u64 fhe_inv_mod(fhe::u64 q, fhe::u64 x);
 // FHE_NTT_CHECK_CANONICAL / fhe_ntt_set_check_canonical(1): FHE_E_NOT_CANONICAL if any of `count` device words is >= q (synchronises `st`); FHE_OK when the check is off
 int fhe_check_canonical_words(uint64_t q, const void *d_x, size_t count, hipStream_t st, const char *who);
 int fhe_device_plan(const fhe_ntt_plan *plan, fhe::DevicePlan *dp);

@@ -21,6 +21,10 @@
 // vector stores and no scratch.  The transforms are fhe_ntt_forward_dev / fhe_ntt_inverse_dev on the workspace (slot 12),
 // one call per limb and direction over everything of that limb that is ready; a chunk is 2^21 / (n k^2) ciphertexts
 // (2^21 / (n k) for a rescale, which stages 2k slabs a ciphertext).
+//
+// One of each: key_sum is the digit-times-key sum of both accumulating kernels; moddown_rows the modulus-down
+// of every key switch and of the rescale (lift, forward and divide-and-round per remaining limb); SwitchBufs the layout and
+// the size of a key switch's workspace; switch_call the chunking, workspace and inverses of P of every key-switch entry point.
 #include "bfv_client_kernels.hpp"
 
 using fhe::Mod;
@@ -91,12 +95,30 @@ __global__ __launch_bounds__(256) void ckks_rns_tensor_kernel(const u64 *__restr
     }
 }
 
-// One target limb of the key switch: out[c][i] = sum_{j < k} D_j[i] key[j][c][i mod n], c = 0, 1, `count` words a component.
-// Digit j is `own` for j = own_j (the limb's own d2 evals, never lifted) and dig + (j - (j > own_j)) dig_stride otherwise; the
-// key row of digit j is key + j key_stride, [2][n], shared by the batch.
-// Overflow: operands are canonical, so a term is below q^2.  q < 2^62: k <= 8 terms below 2^124 sum to less than 2^127 and
-// the accumulators fold once, at the end.  q >= 2^62: a term is below 2^126, so the accumulators fold before every term of
-// even index j >= 2 (kMacChunk63 = 2): a canonical carry-over below 2^63 and two terms stay below 2^127 + 2^63 < 2^128.
+// The key sum of one word: a_c += sum_{j < k} D_j[s] key[j][c], c = 0, 1.  Digit j is own[s] for j = own_j (the limb's own
+// evals, never lifted; `own` is not read for the special prime, whose own_j is k) and dig[(j - (j > own_j)) dig_stride + s]
+// otherwise; its key words are key[j key_stride + x] and key[j key_stride + x + n], x the word's column.
+// Overflow: operands are canonical, so a term is below q^2, and the accumulators hold `held` <= 1 such terms on entry.
+// q < 2^62: 1 + k <= 9 terms below 2^124 stay below 2^128 and the caller folds once, after the sum.  q >= 2^62 (`wide`): a
+// term is below 2^126, so the accumulators fold before every digit that would be their third term since the last fold
+// (kMacChunk63 = 2; before even j >= 2 where held = 0, before odd j where held = 1): they then hold a canonical carry-over
+// below 2^63 and at most two terms, less than 2^127 + 2^63 < 2^128.
+__device__ __forceinline__ void key_sum(MacAcc &a0, MacAcc &a1, u32 held, const u64 *__restrict__ dig, u64 dig_stride, const u64 *__restrict__ own, u32 own_j,
+                                        const u64 *__restrict__ key, u64 key_stride, u64 n, u64 x, u64 s, u32 k, bool wide, const Mod &m) {
+    for (u32 j = 0; j < k; j++) {
+        if (wide && j && (held + j) % kMacChunk63 == 0) {                // held <= 1: nothing to fold before digit 0
+            a0.fold63(m);
+            a1.fold63(m);
+        }
+        const u64 d = j == own_j ? own[s] : dig[(u64)(j - (j > own_j ? 1u : 0u)) * dig_stride + s];
+        const u64 *__restrict__ kp = key + (u64)j * key_stride + x;
+        a0.mac(d, kp[0]);
+        a1.mac(d, kp[n]);
+    }
+}
+
+// One target limb of the key switch: out[c][i] = sum_{j < k} D_j[i] key[j][c][i mod n], c = 0, 1, `count` words a component;
+// the key row of digit j is key + j key_stride, [2][n], shared by the batch.
 // GATHER (a Galois key switch, §23): the digits and `own` are read at pi_g of the index within the row, the key row at the
 // index itself; g is not read otherwise.
 template <bool GATHER>
@@ -108,46 +130,30 @@ __global__ __launch_bounds__(256) void ckks_rns_keymac_kernel(const u64 *__restr
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
         const u64 x = i & (n - 1), s = GATHER ? i - x + galois_index((u32)x, g, L) : i;
         MacAcc a0, a1;
-        for (u32 j = 0; j < k; j++) {
-            if (wide && j && (j % kMacChunk63) == 0) {
-                a0.fold63(m);
-                a1.fold63(m);
-            }
-            const u64 d = j == own_j ? own[s] : dig[(u64)(j - (j > own_j ? 1u : 0u)) * dig_stride + s];
-            const u64 *__restrict__ kp = key + (u64)j * key_stride + x;
-            a0.mac(d, kp[0]);
-            a1.mac(d, kp[n]);
-        }
+        key_sum(a0, a1, 0, dig, dig_stride, own, own_j, key, key_stride, n, x, s, k, wide, m);
         out[i] = wide ? a0.fold63(m) : a0.fold(m);
         out[count + i] = wide ? a1.fold63(m) : a1.fold(m);
     }
 }
 
-// out = (x - t) inv (+ add) mod q over two components of `count` words, each operand's components `*_cs` words apart
+// out = (x - t) inv (+ add) mod q over two components of `count` words, each operand's components `*_cs` words apart.  The
+// addend is optional, goes to both components and is read at the index itself; g and L, which follow m so that this form's
+// arguments lie where they always did, are not read.
+// GATHER (the divide-and-round of a Galois key switch, rows of n = 2^L): the addend is pi_g(c0) of the input ciphertext,
+// gathered here; it goes to the first component only, and add_cs is not read.
+template <bool GATHER>
 __global__ __launch_bounds__(256) void ckks_rns_divround_kernel(const u64 *__restrict__ x, u64 x_cs, const u64 *__restrict__ t, u64 t_cs,
                                                                 const u64 *__restrict__ add, u64 add_cs, u64 *__restrict__ out, u64 out_cs, u64 count, u64 inv,
-                                                                Mod m) {
-    const u64 stride = (u64)gridDim.x * 256;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < 2 * count; i += stride) {
-        const u64 c = i >= count ? 1u : 0u, e = i - c * count;
-        u64 v = bfv_mulmod(sub63(x[c * x_cs + e], t[c * t_cs + e], m), inv, m);
-        if (add) v = add63(v, add[c * add_cs + e], m);
-        out[c * out_cs + e] = v;
-    }
-}
-
-// the divide-and-round of a Galois key switch: out = (x - t) inv mod q over two components of `count` words (rows of n = 2^L),
-// and the addend pi_g(c0) of the first component gathered from the input ciphertext here
-__global__ __launch_bounds__(256) void ckks_rns_divround_galois_kernel(const u64 *__restrict__ x, u64 x_cs, const u64 *__restrict__ t, u64 t_cs,
-                                                                       const u64 *__restrict__ c0, u64 *__restrict__ out, u64 out_cs, u64 count, u64 inv,
-                                                                       u32 g, u32 L, Mod m) {
+                                                                Mod m, u32 g, u32 L) {
     const u64 stride = (u64)gridDim.x * 256, n = 1ull << L;
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < 2 * count; i += stride) {
         const u64 c = i >= count ? 1u : 0u, e = i - c * count;
         u64 v = bfv_mulmod(sub63(x[c * x_cs + e], t[c * t_cs + e], m), inv, m);
-        if (c == 0) {
+        if (GATHER && c == 0) {
             const u64 xx = e & (n - 1);
-            v = add63(v, c0[e - xx + galois_index((u32)xx, g, L)], m);
+            v = add63(v, add[e - xx + galois_index((u32)xx, g, L)], m);
+        } else if (!GATHER && add) {
+            v = add63(v, add[c * add_cs + e], m);
         }
         out[c * out_cs + e] = v;
     }
@@ -174,9 +180,7 @@ struct DiagGroup {
 // second component.  With pmod = P mod q_i the addend rides through the division by P: (u + P a - E) P^-1 = (u - E) P^-1 + a.
 // With pmod = 1 and no element but the identity, u is the finished sum and `out` the output ciphertext.
 // CARRY: u starts from the canonical words a former group left in `out`; otherwise from zero.
-// Overflow.  Operands are canonical, so a term is below q^2.  Key sum: the addend's term, then the k <= 8 digits.  q < 2^62:
-// nine terms below 2^124 stay below 2^128; one fold, at the end.  q >= 2^62: the accumulators fold before every digit of odd
-// index j: they then hold a canonical carry-over below 2^63 and two terms below 2^126, less than 2^127 + 2^63 < 2^128.
+// Overflow.  Operands are canonical, so a term is below q^2.  Key sum: the addend's term, then key_sum with that one term held.
 // Outer sum: u_o takes one term m t < q^2 an element; it folds before element r > 0 of the group where r is a multiple of
 // kMacChunk (q < 2^62: a carry-over below 2^62 and eight terms below 2^124, less than 2^127 + 2^62) or of kMacChunk63
 // (q >= 2^62: a carry-over below 2^63 and two terms below 2^126).  The carry-over is the last fold or the word CARRY read,
@@ -189,6 +193,7 @@ __global__ __launch_bounds__(256) void ckks_rns_diagmac_kernel(const u64 *__rest
     const u64 stride = (u64)gridDim.x * 256, n = 1ull << L;
     const bool wide = (m.q >> 62) != 0;
     const u32 chunk = wide ? kMacChunk63 : kMacChunk;
+    const u64 *__restrict__ own = ct ? ct + ct_cs : nullptr;
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
         const u64 x = i & (n - 1);
         MacAcc u[NOUT][2];
@@ -215,19 +220,7 @@ __global__ __launch_bounds__(256) void ckks_rns_diagmac_kernel(const u64 *__rest
                 a0.mac(ct[s], pmod);
                 if (g == 1) a1.mac(ct[ct_cs + s], pmod);
             }
-            if (g != 1) {
-                const u64 *__restrict__ kr = grp.key[r] + x;
-                for (u32 j = 0; j < k; j++) {
-                    if (wide && (j & 1)) {
-                        a0.fold63(m);
-                        a1.fold63(m);
-                    }
-                    const u64 d = j == own_j ? ct[ct_cs + s] : dig[(u64)(j - (j > own_j ? 1u : 0u)) * dig_stride + s];
-                    const u64 *__restrict__ kp = kr + (u64)j * key_stride;
-                    a0.mac(d, kp[0]);
-                    a1.mac(d, kp[n]);
-                }
-            }
+            if (g != 1) key_sum(a0, a1, 1, dig, dig_stride, own, own_j, grp.key[r], key_stride, n, x, s, k, wide, m);
             const u64 t0 = wide ? a0.fold63(m) : a0.fold(m), t1 = wide ? a1.fold63(m) : a1.fold(m);
             const u64 *__restrict__ pr = grp.pt[r] + x;
 #pragma unroll
@@ -245,19 +238,15 @@ __global__ __launch_bounds__(256) void ckks_rns_diagmac_kernel(const u64 *__rest
     }
 }
 
-// the diagonal term of the relinearisation key, in evals: pk0 += c s^2 (c = P mod q_j)
-__global__ __launch_bounds__(256) void ckks_rns_keyterm_kernel(u64 *__restrict__ pk0, const u64 *__restrict__ s_evals, u64 c, u64 n, Mod m) {
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
-        const u64 s = s_evals[i];
-        pk0[i] = add63(pk0[i], bfv_mulmod(c, bfv_mulmod(s, s, m), m), m);
-    }
-}
-
-// the diagonal term of a Galois key, in evals: pk0 += c sigma_g(s)^, the secret's evals gathered by pi_g (n = 2^L)
-__global__ __launch_bounds__(256) void ckks_rns_keyterm_galois_kernel(u64 *__restrict__ pk0, const u64 *__restrict__ s_evals, u64 c, u32 g, u32 L, Mod m) {
+// the diagonal term of a switching key, in evals (n = 2^L, c = P mod q_j): pk0 += c s^2 for the relinearisation key, g not
+// read; GALOIS: pk0 += c sigma_g(s)^, the secret's evals gathered by pi_g
+template <bool GALOIS>
+__global__ __launch_bounds__(256) void ckks_rns_keyterm_kernel(u64 *__restrict__ pk0, const u64 *__restrict__ s_evals, u64 c, u32 g, u32 L, Mod m) {
     const u64 n = 1ull << L;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
-        pk0[i] = add63(pk0[i], bfv_mulmod(c, s_evals[galois_index((u32)i, g, L)], m), m);
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+        const u64 s = s_evals[GALOIS ? galois_index((u32)i, g, L) : i];
+        pk0[i] = add63(pk0[i], bfv_mulmod(c, GALOIS ? s : bfv_mulmod(s, s, m), m), m);
+    }
 }
 
 }  // namespace fhe
@@ -274,15 +263,14 @@ struct Chain {
     const fhe_ntt_plan *p[fhe::kRnsMaxTargets] = {};   // p[k] is the special prime's plan where the call has one
 };
 
-u64 pow_mod(u64 b, u64 e, u64 q) {
-    u64 r = 1;
-    for (b %= q; e; e >>= 1) {
-        if (e & 1) r = (u64)((unsigned __int128)r * b % q);
-        b = (u64)((unsigned __int128)b * b % q);
-    }
-    return r;
+// the chain of a *_workspace_bytes query, which has sizes and no plans; false where one of them is out of range
+bool chain_of(uint64_t n, unsigned limbs, size_t batch, Chain *c) {
+    if (n < 2 || (n & (n - 1)) != 0 || n > (1ull << 19) || limbs < 1 || limbs > fhe::kRnsMaxLimbs || batch == 0) return false;
+    c->k = limbs;
+    c->n = n;
+    c->L = log2_of(n);
+    return true;
 }
-u64 inv_mod(u64 a, u64 q) { return pow_mod(a % q, q - 2, q); }   // q prime, a not a multiple of q
 
 // plans[0 .. limbs) and, where the entry point takes one, the special prime: FHE_E_NULL, then the limb count, the ring, the
 // repeated moduli, P >= max q_i
@@ -314,10 +302,16 @@ int check_chain(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_
 u64 chunk_rows(const Chain &c, u64 batch) { return std::min<u64>(batch, std::max<u64>(1, (kChunkWords >> c.L) / ((u64)c.k * c.k))); }
 // a rescale stages 2k slabs a ciphertext, not k^2 + 8k + 2: its chunk is 2^21 / (n k) ciphertexts, at least one
 u64 rescale_chunk_rows(const Chain &c, u64 batch) { return std::min<u64>(batch, std::max<u64>(1, (kChunkWords >> c.L) / (u64)c.k)); }
-// words of workspace per ciphertext of a chunk: tensor 3k, digits k, lifted digits k^2, t 2(k + 1), lifted t_P 2k
-u64 words_per_row(const Chain &c) { return ((u64)c.k * c.k + 8ull * c.k + 2) * c.n; }
-// a Galois key switch has no tensor: digits k, lifted digits k^2, t 2(k + 1), lifted t_P 2k, whatever the number of elements
-u64 galois_words_per_row(const Chain &c) { return ((u64)c.k * c.k + 5ull * c.k + 2) * c.n; }
+
+// body(r0, cr) over the batch in chunks of cb ciphertexts
+template <class Body>
+int for_chunks(u64 batch, u64 cb, Body body) {
+    for (u64 r0 = 0; r0 < batch; r0 += cb) {
+        const int rc = body(r0, std::min<u64>(cb, batch - r0));
+        if (rc != FHE_OK) return rc;
+    }
+    return FHE_OK;
+}
 
 int lift_launch(bool is_signed, const u64 *src, u64 *dst, u64 count, u64 qs, const fhe::LiftArgs &a, u32 L, hipStream_t st) {
     if (a.targets == 0) return FHE_OK;
@@ -348,15 +342,25 @@ int tensor_rows(const Chain &c, const u64 *a, const u64 *b, u64 batch, u64 r0, u
 }
 
 // The workspace of one key switch over cr ciphertexts (slab = cr n words): C the k digits in coefficients, D their lifts as
-// evals (limb i < k holds the k - 1 digits j != i, P all k), T the k + 1 key sums of two components, E the lifted t_P
+// evals (limb i < k holds the k - 1 digits j != i, P all k), `sets` sets T of the k + 1 key sums of two components (one
+// for a relinearisation or a Galois element, one per output of a diagonal launch), E the lifted t_P of one set at a time
 struct SwitchBufs {
     u64 *C, *D, *T, *E;
-    u64 slab;
+    u64 slab, set;                                                   // words of one T set: 2 (k + 1) slabs
     unsigned k;
-    SwitchBufs(u64 *W, unsigned k_, u64 slab_) : C(W), D(C + k_ * slab_), T(D + (u64)k_ * k_ * slab_), E(T + 2ull * (k_ + 1) * slab_), slab(slab_), k(k_) {}
+    static u64 words(unsigned k, unsigned sets) { return (u64)k * k + 3ull * k + 2ull * (k + 1) * sets; }   // in slabs: C k, D k^2, E 2k, T
+    SwitchBufs(u64 *W, unsigned k_, unsigned sets, u64 slab_)
+        : C(W), D(C + k_ * slab_), T(D + (u64)k_ * k_ * slab_), E(T + 2ull * (k_ + 1) * slab_ * sets), slab(slab_), set(2ull * (k_ + 1) * slab_), k(k_) {}
     u64 *D_of(unsigned i) const { return D + (u64)i * (k - 1) * slab; }
-    u64 *TP() const { return T + 2ull * k * slab; }
+    u64 *T_of(unsigned o) const { return T + o * set; }
+    u64 *TP(unsigned o) const { return T_of(o) + 2ull * k * slab; }
 };
+// words of workspace per ciphertext of a chunk.  A Galois key switch shares the digits among its elements and a diagonal sum
+// adds the elements in registers, so their count does not enter; ct x ct stages the tensor's 3k slabs in front (and the
+// relinearisation of a given tensor asks for as much)
+u64 galois_words_per_row(const Chain &c) { return SwitchBufs::words(c.k, 1) * c.n; }
+u64 words_per_row(const Chain &c) { return galois_words_per_row(c) + 3ull * c.k * c.n; }
+u64 diag_words_per_row(const Chain &c, unsigned outputs) { return SwitchBufs::words(c.k, std::min<unsigned>(outputs, fhe::kDiagOutputs)) * c.n; }
 
 // steps (1)-(3) of §22: digit j = src(j) (cr rows of evals modulo q_j) in coefficients, lifted to every limb i != j of
 // {0 .. k - 1, P} and transformed
@@ -379,51 +383,65 @@ int digit_rows(const Chain &c, Src src, const SwitchBufs &b, u64 cr, hipStream_t
     return FHE_OK;
 }
 
-// step (4): t_i = sum_j D_ji (.) key[j][i], i in {0 .. k - 1, P}; own(i) is limb i's own digit in evals.  GATHER: a Galois key
+// the rows of limb i of a ciphertext-shaped operand: limbs ls words apart, the two components cs words apart; p NULL for none
+template <class T>
+struct LimbRows {
+    T *p;
+    u64 ls, cs;
+    T *of(unsigned i) const { return p ? p + (u64)i * ls : nullptr; }
+};
+
+// The modulus-down by the prime of plan `drop`, which leaves limbs 0 .. drop - 1 (the special prime after a key switch, the
+// top limb in a rescale).  X holds the dropped limb's two components in coefficients, `slab` words each; they are lifted to
+// every remaining limb and transformed in E (2 drop slabs), and out_i = (x_i - E_i) inv[i] (+ add_i) mod q_i.  g != 0: the
+// modulus-down of a Galois key switch, whose addend is pi_g of add's first component, for the first component only.
+int moddown_rows(const Chain &c, unsigned drop, const u64 *X, u64 *E, u64 slab, LimbRows<const u64> x, LimbRows<const u64> add, LimbRows<u64> out, const u64 *inv,
+                 u32 g, hipStream_t st) {
+    int rc;
+    fhe::LiftArgs a{};
+    for (unsigned i = 0; i < drop; i++) lift_target(&a, c.p[i], 2ull * i * slab);
+    if ((rc = lift_launch(false, X, E, 2 * slab, c.p[drop]->q, a, c.L, st)) != FHE_OK) return rc;
+    for (unsigned i = 0; i < drop; i++)
+        if ((rc = fhe_ntt_forward_dev(c.p[i], E + a.off[i], E + a.off[i], 2 * (slab >> c.L), st)) != FHE_OK) return rc;
+    for (unsigned i = 0; i < drop; i++)
+        if ((rc = launch(g ? "ckks_rns_divround_galois" : "ckks_rns_divround", (int)c.L, st, g ? fhe::ckks_rns_divround_kernel<true> : fhe::ckks_rns_divround_kernel<false>,
+                         fhe_ew_grid(2 * slab), 256, x.of(i), x.cs, E + a.off[i], slab, add.of(i), add.cs, out.of(i), out.cs, slab, inv[i], c.p[i]->mod, g, c.L)) != FHE_OK)
+            return rc;
+    return FHE_OK;
+}
+
+// step (4): T = sum_j D_ji (.) key[j][i], i in {0 .. k - 1, P}; own(i) is limb i's own digit in evals.  g != 0: a Galois key
 // switch, the digits read at pi_g
-template <bool GATHER, class Own>
+template <class Own>
 int keymac_rows(const Chain &c, const u64 *key, unsigned key_limbs, Own own, const SwitchBufs &b, u32 g, hipStream_t st) {
     const unsigned k = c.k;
     const u64 n = c.n;
     for (unsigned i = 0; i <= k; i++) {
         const u64 *col = key + (u64)(i < k ? i : key_limbs) * 2 * n;
-        const int rc = launch(GATHER ? "ckks_rns_keymac_galois" : "ckks_rns_keymac", (int)c.L, st, fhe::ckks_rns_keymac_kernel<GATHER>, fhe_ew_grid(b.slab), 256, b.D_of(i),
-                              b.slab, i < k ? own(i) : nullptr, i, col, (u64)(key_limbs + 1) * 2 * n, b.T + 2ull * i * b.slab, k, c.L, b.slab, g, c.p[i]->mod);
+        const int rc = launch(g ? "ckks_rns_keymac_galois" : "ckks_rns_keymac", (int)c.L, st, g ? fhe::ckks_rns_keymac_kernel<true> : fhe::ckks_rns_keymac_kernel<false>,
+                              fhe_ew_grid(b.slab), 256, b.D_of(i), b.slab, i < k ? own(i) : nullptr, i, col, (u64)(key_limbs + 1) * 2 * n, b.T + 2ull * i * b.slab, k, c.L,
+                              b.slab, g, c.p[i]->mod);
         if (rc != FHE_OK) return rc;
     }
     return FHE_OK;
 }
 
-// the first half of step (5): t_P in coefficients, lifted to every limb and transformed -> E
-int special_rows(const Chain &c, const SwitchBufs &b, u64 cr, hipStream_t st) {
-    const unsigned k = c.k;
-    int rc;
-    if ((rc = fhe_ntt_inverse_dev(c.p[k], b.TP(), b.TP(), 2 * cr, st)) != FHE_OK) return rc;
-    fhe::LiftArgs a{};
-    for (unsigned i = 0; i < k; i++) lift_target(&a, c.p[i], 2ull * i * b.slab);
-    if ((rc = lift_launch(false, b.TP(), b.E, 2 * b.slab, c.p[k]->q, a, c.L, st)) != FHE_OK) return rc;
-    for (unsigned i = 0; i < k; i++)
-        if ((rc = fhe_ntt_forward_dev(c.p[i], b.E + 2ull * i * b.slab, b.E + 2ull * i * b.slab, 2 * cr, st)) != FHE_OK) return rc;
-    return FHE_OK;
+// step (5) on set o of T: t_P in coefficients, in place, and the modulus-down by P of the set's k limbs
+int special_down(const Chain &c, const SwitchBufs &b, unsigned o, LimbRows<const u64> add, LimbRows<u64> out, const u64 *pinv, u32 g, hipStream_t st) {
+    const int rc = fhe_ntt_inverse_dev(c.p[c.k], b.TP(o), b.TP(o), 2 * (b.slab >> c.L), st);
+    return rc != FHE_OK ? rc : moddown_rows(c, c.k, b.TP(o), b.E, b.slab, {b.T_of(o), 2 * b.slab, b.slab}, add, out, pinv, g, st);
 }
 
-// rows d_r0 .. d_r0 + cr of d [k][3][d_rows][n] -> rows o_r0 .. of out [k][2][o_rows][n]; W holds (k^2 + 5k + 2) cr n words
+// rows d_r0 .. d_r0 + cr of d [k][3][d_rows][n] -> rows o_r0 .. of out [k][2][o_rows][n]; W holds SwitchBufs::words(k, 1) slabs
 int relin_rows(const Chain &c, const u64 *rlk, unsigned key_limbs, const u64 *pinv, const u64 *d, u64 d_rows, u64 d_r0, u64 *out, u64 o_rows, u64 o_r0, u64 cr,
                u64 *W, hipStream_t st) {
-    const u64 n = c.n, slab = cr * n;
-    const unsigned k = c.k;
-    const SwitchBufs b(W, k, slab);
-    auto d_at = [&](unsigned limb, unsigned comp) { return d + (((u64)limb * 3 + comp) * d_rows + d_r0) * n; };
-    auto d2 = [&](unsigned limb) { return d_at(limb, 2); };
+    const u64 n = c.n;
+    const SwitchBufs b(W, c.k, 1, cr * n);
+    auto d2 = [&](unsigned limb) { return d + (((u64)limb * 3 + 2) * d_rows + d_r0) * n; };
     int rc;
     if ((rc = digit_rows(c, d2, b, cr, st)) != FHE_OK) return rc;
-    if ((rc = keymac_rows<false>(c, rlk, key_limbs, d2, b, 0u, st)) != FHE_OK) return rc;
-    if ((rc = special_rows(c, b, cr, st)) != FHE_OK) return rc;
-    for (unsigned i = 0; i < k; i++)
-        if ((rc = launch("ckks_rns_divround", (int)c.L, st, fhe::ckks_rns_divround_kernel, fhe_ew_grid(2 * slab), 256, b.T + 2ull * i * slab, slab, b.E + 2ull * i * slab,
-                         slab, d_at(i, 0), d_rows * n, out + ((u64)i * 2 * o_rows + o_r0) * n, o_rows * n, slab, pinv[i], c.p[i]->mod)) != FHE_OK)
-            return rc;
-    return FHE_OK;
+    if ((rc = keymac_rows(c, rlk, key_limbs, d2, b, 0u, st)) != FHE_OK) return rc;
+    return special_down(c, b, 0, {d + d_r0 * n, 3 * d_rows * n, d_rows * n}, {out + o_r0 * n, 2 * o_rows * n, o_rows * n}, pinv, 0u, st);
 }
 
 // §23: rows r0 .. r0 + cr of in [k][2][batch][n] under each of `count` Galois elements -> the same rows of out
@@ -431,22 +449,16 @@ int relin_rows(const Chain &c, const u64 *rlk, unsigned key_limbs, const u64 *pi
 // digits read at pi_g, the divide-and-round by P, and pi_g(c0) gathered in that last kernel.  W as for relin_rows.
 int galois_rows(const Chain &c, const u64 *const *gks, const uint64_t *gs, unsigned count, unsigned key_limbs, const u64 *pinv, const u64 *in, u64 *out, u64 batch,
                 u64 r0, u64 cr, u64 *W, hipStream_t st) {
-    const u64 n = c.n, slab = cr * n;
-    const unsigned k = c.k;
-    const SwitchBufs b(W, k, slab);
-    auto in_at = [&](unsigned limb, unsigned comp) { return in + (((u64)limb * 2 + comp) * batch + r0) * n; };
-    auto c1 = [&](unsigned limb) { return in_at(limb, 1); };
+    const u64 n = c.n, o_words = 2ull * c.k * batch * n;
+    const SwitchBufs b(W, c.k, 1, cr * n);
+    const LimbRows<const u64> ct{in + r0 * n, 2 * batch * n, batch * n};
+    auto c1 = [&](unsigned limb) { return ct.of(limb) + ct.cs; };
     int rc;
     if ((rc = digit_rows(c, c1, b, cr, st)) != FHE_OK) return rc;
     for (unsigned r = 0; r < count; r++) {
         const u32 g = (u32)gs[r];
-        u64 *o = out + (u64)r * k * 2 * batch * n;
-        if ((rc = keymac_rows<true>(c, gks[r], key_limbs, c1, b, g, st)) != FHE_OK) return rc;
-        if ((rc = special_rows(c, b, cr, st)) != FHE_OK) return rc;
-        for (unsigned i = 0; i < k; i++)
-            if ((rc = launch("ckks_rns_divround_galois", (int)c.L, st, fhe::ckks_rns_divround_galois_kernel, fhe_ew_grid(2 * slab), 256, b.T + 2ull * i * slab, slab,
-                             b.E + 2ull * i * slab, slab, in_at(i, 0), o + ((u64)i * 2 * batch + r0) * n, batch * n, slab, pinv[i], g, c.L, c.p[i]->mod)) != FHE_OK)
-                return rc;
+        if ((rc = keymac_rows(c, gks[r], key_limbs, c1, b, g, st)) != FHE_OK) return rc;
+        if ((rc = special_down(c, b, 0, ct, {out + r * o_words + r0 * n, ct.ls, ct.cs}, pinv, g, st)) != FHE_OK) return rc;
     }
     return FHE_OK;
 }
@@ -457,18 +469,51 @@ int check_key_limbs(const Chain &c, unsigned key_limbs, const char *who) {
     return FHE_OK;
 }
 
-void special_inverses(const Chain &c, u64 *pinv) {
-    for (unsigned i = 0; i < c.k; i++) pinv[i] = inv_mod(c.p[c.k]->q, c.p[i]->q);
+// r < 0: the call's one element g; otherwise element r of its list
+int check_galois_element(uint64_t g, u64 n, int r, const char *who) {
+    if ((g & 1) != 0 && g < 2 * n) return FHE_OK;
+    char name[16] = "g";
+    if (r >= 0) snprintf(name, sizeof name, "g[%d]", r);
+    return fhe_fail(FHE_E_INVALID, "%s: %s=%llu must be odd and below 2n", who, name, (unsigned long long)g);
+}
+
+// The `count` elements and keys [key_limbs][key_limbs + 1][2][n] of a call that writes out_bytes at d_out: every key present,
+// aligned and clear of the output, every element odd and below 2n.  skip_identity (a diagonal sum): g = 1 takes no key and
+// its entry is not read, so the element is looked at before its key; *switched says whether any key is read at all.
+int check_switch_keys(const void *const *d_gks, const uint64_t *gs, unsigned count, bool skip_identity, u64 n, unsigned key_limbs, const void *d_out, u64 out_bytes,
+                      bool *switched, const char *who) {
+    const u64 gk_bytes = (u64)key_limbs * (key_limbs + 1) * 2 * n * 8;
+    int rc;
+    for (unsigned r = 0; r < count; r++) {
+        if (skip_identity && (rc = check_galois_element(gs[r], n, (int)r, who)) != FHE_OK) return rc;
+        if (skip_identity && gs[r] == 1) continue;
+        *switched = true;
+        if (!d_gks || !d_gks[r]) return fhe_fail(FHE_E_NULL, "%s: key %u is NULL", who, r);
+        if (misaligned8(d_gks[r])) return fhe_fail(FHE_E_INVALID, "%s: key %u must be 8-byte aligned", who, r);
+        if (!skip_identity && (rc = check_galois_element(gs[r], n, (int)r, who)) != FHE_OK) return rc;
+        if (overlaps_any(d_out, out_bytes, {{d_gks[r], gk_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps key %u", who, r);
+    }
+    return FHE_OK;
+}
+
+// The frame of a key-switch call: chunks of chunk_rows ciphertexts, `words` words of workspace a ciphertext (none: the call
+// only needs a device), the inverses of P, and body(r0, cr, W, pinv) per chunk
+template <class Body>
+int switch_call(const Chain &c, u64 batch, u64 words, hipStream_t st, Body body) {
+    const u64 cb = chunk_rows(c, batch);
+    void *w = nullptr;
+    int rc, dev;
+    if ((rc = words ? fhe_workspace_get(kCkksEvalSlot, (size_t)(words * cb * 8), st, &w) : fhe_current_device(&dev)) != FHE_OK) return rc;
+    u64 pinv[fhe::kRnsMaxLimbs];
+    for (unsigned i = 0; i < c.k; i++) pinv[i] = fhe_inv_mod(c.p[i]->q, c.p[c.k]->q);
+    return for_chunks(batch, cb, [&](u64 r0, u64 cr) { return body(r0, cr, (u64 *)w, pinv); });
 }
 
 }  // namespace
 
 extern "C" size_t fhe_ckks_rns_workspace_bytes(uint64_t n, unsigned limbs, size_t batch) {
-    if (n < 2 || (n & (n - 1)) != 0 || n > (1ull << 19) || limbs < 1 || limbs > fhe::kRnsMaxLimbs || batch == 0) return 0;
     Chain c;
-    c.k = limbs;
-    c.n = n;
-    c.L = log2_of(n);
+    if (!chain_of(n, limbs, batch, &c)) return 0;
     return (size_t)(std::max<u64>(words_per_row(c) * chunk_rows(c, batch), 2ull * limbs * n * rescale_chunk_rows(c, batch)) * 8);
 }
 
@@ -522,7 +567,7 @@ int switch_key(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_p
     if (!seed) return fhe_fail(FHE_E_NULL, "%s: NULL seed", who);
     const u64 n = c.n;
     const unsigned k = c.k, cols = k + 1;
-    if (galois && ((g & 1) == 0 || g >= 2 * n)) return fhe_fail(FHE_E_INVALID, "%s: g=%llu must be odd and below 2n", who, (unsigned long long)g);
+    if (galois && (rc = check_galois_element(g, n, -1, who)) != FHE_OK) return rc;
     u64 qmin = c.p[0]->q;
     for (unsigned i = 1; i < k; i++) qmin = std::min<u64>(qmin, c.p[i]->q);
     if ((rc = check_cdt_shape(d_cdt, m, qmin, who)) != FHE_OK) return rc;
@@ -544,10 +589,9 @@ int switch_key(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_p
             if ((rc = fhe_ntt_forward_dev(p, PK, PK, 2, st)) != FHE_OK) return rc;
             if (i == j) {
                 if ((rc = fhe_ntt_forward_dev(p, S, SE, 1, st)) != FHE_OK) return rc;
-                rc = galois ? launch("ckks_rns_keyterm_galois", (int)c.L, st, fhe::ckks_rns_keyterm_galois_kernel, fhe_ew_grid(n), 256, PK, SE, special->q % p->q, (u32)g, c.L,
-                                     p->mod)
-                            : launch("ckks_rns_keyterm", (int)c.L, st, fhe::ckks_rns_keyterm_kernel, fhe_ew_grid(n), 256, PK, SE, special->q % p->q, n, p->mod);
-                if (rc != FHE_OK) return rc;
+                if ((rc = launch(galois ? "ckks_rns_keyterm_galois" : "ckks_rns_keyterm", (int)c.L, st, galois ? fhe::ckks_rns_keyterm_kernel<true> : fhe::ckks_rns_keyterm_kernel<false>,
+                                 fhe_ew_grid(n), 256, PK, SE, special->q % p->q, (u32)g, c.L, p->mod)) != FHE_OK)
+                    return rc;
             }
             HIP_TRY(hipMemcpyAsync((u64 *)d_key + ((u64)j * cols + i) * 2 * n, PK, 2 * n * 8, hipMemcpyDeviceToDevice, st));
         }
@@ -601,16 +645,9 @@ extern "C" int fhe_ckks_rns_relinearize_dev(const fhe_ntt_plan *const *plans, un
     if (overlaps_any(d_out, 2ull * c.k * batch * n * 8, {{d_d, 3ull * c.k * batch * n * 8}, {d_rlk, rlk_bytes}}))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the tensor or the key", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    const u64 cb = chunk_rows(c, batch);
-    void *w = nullptr;
-    if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(words_per_row(c) * cb * 8), st, &w)) != FHE_OK) return rc;
-    u64 pinv[fhe::kRnsMaxLimbs];
-    special_inverses(c, pinv);
-    for (u64 r0 = 0; r0 < batch; r0 += cb) {
-        const u64 cr = std::min<u64>(cb, batch - r0);
-        if ((rc = relin_rows(c, (const u64 *)d_rlk, key_limbs, pinv, (const u64 *)d_d, batch, r0, (u64 *)d_out, batch, r0, cr, (u64 *)w, st)) != FHE_OK) return rc;
-    }
-    return FHE_OK;
+    return switch_call(c, batch, words_per_row(c), st, [&](u64 r0, u64 cr, u64 *W, const u64 *pinv) {
+        return relin_rows(c, (const u64 *)d_rlk, key_limbs, pinv, (const u64 *)d_d, batch, r0, (u64 *)d_out, batch, r0, cr, W, st);
+    });
 }
 
 extern "C" int fhe_ckks_rns_mul_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *d_rlk, unsigned key_limbs,
@@ -628,18 +665,10 @@ extern "C" int fhe_ckks_rns_mul_dev(const fhe_ntt_plan *const *plans, unsigned l
     const u64 ct_bytes = 2ull * c.k * batch * n * 8, rlk_bytes = (u64)key_limbs * (key_limbs + 1) * 2 * n * 8;
     if (overlaps_any(d_out, ct_bytes, {{d_a, ct_bytes}, {d_b, ct_bytes}, {d_rlk, rlk_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an operand or the key", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    const u64 cb = chunk_rows(c, batch);
-    void *w = nullptr;
-    if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(words_per_row(c) * cb * 8), st, &w)) != FHE_OK) return rc;
-    u64 pinv[fhe::kRnsMaxLimbs];
-    special_inverses(c, pinv);
-    for (u64 r0 = 0; r0 < batch; r0 += cb) {
-        const u64 cr = std::min<u64>(cb, batch - r0);
-        u64 *Dt = (u64 *)w, *W = Dt + 3ull * c.k * cr * n;           // the chunk's tensor, then relin_rows' buffers
-        if ((rc = tensor_rows(c, (const u64 *)d_a, (const u64 *)d_b, batch, r0, Dt, cr, 0, cr, st)) != FHE_OK) return rc;
-        if ((rc = relin_rows(c, (const u64 *)d_rlk, key_limbs, pinv, Dt, cr, 0, (u64 *)d_out, batch, r0, cr, W, st)) != FHE_OK) return rc;
-    }
-    return FHE_OK;
+    return switch_call(c, batch, words_per_row(c), st, [&](u64 r0, u64 cr, u64 *Dt, const u64 *pinv) {   // Dt: the chunk's tensor, then relin_rows' buffers
+        const int rc = tensor_rows(c, (const u64 *)d_a, (const u64 *)d_b, batch, r0, Dt, cr, 0, cr, st);
+        return rc != FHE_OK ? rc : relin_rows(c, (const u64 *)d_rlk, key_limbs, pinv, Dt, cr, 0, (u64 *)d_out, batch, r0, cr, Dt + 3ull * c.k * cr * n, st);
+    });
 }
 
 extern "C" int fhe_ckks_rns_rescale_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *d_in, void *d_out, size_t batch, void *hip_stream) {
@@ -660,30 +689,21 @@ extern "C" int fhe_ckks_rns_rescale_dev(const fhe_ntt_plan *const *plans, unsign
     void *w = nullptr;
     if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(2ull * k * cb * n * 8), st, &w)) != FHE_OK) return rc;
     u64 qinv[fhe::kRnsMaxLimbs];
-    for (unsigned i = 0; i < top; i++) qinv[i] = inv_mod(c.p[top]->q, c.p[i]->q);
-    const u64 *in = (const u64 *)d_in;
-    u64 *out = (u64 *)d_out;
-    for (u64 r0 = 0; r0 < batch; r0 += cb) {
-        const u64 cr = std::min<u64>(cb, batch - r0), slab = cr * n;
+    for (unsigned i = 0; i < top; i++) qinv[i] = fhe_inv_mod(c.p[i]->q, c.p[top]->q);
+    const LimbRows<const u64> in{(const u64 *)d_in, 2 * batch * n, batch * n};
+    return for_chunks(batch, cb, [&](u64 r0, u64 cr) {
+        const u64 slab = cr * n;
         u64 *C = (u64 *)w, *E = C + 2 * slab;
-        const u64 *t0 = in + ((u64)top * 2 * batch + r0) * n;         // the top limb's two components, batch n apart
+        const u64 *t0 = in.of(top) + r0 * n;                         // the top limb's two components, batch n apart
+        int rc;
         if (cr == batch) {
             if ((rc = inverse_into(c.p[top], t0, C, 2 * cr, st)) != FHE_OK) return rc;
         } else {
             if ((rc = inverse_into(c.p[top], t0, C, cr, st)) != FHE_OK) return rc;
-            if ((rc = inverse_into(c.p[top], t0 + batch * n, C + slab, cr, st)) != FHE_OK) return rc;
+            if ((rc = inverse_into(c.p[top], t0 + in.cs, C + slab, cr, st)) != FHE_OK) return rc;
         }
-        fhe::LiftArgs a{};
-        for (unsigned i = 0; i < top; i++) lift_target(&a, c.p[i], 2ull * i * slab);
-        if ((rc = lift_launch(false, C, E, 2 * slab, c.p[top]->q, a, c.L, st)) != FHE_OK) return rc;
-        for (unsigned i = 0; i < top; i++)
-            if ((rc = fhe_ntt_forward_dev(c.p[i], E + 2ull * i * slab, E + 2ull * i * slab, 2 * cr, st)) != FHE_OK) return rc;
-        for (unsigned i = 0; i < top; i++)
-            if ((rc = launch("ckks_rns_divround", (int)c.L, st, fhe::ckks_rns_divround_kernel, fhe_ew_grid(2 * slab), 256, in + ((u64)i * 2 * batch + r0) * n, batch * n,
-                             E + 2ull * i * slab, slab, nullptr, 0, out + ((u64)i * 2 * batch + r0) * n, batch * n, slab, qinv[i], c.p[i]->mod)) != FHE_OK)
-                return rc;
-    }
-    return FHE_OK;
+        return moddown_rows(c, top, C, E, slab, {in.p + r0 * n, in.ls, in.cs}, {}, {(u64 *)d_out + r0 * n, in.ls, in.cs}, qinv, 0u, st);
+    });
 }
 
 // ---- Galois automorphisms: slot rotations and conjugation ---------------------------------------------------------
@@ -692,27 +712,24 @@ extern "C" int fhe_ckks_galois_evals_dev(const fhe_ntt_plan *plan, uint64_t g, c
     if (!plan) return fhe_fail(FHE_E_NULL, "%s: plan is NULL", who);
     const u64 n = plan->n;
     if (n < 2) return fhe_fail(FHE_E_BAD_N, "%s: n must be at least 2", who);
-    if ((g & 1) == 0 || g >= 2 * n) return fhe_fail(FHE_E_INVALID, "%s: g=%llu must be odd and below 2n", who, (unsigned long long)g);
+    int rc = check_galois_element(g, n, -1, who);
+    if (rc != FHE_OK) return rc;
     if (polys == 0) return FHE_OK;
     if (!mul_fits((u64)polys, n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: polys too large", who);
     if (!d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     if (misaligned8(d_in) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
     const u64 words = (u64)polys * n;
     if (overlaps_any(d_out, words * 8, {{d_in, words * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps d_in (the permutation is not in place)", who);
-    int dev, rc;
+    int dev;
     if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
     return launch("ckks_rns_galois", (int)plan->log_n, (hipStream_t)hip_stream, fhe::ckks_rns_galois_kernel, fhe_ew_grid(words), 256, (const u64 *)d_in, (u64 *)d_out, words,
                   (u32)g, plan->log_n);
 }
 
 extern "C" size_t fhe_ckks_rns_galois_workspace_bytes(uint64_t n, unsigned limbs, size_t batch, unsigned count) {
-    if (n < 2 || (n & (n - 1)) != 0 || n > (1ull << 19) || limbs < 1 || limbs > fhe::kRnsMaxLimbs || batch == 0 || count == 0 || count > FHE_CKKS_GALOIS_MAX_COUNT)
-        return 0;
     Chain c;
-    c.k = limbs;
-    c.n = n;
-    c.L = log2_of(n);
-    return (size_t)(galois_words_per_row(c) * chunk_rows(c, batch) * 8);       // the digits are shared: count does not enter
+    if (!chain_of(n, limbs, batch, &c) || count == 0 || count > FHE_CKKS_GALOIS_MAX_COUNT) return 0;
+    return (size_t)(galois_words_per_row(c) * chunk_rows(c, batch) * 8);
 }
 
 extern "C" int fhe_ckks_rns_galois_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *const *d_gks, const uint64_t *gs,
@@ -728,34 +745,18 @@ extern "C" int fhe_ckks_rns_galois_dev(const fhe_ntt_plan *const *plans, unsigne
     if (!mul_fits((u64)batch, 2ull * c.k * n * count, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
     if (!d_gks || !gs || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     if (misaligned8(d_in) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
-    const u64 ct_bytes = 2ull * c.k * batch * n * 8, gk_bytes = (u64)key_limbs * (key_limbs + 1) * 2 * n * 8;
-    for (unsigned r = 0; r < count; r++) {
-        if (!d_gks[r]) return fhe_fail(FHE_E_NULL, "%s: key %u is NULL", who, r);
-        if (misaligned8(d_gks[r])) return fhe_fail(FHE_E_INVALID, "%s: key %u must be 8-byte aligned", who, r);
-        if ((gs[r] & 1) == 0 || gs[r] >= 2 * n) return fhe_fail(FHE_E_INVALID, "%s: g[%u]=%llu must be odd and below 2n", who, r, (unsigned long long)gs[r]);
-        if (overlaps_any(d_out, ct_bytes * count, {{d_gks[r], gk_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps key %u", who, r);
-    }
+    const u64 ct_bytes = 2ull * c.k * batch * n * 8;
+    bool switched;
+    if ((rc = check_switch_keys(d_gks, gs, count, false, n, key_limbs, d_out, ct_bytes * count, &switched, who)) != FHE_OK) return rc;
     if (overlaps_any(d_out, ct_bytes * count, {{d_in, ct_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the ciphertexts", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    const u64 cb = chunk_rows(c, batch);
-    void *w = nullptr;
-    if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(galois_words_per_row(c) * cb * 8), st, &w)) != FHE_OK) return rc;
-    u64 pinv[fhe::kRnsMaxLimbs];
-    special_inverses(c, pinv);
-    for (u64 r0 = 0; r0 < batch; r0 += cb) {
-        const u64 cr = std::min<u64>(cb, batch - r0);
-        if ((rc = galois_rows(c, (const u64 *const *)d_gks, gs, count, key_limbs, pinv, (const u64 *)d_in, (u64 *)d_out, batch, r0, cr, (u64 *)w, st)) != FHE_OK) return rc;
-    }
-    return FHE_OK;
+    return switch_call(c, batch, galois_words_per_row(c), st, [&](u64 r0, u64 cr, u64 *W, const u64 *pinv) {
+        return galois_rows(c, (const u64 *const *)d_gks, gs, count, key_limbs, pinv, (const u64 *)d_in, (u64 *)d_out, batch, r0, cr, W, st);
+    });
 }
 
 // ---- plaintext linear transforms: the double-hoisted diagonal sum ---------------------------------------------------
 namespace {
-
-// words of workspace per ciphertext of a chunk: digits k, lifted digits k^2, lifted U_P 2k, then U, 2 (k + 1) an output of a launch
-u64 diag_words_per_row(const Chain &c, unsigned outputs) {
-    return ((u64)c.k * c.k + 3ull * c.k + 2ull * (c.k + 1) * std::min<unsigned>(outputs, fhe::kDiagOutputs)) * c.n;
-}
 
 template <class... A>
 int diagmac_launch(unsigned nout, bool carry, int L, hipStream_t st, unsigned grid, A... a) {
@@ -778,14 +779,12 @@ int diag_rows(const Chain &c, const u64 *const *gks, const uint64_t *gs, unsigne
               const u64 *pinv, const u64 *in, u64 *out, u64 batch, u64 r0, u64 cr, u64 *W, hipStream_t st) {
     const u64 n = c.n, slab = cr * n;
     const unsigned k = c.k;
-    SwitchBufs b(W, k, slab);
-    b.E = b.T;                                                       // E first: the U of a launch's outputs lie 2 (k + 1) slabs apart
-    b.T = b.E + 2ull * k * slab;
-    const u64 u_os = 2ull * (k + 1) * slab, o_words = 2ull * k * batch * n, pt_os = (u64)count * (k + 1) * n;
-    auto in_at = [&](unsigned limb, unsigned comp) { return in + (((u64)limb * 2 + comp) * batch + r0) * n; };
-    auto out_at = [&](unsigned o, unsigned limb) { return out + (u64)o * o_words + ((u64)limb * 2 * batch + r0) * n; };
+    const SwitchBufs b(W, k, std::min<unsigned>(outputs, fhe::kDiagOutputs), slab);   // set o of T is the U of a launch's output o
+    const u64 o_words = 2ull * k * batch * n, pt_os = (u64)count * (k + 1) * n;
+    const LimbRows<const u64> ct{in + r0 * n, 2 * batch * n, batch * n};
+    auto out_rows = [&](unsigned o) { return LimbRows<u64>{out + o * o_words + r0 * n, ct.ls, ct.cs}; };
     int rc;
-    if (switched && (rc = digit_rows(c, [&](unsigned limb) { return in_at(limb, 1); }, b, cr, st)) != FHE_OK) return rc;
+    if (switched && (rc = digit_rows(c, [&](unsigned limb) { return ct.of(limb) + ct.cs; }, b, cr, st)) != FHE_OK) return rc;
     for (unsigned o0 = 0; o0 < outputs; o0 += fhe::kDiagOutputs) {
         const unsigned nout = std::min<unsigned>(fhe::kDiagOutputs, outputs - o0);
         for (unsigned i = 0; i < (switched ? k + 1 : k); i++) {
@@ -797,23 +796,16 @@ int diag_rows(const Chain &c, const u64 *const *gks, const uint64_t *gs, unsigne
                     grp.key[r] = grp.g[r] == 1 ? nullptr : gks[e0 + r] + (u64)(i < k ? i : key_limbs) * 2 * n;
                     grp.pt[r] = pts + (((u64)o0 * count + e0 + r) * (k + 1) + i) * n;
                 }
-                u64 *dst = switched ? b.T + 2ull * i * slab : out_at(o0, i);
+                u64 *dst = switched ? b.T + 2ull * i * slab : out_rows(o0).of(i);
                 const u64 pmod = !switched ? 1 : i < k ? c.p[k]->q % c.p[i]->q : 0;
-                if ((rc = diagmac_launch(nout, e0 > 0, (int)c.L, st, fhe_ew_grid(slab), switched ? b.D_of(i) : nullptr, slab, i < k ? in_at(i, 0) : nullptr, batch * n, i,
-                                         (u64)(key_limbs + 1) * 2 * n, pt_os, dst, switched ? slab : batch * n, switched ? u_os : o_words, k, c.L, slab, pmod, grp,
+                if ((rc = diagmac_launch(nout, e0 > 0, (int)c.L, st, fhe_ew_grid(slab), switched ? b.D_of(i) : nullptr, slab, i < k ? ct.of(i) : nullptr, ct.cs, i,
+                                         (u64)(key_limbs + 1) * 2 * n, pt_os, dst, switched ? slab : ct.cs, switched ? b.set : o_words, k, c.L, slab, pmod, grp,
                                          c.p[i]->mod)) != FHE_OK)
                     return rc;
             }
         }
-        for (unsigned o = 0; switched && o < nout; o++) {
-            SwitchBufs bo = b;
-            bo.T = b.T + (u64)o * u_os;
-            if ((rc = special_rows(c, bo, cr, st)) != FHE_OK) return rc;
-            for (unsigned i = 0; i < k; i++)
-                if ((rc = launch("ckks_rns_divround", (int)c.L, st, fhe::ckks_rns_divround_kernel, fhe_ew_grid(2 * slab), 256, bo.T + 2ull * i * slab, slab,
-                                 bo.E + 2ull * i * slab, slab, nullptr, 0, out_at(o0 + o, i), batch * n, slab, pinv[i], c.p[i]->mod)) != FHE_OK)
-                    return rc;
-        }
+        for (unsigned o = 0; switched && o < nout; o++)
+            if ((rc = special_down(c, b, o, {}, out_rows(o0 + o), pinv, 0u, st)) != FHE_OK) return rc;
     }
     return FHE_OK;
 }
@@ -821,14 +813,9 @@ int diag_rows(const Chain &c, const u64 *const *gks, const uint64_t *gs, unsigne
 }  // namespace
 
 extern "C" size_t fhe_ckks_rns_diag_workspace_bytes(uint64_t n, unsigned limbs, size_t batch, unsigned count, unsigned outputs) {
-    if (n < 2 || (n & (n - 1)) != 0 || n > (1ull << 19) || limbs < 1 || limbs > fhe::kRnsMaxLimbs || batch == 0 || count == 0 || count > FHE_CKKS_GALOIS_MAX_COUNT ||
-        outputs == 0 || outputs > FHE_CKKS_DIAG_MAX_OUTPUTS)
-        return 0;
     Chain c;
-    c.k = limbs;
-    c.n = n;
-    c.L = log2_of(n);
-    return (size_t)(diag_words_per_row(c, outputs) * chunk_rows(c, batch) * 8);   // the digits are shared and the elements summed in registers: count does not enter
+    if (!chain_of(n, limbs, batch, &c) || count == 0 || count > FHE_CKKS_GALOIS_MAX_COUNT || outputs == 0 || outputs > FHE_CKKS_DIAG_MAX_OUTPUTS) return 0;
+    return (size_t)(diag_words_per_row(c, outputs) * chunk_rows(c, batch) * 8);
 }
 
 extern "C" int fhe_ckks_rns_diag_sum_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *const *d_gks, const uint64_t *gs,
@@ -846,34 +833,13 @@ extern "C" int fhe_ckks_rns_diag_sum_dev(const fhe_ntt_plan *const *plans, unsig
     if (!mul_fits((u64)batch, 2ull * c.k * n * outputs, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
     if (!gs || !d_pts || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
     if (misaligned8(d_pts) || misaligned8(d_in) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
-    const u64 ct_bytes = 2ull * c.k * batch * n * 8, gk_bytes = (u64)key_limbs * (key_limbs + 1) * 2 * n * 8, out_bytes = ct_bytes * outputs;
+    const u64 ct_bytes = 2ull * c.k * batch * n * 8, out_bytes = ct_bytes * outputs;
     bool switched = false;
-    for (unsigned r = 0; r < count; r++) {
-        if ((gs[r] & 1) == 0 || gs[r] >= 2 * n) return fhe_fail(FHE_E_INVALID, "%s: g[%u]=%llu must be odd and below 2n", who, r, (unsigned long long)gs[r]);
-        if (gs[r] == 1) continue;                                    // the identity takes no key: its entry is not read
-        switched = true;
-        if (!d_gks || !d_gks[r]) return fhe_fail(FHE_E_NULL, "%s: key %u is NULL", who, r);
-        if (misaligned8(d_gks[r])) return fhe_fail(FHE_E_INVALID, "%s: key %u must be 8-byte aligned", who, r);
-        if (overlaps_any(d_out, out_bytes, {{d_gks[r], gk_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps key %u", who, r);
-    }
+    if ((rc = check_switch_keys(d_gks, gs, count, true, n, key_limbs, d_out, out_bytes, &switched, who)) != FHE_OK) return rc;
     if (overlaps_any(d_out, out_bytes, {{d_in, ct_bytes}, {d_pts, (u64)outputs * count * (c.k + 1) * n * 8}}))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the ciphertexts or the plaintexts", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    const u64 cb = chunk_rows(c, batch);
-    void *w = nullptr;
-    if (switched) {
-        if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(diag_words_per_row(c, outputs) * cb * 8), st, &w)) != FHE_OK) return rc;
-    } else {
-        int dev;
-        if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
-    }
-    u64 pinv[fhe::kRnsMaxLimbs];
-    special_inverses(c, pinv);
-    for (u64 r0 = 0; r0 < batch; r0 += cb) {
-        const u64 cr = std::min<u64>(cb, batch - r0);
-        if ((rc = diag_rows(c, (const u64 *const *)d_gks, gs, count, key_limbs, (const u64 *)d_pts, outputs, switched, pinv, (const u64 *)d_in, (u64 *)d_out, batch, r0,
-                            cr, (u64 *)w, st)) != FHE_OK)
-            return rc;
-    }
-    return FHE_OK;
+    return switch_call(c, batch, switched ? diag_words_per_row(c, outputs) : 0, st, [&](u64 r0, u64 cr, u64 *W, const u64 *pinv) {
+        return diag_rows(c, (const u64 *const *)d_gks, gs, count, key_limbs, (const u64 *)d_pts, outputs, switched, pinv, (const u64 *)d_in, (u64 *)d_out, batch, r0, cr, W, st);
+    });
 }
