@@ -42,32 +42,16 @@ int fhe_hip_fail(hipError_t e, const char *what) {
 #define fail fhe_fail
 #define hip_fail fhe_hip_fail
 
-// ---------------------------------------------------------------------------
-// host number theory (one-off, per plan) — follows arith/src/ntt.rs:115-185
-// ---------------------------------------------------------------------------
-static inline u64 mulmod(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
-
-// ntt.rs:164-179 const_exp_mod
-u64 fhe_exp_mod(u64 q, u64 x, u64 k) {
-    u64 r = 1;
-    x %= q;
-    while (k > 0) {
-        if (k & 1) r = mulmod(r, x, q);
-        x = mulmod(x, x, q);
-        k >>= 1;
-    }
-    return r;
-}
-// ntt.rs:182-185 const_inv_mod (Fermat; q assumed prime as in the reference)
-u64 fhe_inv_mod(u64 q, u64 x) { return fhe_exp_mod(q, x, q - 2); }
-
-static inline u64 shoup(u64 w, u64 q) { return (u64)((((u128)w) << 64) / q); }
-
-static inline u64 bitrev(u64 i, unsigned log_n) {
-    u64 r = 0;
-    for (unsigned b = 0; b < log_n; b++) r |= ((i >> b) & 1ull) << (log_n - 1 - b);
-    return r;
-}
+// host number theory (one-off, per plan), following arith/src/ntt.rs:115-185: host_tables.hpp
+using fhe::host::bitrev;
+using fhe::host::exp_mod;
+using fhe::host::inv_mod;
+using fhe::host::mg_pair;
+using fhe::host::mulmod;
+using fhe::host::pm_pair;
+using fhe::host::shoup;
+using fhe::host::shoup32_pair;
+using fhe::host::shoup_pair;
 
 // ---------------------------------------------------------------------------
 // plans
@@ -94,13 +78,13 @@ static int build_plan(u64 q, u64 n, fhe_ntt_plan *p) {
     // first k = 1,2,.. with w = k^((q-1)/2n), w^n != 1   (ntt.rs:120-129)
     u64 psi = 0;
     for (u64 k = 1; k < q; k++) {
-        u64 w = fhe_exp_mod(q, k, (q - 1) / (2 * n));
-        if (fhe_exp_mod(q, w, n) != 1) { psi = w; break; }
+        u64 w = exp_mod(q, k, (q - 1) / (2 * n));
+        if (exp_mod(q, w, n) != 1) { psi = w; break; }
     }
     if (psi == 0) return fail(FHE_E_NO_ROOT, "No primitive root of unity (ntt.rs:130)");
 
     p->q = q; p->n = n; p->log_n = log_n; p->psi = psi;
-    p->n_inv = fhe_inv_mod(q, n);  // ntt.rs:27-30
+    p->n_inv = inv_mod(q, n);  // ntt.rs:27-30
     p->roots.resize(n);
     p->roots_inv.resize(n);
     // roots[i] = psi^bitrev(i) (ntt.rs:133-147): running powers, then bit-reverse
@@ -114,7 +98,7 @@ static int build_plan(u64 q, u64 n, fhe_ntt_plan *p) {
     }
     // roots_inv[i] = roots[i]^(q-2) (ntt.rs:149-161) — kept as the reference's
     // Fermat power so that the tables agree even if q is not prime.
-    for (u64 i = 0; i < n; i++) p->roots_inv[i] = fhe_inv_mod(q, p->roots[i]);
+    for (u64 i = 0; i < n; i++) p->roots_inv[i] = inv_mod(q, p->roots[i]);
 
     p->mod.q = q;
     p->mod.q2 = 2 * q;
@@ -125,10 +109,8 @@ static int build_plan(u64 q, u64 n, fhe_ntt_plan *p) {
     p->mod.r64 = (u64)((((u128)1) << 64) % q);
     p->mod.r64p = shoup(p->mod.r64, q);
     p->mod.onep = (u64)((((u128)1) << 64) / q);
-    p->ninv.w = p->n_inv;
-    p->ninv.wp = shoup(p->n_inv, q);
-    p->s_ninv.w = mulmod(p->roots_inv[1], p->n_inv, q);
-    p->s_ninv.wp = shoup(p->s_ninv.w, q);
+    p->ninv = shoup_pair<fhe::Tw>(p->n_inv, q);
+    p->s_ninv = shoup_pair<fhe::Tw>(mulmod(p->roots_inv[1], p->n_inv, q), q);
     // Pseudo-Mersenne form q = 2^k - delta, 56 <= k <= 61, delta <= 2^(k-39) (zq_device.hpp): the transforms then run the
     // five-multiply butterflies on {w, w 2^32 mod q}.  2^61 - 2^21 + 1 (SURVEY.md section 8's modulus) qualifies.
     p->mod.q3p1 = 3 * q + 1;
@@ -144,10 +126,8 @@ static int build_plan(u64 q, u64 n, fhe_ntt_plan *p) {
             p->mod.pm_mask = (1u << (k - 31)) - 1u;
             p->mod.pm_rsh = k - 32;
             p->mod.pm_rmask = (1u << (k - 32)) - 1u;
-            p->ninv_pm.w = p->ninv.w;
-            p->ninv_pm.wp = mulmod(p->ninv.w, 1ull << 32, q);
-            p->s_ninv_pm.w = p->s_ninv.w;
-            p->s_ninv_pm.wp = mulmod(p->s_ninv.w, 1ull << 32, q);
+            p->ninv_pm = pm_pair<fhe::Tw>(p->ninv.w, q);
+            p->s_ninv_pm = pm_pair<fhe::Tw>(p->s_ninv.w, q);
         }
     }
     // q = qh 2^32 + 1 below 2^61 (zq_device.hpp, word Montgomery): the forward transforms run on {w 2^32, w 2^64 mod q}
@@ -155,10 +135,8 @@ static int build_plan(u64 q, u64 n, fhe_ntt_plan *p) {
         p->mod.mg_nqh = (uint32_t)(0u - (uint32_t)(q >> 32));
         p->mod.mg_r96 = mulmod(p->mod.r64, 1ull << 32, q);
         p->mod.mg_r128 = mulmod(p->mod.r64, p->mod.r64, q);
-        p->ninv_mg.w = mulmod(p->ninv.w, 1ull << 32, q);
-        p->ninv_mg.wp = mulmod(p->ninv_mg.w, 1ull << 32, q);
-        p->s_ninv_mg.w = mulmod(p->s_ninv.w, 1ull << 32, q);
-        p->s_ninv_mg.wp = mulmod(p->s_ninv_mg.w, 1ull << 32, q);
+        p->ninv_mg = mg_pair<fhe::Tw>(p->ninv.w, q);
+        p->s_ninv_mg = mg_pair<fhe::Tw>(p->s_ninv.w, q);
     }
     return FHE_OK;
 }
@@ -231,128 +209,38 @@ int fhe_device_plan(const fhe_ntt_plan *plan, fhe::DevicePlan *dp) {
     if (!t.ready) {
         // First use on this device: a blocking allocation + upload (fhe_ntt_plan_prepare does it
         // ahead of time, e.g. before a stream capture).  Nothing is kept on a failure.
+        // Each family is one pair of tables, element k made from roots[k] / roots_inv[k] by `form`; `tu` owns every
+        // allocation until the commit below.
         const u64 n = plan->n, q = plan->q;
-        std::vector<fhe::Tw> f(n), i(n);
-        for (u64 k = 0; k < n; k++) {
-            f[k].w = plan->roots[k];
-            f[k].wp = shoup(plan->roots[k], q);
-            i[k].w = plan->roots_inv[k];
-            i[k].wp = shoup(plan->roots_inv[k], q);
-        }
-        // tables for transforms of 0/1 polynomials (gadget digits): outcomes of the first stages per
-        // input bit pattern (ntt_rounds.hpp: round0_bits).  Needs roots[1..7]: n >= 8.
-        std::vector<u64> lut;
-        if (n >= 8) {
-            lut.assign(136, 0);
-            const u64 *r = plan->roots.data();
-            auto add = [&](u64 x, u64 y) { u64 s = x + y; return s >= q ? s - q : s; };
-            auto sub = [&](u64 x, u64 y) { return x >= y ? x - y : x + q - y; };
-            for (unsigned p = 0; p < 16; p++) {
-                const u64 x0 = p & 1, x1 = (p >> 1) & 1, x2 = (p >> 2) & 1, x3 = (p >> 3) & 1;   // registers c, c+4, c+8, c+12
-                const u64 a0 = add(x0, mulmod(r[1], x2, q)), a2 = sub(x0, mulmod(r[1], x2, q));   // stage 0: pairs (c, c+8), (c+4, c+12)
-                const u64 a1 = add(x1, mulmod(r[1], x3, q)), a3 = sub(x1, mulmod(r[1], x3, q));
-                u64 y[4];
-                y[0] = add(a0, mulmod(r[2], a1, q)); y[1] = sub(a0, mulmod(r[2], a1, q));         // stage 1: (c, c+4) with roots[2]
-                y[2] = add(a2, mulmod(r[3], a3, q)); y[3] = sub(a2, mulmod(r[3], a3, q));         //          (c+8, c+12) with roots[3]
-                for (int j = 0; j < 4; j++) {
-                    lut[4 * p + j] = y[j];
-                    lut[64 + 4 * p + j] = mulmod(r[4 + j], y[j], q);                              // stage 2's products
-                }
+        FheTableUpload tu;
+        DeviceTables nt;
+        auto pair_of = [&](auto form, auto **d_fwd, auto **d_inv) {
+            std::vector<decltype(form(q, q))> f(n), i(n);
+            for (u64 k = 0; k < n; k++) {
+                f[k] = form(plan->roots[k], q);
+                i[k] = form(plan->roots_inv[k], q);
             }
-            for (unsigned p = 0; p < 4; p++) {
-                const u64 x = p & 1, y = (p >> 1) & 1;
-                lut[128 + 2 * p] = add(x, mulmod(r[1], y, q));
-                lut[128 + 2 * p + 1] = sub(x, mulmod(r[1], y, q));
-            }
+            *d_fwd = tu.up(f.data(), n);
+            *d_inv = tu.up(i.data(), n);
+        };
+        pair_of(shoup_pair<fhe::Tw>, &nt.tw_fwd, &nt.tw_inv);
+        if (n >= 8) {   // tables for transforms of 0/1 polynomials (gadget digits); they need roots[1..7]
+            const auto lut = fhe::host::bit_lut<u64>(plan->roots.data(), q);
+            nt.digit_lut = tu.up(lut.data(), lut.size());
         }
-        fhe::Tw *df = nullptr, *di = nullptr;
-        u64 *dl = nullptr;
-        hipError_t e = hipMalloc((void **)&df, n * sizeof(fhe::Tw));
-        if (e == hipSuccess) e = hipMalloc((void **)&di, n * sizeof(fhe::Tw));
-        if (e == hipSuccess && !lut.empty()) e = hipMalloc((void **)&dl, lut.size() * sizeof(u64));
-        if (e == hipSuccess) e = hipMemcpy(df, f.data(), n * sizeof(fhe::Tw), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(di, i.data(), n * sizeof(fhe::Tw), hipMemcpyHostToDevice);
-        if (e == hipSuccess && dl) e = hipMemcpy(dl, lut.data(), lut.size() * sizeof(u64), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (df) (void)hipFree(df);
-            if (di) (void)hipFree(di);
-            if (dl) (void)hipFree(dl);
-            return hip_fail(e, "uploading the twiddle tables");
-        }
+        if (tu.err != hipSuccess) return hip_fail(tu.err, "uploading the twiddle tables");
         // small moduli: the same two tables as 32-bit Shoup pairs (smallq.hip)
-        fhe::Tw32 *sf = nullptr, *si = nullptr;
-        if (fhe::smallq_supported(q, plan->log_n)) {
-            std::vector<fhe::Tw32> f32(n), i32(n);
-            for (u64 k = 0; k < n; k++) {
-                f32[k] = fhe::Tw32{(uint32_t)plan->roots[k], (uint32_t)((plan->roots[k] << 32) / q)};
-                i32[k] = fhe::Tw32{(uint32_t)plan->roots_inv[k], (uint32_t)((plan->roots_inv[k] << 32) / q)};
-            }
-            e = hipMalloc((void **)&sf, n * sizeof(fhe::Tw32));
-            if (e == hipSuccess) e = hipMalloc((void **)&si, n * sizeof(fhe::Tw32));
-            if (e == hipSuccess) e = hipMemcpy(sf, f32.data(), n * sizeof(fhe::Tw32), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(si, i32.data(), n * sizeof(fhe::Tw32), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                if (sf) (void)hipFree(sf);
-                if (si) (void)hipFree(si);
-                (void)hipFree(df); (void)hipFree(di);
-                if (dl) (void)hipFree(dl);
-                return hip_fail(e, "uploading the 32-bit twiddle tables");
-            }
-        }
+        if (fhe::smallq_supported(q, plan->log_n)) pair_of(shoup32_pair<fhe::Tw32>, &nt.tw32_fwd, &nt.tw32_inv);
+        if (tu.err != hipSuccess) return hip_fail(tu.err, "uploading the 32-bit twiddle tables");
         // pseudo-Mersenne moduli: the second pair of tables, {w, w 2^32 mod q}
-        fhe::Tw *pf = nullptr, *pi = nullptr;
-        if (plan->mod.pm_k != 0) {
-            for (u64 k = 0; k < n; k++) {
-                f[k].wp = mulmod(plan->roots[k], 1ull << 32, q);
-                i[k].wp = mulmod(plan->roots_inv[k], 1ull << 32, q);
-            }
-            e = hipMalloc((void **)&pf, n * sizeof(fhe::Tw));
-            if (e == hipSuccess) e = hipMalloc((void **)&pi, n * sizeof(fhe::Tw));
-            if (e == hipSuccess) e = hipMemcpy(pf, f.data(), n * sizeof(fhe::Tw), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(pi, i.data(), n * sizeof(fhe::Tw), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                if (pf) (void)hipFree(pf);
-                if (pi) (void)hipFree(pi);
-                if (sf) (void)hipFree(sf);
-                if (si) (void)hipFree(si);
-                (void)hipFree(df); (void)hipFree(di);
-                if (dl) (void)hipFree(dl);
-                return hip_fail(e, "uploading the pseudo-Mersenne twiddle tables");
-            }
-        }
+        if (plan->mod.pm_k != 0) pair_of(pm_pair<fhe::Tw>, &nt.tw_fwd_pm, &nt.tw_inv_pm);
+        if (tu.err != hipSuccess) return hip_fail(tu.err, "uploading the pseudo-Mersenne twiddle tables");
         // q = 1 (mod 2^32): both tables in word-Montgomery form {w 2^32, w 2^64 mod q}
-        fhe::Tw *mf = nullptr, *mi = nullptr;
-        if (plan->mod.mg_nqh != 0) {
-            for (u64 k = 0; k < n; k++) {
-                f[k].w = mulmod(plan->roots[k], 1ull << 32, q);
-                f[k].wp = mulmod(f[k].w, 1ull << 32, q);
-                i[k].w = mulmod(plan->roots_inv[k], 1ull << 32, q);
-                i[k].wp = mulmod(i[k].w, 1ull << 32, q);
-            }
-            e = hipMalloc((void **)&mf, n * sizeof(fhe::Tw));
-            if (e == hipSuccess) e = hipMalloc((void **)&mi, n * sizeof(fhe::Tw));
-            if (e == hipSuccess) e = hipMemcpy(mf, f.data(), n * sizeof(fhe::Tw), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(mi, i.data(), n * sizeof(fhe::Tw), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                if (mf) (void)hipFree(mf);
-                if (mi) (void)hipFree(mi);
-                if (sf) (void)hipFree(sf);
-                if (si) (void)hipFree(si);
-                (void)hipFree(df); (void)hipFree(di);
-                if (dl) (void)hipFree(dl);
-                return hip_fail(e, "uploading the Montgomery twiddle table");
-            }
-        }
-        t.tw_fwd_mg = mf;
-        t.tw_inv_mg = mi;
-        t.tw_fwd_pm = pf;
-        t.tw_inv_pm = pi;
-        t.tw_fwd = df;
-        t.tw_inv = di;
-        t.digit_lut = dl;
-        t.tw32_fwd = sf;
-        t.tw32_inv = si;
-        t.ready = true;
+        if (plan->mod.mg_nqh != 0) pair_of(mg_pair<fhe::Tw>, &nt.tw_fwd_mg, &nt.tw_inv_mg);
+        if (tu.err != hipSuccess) return hip_fail(tu.err, "uploading the Montgomery twiddle table");
+        tu.commit(&nt.owned);
+        nt.ready = true;
+        t = std::move(nt);
     }
     dp->tw_fwd = t.tw_fwd;
     dp->tw_inv = t.tw_inv;
@@ -378,13 +266,13 @@ int fhe_device_plan(const fhe_ntt_plan *plan, fhe::DevicePlan *dp) {
 
 // FHE_MG=0 (read once): q = 1 (mod 2^32) keeps the Shoup forward kernels — the A/B of profiles/r04_montgomery_ab.txt
 bool fhe_mg_enabled() {
-    static const bool on = [] { const char *e = getenv("FHE_MG"); return !(e && e[0] == '0'); }();
+    static const bool on = fhe_env_switch("FHE_MG", true);
     return on;
 }
 
 // FHE_PM=0 (read once): pseudo-Mersenne moduli stay on the Shoup kernels — how the A/B numbers of DESIGN.md were taken
 bool fhe_pm_enabled() {
-    static const bool on = [] { const char *e = getenv("FHE_PM"); return !(e && e[0] == '0'); }();
+    static const bool on = fhe_env_switch("FHE_PM", true);
     return on;
 }
 
@@ -534,50 +422,51 @@ static fhe::PersistTune g_persist{};
 static bool g_persist_on = false;
 static int g_persist_grid = -1;                      // > 0: workgroups to launch instead of what the chip holds; -1: not read yet
 static uint32_t *g_persist_host_err = nullptr;      // pinned, device-visible: a bounded wait that ran out lands here
+// The settings of mode 0 (off), 1 = A, 2 = B, 3 = D, 4 = E from the four numbers both the environment and the setter
+// give: FHE_OK and *t, or FHE_E_INVALID and the reason in `why`.
+static int persist_tune_make(unsigned mode, unsigned tile_polys, unsigned lag, unsigned ringslots, fhe::PersistTune *t, char (&why)[256]) {
+    why[0] = 0;
+    if (mode > 4) snprintf(why, sizeof why, "mode %u (0 off, 1 = A: lagged tiles, 2 = B: teams, 3 = D: teams at two workgroups per CU, 4 = E: teams that never wait)", mode);
+    else if (mode == 4 && ringslots < 2) snprintf(why, sizeof why, "mode 4 needs at least two ring slots per group");
+    else if (mode == 1 && (tile_polys == 0 || (tile_polys & (tile_polys - 1)) != 0 || tile_polys > 1024))
+        snprintf(why, sizeof why, "tile of %u polynomials (need a power of two <= 1024)", tile_polys);
+    else if (mode == 1 && ringslots && ringslots < lag + 1)
+        snprintf(why, sizeof why, "a ring of %u slots cannot hold a lag of %u tiles (need >= lag + 1)", ringslots, lag);
+    else if (mode >= 2 && ringslots == 0) snprintf(why, sizeof why, "teams need a ring (ringslots >= 1)");
+    if (why[0]) return FHE_E_INVALID;
+    *t = fhe::PersistTune{};
+    if (mode == 0) return FHE_OK;
+    t->lag = lag; t->ringslots = ringslots;   // teams: lag is the start-up stagger
+    if (mode == 1) while ((1u << t->log_t) < tile_polys) t->log_t++;
+    t->teams = mode >= 2;
+    t->deep = mode == 3;      // the teams at two workgroups per CU
+    t->flow = mode == 4;      // ... that never wait (a FIFO of pending parts per workgroup)
+    return FHE_OK;
+}
 static bool persist_tune(fhe::PersistTune *t) {
     std::lock_guard<std::mutex> lk(g_cfg_lock);
     if (!g_persist_set) {
         g_persist_set = true;
-        const char *e = getenv("FHE_NTT_PERSIST");       // "A:T,L,R" (tiles, lagged) or "B:R" (teams)
-        unsigned T = 0, L = 1, R = 4;
-        unsigned stagger = 0;
-        if (e && strchr("BbDdEe", e[0]) && e[1] == ':' && sscanf(e + 2, "%u,%u", &R, &stagger) >= 1 && R >= ((e[0] == 'E' || e[0] == 'e') ? 2u : 1u)) {
-            g_persist = fhe::PersistTune{};
-            g_persist.log_t = 0; g_persist.lag = stagger; g_persist.ringslots = R; g_persist.teams = true;
-            g_persist.deep = e[0] == 'D' || e[0] == 'd';      // "D:R,s": the teams at two workgroups per CU
-            g_persist.flow = e[0] == 'E' || e[0] == 'e';      // "E:R,s": ... that never wait (a FIFO of pending parts per workgroup)
-            g_persist_on = true;
-        } else if (e && (e[0] == 'A' || e[0] == 'a') && e[1] == ':' && sscanf(e + 2, "%u,%u,%u", &T, &L, &R) >= 1 && T > 0 &&
-                   (T & (T - 1)) == 0 && T <= 1024 && (R == 0 || R >= L + 1)) {
-            g_persist = fhe::PersistTune{};
-            while ((1u << g_persist.log_t) < T) g_persist.log_t++;
-            g_persist.lag = L; g_persist.ringslots = R;
-            g_persist_on = true;
-        }
+        const char *e = getenv("FHE_NTT_PERSIST");       // "A:T,L,R" (tiles, lagged) or "B:R", "D:R,s", "E:R,s" (teams, start-up stagger s)
+        const char *letter = e && e[0] && e[1] == ':' ? strchr("AaBbDdEe", e[0]) : nullptr;
+        unsigned T = 0, L = 1, R = 4, stagger = 0;
+        const unsigned mode = letter ? 1u + (unsigned)(letter - "AaBbDdEe") / 2u : 0u;
+        const int fields = mode == 1 ? sscanf(e + 2, "%u,%u,%u", &T, &L, &R) : mode ? sscanf(e + 2, "%u,%u", &R, &stagger) : 0;
+        char why[256];   // a string that does not validate means "off", silently
+        g_persist_on = fields >= 1 && persist_tune_make(mode, T, mode == 1 ? L : stagger, R, &g_persist, why) == FHE_OK;
     }
     *t = g_persist;
     return g_persist_on;
 }
 extern "C" int fhe_ntt_set_persist(unsigned mode, unsigned tile_polys, unsigned lag, unsigned ringslots) {
-    if (mode > 4) return fail(FHE_E_INVALID, "fhe_ntt_set_persist: mode %u (0 off, 1 = A: lagged tiles, 2 = B: teams, 3 = D: teams at two workgroups per CU, 4 = E: teams that never wait)", mode);
-    if (mode == 4 && ringslots < 2) return fail(FHE_E_INVALID, "fhe_ntt_set_persist: mode 4 needs at least two ring slots per group");
-    if (mode == 1 && (tile_polys == 0 || (tile_polys & (tile_polys - 1)) != 0 || tile_polys > 1024))
-        return fail(FHE_E_INVALID, "fhe_ntt_set_persist: tile of %u polynomials (need a power of two <= 1024)", tile_polys);
-    if (mode == 1 && ringslots && ringslots < lag + 1)
-        return fail(FHE_E_INVALID, "fhe_ntt_set_persist: a ring of %u slots cannot hold a lag of %u tiles (need >= lag + 1)", ringslots, lag);
-    if (mode >= 2 && ringslots == 0) return fail(FHE_E_INVALID, "fhe_ntt_set_persist: teams need a ring (ringslots >= 1)");
+    fhe::PersistTune t;
+    char why[256];
+    const int rc = persist_tune_make(mode, tile_polys, lag, ringslots, &t, why);
+    if (rc != FHE_OK) return fail(rc, "fhe_ntt_set_persist: %s", why);
     std::lock_guard<std::mutex> lk(g_cfg_lock);
     g_persist_set = true;
     g_persist_on = mode != 0;
-    g_persist = fhe::PersistTune{};
-    if (mode == 1) {
-        while ((1u << g_persist.log_t) < tile_polys) g_persist.log_t++;
-        g_persist.lag = lag; g_persist.ringslots = ringslots;
-    } else if (mode >= 2) {
-        g_persist.log_t = 0; g_persist.lag = lag; g_persist.ringslots = ringslots; g_persist.teams = true;   // lag: start-up stagger
-        g_persist.deep = mode == 3;
-        g_persist.flow = mode == 4;
-    }
+    g_persist = t;
     return FHE_OK;
 }
 // Diagnostic: with a device buffer of 26 u64 words registered here, lane 0 of every persistent workgroup adds the shader-
@@ -660,12 +549,14 @@ static int persist_tables(const fhe_ntt_plan *plan, const fhe::DevicePlan &dp, c
     DeviceTables &t = plan->dev[dev];
     if (!t.twc_pm) {
         const size_t n = fhe::persist_twc_entries(plan->log_n);
-        fhe::Tw *d = nullptr;
-        HIP_TRY(hipMalloc((void **)&d, n * (sizeof(fhe::Tw) + sizeof(u64))));      // [Tw x n][u64 x n]
+        FheTableUpload tu;
+        fhe::Tw *d = (fhe::Tw *)tu.alloc(n * (sizeof(fhe::Tw) + sizeof(u64)));      // [Tw x n][u64 x n]
+        if (!d) return hip_fail(tu.err, "hipMalloc((void **)&d, n * (sizeof(fhe::Tw) + sizeof(u64)))");
         u64 *d8 = (u64 *)(d + n);
         hipError_t e = fhe::launch_persist_twc(dp.tw_fwd_pm, d, d8, plan->log_n, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) { (void)hipFree(d); return hip_fail(e, "persist_twc_kernel"); }
+        if (e != hipSuccess) return hip_fail(e, "persist_twc_kernel");
+        tu.commit(&t.owned);
         t.twc_pm = d;
     }
     *twc = t.twc_pm;
@@ -726,6 +617,26 @@ static std::multimap<WsKey, Workspace> g_ws_orphans;
 
 static size_t ws_thread_id() { return std::hash<std::thread::id>()(std::this_thread::get_id()); }
 
+// The one erase loop of the two maps (g_ws_lock held): every entry whose key `match` accepts leaves its map, and its
+// buffer goes where `fate` says.
+enum class WsFate {
+    Free,     // nothing enqueued can still use it: hipFree now
+    Retire,   // enqueued work may: freed at fhe_ntt_shutdown()
+    Orphan,   // its thread is gone, its stream is not: the next thread on that (slot, device, stream) adopts it
+};
+template <class Map, class Match, class Fate>
+static void ws_erase_if(Map &map, Match match, Fate fate) {
+    for (auto it = map.begin(); it != map.end();) {
+        if (!match(it->first)) { ++it; continue; }
+        if (it->second.ptr) switch (fate(it->first)) {
+            case WsFate::Free: (void)hipFree(it->second.ptr); break;
+            case WsFate::Retire: g_ws_retired.push_back(it->second.ptr); break;
+            case WsFate::Orphan: g_ws_orphans.emplace(WsKey{it->first.slot, it->first.dev, it->first.st, kWsOrphanTid}, it->second); break;
+        }
+        it = map.erase(it);
+    }
+}
+
 namespace {
 struct WsThreadReaper {      // one per thread that ever took a workspace; runs at thread exit
     bool armed = false;
@@ -733,18 +644,9 @@ struct WsThreadReaper {      // one per thread that ever took a workspace; runs 
         if (!armed || !g_ws_alive) return;
         const size_t tid = ws_thread_id();
         std::lock_guard<std::mutex> lk(g_ws_lock);
-        for (auto it = g_ws.begin(); it != g_ws.end();) {
-            if (it->first.tid == tid) {
-                // hipStreamPerThread named THIS thread's own stream, which dies with it: nobody can adopt in stream order
-                if (it->second.ptr) {
-                    if (it->first.st == hipStreamPerThread) g_ws_retired.push_back(it->second.ptr);
-                    else g_ws_orphans.emplace(WsKey{it->first.slot, it->first.dev, it->first.st, kWsOrphanTid}, it->second);
-                }
-                it = g_ws.erase(it);
-            } else {
-                ++it;
-            }
-        }
+        // hipStreamPerThread named THIS thread's own stream, which dies with it: nobody can adopt in stream order
+        ws_erase_if(g_ws, [&](const WsKey &k) { return k.tid == tid; },
+                    [](const WsKey &k) { return k.st == hipStreamPerThread ? WsFate::Retire : WsFate::Orphan; });
     }
 };
 struct WsStaticsGuard { ~WsStaticsGuard() { g_ws_alive = false; } } g_ws_statics_guard;   // destroyed before the maps above (reverse order)
@@ -869,24 +771,12 @@ extern "C" int fhe_ntt_release_stream_workspace(void *hip_stream) {
     // hipStreamPerThread names a different stream in every thread: only the caller's buffers; an explicit stream is
     // about to be destroyed: the buffers of EVERY thread that used it
     const bool per_thread = st == hipStreamPerThread;
-    const size_t tid = std::hash<std::thread::id>()(std::this_thread::get_id());
+    const size_t tid = ws_thread_id();
+    const auto free_it = [](const WsKey &) { return WsFate::Free; };
     std::lock_guard<std::mutex> lk(g_ws_lock);
-    for (auto it = g_ws.begin(); it != g_ws.end();) {        // every slot of this (device, stream[, thread])
-        if (it->first.dev == dev && it->first.st == st && (!per_thread || it->first.tid == tid)) {
-            if (it->second.ptr) (void)hipFree(it->second.ptr);
-            it = g_ws.erase(it);
-        } else {
-            ++it;
-        }
-    }
-    for (auto it = g_ws_orphans.begin(); it != g_ws_orphans.end();) {   // and what dead threads left on it
-        if (it->first.dev == dev && it->first.st == st) {
-            if (it->second.ptr) (void)hipFree(it->second.ptr);
-            it = g_ws_orphans.erase(it);
-        } else {
-            ++it;
-        }
-    }
+    // every slot of this (device, stream[, thread]), and what dead threads left on it
+    ws_erase_if(g_ws, [&](const WsKey &k) { return k.dev == dev && k.st == st && (!per_thread || k.tid == tid); }, free_it);
+    ws_erase_if(g_ws_orphans, [&](const WsKey &k) { return k.dev == dev && k.st == st; }, free_it);
     return FHE_OK;
 }
 
@@ -903,12 +793,10 @@ extern "C" size_t fhe_ntt_workspace_bytes(void) {
 void fhe_workspace_free_all() {
     stage_free_all();
     std::lock_guard<std::mutex> lk(g_ws_lock);
-    for (auto &kv : g_ws)
-        if (kv.second.ptr) (void)hipFree(kv.second.ptr);
-    g_ws.clear();
-    for (auto &kv : g_ws_orphans)
-        if (kv.second.ptr) (void)hipFree(kv.second.ptr);
-    g_ws_orphans.clear();
+    const auto all = [](const WsKey &) { return true; };
+    const auto free_it = [](const WsKey &) { return WsFate::Free; };
+    ws_erase_if(g_ws, all, free_it);
+    ws_erase_if(g_ws_orphans, all, free_it);
     for (void *p : g_ws_retired) (void)hipFree(p);
     g_ws_retired.clear();
 }
@@ -998,12 +886,9 @@ bool fhe_smallq_args(const fhe_ntt_plan *plan, const fhe::DevicePlan &dp, fhe::S
     const u64 q = plan->q;
     a->tw_fwd = dp.tw32_fwd; a->tw_inv = dp.tw32_inv;
     a->q = (uint32_t)q; a->bq = (uint32_t)(0xffffffffull / q);
-    uint32_t inv = (uint32_t)q;                                 // Newton: q^-1 mod 2^32 (q odd)
-    for (int it = 0; it < 5; it++) inv *= 2u - (uint32_t)q * inv;
-    a->qinv_neg = 0u - inv;
-    a->ninv = fhe::Tw32{(uint32_t)plan->n_inv, (uint32_t)((plan->n_inv << 32) / q)};
-    const u64 nm = (plan->n_inv << 32) % q;
-    a->ninv_mont = fhe::Tw32{(uint32_t)nm, (uint32_t)((nm << 32) / q)};
+    a->qinv_neg = fhe::host::neg_inv32((uint32_t)q);
+    a->ninv = shoup32_pair<fhe::Tw32>(plan->n_inv, q);
+    a->ninv_mont = shoup32_pair<fhe::Tw32>(mulmod(plan->n_inv, 1ull << 32, q), q);
     a->mu = ~0ull / q;
     a->loose = fhe::smallq_loose(q) ? 1u : 0u;
     return true;
@@ -1022,55 +907,37 @@ int fhe_smallq_scratch(unsigned log_n, uint64_t rows, hipStream_t st, fhe::Small
 // ---------------------------------------------------------------------------
 // device-resident entry points
 // ---------------------------------------------------------------------------
-extern "C" int fhe_ntt_forward_dev(const fhe_ntt_plan *plan, const void *d_in, void *d_out,
-                                   size_t batch, void *hip_stream) {
+// fhe_ntt_forward_dev / fhe_ntt_inverse_dev (`who`): one body; only the forward direction has a persistent form
+static int ntt_dev(const fhe_ntt_plan *plan, const void *d_in, void *d_out, size_t batch, hipStream_t st, bool inverse, const char *who) {
     if (!plan) return fail(FHE_E_NULL, "plan is NULL");
     if (batch == 0) return FHE_OK;
-    if (!d_in || !d_out) return fail(FHE_E_NULL, "fhe_ntt_forward_dev: NULL buffer");
+    if (!d_in || !d_out) return fail(FHE_E_NULL, "%s: NULL buffer", who);
     REQUIRE_ALIGNED(d_in);
     REQUIRE_ALIGNED(d_out);
     fhe::DevicePlan dp;
     int rc = fhe_device_plan(plan, &dp);
     if (rc != FHE_OK) return rc;
-    if ((rc = check_canonical_dev(plan, d_in, batch * plan->n, (hipStream_t)hip_stream, "fhe_ntt_forward_dev")) != FHE_OK) return rc;
+    if ((rc = check_canonical_dev(plan, d_in, batch * plan->n, st, who)) != FHE_OK) return rc;
     fhe::SmallQArgs sq{};
     if (fhe_smallq_args(plan, dp, &sq)) {
         sq.a = (const u64 *)d_in; sq.out = (u64 *)d_out; sq.rows = batch;
-        if ((rc = fhe_smallq_scratch(dp.log_n, batch, (hipStream_t)hip_stream, &sq)) != FHE_OK) return rc;
-        hipError_t se = fhe::launch_sq_forward(sq, (int)dp.log_n, (hipStream_t)hip_stream);
-        return se == hipSuccess ? FHE_OK : hip_fail(se, "sq_forward_kernel");
+        if ((rc = fhe_smallq_scratch(dp.log_n, batch, st, &sq)) != FHE_OK) return rc;
+        hipError_t se = inverse ? fhe::launch_sq_inverse(sq, (int)dp.log_n, st) : fhe::launch_sq_forward(sq, (int)dp.log_n, st);
+        return se == hipSuccess ? FHE_OK : hip_fail(se, inverse ? "sq_inverse_kernel" : "sq_forward_kernel");
     }
     fhe::PersistTune tune;
-    if (persist_tune(&tune) && fhe::persist_supported(dp))
-        return forward_persist(plan, dp, tune, d_in, d_out, batch, (hipStream_t)hip_stream);
-    hipError_t e = fhe::launch_ntt_forward(dp, (const u64 *)d_in, (u64 *)d_out, batch,
-                                           fhe_batch_tile_for(plan), (hipStream_t)hip_stream);
-    if (e != hipSuccess) return hip_fail(e, "launch_ntt_forward");
+    if (!inverse && persist_tune(&tune) && fhe::persist_supported(dp)) return forward_persist(plan, dp, tune, d_in, d_out, batch, st);
+    const u64 tile = fhe_batch_tile_for(plan);
+    hipError_t e = inverse ? fhe::launch_ntt_inverse(dp, (const u64 *)d_in, nullptr, nullptr, (u64 *)d_out, batch, tile, st)
+                           : fhe::launch_ntt_forward(dp, (const u64 *)d_in, (u64 *)d_out, batch, tile, st);
+    if (e != hipSuccess) return hip_fail(e, inverse ? "launch_ntt_inverse" : "launch_ntt_forward");
     return FHE_OK;
 }
-
-extern "C" int fhe_ntt_inverse_dev(const fhe_ntt_plan *plan, const void *d_in, void *d_out,
-                                   size_t batch, void *hip_stream) {
-    if (!plan) return fail(FHE_E_NULL, "plan is NULL");
-    if (batch == 0) return FHE_OK;
-    if (!d_in || !d_out) return fail(FHE_E_NULL, "fhe_ntt_inverse_dev: NULL buffer");
-    REQUIRE_ALIGNED(d_in);
-    REQUIRE_ALIGNED(d_out);
-    fhe::DevicePlan dp;
-    int rc = fhe_device_plan(plan, &dp);
-    if (rc != FHE_OK) return rc;
-    if ((rc = check_canonical_dev(plan, d_in, batch * plan->n, (hipStream_t)hip_stream, "fhe_ntt_inverse_dev")) != FHE_OK) return rc;
-    fhe::SmallQArgs sq{};
-    if (fhe_smallq_args(plan, dp, &sq)) {
-        sq.a = (const u64 *)d_in; sq.out = (u64 *)d_out; sq.rows = batch;
-        if ((rc = fhe_smallq_scratch(dp.log_n, batch, (hipStream_t)hip_stream, &sq)) != FHE_OK) return rc;
-        hipError_t se = fhe::launch_sq_inverse(sq, (int)dp.log_n, (hipStream_t)hip_stream);
-        return se == hipSuccess ? FHE_OK : hip_fail(se, "sq_inverse_kernel");
-    }
-    hipError_t e = fhe::launch_ntt_inverse(dp, (const u64 *)d_in, nullptr, nullptr, (u64 *)d_out,
-                                           batch, fhe_batch_tile_for(plan), (hipStream_t)hip_stream);
-    if (e != hipSuccess) return hip_fail(e, "launch_ntt_inverse");
-    return FHE_OK;
+extern "C" int fhe_ntt_forward_dev(const fhe_ntt_plan *plan, const void *d_in, void *d_out, size_t batch, void *hip_stream) {
+    return ntt_dev(plan, d_in, d_out, batch, (hipStream_t)hip_stream, false, "fhe_ntt_forward_dev");
+}
+extern "C" int fhe_ntt_inverse_dev(const fhe_ntt_plan *plan, const void *d_in, void *d_out, size_t batch, void *hip_stream) {
+    return ntt_dev(plan, d_in, d_out, batch, (hipStream_t)hip_stream, true, "fhe_ntt_inverse_dev");
 }
 
 extern "C" size_t fhe_rq_mul_workspace_bytes(const fhe_ntt_plan *plan, size_t batch) {
@@ -1115,10 +982,7 @@ extern "C" int fhe_rq_mul_dev(const fhe_ntt_plan *plan, const void *d_a, int a_i
     }
     // single-pass sizes: the whole product in one kernel (both forward transforms, the pointwise
     // product and the inverse transform stay on chip); FHE_RQ_MUL_FUSED=0 selects the three-kernel path
-    static const bool fused_on = [] {
-        const char *e = getenv("FHE_RQ_MUL_FUSED");
-        return !(e && e[0] == '0');
-    }();
+    static const bool fused_on = fhe_env_switch("FHE_RQ_MUL_FUSED", true);
     if (fused_on) {
         hipError_t fe = fhe::launch_rq_mul_fused(dp, (const u64 *)d_a, a_is_evals != 0, (const u64 *)d_b, b_is_evals != 0,
                                                  (u64 *)d_c, (u64 *)d_c_evals, (u64 *)d_a_evals_out,
@@ -1211,21 +1075,8 @@ extern "C" int fhe_fill_synthetic_dev(uint64_t q, uint64_t seed, uint64_t first_
 // ---------------------------------------------------------------------------
 // host-buffer entry points: stage through device memory around the same kernels
 // ---------------------------------------------------------------------------
-// Every host entry point synchronises its stream before it returns; on an error path the
-// buffer may still be in use, so it is drained before going back to the pool.
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int dev = 0;          // the device the buffer lives on (the caller's current device at alloc)
-    bool clean = false;   // set once the stream has been synchronised after the last use
-    ~DevBuf() {
-        if (!p) return;
-        if (!clean) (void)hipStreamSynchronize(hipStreamPerThread);
-        fhe_stage_release(p, cap, dev);
-    }
-    int alloc(size_t bytes) { return fhe_stage_acquire(bytes, &p, &cap, &dev); }
-};
-
+// Every host entry point synchronises its stream before it returns; on an error path the buffers may still be in use,
+// so FheHostStage drains the stream before they go back to the pool.
 static int host_transform(const fhe_ntt_plan *plan, const uint64_t *in, uint64_t *out, size_t batch,
                           bool inverse) {
     if (!plan) return fail(FHE_E_NULL, "plan is NULL");
@@ -1235,16 +1086,13 @@ static int host_transform(const fhe_ntt_plan *plan, const uint64_t *in, uint64_t
     int rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
     const size_t bytes = batch * plan->n * sizeof(u64);
-    DevBuf d;
-    if ((rc = d.alloc(bytes)) != FHE_OK) return rc;
-    hipStream_t st = hipStreamPerThread;
-    HIP_TRY(hipMemcpyAsync(d.p, in, bytes, hipMemcpyHostToDevice, st));
-    rc = inverse ? fhe_ntt_inverse_dev(plan, d.p, d.p, batch, st)
-                 : fhe_ntt_forward_dev(plan, d.p, d.p, batch, st);
+    FheHostStage hs;
+    void *d = nullptr;   // the transform runs in place in the staged copy
+    if ((rc = hs.up(in, bytes, &d)) != FHE_OK) return rc;
+    rc = inverse ? fhe_ntt_inverse_dev(plan, d, d, batch, hipStreamPerThread)
+                 : fhe_ntt_forward_dev(plan, d, d, batch, hipStreamPerThread);
     if (rc != FHE_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out, d.p, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    d.clean = true;
+    if ((rc = hs.down(out, d, bytes)) != FHE_OK) return rc;
     // a persistent launch (FHE_NTT_PERSIST) that gave up a bounded wait left words that are not the transform
     if (!inverse && (rc = fhe_ntt_persist_status()) != FHE_OK) return rc;
     return FHE_OK;
@@ -1269,25 +1117,22 @@ extern "C" int fhe_rq_mul(const fhe_ntt_plan *plan, const uint64_t *a, int a_is_
     int rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
     const size_t bytes = batch * plan->n * sizeof(u64);
-    DevBuf da, db, dc, dce;
-    if ((rc = da.alloc(bytes)) != FHE_OK) return rc;
-    if ((rc = db.alloc(bytes)) != FHE_OK) return rc;
-    if ((rc = dc.alloc(bytes)) != FHE_OK) return rc;
-    if (c_evals && (rc = dce.alloc(bytes)) != FHE_OK) return rc;
-    hipStream_t st = hipStreamPerThread;
-    HIP_TRY(hipMemcpyAsync(da.p, a, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(db.p, b, bytes, hipMemcpyHostToDevice, st));
+    FheHostStage hs;
+    void *da = nullptr, *db = nullptr, *dc = nullptr, *dce = nullptr;
+    if ((rc = hs.up(a, bytes, &da)) != FHE_OK) return rc;
+    if ((rc = hs.up(b, bytes, &db)) != FHE_OK) return rc;
+    if ((rc = hs.up(nullptr, bytes, &dc)) != FHE_OK) return rc;
+    if (c_evals && (rc = hs.up(nullptr, bytes, &dce)) != FHE_OK) return rc;
     // forward transforms run in place on the staged copies, which then ARE the evals
-    rc = fhe_rq_mul_dev(plan, da.p, a_is_evals, db.p, b_is_evals, dc.p, dce.p,
-                        a_is_evals ? nullptr : da.p, b_is_evals ? nullptr : db.p, batch, nullptr, st);
+    rc = fhe_rq_mul_dev(plan, da, a_is_evals, db, b_is_evals, dc, dce, a_is_evals ? nullptr : da, b_is_evals ? nullptr : db, batch, nullptr,
+                        hipStreamPerThread);
     if (rc != FHE_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c, dc.p, bytes, hipMemcpyDeviceToHost, st));
-    if (c_evals) HIP_TRY(hipMemcpyAsync(c_evals, dce.p, bytes, hipMemcpyDeviceToHost, st));
-    if (a_evals_out) HIP_TRY(hipMemcpyAsync(a_evals_out, da.p, bytes, hipMemcpyDeviceToHost, st));
-    if (b_evals_out) HIP_TRY(hipMemcpyAsync(b_evals_out, db.p, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    da.clean = db.clean = dc.clean = dce.clean = true;
-    return FHE_OK;
+    // up to four results, one synchronisation
+    if ((rc = hs.down_async(c, dc, bytes)) != FHE_OK) return rc;
+    if (c_evals && (rc = hs.down_async(c_evals, dce, bytes)) != FHE_OK) return rc;
+    if (a_evals_out && (rc = hs.down_async(a_evals_out, da, bytes)) != FHE_OK) return rc;
+    if (b_evals_out && (rc = hs.down_async(b_evals_out, db, bytes)) != FHE_OK) return rc;
+    return hs.finish();
 }
 
 extern "C" int fhe_rq_mul_checked(const fhe_ntt_plan *plan_a, const fhe_ntt_plan *plan_b,
@@ -1312,18 +1157,12 @@ extern "C" int fhe_rq_pointwise_mul(const fhe_ntt_plan *plan, const uint64_t *a,
     int rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
     const size_t bytes = batch * plan->n * sizeof(u64);
-    DevBuf da, db;
-    if ((rc = da.alloc(bytes)) != FHE_OK) return rc;
-    if ((rc = db.alloc(bytes)) != FHE_OK) return rc;
-    hipStream_t st = hipStreamPerThread;
-    HIP_TRY(hipMemcpyAsync(da.p, a, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(db.p, b, bytes, hipMemcpyHostToDevice, st));
-    rc = fhe_rq_pointwise_mul_dev(plan, da.p, db.p, da.p, batch, st);
-    if (rc != FHE_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(c, da.p, bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    da.clean = db.clean = true;
-    return FHE_OK;
+    FheHostStage hs;
+    void *da = nullptr, *db = nullptr;   // the product runs in place in a
+    if ((rc = hs.up(a, bytes, &da)) != FHE_OK) return rc;
+    if ((rc = hs.up(b, bytes, &db)) != FHE_OK) return rc;
+    if ((rc = fhe_rq_pointwise_mul_dev(plan, da, db, da, batch, hipStreamPerThread)) != FHE_OK) return rc;
+    return hs.down(c, da, bytes);
 }
 
 extern "C" int fhe_rq_check_canonical(const fhe_ntt_plan *plan, const uint64_t *x, size_t batch) {
@@ -1334,18 +1173,16 @@ extern "C" int fhe_rq_check_canonical(const fhe_ntt_plan *plan, const uint64_t *
     int rc = fhe_current_device(&dev);
     if (rc != FHE_OK) return rc;
     const size_t count = batch * plan->n, bytes = count * sizeof(u64);
-    DevBuf dx, df;
-    if ((rc = dx.alloc(bytes)) != FHE_OK) return rc;
-    if ((rc = df.alloc(sizeof(int))) != FHE_OK) return rc;
+    FheHostStage hs;
+    void *dx = nullptr, *df = nullptr;
+    if ((rc = hs.up(x, bytes, &dx)) != FHE_OK) return rc;
+    if ((rc = hs.up(nullptr, sizeof(int), &df)) != FHE_OK) return rc;
     hipStream_t st = hipStreamPerThread;
-    HIP_TRY(hipMemcpyAsync(dx.p, x, bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(df.p, 0, sizeof(int), st));
-    hipError_t e = fhe::launch_check_canonical((const u64 *)dx.p, count, plan->q, (int *)df.p, st);
+    HIP_TRY(hipMemsetAsync(df, 0, sizeof(int), st));
+    hipError_t e = fhe::launch_check_canonical((const u64 *)dx, count, plan->q, (int *)df, st);
     if (e != hipSuccess) return hip_fail(e, "launch_check_canonical");
     int flag = 0;
-    HIP_TRY(hipMemcpyAsync(&flag, df.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    dx.clean = df.clean = true;
+    if ((rc = hs.down(&flag, df, sizeof(int))) != FHE_OK) return rc;
     if (flag) return fail(FHE_E_NOT_CANONICAL, "a coefficient >= q=%llu was found", (unsigned long long)plan->q);
     return FHE_OK;
 }
@@ -1382,19 +1219,7 @@ extern "C" int fhe_ntt_shutdown(void) {
     for (auto &kv : g_plans) {
         fhe_ntt_plan *p = kv.second.get();
         std::lock_guard<std::mutex> lk2(p->dev_lock);
-        for (auto &t : p->dev) {
-            if (t.tw_fwd) (void)hipFree(t.tw_fwd);
-            if (t.tw_inv) (void)hipFree(t.tw_inv);
-            if (t.digit_lut) (void)hipFree(t.digit_lut);
-            if (t.tw32_fwd) (void)hipFree(t.tw32_fwd);
-            if (t.tw32_inv) (void)hipFree(t.tw32_inv);
-            if (t.tw_fwd_mg) (void)hipFree(t.tw_fwd_mg);
-            if (t.tw_inv_mg) (void)hipFree(t.tw_inv_mg);
-            if (t.tw_fwd_pm) (void)hipFree(t.tw_fwd_pm);
-            if (t.tw_inv_pm) (void)hipFree(t.tw_inv_pm);
-            if (t.twc_pm) (void)hipFree(t.twc_pm);
-            t = DeviceTables();
-        }
+        for (auto &t : p->dev) t.release();
     }
     g_plans.clear();
     return FHE_OK;

@@ -1,12 +1,15 @@
 // capi_internal.hpp — what the sources of the library share behind the public boundary: the plan and its device tables,
 // the services of capi.hip (error reporting, device plans, workspace, staging pool, switches), and the host helpers every
 // entry point is written with: the argument checks (REQUIRE_ALIGNED, overlaps / overlaps_any, mul_fits, check_ring),
-// the timed launch with its check (launch / launch_named) and the staging of host buffers around a *_dev call
-// (FheHostStage, fhe_host_call).
+// the timed launch with its check (launch / launch_named), the staging of host buffers around a *_dev call
+// (FheHostStage, fhe_host_call), the owner of a table build's device allocations (FheTableUpload; DeviceTables keeps what
+// it commits and frees it in release()), the read-once environment switches (fhe_env_switch) and, through
+// host_tables.hpp, the host arithmetic behind every table (fhe::host).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <initializer_list>
 #include <mutex>
 #include <type_traits>
@@ -15,6 +18,7 @@
 
 #include "../../include/fhe_ntt.h"
 #include "../../include/fhe_ntt_experimental.h"   // the persistent kernels' switches: exported, outside the boundary
+#include "host_tables.hpp"
 #include "ntt_kernels.hpp"
 
 constexpr int kMaxDevices = 16;
@@ -28,6 +32,11 @@ struct DeviceTables {
     fhe::Tw *tw_fwd_mg = nullptr, *tw_inv_mg = nullptr;   // q = 1 (mod 2^32) below 2^61: {w 2^32, w 2^64 mod q}
     fhe::Tw *twc_pm = nullptr;   // the one-launch transform's lane-ordered table of the last four stages (ntt_persist.hip), built on first use
     bool ready = false;
+    std::vector<void *> owned;   // every allocation behind the pointers above (FheTableUpload::commit)
+    void release() {
+        for (void *p : owned) (void)hipFree(p);
+        *this = DeviceTables();
+    }
 };
 
 struct fhe_ntt_plan {
@@ -51,9 +60,6 @@ int fhe_hip_fail(hipError_t e, const char *what);
     } while (0)
 
 int fhe_current_device(int *dev);
-// host number theory (capi.hip): x^k mod q, and x^-1 mod q for a prime q that does not divide x
-fhe::u64 fhe_exp_mod(fhe::u64 q, fhe::u64 x, fhe::u64 k);
-fhe::u64 fhe_inv_mod(fhe::u64 q, fhe::u64 x);
 // FHE_NTT_CHECK_CANONICAL / fhe_ntt_set_check_canonical(1): FHE_E_NOT_CANONICAL if any of `count` device words is >= q (synchronises `st`); FHE_OK when the check is off
 int fhe_check_canonical_words(uint64_t q, const void *d_x, size_t count, hipStream_t st, const char *who);
 int fhe_device_plan(const fhe_ntt_plan *plan, fhe::DevicePlan *dp);
@@ -73,6 +79,13 @@ int fhe_smallq_scratch(unsigned log_n, uint64_t rows, hipStream_t st, fhe::Small
 bool fhe_mg_enabled();                                 // FHE_MG=0 keeps q = 1 (mod 2^32) on the Shoup forward kernels
 bool fhe_pm_enabled();                                 // FHE_PM=0 keeps pseudo-Mersenne moduli on the Shoup kernels
 bool fhe_ext32_enabled();                              // FHE_EXT32=0 keeps every product on the 61-bit kernels
+bool fhe_digit_mac_fused();                            // FHE_DIGIT_MAC_FUSED=0 (zring.hip): digit transforms written out, then one multiply-accumulate pass
+// A switch of the environment: "0" turns one that defaults to on off, "1" turns one that defaults to off on, anything
+// else leaves the default.  Read once per process, at first use: `static const bool on = fhe_env_switch("FHE_X", true);`
+static inline bool fhe_env_switch(const char *name, bool dflt) {
+    const char *e = getenv(name);
+    return e ? (dflt ? e[0] != '0' : e[0] == '1') : dflt;
+}
 // pooled device staging for the host-buffer entry points (capi.hip); release only idle buffers
 int fhe_stage_acquire(size_t bytes, void **out, size_t *got, int *dev);
 void fhe_stage_release(void *ptr, size_t bytes, int dev);
@@ -144,6 +157,35 @@ int launch(const char *label, int L, hipStream_t st, K kernel, unsigned grid, un
     return launch_named(label, nullptr, L, st, kernel, grid, block, args...);
 }
 
+// The device allocations of one table build.  alloc / up allocate on the current device (up also uploads `count` host
+// elements, blocking); the first hipError_t stays in `err` and turns every later step into a no-op that returns nullptr;
+// whatever was allocated is freed again by the destructor unless commit() handed it to the table's own list first.
+struct FheTableUpload {
+    std::vector<void *> owned;
+    hipError_t err = hipSuccess;
+    FheTableUpload() = default;
+    FheTableUpload(const FheTableUpload &) = delete;
+    FheTableUpload &operator=(const FheTableUpload &) = delete;
+    ~FheTableUpload() {
+        for (void *p : owned) (void)hipFree(p);
+    }
+    void *alloc(size_t bytes) {
+        void *d = nullptr;
+        if (err == hipSuccess && (err = hipMalloc(&d, bytes)) == hipSuccess) owned.push_back(d);
+        return err == hipSuccess ? d : nullptr;
+    }
+    template <class T>
+    T *up(const T *h, size_t count) {
+        void *d = alloc(count * sizeof(T));
+        if (d) err = hipMemcpy(d, h, count * sizeof(T), hipMemcpyHostToDevice);
+        return err == hipSuccess ? static_cast<T *>(d) : nullptr;
+    }
+    void commit(std::vector<void *> *keep) {
+        keep->insert(keep->end(), owned.begin(), owned.end());
+        owned.clear();
+    }
+};
+
 // Staging of HOST buffers around a *_dev entry point: uploads on the calling thread's stream
 // (hipStreamPerThread, for which the library workspace is per thread: no lock is needed); the
 // destructor drains the stream on error paths before the buffers go back to the pool.
@@ -168,11 +210,19 @@ struct FheHostStage {
         }
         return FHE_OK;
     }
-    int down(void *h, const void *d, size_t bytes) {
+    // several results: down_async each, then finish() once (one synchronisation per call)
+    int down_async(void *h, const void *d, size_t bytes) {
         HIP_TRY(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, hipStreamPerThread));
+        return FHE_OK;
+    }
+    int finish() {
         HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
         clean = true;
         return FHE_OK;
+    }
+    int down(void *h, const void *d, size_t bytes) {
+        int rc = down_async(h, d, bytes);
+        return rc != FHE_OK ? rc : finish();
     }
 };
 

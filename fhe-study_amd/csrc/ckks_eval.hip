@@ -505,7 +505,7 @@ int switch_call(const Chain &c, u64 batch, u64 words, hipStream_t st, Body body)
     int rc, dev;
     if ((rc = words ? fhe_workspace_get(kCkksEvalSlot, (size_t)(words * cb * 8), st, &w) : fhe_current_device(&dev)) != FHE_OK) return rc;
     u64 pinv[fhe::kRnsMaxLimbs];
-    for (unsigned i = 0; i < c.k; i++) pinv[i] = fhe_inv_mod(c.p[i]->q, c.p[c.k]->q);
+    for (unsigned i = 0; i < c.k; i++) pinv[i] = fhe::host::inv_mod(c.p[i]->q, c.p[c.k]->q);
     return for_chunks(batch, cb, [&](u64 r0, u64 cr) { return body(r0, cr, (u64 *)w, pinv); });
 }
 
@@ -689,7 +689,7 @@ extern "C" int fhe_ckks_rns_rescale_dev(const fhe_ntt_plan *const *plans, unsign
     void *w = nullptr;
     if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(2ull * k * cb * n * 8), st, &w)) != FHE_OK) return rc;
     u64 qinv[fhe::kRnsMaxLimbs];
-    for (unsigned i = 0; i < top; i++) qinv[i] = fhe_inv_mod(c.p[i]->q, c.p[top]->q);
+    for (unsigned i = 0; i < top; i++) qinv[i] = fhe::host::inv_mod(c.p[i]->q, c.p[top]->q);
     const LimbRows<const u64> in{(const u64 *)d_in, 2 * batch * n, batch * n};
     return for_chunks(batch, cb, [&](u64 r0, u64 cr) {
         const u64 slab = cr * n;

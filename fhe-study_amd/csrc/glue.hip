@@ -425,7 +425,7 @@ extern "C" int fhe_glwe_key_switch_dev(const fhe_ntt_plan *plan, unsigned k, uns
     // Base 2, k = 1, key in coefficients: two 27-bit primes and 32-bit arithmetic (ks32_run above)
     if (!(flags & FHE_A_IS_EVALS) && ks32_usable(plan, k, beta, l))
         return ks32_run(plan, dp, k, l, d_glwe, nullptr, d_ksk, d_out, batch, st);
-    static const bool fused_on = [] { const char *e = getenv("FHE_DIGIT_MAC_FUSED"); return !(e && e[0] == '0'); }();
+    const bool fused_on = fhe_digit_mac_fused();
     if (beta == 2 && fused_on && dp.wide && dp.log_n >= 8 && dp.log_n <= 12 && (k1 == 2 || k1 == 3)) {
         const u32 parts = fhe::digit_mac_parts(batch, T, dp.log_n, k1);
         // [key transforms: T*k1 rows] [rhs: batch*k1 rows] [partial sums: parts*batch*k1 rows]

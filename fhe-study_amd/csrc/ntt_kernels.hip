@@ -24,7 +24,7 @@
 //   of the round is (T0 << i) + (k >> (4-i)),  T0 = (1<<(s0+ls0)) + (blk<<ls0) + H.
 #include "ntt_rounds.hpp"
 
-#include <cstdlib>
+#include "capi_internal.hpp"   // fhe_env_switch
 
 // A/B switches of round 4 (defaults = what was measured faster on one box; tools/abl_build.sh builds the others)
 #ifndef FHE_MID_ONE_TILE
@@ -944,7 +944,7 @@ static inline bool plan_runs_montgomery(const DevicePlan &p) {
 // FHE_G63_PLAIN=1: 2^62 <= q < 2^63 on the plain strict kernels of generic63.hip at every size (what shipped until round 5:
 // ceil(log2 n / 4) launches); default: the two-pass / fused kernels above with AR = 3
 static bool g63_plain() {
-    static const bool v = [] { const char *e = getenv("FHE_G63_PLAIN"); return e && e[0] == '1'; }();
+    static const bool v = fhe_env_switch("FHE_G63_PLAIN", false);
     return v;
 }
 static inline void set_tables(PassArgs &a, const DevicePlan &p, bool inverse) {

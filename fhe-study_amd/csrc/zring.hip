@@ -343,14 +343,10 @@ __global__ __launch_bounds__(256) void zr_rq_add_kernel(const u64 *__restrict__ 
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-static inline u64 hmulmod(u64 a, u64 b, u64 p) { return (u64)(((u128)a * b) % p); }
-static u64 hpow(u64 a, u64 e, u64 p) {
-    u64 r = 1;
-    a %= p;
-    while (e) { if (e & 1) r = hmulmod(r, a, p); a = hmulmod(a, a, p); e >>= 1; }
-    return r;
-}
-static inline Tw htw(u64 w, u64 p) { return Tw{w, (u64)((((u128)w) << 64) / p)}; }
+using fhe::host::inv_mod;
+using fhe::host::mulmod;
+using fhe::host::shoup_pair;
+static inline fhe::Tw32 tw32(u64 w, u64 p) { return fhe::host::shoup32_pair<fhe::Tw32>(w, p); }
 
 // number of primes for a bound of `bits` on |true value| (signed lift needs one more bit)
 static int primes_for_bits(unsigned bits, bool is_signed) {
@@ -387,9 +383,9 @@ static int zctx_init(ZCtx *z, u64 n2, int K) {
     z->cc.half1 = (P1 + 1) / 2;
     z->cc.half2 = (P2 - 1) / 2;
     z->cc.half3 = (P3 - 1) / 2;
-    z->cc.inv1_mod2 = htw(hpow(P1 % P2, P2 - 2, P2), P2);
-    z->cc.p1_mod3 = htw(P1 % P3, P3);
-    z->cc.inv12_mod3 = htw(hpow(hmulmod(P1 % P3, P2 % P3, P3), P3 - 2, P3), P3);
+    z->cc.inv1_mod2 = shoup_pair<Tw>(inv_mod(P2, P1), P2);
+    z->cc.p1_mod3 = shoup_pair<Tw>(P1 % P3, P3);
+    z->cc.inv12_mod3 = shoup_pair<Tw>(inv_mod(P3, mulmod(P1 % P3, P2 % P3, P3)), P3);
     if (K < 2) z->cc.m[1] = z->cc.m[0];
     if (K < 3) z->cc.m[2] = z->cc.m[0];
     return FHE_OK;
@@ -564,15 +560,12 @@ static int bfv32_args(uint64_t n, fhe::Bfv32Args *a) {
     a->log_n2 = ceil_log2(2 * n);
     for (int i = 0; i < 3; i++) {
         const uint32_t p = a->t.p[i];
-        uint32_t inv = p;                                       // Newton: p^-1 mod 2^32 (p odd: 3 correct bits, doubled per step)
-        for (int it = 0; it < 5; it++) inv *= 2u - p * inv;
-        a->pinv_neg[i] = 0u - inv;
-        const u64 w = ((u64)a->t.ninv[i].w << 32) % p;          // (2n)^-1 * 2^32 mod p
-        a->ninv_mont[i] = fhe::Tw32{(uint32_t)w, (uint32_t)((w << 32) / p)};
+        a->pinv_neg[i] = fhe::host::neg_inv32(p);
+        const u64 w = mulmod(a->t.ninv[i].w, 1ull << 32, p);    // (2n)^-1 * 2^32 mod p
+        a->ninv_mont[i] = tw32(w, p);
         const fhe_ntt_plan *plan = nullptr;                     // (cached: fhe_ext32_tables built the tables from it)
         if ((rc = fhe_ntt_plan_get(p, 2 * n, &plan)) != FHE_OK) return rc;
-        const u64 w1 = (plan->roots_inv[1] * w) % p;            // roots_inv[1] * (2n)^-1 * 2^32 mod p: the last stage and the scaling in one
-        a->w1ninv_mont[i] = fhe::Tw32{(uint32_t)w1, (uint32_t)((w1 << 32) / p)};
+        a->w1ninv_mont[i] = tw32(mulmod(plan->roots_inv[1], w, p), p);   // roots_inv[1] * (2n)^-1 * 2^32 mod p: the last stage and the scaling in one
     }
     return FHE_OK;
 }
@@ -583,19 +576,19 @@ static int bfv32_args(uint64_t n, fhe::Bfv32Args *a) {
 // faster one — tensor 867 -> 821 us, relinearisation 815 -> 796 us, VALU instructions per wave 8120 -> 6946 / 11297 -> 10133
 // (gpurun_out/bfv/small*.json) — and the default.  FHE_BFV_SMALL_F64=0 selects the general conversion.
 static bool bfv32_small_f64_on() {
-    static const bool on = [] { const char *e = getenv("FHE_BFV_SMALL_F64"); return !(e && e[0] == '0'); }();
+    static const bool on = fhe_env_switch("FHE_BFV_SMALL_F64", true);
     return on;
 }
 // the epilogue's quotient as reciprocal + two fma (bfv32.hip: exact_quotient) needs an ODD integer denominator; the argument
 // written there covers denominators below 2^48 (what is used: q < 2^21, p = q^2 < 2^42) — the gate is that, not 2^53
 // (FHE_BFV_FAST_DIV=0: the IEEE division sequence — the A/B)
 static double bfv32_rden(uint64_t den) {
-    static const bool on = [] { const char *e = getenv("FHE_BFV_FAST_DIV"); return !(e && e[0] == '0'); }();
+    static const bool on = fhe_env_switch("FHE_BFV_FAST_DIV", true);
     return (on && (den & 1ull) && den < (1ull << 48)) ? 1.0 / (double)den : 0.0;
 }
 // q <= every prime in use: canonical source words need no reduction (FHE_BFV_BELOW_P=0: reduce anyway)
 static uint32_t bfv32_below_p(uint64_t q, const fhe::Bfv32Args &a, int primes) {
-    static const bool on = [] { const char *e = getenv("FHE_BFV_BELOW_P"); return !(e && e[0] == '0'); }();
+    static const bool on = fhe_env_switch("FHE_BFV_BELOW_P", true);
     for (int i = 0; i < primes; i++) if (q > a.t.p[i]) return 0u;
     return on ? 1u : 0u;
 }
@@ -618,7 +611,7 @@ static int bfv32_tensor(uint64_t q, uint64_t n, uint64_t t, const void *d_ab, vo
     {   // the integer epilogue (bfv32.hip: zq_scale_round_int) where t * v < 2^52 for every coefficient v <= 2 n (q - 1)^2
         // — opt-in with FHE_BFV_INT_ROUND=1: bit-identical (tests/test_round3_gpu.py) but measured SLOWER than the f64 form
         // on MI355X (951 vs 855 us per 2048 pairs: f64 runs at full rate here, two 64-bit quotients cost more than one division)
-        static const bool on = [] { const char *e = getenv("FHE_BFV_INT_ROUND"); return e && e[0] == '1'; }();
+        static const bool on = fhe_env_switch("FHE_BFV_INT_ROUND", false);
         const unsigned __int128 vmax = (unsigned __int128)2 * n * (q - 1) * (q - 1);
         a.int_num = (on && t != 0 && vmax * t < ((unsigned __int128)1 << 52)) ? t : 0;
         // Zq::from_f64 in f64 alone (bfv32.hip: zq_from_f64_small) where every scaled coefficient stays below 2^50
@@ -865,20 +858,19 @@ struct Ext32Tables {
     fhe::Tw32 *fwd[3] = {nullptr, nullptr, nullptr}, *inv[3] = {nullptr, nullptr, nullptr};
     uint32_t *lut[3] = {nullptr, nullptr, nullptr};
     fhe::Tw32 ninv[3]{};
+    std::vector<void *> owned;   // every allocation behind the pointers above (FheTableUpload::commit)
+    void release() {
+        for (void *p : owned) (void)hipFree(p);
+        *this = Ext32Tables();
+    }
 };
 std::mutex g_e32_lock;
 std::map<std::pair<u64, int>, Ext32Tables> g_e32;
-inline fhe::Tw32 tw32(u64 w, u64 p) { return fhe::Tw32{(uint32_t)w, (uint32_t)((w << 32) / p)}; }
 }  // namespace
 
 void fhe_ext32_free_all() {
     std::lock_guard<std::mutex> lk(g_e32_lock);
-    for (auto &kv : g_e32)
-        for (int i = 0; i < 3; i++) {
-            if (kv.second.fwd[i]) (void)hipFree(kv.second.fwd[i]);
-            if (kv.second.inv[i]) (void)hipFree(kv.second.inv[i]);
-            if (kv.second.lut[i]) (void)hipFree(kv.second.lut[i]);
-        }
+    for (auto &kv : g_e32) kv.second.release();
     g_e32.clear();
 }
 
@@ -892,54 +884,24 @@ int fhe_ext32_tables(uint64_t n, fhe::Ext32Args *a) {
     std::lock_guard<std::mutex> lk(g_e32_lock);
     Ext32Tables &t = g_e32[std::make_pair(n, dev)];
     if (!t.fwd[0]) {
+        // a failure at any prime keeps nothing: `tu` owns the allocations until all three primes are up
+        FheTableUpload tu;
+        Ext32Tables nt;
         for (int i = 0; i < 3; i++) {
             const u64 p = primes[i];
             const fhe_ntt_plan *plan = nullptr;
             if ((rc = fhe_ntt_plan_get(p, n, &plan)) != FHE_OK) return rc;
             std::vector<fhe::Tw32> f(n), v(n);
             for (u64 k = 0; k < n; k++) { f[k] = tw32(plan->roots[k], p); v[k] = tw32(plan->roots_inv[k], p); }
-            // bit tables: as capi.hip builds them for the 61-bit plans (ntt_rounds.hpp: round0_bits)
-            std::vector<uint32_t> lut(136, 0);
-            const u64 *r = plan->roots.data();
-            auto add = [&](u64 x, u64 y) { u64 z = x + y; return z >= p ? z - p : z; };
-            auto sub = [&](u64 x, u64 y) { return x >= y ? x - y : x + p - y; };
-            auto mul = [&](u64 x, u64 y) { return (x * y) % p; };
-            for (unsigned pt = 0; pt < 16; pt++) {
-                const u64 x0 = pt & 1, x1 = (pt >> 1) & 1, x2 = (pt >> 2) & 1, x3 = (pt >> 3) & 1;
-                const u64 a0 = add(x0, mul(r[1], x2)), a2 = sub(x0, mul(r[1], x2));
-                const u64 a1 = add(x1, mul(r[1], x3)), a3 = sub(x1, mul(r[1], x3));
-                u64 y[4];
-                y[0] = add(a0, mul(r[2], a1)); y[1] = sub(a0, mul(r[2], a1));
-                y[2] = add(a2, mul(r[3], a3)); y[3] = sub(a2, mul(r[3], a3));
-                for (int j = 0; j < 4; j++) {
-                    lut[4 * pt + j] = (uint32_t)y[j];
-                    lut[64 + 4 * pt + j] = (uint32_t)mul(r[4 + j], y[j]);
-                }
-            }
-            for (unsigned pt = 0; pt < 4; pt++) {
-                const u64 x = pt & 1, y = (pt >> 1) & 1;
-                lut[128 + 2 * pt] = (uint32_t)add(x, mul(r[1], y));
-                lut[128 + 2 * pt + 1] = (uint32_t)sub(x, mul(r[1], y));
-            }
-            fhe::Tw32 *df = nullptr, *di = nullptr;
-            uint32_t *dl = nullptr;
-            hipError_t e = hipMalloc((void **)&df, n * sizeof(fhe::Tw32));
-            if (e == hipSuccess) e = hipMalloc((void **)&di, n * sizeof(fhe::Tw32));
-            if (e == hipSuccess) e = hipMalloc((void **)&dl, lut.size() * 4);
-            if (e == hipSuccess) e = hipMemcpy(df, f.data(), n * sizeof(fhe::Tw32), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(di, v.data(), n * sizeof(fhe::Tw32), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(dl, lut.data(), lut.size() * 4, hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                if (df) (void)hipFree(df);
-                if (di) (void)hipFree(di);
-                if (dl) (void)hipFree(dl);
-                for (int j = 0; j < i; j++) { (void)hipFree(t.fwd[j]); (void)hipFree(t.inv[j]); (void)hipFree(t.lut[j]); }
-                t = Ext32Tables();
-                return fhe_hip_fail(e, "uploading the 27-bit tables");
-            }
-            t.fwd[i] = df; t.inv[i] = di; t.lut[i] = dl;
-            t.ninv[i] = tw32(plan->n_inv, p);
+            const auto lut = fhe::host::bit_lut<uint32_t>(plan->roots.data(), p);   // (ntt_rounds.hpp: round0_bits)
+            nt.fwd[i] = tu.up(f.data(), n);
+            nt.inv[i] = tu.up(v.data(), n);
+            nt.lut[i] = tu.up(lut.data(), lut.size());
+            if (tu.err != hipSuccess) return fhe_hip_fail(tu.err, "uploading the 27-bit tables");
+            nt.ninv[i] = tw32(plan->n_inv, p);
         }
+        tu.commit(&nt.owned);
+        t = std::move(nt);
     }
     const u64 pA = primes[0], pB = primes[1];
     for (int i = 0; i < 3; i++) {
@@ -949,16 +911,20 @@ int fhe_ext32_tables(uint64_t n, fhe::Ext32Args *a) {
         a->bq[i] = (uint32_t)(0xffffffffull / primes[i]);
         a->ninv[i] = t.ninv[i];
     }
-    a->crt = tw32(hpow(pA % pB, pB - 2, pB), pB);     // pA^-1 mod pB
+    a->crt = tw32(inv_mod(pB, pA), pB);               // pA^-1 mod pB
     const u64 pC = primes[2];
-    a->crt_ac = tw32(hpow(pA % pC, pC - 2, pC), pC);
-    a->crt_bc = tw32(hpow(pB % pC, pC - 2, pC), pC);
+    a->crt_ac = tw32(inv_mod(pC, pA), pC);
+    a->crt_bc = tw32(inv_mod(pC, pB), pC);
     a->P = pA * pB;
     a->halfP = (a->P + 1) / 2;
     return FHE_OK;
 }
 bool fhe_ext32_enabled() {
-    static const bool on = [] { const char *e = getenv("FHE_EXT32"); return !(e && e[0] == '0'); }();
+    static const bool on = fhe_env_switch("FHE_EXT32", true);
+    return on;
+}
+bool fhe_digit_mac_fused() {
+    static const bool on = fhe_env_switch("FHE_DIGIT_MAC_FUSED", true);
     return on;
 }
 static bool ext32_on(u64 n, unsigned k, unsigned l) { return fhe_ext32_enabled() && fhe::ext32_shape_supported(n, k, l); }
@@ -1062,7 +1028,7 @@ extern "C" int fhe_tggsw_external_product_prepared_dev(uint64_t n, unsigned k, u
     }
     // Fused form: digit extraction, forward transform and multiply-accumulate in one kernel
     // (digit_mac.hip); the digit transforms never reach memory.  R[b][half][c] = sum_t G2[t][half][c] * NTT(digit_t(b)).
-    static const bool fused_on = [] { const char *e = getenv("FHE_DIGIT_MAC_FUSED"); return !(e && e[0] == '0'); }();
+    const bool fused_on = fhe_digit_mac_fused();
     const u32 parts = fhe::digit_mac_parts(batch, (u32)T, z1.dp[0].log_n, 2 * k1);
     if (fused_on) {
         if ((rc = fhe_workspace_get(1, ((u64)parts + 1) * 2 * orows * n * 8, st, &wsv)) != FHE_OK) return rc;

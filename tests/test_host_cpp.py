@@ -94,6 +94,17 @@ def test_persistent_transform_protocols_simulated(pkg):
     assert "all persist schedule tests passed" in r.stdout
 
 
+def test_host_table_arithmetic_against_its_definitions(pkg):
+    """csrc/host_tables.hpp, the one copy of the host arithmetic behind every uploaded table: the 136-word bit-pattern
+    table against its closed form in both word sizes, the Shoup / pseudo-Mersenne / Montgomery pairs, the inverses and
+    bitrev against their definitions, exactly, for one modulus of each table family at n = 8 and 16
+    (fhe-study_amd/host/test_host_tables.cpp; needs neither the library nor a GPU)"""
+    exe = _build(pkg, "test_host_tables")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "all host table tests passed" in r.stdout
+
+
 def test_c_abi_without_a_device_or_with_one(pkg):
     """every path of include/fhe_ntt.h that needs no device — plan construction and cache (16 threads), the reference's
     argument checks in the reference's order, shard arithmetic, switches — and the compute entry points, which must return

@@ -464,6 +464,58 @@ def test_three_kernel_product_path_for_single_pass_sizes(pkg, oracle):
 
 
 @pytest.mark.gpu
+def test_tables_are_rebuilt_after_shutdown(pkg):
+    """Every table family's first-use upload, its release in fhe_ntt_shutdown() and its rebuild, in a fresh process: one
+    modulus per family at n = 16 (Shoup-62, strict-63, pseudo-Mersenne, word-Montgomery) and the 32-bit words at their
+    smallest size n = 256 transform three polynomials forward and back to the oracle's words; Tn x Tn and the external
+    product at the smallest shape of the 27-bit form (n = 256, k = 1, l = 1) likewise; then shutdown(), the same plans are
+    fetched again and the same calls return the same words: nothing dangles after the free, nothing stale survives it."""
+    import os
+    import subprocess
+    import sys
+
+    import test_rq_rows_cpu as S
+
+    families = [(S.Q62, 16, S.SHOUP62), (S.Q63, 16, S.STRICT63), (Q61, 16, S.PMERSENNE), (S.QMG, 16, S.MONTGOMERY), (Q16, 256, S.WORD32)]
+    code = (
+        "import sys, numpy as np; sys.path.insert(0, %r)\n"
+        "import fhe_study_amd as pkg\n"
+        "from oracle import load_oracle\n"
+        "O = load_oracle()\n"
+        "rng = np.random.default_rng(77)\n"
+        "n, k, l = 256, 1, 1\n"
+        "ta, tb = (rng.integers(0, 1 << 64, (2, n), dtype=np.uint64) for _ in range(2))\n"
+        "gg = rng.integers(0, 1 << 64, ((k + 1) * l, k + 1, n), dtype=np.uint64)\n"
+        "ct = rng.integers(0, 1 << 64, (2, k + 1, n), dtype=np.uint64)\n"
+        "want_tn, want_ep = O.tn_mul(n, ta, tb), O.external_product(n, k, l, gg, ct)\n"
+        "cases = []\n"
+        "for q, m, arith in %r:\n"
+        "    a = rng.integers(0, q, (3, m), dtype=np.uint64)\n"
+        "    cases.append((q, m, arith, a, O.ntt(q, m, a).reshape(3, m), O.intt(q, m, a).reshape(3, m)))\n"
+        "def run():\n"
+        "    out = []\n"
+        "    for q, m, arith, a, fwd, inv in cases:\n"
+        "        P = pkg.Plan(q, m)\n"
+        "        assert P.arithmetic() == arith, (q, m, P.arithmetic())\n"
+        "        got = (P.forward(a).reshape(3, m), P.inverse(a).reshape(3, m))\n"
+        "        assert np.array_equal(got[0], fwd) and np.array_equal(got[1], inv), (q, m)\n"
+        "        out += got\n"
+        "    out += [pkg.binding.tn_mul(n, ta, tb), pkg.binding.tggsw_external_product(n, k, l, gg, ct)]\n"
+        "    assert np.array_equal(out[-2].reshape(-1), want_tn.reshape(-1)), 'tn_mul'\n"
+        "    assert np.array_equal(out[-1].reshape(-1), want_ep.reshape(-1)), 'external product'\n"
+        "    return out\n"
+        "first = run()\n"
+        "pkg.binding.shutdown()\n"
+        "assert pkg.binding.load_library().fhe_ntt_workspace_bytes() == 0\n"
+        "again = run()\n"
+        "assert all(np.array_equal(x, y) for x, y in zip(first, again))\n"
+        "pkg.binding.shutdown()\n"
+        "print('tables rebuilt ok')\n" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), families))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "tables rebuilt ok" in r.stdout, r.stdout + r.stderr
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("log_n", [18, 19, 20])
 def test_largest_sizes(pkg, oracle, log_n):
     """n = 2^18 .. 2^20 (the engine's limit): 8 strided + 10..12 contiguous stages, the only sizes
