@@ -93,9 +93,12 @@ EXPORTS = [
     "fhe_ckks_galois_evals_dev", "fhe_ckks_rns_galois_key_dev", "fhe_ckks_rns_galois_dev", "fhe_ckks_rns_galois_workspace_bytes",
     # CKKS on the RNS chain: plaintext linear transforms, the double-hoisted diagonal sum (ckks_eval.hip)
     "fhe_ckks_rns_diag_sum_dev", "fhe_ckks_rns_diag_workspace_bytes",
+    # CKKS on the RNS chain: fused sums of ciphertexts by public scalars (ckks_eval.hip)
+    "fhe_ckks_rns_lincomb_dev",
 ]
 FHE_CKKS_GALOIS_MAX_COUNT = 256              # include/fhe_ntt.h: the most Galois elements of one fhe_ckks_rns_galois_dev call
 FHE_CKKS_DIAG_MAX_OUTPUTS = 64               # include/fhe_ntt.h: the most outputs of one fhe_ckks_rns_diag_sum_dev call
+FHE_CKKS_LINCOMB_MAX_COUNT, FHE_CKKS_LINCOMB_MAX_OUTPUTS = 64, 16    # include/fhe_ntt.h: the most inputs and outputs of one fhe_ckks_rns_lincomb_dev call
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
 GATES = {"AND": 0, "NAND": 1, "OR": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -322,6 +325,7 @@ def load_library():
     L.fhe_ckks_rns_diag_sum_dev.argtypes = [_pp, _uint, _vp, _pp, ctypes.POINTER(_u64), _uint, _uint, _vp, _uint, _vp, _vp, _sz, _vp]
     L.fhe_ckks_rns_diag_workspace_bytes.argtypes = [_u64, _uint, _sz, _uint, _uint]
     L.fhe_ckks_rns_diag_workspace_bytes.restype = _sz
+    L.fhe_ckks_rns_lincomb_dev.argtypes = [_pp, _uint, _pp, _uint, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _uint, _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -872,6 +876,17 @@ def ckks_rns_diag_sum_dev(plans, special, d_gks, gs, key_limbs, d_pts, outputs, 
 
 def ckks_rns_diag_workspace_bytes(n, limbs, batch, count, outputs):
     return int(load_library().fhe_ckks_rns_diag_workspace_bytes(n, limbs, batch, count, outputs))
+
+
+def ckks_rns_lincomb_dev(plans, d_cts, w, k, outputs, d_out, batch, stream=None, limbs=None, count=None):
+    """fhe_ckks_rns_lincomb_dev (DESIGN.md §27): out_o = sum_r w[o][r] ct_r + (k[o], 0) per limb -> [outputs][limbs][2][batch][n];
+    d_cts a list of device pointers, w the canonical residues [outputs][count][limbs] and k [outputs][limbs] (None: no constant)
+    as flat sequences of integers"""
+    cts = None if d_cts is None else (_vp * max(len(d_cts), 1))(*d_cts)
+    ws = None if w is None else (_u64 * max(len(w), 1))(*w)
+    ks = None if k is None else (_u64 * max(len(k), 1))(*k)
+    _check(load_library().fhe_ckks_rns_lincomb_dev(None if plans is None else _plan_array(plans), len(plans) if limbs is None else limbs, cts, len(d_cts) if count is None else count, ws, ks,
+                                                   outputs, d_out, batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

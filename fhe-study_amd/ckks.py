@@ -509,6 +509,267 @@ class RnsCiphertext:
                 plan.pointwise_mul_dev(self.d[i, c].data_ptr(), pt[i].data_ptr(), out[i, c].data_ptr(), self.batch)
         return RnsCiphertext(self.param, out, self.level, self.scale * float(scale))
 
+    # ---- polynomial evaluation ----
+    def mul_const(self, c, scale=None):
+        """c times this ciphertext for a public real c, as lincomb([self], [c], scale=scale): with scale=None the weight is
+        round(c), so pass the target scale (scale * q_level, then rescale()) for a c that is no integer"""
+        return lincomb([self], [c], scale=scale)[0]
+
+    def add_const(self, c):
+        """this ciphertext plus the public real c in every slot: round(c * scale) added to component 0, level and scale unchanged"""
+        return lincomb([self], [1], consts=[c])[0]
+
+    def __neg__(self):
+        return lincomb([self], [-1])[0]
+
+    def eval_chebyshev(self, plan_or_coeffs, rlk, interval=(-1, 1)):
+        """sum_i coeffs[i] T_i(y) of every slot x, y = (2x - a - b)/(b - a): a ChebyshevPlan, or Chebyshev coefficients from which
+        one is built.  Consumes plan.levels levels; the result has this ciphertext's scale (up to float rounding).  A
+        ciphertext with fewer levels is refused before anything runs."""
+        plan = plan_or_coeffs if isinstance(plan_or_coeffs, ChebyshevPlan) else ChebyshevPlan.build(plan_or_coeffs, interval)
+        return plan.run(self, rlk)
+
+
+def _real(x, what):
+    if np.iscomplexobj(np.asarray(x)):
+        raise ValueError(f"lincomb: {what} must be real: a complex constant is no constant polynomial (i is X^(n/2) in the ring, not a scalar)")
+    x = np.asarray(x, dtype=np.float64)
+    if not np.all(np.isfinite(x)):
+        raise ValueError(f"lincomb: {what} must be finite")
+    return x
+
+
+def lincomb(cts, coeffs, consts=None, scale=None, level=None):
+    """-> [sum_r coeffs[o][r] cts[r] + consts[o] for each output o] from fhe_ckks_rns_lincomb_dev: every input is read once for
+    up to four outputs, nothing is transformed and no level is used.  coeffs real [outputs][count] (1-D: one output), consts
+    real [outputs] or None.  The level is the minimum over the inputs (or `level`, not above it: dropping limbs is truncation).
+    scale is the target scale S of every output (or one per output, [outputs]): input r takes the integer weight round(coeffs[o][r] S / cts[r].scale), reduced
+    per limb, and the constant is round(consts[o] S).  scale=None: S is the largest input scale, so an input at that scale takes
+    round(coeff): integers are exact and anything else is the caller's business, who passes S = s q_level and rescales (one
+    level) for real coefficients.  lincomb([P, T], [2, -1], scale=P.scale) on an unrescaled product P costs no level."""
+    cts = list(cts)
+    if not cts:
+        raise ValueError("lincomb: no input")
+    a = _real(coeffs, "a coefficient")
+    if a.ndim == 1:
+        a = a[None]
+    if a.ndim != 2 or a.shape[1] != len(cts) or a.shape[0] < 1:
+        raise ValueError("lincomb: coeffs must be [outputs][len(cts)]")
+    outputs = a.shape[0]
+    k = None if consts is None else _real(consts, "a constant").reshape(-1)
+    if k is not None and k.shape[0] != outputs:
+        raise ValueError("lincomb: consts must be [outputs]")
+    param, batch = cts[0].param, cts[0].batch
+    if any(ct.param != param or ct.batch != batch for ct in cts):
+        raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "lincomb: operands differ in RnsParam or batch")
+    top = min(ct.level for ct in cts)
+    level = top if level is None else int(level)
+    if not 0 <= level <= top:
+        raise ValueError(f"lincomb: level {level} is not in [0, {top}]")
+    S = np.broadcast_to(np.asarray(max(ct.scale for ct in cts) if scale is None else scale, dtype=np.float64), (outputs,)).tolist()
+    if not all(np.isfinite(x) and x > 0 for x in S):
+        raise ValueError("lincomb: the target scale must be positive and finite")
+    mods = param.moduli[:level + 1]
+    w = [[round(float(a[o, r]) * S[o] / ct.scale) for r, ct in enumerate(cts)] for o in range(outputs)]
+    kk = None if k is None else [round(float(c) * S[o]) for o, c in enumerate(k)]
+    torch = _torch()
+    out = torch.empty((outputs, level + 1, 2, batch, param.n), dtype=torch.int64, device="cuda")
+    cap = binding.FHE_CKKS_LINCOMB_MAX_OUTPUTS
+    for o0 in range(0, outputs, cap):
+        o1 = min(outputs, o0 + cap)
+        binding.ckks_rns_lincomb_dev(param.plans(level), [ct.d.data_ptr() for ct in cts], [x % q for row in w[o0:o1] for x in row for q in mods],
+                                     None if kk is None else [x % q for x in kk[o0:o1] for q in mods], o1 - o0, out[o0].data_ptr(), batch)
+    return [RnsCiphertext(param, out[o], level, S[o]) for o in range(outputs)]
+
+
+def chebyshev_fit(f, degree, interval=(-1, 1)):
+    """the Chebyshev coefficients c_0 .. c_degree of the interpolant of f at the degree + 1 Chebyshev nodes of `interval`:
+    f(x) ~ sum_i c_i T_i((2x - a - b)/(b - a))"""
+    a, b = float(interval[0]), float(interval[1])
+    N = int(degree) + 1
+    t = np.cos(np.pi * (np.arange(N) + 0.5) / N)
+    fx = np.asarray(f((b - a) / 2 * t + (a + b) / 2), dtype=np.float64)
+    c = np.array([2.0 / N * np.sum(fx * np.cos(np.pi * i * (np.arange(N) + 0.5) / N)) for i in range(N)])
+    c[0] /= 2
+    return c
+
+
+class ChebyshevPlan:
+    """sum_i coeffs[i] T_i(y), y = (2x - a - b)/(b - a), as a straight-line program: Paterson-Stockmeyer in the
+    Chebyshev basis.  d = deg, m = ceil(log2(d + 1)), n1 = 2^ceil(m/2); babies T_1 .. T_(n1-1), giants T_(n1 2^t) <= d, all from
+    T_(a+b) = 2 T_a T_b - T_(a-b); p = q T_g + r (chebdiv) with g the largest giant <= deg p; a leaf is a lincomb over the babies.
+
+    ops, in order, each writing the wires `out`:
+        ("lincomb", out [ids], inputs [ids], coeffs [outputs][count], consts [outputs] or None, scales [outputs], drop)
+        ("mul", out, a, b)      ("rescale", out, a)
+    wire 0 is the input.  A wire has a drop (levels below the input's) and a symbolic scale (p, e): s^p prod_j q_(l-j)^e[j], s and l
+    the input's scale and level; scale_value() evaluates it.  A lincomb's `scales` are its outputs' targets as such pairs, `drop`
+    its level.  All leaves of one level are the outputs of one lincomb: the babies are read once for them.
+    Every sum of two wires is one lincomb whose target is the symbolic scale of the unrescaled product in it, and the targets
+    are handed down the tree so that q T_g lands on r's scale: the weights of such a sum are 1 (or 2 and s_a s_b / s_c)."""
+
+    def __init__(self, coeffs, interval, ops, drop, scale, result, levels, products, n1, babies, giants):
+        self.coeffs, self.interval, self.ops, self.drop, self.scale, self.result = coeffs, interval, ops, drop, scale, result
+        self.levels, self.products, self.n1, self.babies, self.giants = levels, products, n1, babies, giants
+
+    @staticmethod
+    def scale_value(sym, s, mods, level):
+        """s^p prod_j q_(level-j)^e[j] in float64, the factors taken in this order"""
+        p, e = sym
+        v = 1.0
+        for _ in range(abs(p)):
+            v = v * s if p > 0 else v / s
+        for j, x in enumerate(e):
+            for _ in range(abs(x)):
+                v = v * mods[level - j] if x > 0 else v / mods[level - j]
+        return v
+
+    @classmethod
+    def build(cls, coeffs, interval=(-1, 1)):
+        from numpy.polynomial import chebyshev as Ch
+
+        c = np.trim_zeros(_real(coeffs, "a Chebyshev coefficient").reshape(-1), "b")
+        lo, hi = float(interval[0]), float(interval[1])
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise ValueError("ChebyshevPlan: the interval must be finite with a < b")
+        if len(c) < 2:
+            raise ValueError("ChebyshevPlan: the degree must be at least 1")
+        d = len(c) - 1
+        m = int(d).bit_length()                                   # ceil(log2(d + 1))
+        n1 = 1 << ((m + 1) // 2)
+        if n1 - 1 > binding.FHE_CKKS_LINCOMB_MAX_COUNT:
+            raise ValueError(f"ChebyshevPlan: degree {d} needs {n1 - 1} baby steps, more than one lincomb takes")
+        ops, drop, scale = [], {0: 0}, {0: (1, ())}
+
+        def new(dr, sc):
+            w = len(drop)
+            drop[w], scale[w] = dr, sc
+            return w
+
+        def smul(x, y):
+            n = max(len(x[1]), len(y[1]))
+            return (x[0] + y[0], tuple((x[1] + (0,) * n)[j] + (y[1] + (0,) * n)[j] for j in range(n)))
+
+        def sq(j, e=1):                                           # q_(l-j)^e
+            return (0, (0,) * j + (e,))
+
+        def sinv(x):
+            return (-x[0], tuple(-v for v in x[1]))
+
+        def norm(x):
+            e = list(x[1])
+            while e and e[-1] == 0:
+                e.pop()
+            return (x[0], tuple(e))
+
+        def lin(inputs, co, consts, scs, dr):
+            scs = [norm(sc) for sc in (scs if isinstance(scs, list) else [scs])]
+            outs = [new(dr, sc) for sc in scs]
+            ops.append(("lincomb", outs, list(inputs), [list(map(float, row)) for row in co], None if consts is None else list(map(float, consts)), scs, dr))
+            return outs
+
+        def mul(a, b):
+            w = new(max(drop[a], drop[b]), norm(smul(scale[a], scale[b])))
+            ops.append(("mul", w, a, b))
+            return w
+
+        def rescale(a):
+            w = new(drop[a] + 1, norm(smul(scale[a], sq(drop[a], -1))))
+            ops.append(("rescale", w, a))
+            return w
+
+        T = {1: 0}
+        if (lo, hi) != (-1.0, 1.0):                               # y = (2x - a - b)/(b - a): one lincomb, one rescale
+            T[1] = rescale(lin([0], [[2.0 / (hi - lo)]], [-(lo + hi) / (hi - lo)], smul(scale[0], sq(0)), 0)[0])
+
+        def cheb(i):                                              # T_i = 2 T_a T_b - T_(a-b), a = ceil(i/2), b = floor(i/2)
+            if i not in T:
+                a, b = (i + 1) // 2, i // 2
+                P = mul(cheb(a), cheb(b))
+                if a == b:
+                    T[i] = rescale(lin([P], [[2.0]], [-1.0], scale[P], drop[P])[0])
+                else:
+                    T[i] = rescale(lin([P, cheb(1)], [[2.0, -1.0]], None, scale[P], drop[P])[0])
+            return T[i]
+
+        babies = list(range(1, n1))
+        giants = [n1 << t for t in range(m) if (n1 << t) <= d]
+        for i in babies + giants:
+            cheb(i)
+
+        # the tree: a node is (poly, drop D of its unrescaled value); need(p) is the least D
+        def split(p):
+            g = max(x for x in giants if x <= len(p) - 1)
+            q, r = Ch.chebdiv(p, [0.0] * g + [1.0])
+            return g, np.atleast_1d(q), np.atleast_1d(r)
+
+        def need(p):
+            if len(p) - 1 < n1:
+                return drop[T[max(len(p) - 1, 1)]]
+            g, q, r = split(p)
+            return max(need(q) + 1, drop[T[g]], need(r))
+
+        leaves = {}                                               # drop -> [(poly, target, holder)]
+
+        def plant(p, D, S):
+            """-> a thunk that emits the ops of the unrescaled value of p at drop D with scale S and returns its wire"""
+            if len(p) - 1 < n1:
+                holder = {}
+                leaves.setdefault(D, []).append((p, S, holder))
+                return lambda: holder["wire"]
+            g, q, r = split(p)
+            Sq = smul(smul(S, sinv(scale[T[g]])), sq(D - 1))      # so that rescale(q) T_g has scale S
+            tq, tr = plant(q, D - 1, Sq), plant(r, D, S)
+
+            def emit():
+                P = mul(rescale(tq()), T[g])
+                return lin([P, tr()], [[1.0, 1.0]], None, S, D)[0]
+            return emit
+
+        D = need(c)
+        top = plant(c, D, smul(scale[0], sq(D)))                  # the result has the input's scale
+        cap = binding.FHE_CKKS_LINCOMB_MAX_OUTPUTS
+        for dr in sorted(leaves):                                 # all leaves of one level: one multi-output lincomb, each its own target
+            ins = [i for i in babies if drop[T[i]] <= dr] or [1]
+            for g0 in range(0, len(leaves[dr]), cap):
+                group = leaves[dr][g0:g0 + cap]
+                co = [[float(p[i]) if i < len(p) else 0.0 for i in ins] for p, _, _ in group]
+                for (_, _, holder), w in zip(group, lin([T[i] for i in ins], co, [float(p[0]) for p, _, _ in group], [sc for _, sc, _ in group], dr)):
+                    holder["wire"] = w
+        result = rescale(top())
+        products = sum(1 for op in ops if op[0] == "mul")
+        return cls(c, (lo, hi), ops, drop, scale, result, drop[result], products, n1, babies, giants)
+
+    def simulate(self, x):
+        """the program on plain floats: every wire is its slot value, lincomb is the real sum (the scales do not enter)"""
+        v = {0: np.asarray(x, dtype=np.float64)}
+        for op in self.ops:
+            if op[0] == "lincomb":
+                _, outs, ins, co, consts, _, _ = op
+                for o, w in enumerate(outs):
+                    v[w] = sum(co[o][r] * v[i] for r, i in enumerate(ins)) + (0.0 if consts is None else consts[o])
+            elif op[0] == "mul":
+                v[op[1]] = v[op[2]] * v[op[3]]
+            else:
+                v[op[1]] = v[op[2]]
+        return v[self.result]
+
+    def run(self, ct, rlk):
+        if ct.level < self.levels:
+            raise ValueError(f"eval_chebyshev: the plan needs {self.levels} levels, the ciphertext has {ct.level}")
+        mods = ct.param.moduli
+        w = {0: ct}
+        for op in self.ops:
+            if op[0] == "lincomb":
+                _, outs, ins, co, consts, sc, dr = op
+                res = lincomb([w[i] for i in ins], co, consts, scale=[self.scale_value(x, ct.scale, mods, ct.level) for x in sc], level=ct.level - dr)
+                w.update(zip(outs, res))
+            elif op[0] == "mul":
+                w[op[1]] = w[op[2]].mul(w[op[3]], rlk)
+            else:
+                w[op[1]] = w[op[2]].rescale()
+        return w[self.result]
+
 
 class RnsClientKey(ClientKeyBase):
     """The CKKS secret under every prime of an RnsParam: the same ternary row (KEY row 0) as residues and evals per limb, the

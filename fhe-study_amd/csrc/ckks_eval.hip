@@ -238,6 +238,54 @@ __global__ __launch_bounds__(256) void ckks_rns_diagmac_kernel(const u64 *__rest
     }
 }
 
+// ---- polynomial evaluation: fused sums by public scalars ------------------------------------------------------------
+constexpr u32 kLinGroup = 16;      // inputs of one launch, passed by value
+constexpr u32 kLinOutputs = 4;     // outputs whose accumulators one launch keeps in registers: 8 waves a SIMD still (§27)
+
+// The inputs of one launch for one limb.  Indexed by the loop counter, which is uniform: scalar loads from the kernel-argument
+// segment, as DiagGroup.
+struct LinGroup {
+    const u64 *ct[kLinGroup];          // input r's limb: its two components, contiguous, 2 count words
+    u64 w[kLinOutputs][kLinGroup];     // w[o][r] of this limb for the launch's outputs, canonical
+    u64 k[kLinOutputs];                // k[o] of this limb, canonical; not read where CARRY (the first group has added it)
+    u32 count;
+};
+
+// One limb of out_o = sum_r w[o][r] ct_r + (k[o], 0) for NOUT outputs and the inputs of `grp`, over the 2 count words of a limb
+// (component 0 first): out[o out_os + e] (+)= sum_r w[o][r] ct_r[e] + [e < count] k[o].  A constant polynomial has every eval
+// equal to the constant, so k goes to every word of component 0.  Every input word is read once, for all NOUT outputs.
+// CARRY: the sum starts from the canonical words a former group left in `out`; otherwise from the constant.
+// Overflow.  Operands are canonical, so a term is below q^2, and the accumulator starts from a canonical word (the constant or
+// the carried word, below q).  It folds before input r > 0 of the group where r is a multiple of kMacChunk (q < 2^62: a
+// carry-over below 2^62 and eight terms below 2^124, less than 2^127 + 2^62) or of kMacChunk63 (q >= 2^62: a carry-over below
+// 2^63 and two terms below 2^126, less than 2^127 + 2^63); a fold leaves a canonical word.  So any count holds: 64 inputs are
+// four groups, each folded to canonical words before it is stored.
+template <u32 NOUT, bool CARRY>
+__global__ __launch_bounds__(256) void ckks_rns_lincomb_kernel(u64 *__restrict__ out, u64 out_os, u64 count, LinGroup grp, Mod m) {
+    const u64 stride = (u64)gridDim.x * 256;
+    const bool wide = (m.q >> 62) != 0;
+    const u32 chunk = wide ? kMacChunk63 : kMacChunk;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < 2 * count; i += stride) {
+        MacAcc u[NOUT];
+#pragma unroll
+        for (u32 o = 0; o < NOUT; o++) u[o].v = CARRY ? out[o * out_os + i] : (i < count ? grp.k[o] : 0ull);
+        for (u32 r = 0; r < grp.count; r++) {
+            if (r && r % chunk == 0) {
+#pragma unroll
+                for (u32 o = 0; o < NOUT; o++) {
+                    if (wide) u[o].fold63(m);
+                    else u[o].fold(m);
+                }
+            }
+            const u64 x = grp.ct[r][i];
+#pragma unroll
+            for (u32 o = 0; o < NOUT; o++) u[o].mac(grp.w[o][r], x);
+        }
+#pragma unroll
+        for (u32 o = 0; o < NOUT; o++) out[o * out_os + i] = wide ? u[o].fold63(m) : u[o].fold(m);
+    }
+}
+
 // the diagonal term of a switching key, in evals (n = 2^L, c = P mod q_j): pk0 += c s^2 for the relinearisation key, g not
 // read; GALOIS: pk0 += c sigma_g(s)^, the secret's evals gathered by pi_g
 template <bool GALOIS>
@@ -842,4 +890,75 @@ extern "C" int fhe_ckks_rns_diag_sum_dev(const fhe_ntt_plan *const *plans, unsig
     return switch_call(c, batch, switched ? diag_words_per_row(c, outputs) : 0, st, [&](u64 r0, u64 cr, u64 *W, const u64 *pinv) {
         return diag_rows(c, (const u64 *const *)d_gks, gs, count, key_limbs, (const u64 *)d_pts, outputs, switched, pinv, (const u64 *)d_in, (u64 *)d_out, batch, r0, cr, W, st);
     });
+}
+
+// ---- polynomial evaluation: fused sums by public scalars ------------------------------------------------------------
+namespace {
+
+template <class... A>
+int lincomb_launch(unsigned nout, bool carry, int L, hipStream_t st, unsigned grid, A... a) {
+    const char *lab = "ckks_rns_lincomb";
+#define FHE_LIN_CASE(N) \
+    case N: return carry ? launch(lab, L, st, fhe::ckks_rns_lincomb_kernel<N, true>, grid, 256, a...) : launch(lab, L, st, fhe::ckks_rns_lincomb_kernel<N, false>, grid, 256, a...)
+    switch (nout) {
+        FHE_LIN_CASE(1);
+        FHE_LIN_CASE(2);
+        FHE_LIN_CASE(3);
+        FHE_LIN_CASE(4);
+    }
+#undef FHE_LIN_CASE
+    static_assert(fhe::kLinOutputs == 4, "one case per accumulator count");
+    return fhe_fail(FHE_E_INVALID, "ckks_rns_lincomb: %u outputs in one launch", nout);
+}
+
+}  // namespace
+
+extern "C" int fhe_ckks_rns_lincomb_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *const *d_cts, unsigned count, const uint64_t *w,
+                                        const uint64_t *k, unsigned outputs, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_rns_lincomb_dev";
+    Chain c;
+    int rc = check_chain(plans, limbs, nullptr, false, &c, who);
+    if (rc != FHE_OK) return rc;
+    if (count < 1 || count > FHE_CKKS_LINCOMB_MAX_COUNT) return fhe_fail(FHE_E_INVALID, "%s: count=%u must be in [1, %d]", who, count, FHE_CKKS_LINCOMB_MAX_COUNT);
+    if (outputs < 1 || outputs > FHE_CKKS_LINCOMB_MAX_OUTPUTS)
+        return fhe_fail(FHE_E_INVALID, "%s: outputs=%u must be in [1, %d]", who, outputs, FHE_CKKS_LINCOMB_MAX_OUTPUTS);
+    if (!d_cts || !w) return fhe_fail(FHE_E_NULL, "%s: NULL host array", who);
+    for (unsigned o = 0; o < outputs; o++)
+        for (unsigned i = 0; i < c.k; i++) {
+            for (unsigned r = 0; r < count; r++)
+                if (w[((u64)o * count + r) * c.k + i] >= c.p[i]->q) return fhe_fail(FHE_E_INVALID, "%s: weight [%u][%u][%u] is not below its modulus", who, o, r, i);
+            if (k && k[(u64)o * c.k + i] >= c.p[i]->q) return fhe_fail(FHE_E_INVALID, "%s: constant [%u][%u] is not below its modulus", who, o, i);
+        }
+    if (batch == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, 2ull * c.k * n * outputs, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 limb_words = 2ull * batch * n, ct_bytes = c.k * limb_words * 8;
+    for (unsigned r = 0; r < count; r++) {
+        if (!d_cts[r]) return fhe_fail(FHE_E_NULL, "%s: input %u is NULL", who, r);
+        if (misaligned8(d_cts[r])) return fhe_fail(FHE_E_INVALID, "%s: input %u must be 8-byte aligned", who, r);
+        if (overlaps_any(d_out, ct_bytes * outputs, {{d_cts[r], ct_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps input %u", who, r);
+    }
+    int dev;
+    if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    for (unsigned o0 = 0; o0 < outputs; o0 += fhe::kLinOutputs) {
+        const unsigned nout = std::min<unsigned>(fhe::kLinOutputs, outputs - o0);
+        for (unsigned i = 0; i < c.k; i++) {
+            for (unsigned r0 = 0; r0 < count; r0 += fhe::kLinGroup) {
+                fhe::LinGroup grp{};
+                grp.count = std::min<unsigned>(fhe::kLinGroup, count - r0);
+                for (unsigned r = 0; r < grp.count; r++) grp.ct[r] = (const u64 *)d_cts[r0 + r] + i * limb_words;
+                for (unsigned o = 0; o < nout; o++) {
+                    for (unsigned r = 0; r < grp.count; r++) grp.w[o][r] = w[((u64)(o0 + o) * count + r0 + r) * c.k + i];
+                    grp.k[o] = k ? k[(u64)(o0 + o) * c.k + i] : 0;
+                }
+                if ((rc = lincomb_launch(nout, r0 > 0, (int)c.L, st, fhe_ew_grid(limb_words), (u64 *)d_out + ((u64)o0 * c.k + i) * limb_words, c.k * limb_words,
+                                         limb_words / 2, grp, c.p[i]->mod)) != FHE_OK)
+                    return rc;
+            }
+        }
+    }
+    return FHE_OK;
 }

@@ -708,6 +708,25 @@ int fhe_ckks_rns_diag_sum_dev(const fhe_ntt_plan *const *plans, unsigned limbs, 
                               void *hip_stream);
 size_t fhe_ckks_rns_diag_workspace_bytes(uint64_t n, unsigned limbs, size_t batch, unsigned count, unsigned outputs);
 
+/* ---- CKKS on the RNS chain: fused sums of ciphertexts by public scalars (ckks_eval.hip) ----
+ *   fhe_ckks_rns_lincomb_dev      d_out [outputs][limbs][2][batch][n]: per limb i, component c and word e
+ *            out_o[c][e] = (sum_{r < count} w[o][r][i] ct_r[c][e] + [c = 0] k[o][i]) mod q_i.
+ *            d_cts is a HOST array of `count` device pointers to ciphertexts [>= limbs][2][batch][n] (a ciphertext at a
+ *            higher level is read as it is: the limb stride does not depend on the level); a pointer may repeat.  w
+ *            [outputs][count][limbs] and k [outputs][limbs] (NULL: no constant) are HOST arrays of canonical residues,
+ *            consumed before the call returns.  A constant polynomial has every eval equal to the constant, so k is added
+ *            to every word of component 0.  Every input word is read once per launch of up to four outputs; no workspace.
+ *            The level is `limbs - 1`; what the weights do to the scale is the caller's bookkeeping.
+ * FHE_E_NULL for a NULL plan, array or buffer; FHE_E_PARAM_MISMATCH for plans whose n differ; FHE_E_INVALID for limbs not in
+ * [1, 8], repeated moduli, count not in [1, FHE_CKKS_LINCOMB_MAX_COUNT], outputs not in [1, FHE_CKKS_LINCOMB_MAX_OUTPUTS], a
+ * weight or constant that is not below its q_i, and an output that overlaps an input.  Everything is checked before any
+ * device call and nothing is written on rejection; batch = 0 is a no-op. */
+#define FHE_CKKS_LINCOMB_MAX_COUNT 64
+#define FHE_CKKS_LINCOMB_MAX_OUTPUTS 16
+int fhe_ckks_rns_lincomb_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *const *d_cts, unsigned count,
+                             const uint64_t *w, const uint64_t *k, unsigned outputs, void *d_out, size_t batch,
+                             void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
