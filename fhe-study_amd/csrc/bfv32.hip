@@ -18,18 +18,14 @@
 // Arithmetic, rounding and wrap-around semantics are those of zring.hip's epilogues (same device functions); results are
 // bit-exact with them and with the oracle.
 #include "bfv32.hpp"
+#include "host_dispatch.hpp"
+#include "launch.hpp"
 #include "ntt32_big.hpp"
 
 #include <type_traits>
 
 namespace fhe {
 
-// x * y * 2^-32 mod p, in [0, 2p), for x * y < p * 2^32 (Montgomery; the factor is folded into the inverse's scaling)
-__device__ __forceinline__ u32 mont32(u32 x, u32 y, u32 p, u32 pinv_neg) {
-    const u64 t = (u64)x * y;
-    const u32 m = (u32)t * pinv_neg;
-    return (u32)((t + (u64)m * p) >> 32);
-}
 // the two residues (canonical) -> the integer in [0, pA * pB)
 __device__ __forceinline__ u64 crt2(u32 rA, u32 rB, u32 pA, u32 pB, Tw32 crt) {
     const u32 rAb = csub_u32(rA, pB);                           // rA mod pB (pA - pB < pB)
@@ -498,56 +494,43 @@ bool bfv32_shape_supported(uint64_t q, uint64_t n, uint64_t pq) {
     return true;
 }
 
-template <typename K>
-static hipError_t launch_big(K kernel, const char *name, int lp, size_t lds, unsigned th, u64 grid, const Bfv32Args &a, hipStream_t st,
-                             unsigned gridy = 1) {
-    if (grid == 0) return hipSuccess;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-    if (hipError_t e = allow_big_lds((const void *)kernel, lds)) return e;
-    KernelTimer kt(name, lp, st);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid, gridy), dim3(th), lds, st, a);
-    return hipGetLastError();
+// a.log_n2 = log2(2n) in 11 .. 14; the kernels are instantiated on the block size n = 2^LB, LB = log_n2 - 1; kernel(lb): the kernel of
+// that size; tables: local twiddle tiles; parkw: words per thread the kernel would like to park in LDS (0: none) — Blk::LDS_PARKED
+template <typename KF>
+static hipError_t launch_big(KF kernel, const char *name, LaunchGrid grid, int tables, int parkw, int wps, const Bfv32Args &a, hipStream_t st) {
+    return dispatch_int<10, 13>((int)a.log_n2 - 1, hipErrorNotSupported, [&](auto lb) {
+        return launch_kernel(kernel(lb), name, lb + 1, grid, Big32<lb()>::TH, Blk<lb()>::LDS_PARKED(tables, parkw, wps), st, a);
+    });
 }
-// a.log_n2 = log2(2n); the kernels are instantiated on the block size n = 2^(log_n2 - 1); TABLES local twiddle tiles
-// PARKW: words per thread the kernel would like to park in LDS (0: none) — Blk::LDS_PARKED
-#define FHE_BIG_SWITCH(KERNEL, NAME, GRID, GRIDY, TABLES, PARKW, WPS)                                                               \
-    switch (a.log_n2) {                                                                                                      \
-        case 11: return launch_big(KERNEL<10>, NAME, 11, Blk<10>::LDS_PARKED(TABLES, PARKW, WPS), Big32<10>::TH, GRID, a, st, GRIDY); \
-        case 12: return launch_big(KERNEL<11>, NAME, 12, Blk<11>::LDS_PARKED(TABLES, PARKW, WPS), Big32<11>::TH, GRID, a, st, GRIDY); \
-        case 13: return launch_big(KERNEL<12>, NAME, 13, Blk<12>::LDS_PARKED(TABLES, PARKW, WPS), Big32<12>::TH, GRID, a, st, GRIDY); \
-        case 14: return launch_big(KERNEL<13>, NAME, 14, Blk<13>::LDS_PARKED(TABLES, PARKW, WPS), Big32<13>::TH, GRID, a, st, GRIDY); \
-    }                                                                                                                        \
-    return hipErrorNotSupported;
-
-template <int LB> static constexpr auto bfv32_forward2 = bfv32_forward_kernel<LB, 2, true>;
-template <int LB> static constexpr auto bfv32_forward3 = bfv32_forward_kernel<LB, 3, true>;
-template <int LB> static constexpr auto bfv32_forward2b = bfv32_forward_kernel<LB, 2, true, true>;
-template <int LB> static constexpr auto bfv32_forward3b = bfv32_forward_kernel<LB, 3, true, true>;
-template <int LB> static constexpr auto bfv32_forward1w = bfv32_forward_kernel<LB, 1, false>;
+template <int PRIMES, bool WORD32, bool BELOW>
+static hipError_t launch_forward(const char *name, LaunchGrid grid, const Bfv32Args &a, hipStream_t st) {
+    return launch_big([](auto lb) { return bfv32_forward_kernel<lb(), PRIMES, WORD32, BELOW>; }, name, grid, PRIMES, 0, 4, a, st);
+}
 hipError_t launch_bfv32_forward(const Bfv32Args &a, hipStream_t st) {
     const u64 grid = 16 * ((a.rows + 7) / 8);                                                   // (row, block) pairs, 8 rows x 2 blocks per group
-    if (a.primes == 2 && a.word32 && a.below_p) { FHE_BIG_SWITCH(bfv32_forward2b, "bfv32_forward", grid, 1, 2, 0, 4) }
-    if (a.primes == 3 && a.word32 && a.below_p) { FHE_BIG_SWITCH(bfv32_forward3b, "bfv32_forward3", grid, 1, 3, 0, 4) }
-    if (a.primes == 2 && a.word32) { FHE_BIG_SWITCH(bfv32_forward2, "bfv32_forward", grid, 1, 2, 0, 4) }
-    if (a.primes == 3 && a.word32) { FHE_BIG_SWITCH(bfv32_forward3, "bfv32_forward3", grid, 1, 3, 0, 4) }
-    if (a.primes == 3) { FHE_BIG_SWITCH(bfv32_forward1w, "bfv32_forward_key", grid, 3, 1, 0, 4) }      // grid (row-blocks, primes)
+    if (a.primes == 2 && a.word32 && a.below_p) return launch_forward<2, true, true>("bfv32_forward", {grid}, a, st);
+    if (a.primes == 3 && a.word32 && a.below_p) return launch_forward<3, true, true>("bfv32_forward3", {grid}, a, st);
+    if (a.primes == 2 && a.word32) return launch_forward<2, true, false>("bfv32_forward", {grid}, a, st);
+    if (a.primes == 3 && a.word32) return launch_forward<3, true, false>("bfv32_forward3", {grid}, a, st);
+    if (a.primes == 3) return launch_forward<1, false, false>("bfv32_forward_key", {grid, 3}, a, st);      // grid (row-blocks, primes)
     return hipErrorNotSupported;
 }
-template <int LB> static constexpr auto bfv32_tensor_inverse_f64 = bfv32_tensor_inverse_kernel<LB, false, false>;
-template <int LB> static constexpr auto bfv32_tensor_inverse_f64s = bfv32_tensor_inverse_kernel<LB, false, true>;
-template <int LB> static constexpr auto bfv32_tensor_inverse_int = bfv32_tensor_inverse_kernel<LB, true, false>;
+template <bool INT_NUM, bool SMALL>
+static hipError_t launch_tensor_inverse(const Bfv32Args &a, hipStream_t st) {
+    return launch_big([](auto lb) { return bfv32_tensor_inverse_kernel<lb(), INT_NUM, SMALL>; }, "bfv32_tensor_inverse", {24 * ((a.batch + 7) / 8)}, 4, 0, 4, a, st);
+}
 hipError_t launch_bfv32_tensor_inverse(const Bfv32Args &a, hipStream_t st) {
-    if (a.int_num) { FHE_BIG_SWITCH(bfv32_tensor_inverse_int, "bfv32_tensor_inverse", 24 * ((a.batch + 7) / 8), 1, 4, 0, 4) }
-    if (a.small_f64) { FHE_BIG_SWITCH(bfv32_tensor_inverse_f64s, "bfv32_tensor_inverse", 24 * ((a.batch + 7) / 8), 1, 4, 0, 4) }
-    FHE_BIG_SWITCH(bfv32_tensor_inverse_f64, "bfv32_tensor_inverse", 24 * ((a.batch + 7) / 8), 1, 4, 0, 4)
+    if (a.int_num) return launch_tensor_inverse<true, false>(a, st);
+    return a.small_f64 ? launch_tensor_inverse<false, true>(a, st) : launch_tensor_inverse<false, false>(a, st);
 }
-template <int LB> static constexpr auto bfv32_relin_inverse_gen = bfv32_relin_inverse_kernel<LB, false>;
-template <int LB> static constexpr auto bfv32_relin_inverse_small = bfv32_relin_inverse_kernel<LB, true>;
+template <bool SMALL>
+static hipError_t launch_relin_inverse(const Bfv32Args &a, hipStream_t st) {
+    return launch_big([](auto lb) { return bfv32_relin_inverse_kernel<lb(), SMALL>; }, "bfv32_relin_inverse", {16 * ((a.batch + 7) / 8)}, 6,
+                      FHE_B32_PARK_LDS ? 16 : 0, kRelinWps, a, st);
+}
 hipError_t launch_bfv32_relin_inverse(const Bfv32Args &a, hipStream_t st) {
-    if (a.small_f64) { FHE_BIG_SWITCH(bfv32_relin_inverse_small, "bfv32_relin_inverse", 16 * ((a.batch + 7) / 8), 1, 6, (FHE_B32_PARK_LDS ? 16 : 0), kRelinWps) }
-    FHE_BIG_SWITCH(bfv32_relin_inverse_gen, "bfv32_relin_inverse", 16 * ((a.batch + 7) / 8), 1, 6, (FHE_B32_PARK_LDS ? 16 : 0), kRelinWps)
+    return a.small_f64 ? launch_relin_inverse<true>(a, st) : launch_relin_inverse<false>(a, st);
 }
-#undef FHE_BIG_SWITCH
 
 // timing-only builds (tools/abl_build.sh) produce wrong words by design: fhe_ntt_version() says so (capi.hip)
 bool bfv32_ablated() {

@@ -19,6 +19,7 @@
 #include "../../include/fhe_ntt.h"
 #include "../../include/fhe_ntt_experimental.h"   // the persistent kernels' switches: exported, outside the boundary
 #include "host_tables.hpp"
+#include "launch.hpp"
 #include "ntt_kernels.hpp"
 
 constexpr int kMaxDevices = 16;
@@ -142,11 +143,7 @@ P kernel_arg(A a) {
 // one timed launch (tag L for the timer) and its check: the FHE_* code.  A launch error names kernel_name, <label>_kernel if NULL.
 template <class... P, class... A>
 int launch_named(const char *label, const char *kernel_name, int L, hipStream_t st, void (*kernel)(P...), unsigned grid, unsigned block, A... args) {
-    {
-        fhe::KernelTimer kt_(label, L, st);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, kernel_arg<P>(args)...);
-    }
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = fhe::launch_grid(kernel, label, L, dim3(grid), block, 0, st, kernel_arg<P>(args)...);
     if (e == hipSuccess) return FHE_OK;
     char name[64];
     snprintf(name, sizeof name, "%s_kernel", label);

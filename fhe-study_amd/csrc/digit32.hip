@@ -22,6 +22,8 @@
 //                          modulo q and (0, b) - rhs (key switching)
 // Index algebra, register windows and LDS exchanges are those of ntt_rounds.hpp (ContigCfg, field_of, pad16).
 #include "digit32.hpp"
+#include "host_dispatch.hpp"
+#include "launch.hpp"
 #include "ntt32_rounds.hpp"
 
 namespace fhe {
@@ -59,25 +61,6 @@ __device__ __forceinline__ void fwd_rounds32(u32 (&v)[16], u32 *lds, const Tw32 
 // The same for BOTH primes in lockstep (va modulo p[0] through tile / table 0, vb modulo p[1] through 1): one pair of
 // barriers per exchange instead of two and twice the independent work between barriers; butterflies WITHOUT conditional
 // subtractions (ct32_loose) — the values end below (1 + 2 LP) p <= 25 p < 2^32.
-template <int LP, int AF, int AT, bool FIRST>
-__device__ __forceinline__ void exchange32x2(u32 (&va)[16], u32 (&vb)[16], u32 *la, u32 *lb, u32 w, u32 tf) {
-    constexpr int M = 1 << LP;
-    const u32 bf = pad16(w * M + field_of<AF>(tf, 0)), bt = pad16(w * M + field_of<AT>(tf, 0));   // + a constant per register (ntt_rounds.hpp: pad16_koff)
-    if (!FIRST) __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const u32 s = bf + pad16_koff<AF>(k);
-        la[s] = va[k];
-        lb[s] = vb[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const u32 s = bt + pad16_koff<AT>(k);
-        va[k] = la[s];
-        vb[k] = lb[s];
-    }
-}
 // BITS: round 0 on bits by look-up (va = vb); otherwise on canonical residues (the gadget's signed digits, va != vb)
 template <int LP, bool FRESH, bool BITS = true>
 __device__ __forceinline__ void fwd_rounds32x2(u32 (&va)[16], u32 (&vb)[16], u32 *const (&tile)[2], const Tw32 *const (&ltw)[2],
@@ -128,16 +111,6 @@ __device__ __forceinline__ void inv_rounds32(u32 (&v)[16], u32 *lds, const Tw32 
     round_inv32<C::R0>(v, TW(C::in_lds(0)), 1u, p, p2);
 }
 
-// Shapes of the transform kernels (key preparation, tails): ContigCfg's — 256 threads, W = 4096 / n units side by side.
-template <int LP>
-struct Cfg32 {
-    using C = ContigCfg<LP>;
-    static constexpr int M = C::M, TPB = C::TPB, W = C::W, TH = 256, PPT = M / TH;
-    static constexpr size_t TILE_BYTES = (size_t)(W * M + W * M / 16) * 4;          // one padded tile of u32
-    static constexpr size_t TW_BYTES = (size_t)C::LTW_N * sizeof(Tw32);
-    static constexpr size_t LUT_BYTES = (size_t)kLut32Words * 4;
-    static_assert(LP >= 8 && LP <= 12, "n = 256 .. 4096");
-};
 // Shape of the fused digit kernel: TH threads transform W = 16 TH / n digits side by side, then multiply at
 // PPT = n / TH positions per thread into 2 (primes) * NC * PPT 64-bit accumulators.  With NC = 4 that is 32 accumulators
 // up to n = 1024 — room for both primes' coefficients, so their transforms run in lockstep (LOCK) — and 64 beyond, where
@@ -568,15 +541,8 @@ __global__ __launch_bounds__(256) void digit_tail32_kernel(Ext32Args a) {
 // ---- launchers ----------------------------------------------------------------------------------------------------
 template <int LP>
 static hipError_t launch_key32_lp(const Ext32Args &a, hipStream_t st, unsigned keys = 1) {
-    using C = ContigCfg<LP>;
     using K = Cfg32<LP>;
-    constexpr size_t lds = K::TILE_BYTES + K::TW_BYTES;
-    const u64 grid = (a.rows + C::W - 1) / C::W;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-    if (hipError_t e = allow_big_lds((const void *)ntt32_fwd_key_kernel<LP>, lds)) return e;
-    KernelTimer kt("ntt32_fwd_key", LP, st);
-    hipLaunchKernelGGL((ntt32_fwd_key_kernel<LP>), dim3((unsigned)grid, 2, keys), dim3(256), lds, st, a);
-    return hipGetLastError();
+    return launch_kernel(ntt32_fwd_key_kernel<LP>, "ntt32_fwd_key", LP, {(a.rows + K::W - 1) / K::W, 2, keys}, 256, K::TILE_BYTES + K::TW_BYTES, st, a);
 }
 // `keys` TGGSWs (a bootstrapping key): gridDim.z <= 65535 keys per launch
 template <int LP>
@@ -593,25 +559,17 @@ static hipError_t launch_key32_many_lp(const Ext32Args &a0, hipStream_t st, u64 
 template <int LP, int SRC>
 static hipError_t launch_mac32_lp(const Ext32Args &a, hipStream_t st) {
     using K = Mac32Cfg<LP>;
-    const u64 grid = a.batch * a.parts;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-    if (hipError_t e = allow_big_lds((const void *)digit_mac32_kernel<LP, 4, SRC>, K::LDS_BYTES)) return e;
-    KernelTimer kt(SRC == SRC32_CMUX ? "digit_mac32_cmux" : SRC == SRC32_GADGET ? "digit_mac32_gadget" : SRC == SRC32_GCMUX ? "digit_mac32_gcmux"
-                   : SRC == SRC32_GSEL ? "digit_mac32_gsel" : "digit_mac32", LP, st);
-    hipLaunchKernelGGL((digit_mac32_kernel<LP, 4, SRC>), dim3((unsigned)grid, K::ONEP ? 2u : 1u), dim3(K::TH), K::LDS_BYTES, st, a);
-    return hipGetLastError();
+    return launch_kernel(digit_mac32_kernel<LP, 4, SRC>,
+                         SRC == SRC32_CMUX ? "digit_mac32_cmux" : SRC == SRC32_GADGET ? "digit_mac32_gadget" : SRC == SRC32_GCMUX ? "digit_mac32_gcmux"
+                         : SRC == SRC32_GSEL ? "digit_mac32_gsel" : "digit_mac32",
+                         LP, {a.batch * a.parts, K::ONEP ? 2u : 1u}, K::TH, K::LDS_BYTES, st, a);
 }
 template <int LP, int EPI>
 static hipError_t launch_tail32_lp(const Ext32Args &a, hipStream_t st) {
-    using C = ContigCfg<LP>;
     using K = Cfg32<LP>;
-    constexpr size_t lds = K::TILE_BYTES + 2 * K::TW_BYTES;
-    const u64 grid = (a.batch * (a.k + 1) + C::W - 1) / C::W;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-    if (hipError_t e = allow_big_lds((const void *)digit_tail32_kernel<LP, EPI>, lds)) return e;
-    KernelTimer kt(EPI == EPI32_KS ? "digit_tail32_ks" : EPI == EPI32_CMUX ? "digit_tail32_cmux" : EPI == EPI32_SEL ? "digit_tail32_sel" : "digit_tail32", LP, st);
-    hipLaunchKernelGGL((digit_tail32_kernel<LP, EPI>), dim3((unsigned)grid), dim3(256), lds, st, a);
-    return hipGetLastError();
+    return launch_kernel(digit_tail32_kernel<LP, EPI>,
+                         EPI == EPI32_KS ? "digit_tail32_ks" : EPI == EPI32_CMUX ? "digit_tail32_cmux" : EPI == EPI32_SEL ? "digit_tail32_sel" : "digit_tail32", LP,
+                         {(a.batch * (a.k + 1) + K::W - 1) / K::W}, 256, K::TILE_BYTES + 2 * K::TW_BYTES, st, a);
 }
 
 // TGGSW x TGLWE: k = 1, 2^8 <= n <= 2^12
@@ -657,42 +615,36 @@ void ext32_gadget_split(u64 n, u64 batch, uint32_t T, uint32_t *parts, uint32_t 
     *tpp = per * W;
 }
 
-#define FHE_LP_SWITCH(FN, ...)                                        \
-    switch (log_n) {                                                  \
-        case 8: return FN<8 __VA_ARGS__>(a, st);                      \
-        case 9: return FN<9 __VA_ARGS__>(a, st);                      \
-        case 10: return FN<10 __VA_ARGS__>(a, st);                    \
-        case 11: return FN<11 __VA_ARGS__>(a, st);                    \
-        case 12: return FN<12 __VA_ARGS__>(a, st);                    \
-    }                                                                 \
-    return hipErrorNotSupported;
-#define FHE_COMMA ,
-hipError_t launch_ext32_key(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_key32_lp) }
+// log_n in 8 .. 12 as the LP of f
+template <class F>
+static hipError_t ext32_size(int log_n, F &&f) { return dispatch_int<8, 12>(log_n, hipErrorNotSupported, f); }
+template <int SRC>
+static hipError_t launch_mac32(const Ext32Args &a, int log_n, hipStream_t st) {
+    return ext32_size(log_n, [&](auto lp) { return launch_mac32_lp<lp(), SRC>(a, st); });
+}
+template <int EPI>
+static hipError_t launch_tail32(const Ext32Args &a, int log_n, hipStream_t st) {
+    return ext32_size(log_n, [&](auto lp) { return launch_tail32_lp<lp(), EPI>(a, st); });
+}
+hipError_t launch_ext32_key(const Ext32Args &a, int log_n, hipStream_t st) {
+    return ext32_size(log_n, [&](auto lp) { return launch_key32_lp<lp()>(a, st); });
+}
 hipError_t launch_ext32_key_many(const Ext32Args &a, int log_n, u64 keys, hipStream_t st) {
-    switch (log_n) {
-        case 8: return launch_key32_many_lp<8>(a, st, keys);
-        case 9: return launch_key32_many_lp<9>(a, st, keys);
-        case 10: return launch_key32_many_lp<10>(a, st, keys);
-        case 11: return launch_key32_many_lp<11>(a, st, keys);
-        case 12: return launch_key32_many_lp<12>(a, st, keys);
-    }
-    return hipErrorNotSupported;
+    return ext32_size(log_n, [&](auto lp) { return launch_key32_many_lp<lp()>(a, st, keys); });
 }
 hipError_t launch_ext32_mac(const Ext32Args &a, int log_n, int src_kind, hipStream_t st) {
-    if (src_kind == SRC_DIGITS) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC_DIGITS) }
-    if (src_kind == SRC_ZQBITS) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC_ZQBITS) }
-    if (src_kind == SRC32_CMUX) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_CMUX) }
-    if (src_kind == SRC32_GADGET) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_GADGET) }
-    if (src_kind == SRC32_GCMUX) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_GCMUX) }
-    if (src_kind == SRC32_GSEL) { FHE_LP_SWITCH(launch_mac32_lp, FHE_COMMA SRC32_GSEL) }
+    if (src_kind == SRC_DIGITS) return launch_mac32<SRC_DIGITS>(a, log_n, st);
+    if (src_kind == SRC_ZQBITS) return launch_mac32<SRC_ZQBITS>(a, log_n, st);
+    if (src_kind == SRC32_CMUX) return launch_mac32<SRC32_CMUX>(a, log_n, st);
+    if (src_kind == SRC32_GADGET) return launch_mac32<SRC32_GADGET>(a, log_n, st);
+    if (src_kind == SRC32_GCMUX) return launch_mac32<SRC32_GCMUX>(a, log_n, st);
+    if (src_kind == SRC32_GSEL) return launch_mac32<SRC32_GSEL>(a, log_n, st);
     return hipErrorNotSupported;
 }
-hipError_t launch_ext32_tail_cmux(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_CMUX) }
-hipError_t launch_ext32_tail(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_TORUS) }
-hipError_t launch_ext32_tail_ks(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_KS) }
-hipError_t launch_ext32_tail_sel(const Ext32Args &a, int log_n, hipStream_t st) { FHE_LP_SWITCH(launch_tail32_lp, FHE_COMMA EPI32_SEL) }
-#undef FHE_LP_SWITCH
-#undef FHE_COMMA
+hipError_t launch_ext32_tail_cmux(const Ext32Args &a, int log_n, hipStream_t st) { return launch_tail32<EPI32_CMUX>(a, log_n, st); }
+hipError_t launch_ext32_tail(const Ext32Args &a, int log_n, hipStream_t st) { return launch_tail32<EPI32_TORUS>(a, log_n, st); }
+hipError_t launch_ext32_tail_ks(const Ext32Args &a, int log_n, hipStream_t st) { return launch_tail32<EPI32_KS>(a, log_n, st); }
+hipError_t launch_ext32_tail_sel(const Ext32Args &a, int log_n, hipStream_t st) { return launch_tail32<EPI32_SEL>(a, log_n, st); }
 
 // timing-only builds (tools/abl_build.sh) produce wrong words by design: fhe_ntt_version() says so (capi.hip)
 bool digit32_ablated() {

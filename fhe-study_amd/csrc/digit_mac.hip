@@ -29,6 +29,8 @@
 // (sum_parts_kernel below) before the inverse transforms.  HBM traffic per external product at
 // n = 1024: 16 KiB in + 128 KiB of partial sums, against 2 MiB for the materialised transforms.
 #include "digit_mac.hpp"
+#include "host_dispatch.hpp"
+#include "launch.hpp"
 #include "ntt_rounds.hpp"
 
 #include <cstdlib>
@@ -270,28 +272,15 @@ static inline unsigned dm_ew_grid(u64 count) {
 template <int LP, int SRC, int NC>
 static hipError_t launch_dm(const DigitMacArgs &a, hipStream_t st) {
     using K = DigitMacCfg<LP, NC>;
-    if constexpr (K::ACC > K::MAX_ACC) {
+    if constexpr (K::ACC > K::MAX_ACC)
         return hipErrorNotSupported;
-    } else {
-        const u64 grid = a.batch * a.parts;
-        if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-        if (hipError_t e = allow_big_lds((const void *)digit_mac_kernel<LP, SRC, NC>, K::LDS_BYTES)) return e;
-        KernelTimer kt(SRC == SRC_DIGITS ? "digit_mac_torus" : "digit_mac_zq", LP, st);
-        hipLaunchKernelGGL((digit_mac_kernel<LP, SRC, NC>), dim3((unsigned)grid), dim3(K::TH), K::LDS_BYTES, st, a);
-        return hipGetLastError();
-    }
+    else
+        return launch_kernel(digit_mac_kernel<LP, SRC, NC>, SRC == SRC_DIGITS ? "digit_mac_torus" : "digit_mac_zq", LP, {a.batch * a.parts}, K::TH, K::LDS_BYTES, st, a);
 }
 
 template <int SRC, int NC>
 static hipError_t launch_dm_lp(int lp, const DigitMacArgs &a, hipStream_t st) {
-    switch (lp) {
-        case 8: return launch_dm<8, SRC, NC>(a, st);
-        case 9: return launch_dm<9, SRC, NC>(a, st);
-        case 10: return launch_dm<10, SRC, NC>(a, st);
-        case 11: return launch_dm<11, SRC, NC>(a, st);
-        case 12: return launch_dm<12, SRC, NC>(a, st);
-    }
-    return hipErrorNotSupported;
+    return dispatch_int<8, 12>(lp, hipErrorNotSupported, [&](auto LP) { return launch_dm<LP(), SRC, NC>(a, st); });
 }
 
 // units per step of the kernel that (log_n, nc) selects; 0: no fused kernel for this shape
@@ -335,23 +324,12 @@ hipError_t launch_digit_mac(const DevicePlan &p, int src_kind, const u64 *src, u
 
 template <int EPI>
 static hipError_t launch_tail_lp(int lp, const DigitTailArgs &a, hipStream_t st) {
-    const u64 rows = a.batch * a.nc;
-    switch (lp) {
-#define X(LP_)                                                                                              \
-    case LP_: {                                                                                             \
-        using C = ContigCfg<LP_>;                                                                           \
-        if (EPI == EPI_TORUS && (C::W % a.nc) != 0) return hipErrorNotSupported;                            \
-        const u64 grid = (rows + C::W - 1) / C::W;                                                          \
-        if (grid > 0x7fffffffull) return hipErrorInvalidValue;                                              \
-        if (hipError_t e = allow_big_lds((const void *)digit_tail_kernel<LP_, EPI>, C::LDS_BYTES)) return e; \
-        KernelTimer kt(EPI == EPI_KS ? "digit_tail_ks" : "digit_tail_torus", LP_, st);                       \
-        hipLaunchKernelGGL((digit_tail_kernel<LP_, EPI>), dim3((unsigned)grid), dim3(256), C::LDS_BYTES, st, a); \
-        return hipGetLastError();                                                                           \
-    }
-        X(8) X(9) X(10) X(11) X(12)
-#undef X
-    }
-    return hipErrorNotSupported;
+    return dispatch_int<8, 12>(lp, hipErrorNotSupported, [&](auto LP) {
+        using C = ContigCfg<LP()>;
+        if (EPI == EPI_TORUS && (C::W % a.nc) != 0) return hipErrorNotSupported;
+        return launch_kernel(digit_tail_kernel<LP(), EPI>, EPI == EPI_KS ? "digit_tail_ks" : "digit_tail_torus", LP, {(a.batch * a.nc + C::W - 1) / C::W}, 256,
+                             C::LDS_BYTES, st, a);
+    });
 }
 
 hipError_t launch_digit_tail_ks(const DevicePlan &p, const u64 *partial, uint32_t parts, uint32_t k, const u64 *glwe, u64 *out,

@@ -257,4 +257,43 @@ __device__ __forceinline__ void stage_tw32(Tw32 *ltw, const Tw32 *__restrict__ t
     for (u32 i = tid; i < (u32)count; i += TH) ltw[i] = tw[i];   // s0 = blk = 0: the local table is the head of the global one
 }
 
+// two polynomials (or one modulo two primes) through two tiles with one pair of barriers
+template <int LP, int AF, int AT, bool FIRST>
+__device__ __forceinline__ void exchange32x2(u32 (&va)[16], u32 (&vb)[16], u32 *la, u32 *lb, u32 w, u32 tf) {
+    constexpr int M = 1 << LP;
+    const u32 bf = pad16(w * M + field_of<AF>(tf, 0)), bt = pad16(w * M + field_of<AT>(tf, 0));   // + a constant per register (ntt_rounds.hpp: pad16_koff)
+    if (!FIRST) __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const u32 s = bf + pad16_koff<AF>(k);
+        la[s] = va[k];
+        lb[s] = vb[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const u32 s = bt + pad16_koff<AT>(k);
+        va[k] = la[s];
+        vb[k] = lb[s];
+    }
+}
+
+// x * y * 2^-32 mod p, in [0, 2p), for x * y < p * 2^32 (Montgomery; the factor is folded into the inverse's scaling)
+__device__ __forceinline__ u32 mont32(u32 x, u32 y, u32 p, u32 pinv_neg) {
+    const u64 t = (u64)x * y;
+    const u32 m = (u32)t * pinv_neg;
+    return (u32)((t + (u64)m * p) >> 32);
+}
+
+// Shapes of the transform kernels (key preparation, tails): ContigCfg's — 256 threads, W = 4096 / n units side by side.
+template <int LP>
+struct Cfg32 {
+    using C = ContigCfg<LP>;
+    static constexpr int M = C::M, TPB = C::TPB, W = C::W, TH = 256, PPT = M / TH;
+    static constexpr size_t TILE_BYTES = (size_t)(W * M + W * M / 16) * 4;          // one padded tile of u32
+    static constexpr size_t TW_BYTES = (size_t)C::LTW_N * sizeof(Tw32);
+    static constexpr size_t LUT_BYTES = (size_t)kLut32Words * 4;
+    static_assert(LP >= 8 && LP <= 12, "n = 256 .. 4096");
+};
+
 }  // namespace fhe

@@ -23,6 +23,7 @@
 //   the stages for bits a+3, a+2, ... ; with H = f >> (a+4) the index of stage i
 //   of the round is (T0 << i) + (k >> (4-i)),  T0 = (1<<(s0+ls0)) + (blk<<ls0) + H.
 #include "ntt_rounds.hpp"
+#include "launch.hpp"
 
 #include "capi_internal.hpp"   // fhe_env_switch
 
@@ -718,57 +719,29 @@ __global__ __launch_bounds__(256) void check_canonical_kernel(const u64 *__restr
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-static inline hipError_t post_launch() { return hipGetLastError(); }
-
-
 template <int LP, bool FINAL, int AR, int SRC = SRC_PLAIN>
 static hipError_t launch_fwd_contig(const PassArgs &a, hipStream_t st) {
     using C = ContigCfg<LP>;
-    const u64 nb = 1ull << (a.log_n - LP);
-    const u64 groups = (a.batch + C::W - 1) / C::W;
-    const u64 grid = nb * groups;
-    if (grid == 0) return hipSuccess;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     constexpr size_t lds_bytes = (SRC == SRC_DIGITS || SRC == SRC_ZQBITS) ? C::LDS_BYTES_BITS : C::LDS_BYTES;
-    if (hipError_t e = allow_big_lds((const void *)ntt_fwd_contig_kernel<LP, FINAL, AR, SRC>, lds_bytes)) return e;
-    KernelTimer kt(SRC == SRC_DIGITS ? "ntt_fwd_digits" : SRC == SRC_ZQBITS ? "ntt_fwd_zqbits" : SRC == SRC_REDUCE ? "ntt_fwd_reduce" : (FINAL ? "ntt_fwd_contig_final" : "ntt_fwd_contig"), LP, st);
-    hipLaunchKernelGGL((ntt_fwd_contig_kernel<LP, FINAL, AR, SRC>), dim3((unsigned)grid), dim3(C::TH),
-                       lds_bytes, st, a);
-    return post_launch();
+    return launch_kernel(ntt_fwd_contig_kernel<LP, FINAL, AR, SRC>,
+                         SRC == SRC_DIGITS ? "ntt_fwd_digits" : SRC == SRC_ZQBITS ? "ntt_fwd_zqbits" : SRC == SRC_REDUCE ? "ntt_fwd_reduce" : (FINAL ? "ntt_fwd_contig_final" : "ntt_fwd_contig"),
+                         LP, {(1ull << (a.log_n - LP)) * ((a.batch + C::W - 1) / C::W)}, C::TH, lds_bytes, st, a);
 }
 
 template <int LP, bool FINAL, bool MUL_IN, int AR>
 static hipError_t launch_inv_contig(const PassArgs &a, hipStream_t st) {
     using C = ContigCfg<LP>;
-    const u64 nb = 1ull << (a.log_n - LP);
-    const u64 groups = (a.batch + C::W - 1) / C::W;
-    const u64 grid = nb * groups;
-    if (grid == 0) return hipSuccess;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-    if (hipError_t e = allow_big_lds((const void *)ntt_inv_contig_kernel<LP, FINAL, MUL_IN, AR>, C::LDS_BYTES)) return e;
-    KernelTimer kt(MUL_IN ? "ntt_inv_contig_mul" : (FINAL ? "ntt_inv_contig_final" : "ntt_inv_contig"), LP, st);
-    hipLaunchKernelGGL((ntt_inv_contig_kernel<LP, FINAL, MUL_IN, AR>), dim3((unsigned)grid),
-                       dim3(C::TH), C::LDS_BYTES, st, a);
-    return post_launch();
+    return launch_kernel(ntt_inv_contig_kernel<LP, FINAL, MUL_IN, AR>, MUL_IN ? "ntt_inv_contig_mul" : (FINAL ? "ntt_inv_contig_final" : "ntt_inv_contig"), LP,
+                         {(1ull << (a.log_n - LP)) * ((a.batch + C::W - 1) / C::W)}, C::TH, C::LDS_BYTES, st, a);
 }
 
 template <int LA, int CW, bool INV, int AR, bool RSRC = false>
 static hipError_t launch_strided(const PassArgs &a, hipStream_t st, unsigned operands = 1) {
     using C = StridedCfg<LA, CW>;
-    const u64 ncg = (1ull << (a.log_n - LA)) / CW;
-    const u64 grid = ncg * a.batch;
-    if (grid == 0) return hipSuccess;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-    if (hipError_t e = allow_big_lds(INV ? (const void *)ntt_inv_strided_kernel<LA, CW, AR>
-                                         : (const void *)ntt_fwd_strided_kernel<LA, CW, AR, RSRC>, C::LDS_BYTES)) return e;
-    KernelTimer kt(INV ? "ntt_inv_strided" : (RSRC ? "ntt_fwd_strided_reduce" : "ntt_fwd_strided"), LA, st);
-    if (INV)
-        hipLaunchKernelGGL((ntt_inv_strided_kernel<LA, CW, AR>), dim3((unsigned)grid), dim3(C::TH),
-                           C::LDS_BYTES, st, a);
-    else
-        hipLaunchKernelGGL((ntt_fwd_strided_kernel<LA, CW, AR, RSRC>), dim3((unsigned)grid, operands), dim3(C::TH),
-                           C::LDS_BYTES, st, a);
-    return post_launch();
+    const u64 grid = (1ull << (a.log_n - LA)) / CW * a.batch;
+    if (INV) return launch_kernel(ntt_inv_strided_kernel<LA, CW, AR>, "ntt_inv_strided", LA, {grid}, C::TH, C::LDS_BYTES, st, a);
+    return launch_kernel(ntt_fwd_strided_kernel<LA, CW, AR, RSRC>, RSRC ? "ntt_fwd_strided_reduce" : "ntt_fwd_strided", LA, {grid, operands}, C::TH,
+                         C::LDS_BYTES, st, a);
 }
 
 #ifndef FHE_STRIDED_CW8
@@ -781,28 +754,15 @@ static hipError_t launch_strided(const PassArgs &a, hipStream_t st, unsigned ope
 template <int LP, int AR>
 static hipError_t launch_rq_mul_fused_lp(const PassArgs &a, hipStream_t st) {
     using C = ContigCfg<LP>;
-    const u64 grid = (a.batch + C::W - 1) / C::W;
-    if (grid == 0) return hipSuccess;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     constexpr size_t lds_bytes = C::LDS_BYTES + (size_t)C::LTW_N * sizeof(Tw);   // a second twiddle tile
-    if (hipError_t e = allow_big_lds((const void *)rq_mul_fused_kernel<LP, AR>, lds_bytes)) return e;
-    KernelTimer kt("rq_mul_fused", LP, st);
-    hipLaunchKernelGGL((rq_mul_fused_kernel<LP, AR>), dim3((unsigned)grid), dim3(C::TH), lds_bytes, st, a);
-    return post_launch();
+    return launch_kernel(rq_mul_fused_kernel<LP, AR>, "rq_mul_fused", LP, {(a.batch + C::W - 1) / C::W}, C::TH, lds_bytes, st, a);
 }
 
 template <int LP, int AR>
 static hipError_t launch_rq_mul_mid_lp(const PassArgs &a, hipStream_t st) {
     using C = ContigCfg<LP>;
-    const u64 nb = 1ull << (a.log_n - LP);
-    const u64 grid = nb * ((a.batch + C::W - 1) / C::W);
-    if (grid == 0) return hipSuccess;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
     constexpr size_t lds_bytes = C::LDS_BYTES + (FHE_MID_ONE_TILE ? 0 : (size_t)C::LTW_N * sizeof(Tw));   // ONE twiddle tile: four workgroups per CU
-    if (hipError_t e = allow_big_lds((const void *)rq_mul_mid_kernel<LP, AR>, lds_bytes)) return e;
-    KernelTimer kt("rq_mul_mid", LP, st);
-    hipLaunchKernelGGL((rq_mul_mid_kernel<LP, AR>), dim3((unsigned)grid), dim3(C::TH), lds_bytes, st, a);
-    return post_launch();
+    return launch_kernel(rq_mul_mid_kernel<LP, AR>, "rq_mul_mid", LP, {(1ull << (a.log_n - LP)) * ((a.batch + C::W - 1) / C::W)}, C::TH, lds_bytes, st, a);
 }
 
 // ---- two translation units ------------------------------------------------------------------------------------------------
@@ -975,7 +935,7 @@ hipError_t launch_ntt_forward(const DevicePlan &p, const u64 *in, u64 *out, u64 
         a.in = in; a.out = out; a.batch = batch;
         KernelTimer kt("ntt_tiny_fwd", L, st);
         hipLaunchKernelGGL(ntt_tiny_kernel<false>, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, a);
-        return post_launch();
+        return hipGetLastError();
     }
     if (L <= kMaxSinglePassLog) {
         a.in = in; a.out = out; a.batch = batch;
@@ -1178,7 +1138,7 @@ hipError_t launch_ntt_inverse(const DevicePlan &p, const u64 *in, const u64 *in2
         a.in = src; a.out = out; a.batch = batch;
         KernelTimer kt("ntt_tiny_inv", L, st);
         hipLaunchKernelGGL(ntt_tiny_kernel<true>, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, a);
-        return post_launch();
+        return hipGetLastError();
     }
     if (L <= kMaxSinglePassLog) {
         a.in = in; a.in2 = in2; a.out2 = evals_out; a.out = out; a.batch = batch;
@@ -1226,20 +1186,20 @@ hipError_t launch_pointwise_mul(const DevicePlan &p, const u64 *x, const u64 *y,
     if (count == 0) return hipSuccess;
     KernelTimer kt("pointwise_mul", 0, st);
     hipLaunchKernelGGL(pointwise_mul_kernel, dim3(ew_grid(count)), dim3(256), 0, st, x, y, z, count, p.mod);
-    return post_launch();
+    return hipGetLastError();
 }
 
 hipError_t launch_fill_synthetic(u64 *out, u64 count, u64 q, u64 seed, u64 first, hipStream_t st) {
     if (count == 0) return hipSuccess;
     KernelTimer kt("fill_synthetic", 0, st);
     hipLaunchKernelGGL(fill_synthetic_kernel, dim3(ew_grid(count)), dim3(256), 0, st, out, count, q, seed, first);
-    return post_launch();
+    return hipGetLastError();
 }
 
 hipError_t launch_check_canonical(const u64 *x, u64 count, u64 q, int *d_flag, hipStream_t st) {
     if (count == 0) return hipSuccess;
     hipLaunchKernelGGL(check_canonical_kernel, dim3(ew_grid(count)), dim3(256), 0, st, x, count, q, d_flag);
-    return post_launch();
+    return hipGetLastError();
 }
 
 // timing-only build (memory pattern without the arithmetic): wrong words by design, fhe_ntt_version() says so (capi.hip)

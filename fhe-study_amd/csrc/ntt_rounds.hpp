@@ -767,10 +767,4 @@ __device__ __forceinline__ void exchange_strided(u64 (&v)[16], u64 *lds, u32 c, 
 // pass split for n >= 2^14: LB = max(8, L-8) contiguous stages, LA = L-LB in 6..8
 static inline int contig_bits(int L) { return L <= kMaxSinglePassLog ? L : (L - 8 > 8 ? L - 8 : 8); }
 
-// dynamic LDS above 64 KiB must be opted into per kernel
-static inline hipError_t allow_big_lds(const void *fn, size_t bytes) {
-    if (bytes <= 65536) return hipSuccess;
-    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 }  // namespace fhe

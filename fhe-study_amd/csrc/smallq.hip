@@ -19,38 +19,10 @@
 //   sq_rq_mul_kernel    both forward transforms in lockstep (one twiddle load for both), pointwise Montgomery product,
 //                       inverse transform — the whole product on chip, as rq_mul_fused_kernel does for 61-bit q
 #include "smallq.hpp"
+#include "launch.hpp"
 #include "ntt32_big.hpp"
 
 namespace fhe {
-
-template <int LP>
-struct SqCfg {
-    using C = ContigCfg<LP>;
-    static constexpr int M = C::M, W = C::W, TPB = C::TPB;
-    static constexpr size_t TILE_BYTES = (size_t)(W * M + W * M / 16) * 4, TW_BYTES = (size_t)C::LTW_N * sizeof(Tw32);
-    static_assert(LP >= 8 && LP <= 12, "n = 256 .. 4096");
-};
-
-// two polynomials through two tiles with one pair of barriers
-template <int LP, int AF, int AT, bool FIRST>
-__device__ __forceinline__ void sq_exchange2(u32 (&va)[16], u32 (&vb)[16], u32 *la, u32 *lb, u32 w, u32 tf) {
-    constexpr int M = 1 << LP;
-    const u32 bf = pad16(w * M + field_of<AF>(tf, 0)), bt = pad16(w * M + field_of<AT>(tf, 0));   // + a constant per register (ntt_rounds.hpp: pad16_koff)
-    if (!FIRST) __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const u32 s = bf + pad16_koff<AF>(k);
-        la[s] = va[k];
-        lb[s] = vb[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const u32 s = bt + pad16_koff<AT>(k);
-        va[k] = la[s];
-        vb[k] = lb[s];
-    }
-}
 
 // forward stages of two polynomials in lockstep, ct32_loose (canonical inputs: values end below (1 + 2 LP) q <= 25 q)
 // LOOSE (25 q < 2^32): ct32_loose, no conditional subtraction; otherwise (4 q < 2^32: moduli up to 2^30) Harvey's
@@ -66,14 +38,14 @@ __device__ __forceinline__ void sq_fwd2(u32 (&va)[16], u32 (&vb)[16], u32 *la, u
     {
         constexpr int A = C::a_of(1), LS = C::ls0_of(1);
         load_tw32<4>(t, C::in_lds(1) ? ltw : gtw, (1u << LS) + (tf >> A));
-        sq_exchange2<LP, C::A0, A, true>(va, vb, la, lb, w, tf);
+        exchange32x2<LP, C::A0, A, true>(va, vb, la, lb, w, tf);
         round_fwd32_tw<4, 0, LOOSE>(va, t, q, q2);
         round_fwd32_tw<4, 0, LOOSE>(vb, t, q, q2);
     }
     if constexpr (C::NR > 2) {
         constexpr int A = C::a_of(2), LS = C::ls0_of(2);
         load_tw32<4>(t, C::in_lds(2) ? ltw : gtw, (1u << LS) + (tf >> A));
-        sq_exchange2<LP, C::a_of(1), A, false>(va, vb, la, lb, w, tf);
+        exchange32x2<LP, C::a_of(1), A, false>(va, vb, la, lb, w, tf);
         round_fwd32_tw<4, 0, LOOSE>(va, t, q, q2);
         round_fwd32_tw<4, 0, LOOSE>(vb, t, q, q2);
     }
@@ -133,20 +105,13 @@ __device__ __forceinline__ void sq_load_natural(u32 (&v)[16], const u64 *__restr
     for (int k = 0; k < 16; k++) v[k] = csub_u32(barrett2p_32((u32)src[(u32)k * C::TPB + tf], q, bq), q);   // words are below q; any 32-bit word is reduced
 }
 
-// x * y * 2^-32 mod q, in [0, 2q), for x * y < q * 2^32 (Montgomery; q is odd: 2n divides q - 1)
-__device__ __forceinline__ u32 sq_mont(u32 x, u32 y, u32 q, u32 qinv_neg) {
-    const u64 t = (u64)x * y;
-    const u32 m = (u32)t * qinv_neg;
-    return (u32)((t + (u64)m * q) >> 32);
-}
-
 struct SqLds {
     u32 *tile_a, *tile_b;
     Tw32 *ltw;
 };
 template <int LP, bool TWO>
 __device__ __forceinline__ SqLds sq_lds(unsigned char *smem, const Tw32 *gtw, u32 tid) {
-    using K = SqCfg<LP>;
+    using K = Cfg32<LP>;
     SqLds l;
     l.tile_a = reinterpret_cast<u32 *>(smem);
     l.tile_b = reinterpret_cast<u32 *>(smem + K::TILE_BYTES);
@@ -214,7 +179,7 @@ __global__ __launch_bounds__(256) void sq_inverse_kernel(SmallQArgs a) {
 template <int LP, bool LOOSE>
 __global__ __launch_bounds__(256) void sq_rq_mul_kernel(SmallQArgs a) {
     using C = ContigCfg<LP>;
-    using K = SqCfg<LP>;
+    using K = Cfg32<LP>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const u32 tid = threadIdx.x, w = tid / C::TPB, tf = tid % C::TPB;
     u32 *tile_a = reinterpret_cast<u32 *>(smem_raw), *tile_b = reinterpret_cast<u32 *>(smem_raw + K::TILE_BYTES);
@@ -271,7 +236,7 @@ __global__ __launch_bounds__(256) void sq_rq_mul_kernel(SmallQArgs a) {
         scale = a.ninv;
     } else {
 #pragma unroll
-        for (int k = 0; k < 16; k++) va[k] = sq_mont(va[k], vb[k], q, a.qinv_neg);       // * 2^-32: leaves with n^-1 below
+        for (int k = 0; k < 16; k++) va[k] = mont32(va[k], vb[k], q, a.qinv_neg);       // * 2^-32: leaves with n^-1 below
     }
     sq_inv1<LP, false>(va, tile_a, ltw_inv, a.tw_inv, w, tf, q, q2);
     if (active) {
@@ -383,7 +348,7 @@ __global__ __launch_bounds__((Big32<LP>::TH)) void sq_big_rq_mul_kernel(SmallQAr
         scale = a.ninv;
     } else {
 #pragma unroll
-        for (int k = 0; k < 16; k++) va[0][k] = sq_mont(va[0][k], vb[0][k], q, a.qinv_neg);
+        for (int k = 0; k < 16; k++) va[0][k] = mont32(va[0][k], vb[0][k], q, a.qinv_neg);
     }
     inv_big<LP>(va, lds, ltw_inv, a.tw_inv, tf, q, q2);
     u64 *__restrict__ dst = a.out + row * C::M;
@@ -471,7 +436,7 @@ template <bool LOOSE>
 __global__ __launch_bounds__(256) void sq2_block_fwd_kernel(SmallQArgs a, u32 la) {
     constexpr int LP = kSqBlockLog;
     using C = ContigCfg<LP>;
-    using K = SqCfg<LP>;
+    using K = Cfg32<LP>;
     static_assert(C::W == 1 && C::NR == 3, "one 4096-point block per workgroup");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u32 *lds = reinterpret_cast<u32 *>(smem_raw);
@@ -506,7 +471,7 @@ __global__ __launch_bounds__(256) void sq2_block_fwd_kernel(SmallQArgs a, u32 la
 __global__ __launch_bounds__(256) void sq2_block_inv_kernel(SmallQArgs a, u32 la) {
     constexpr int LP = kSqBlockLog;
     using C = ContigCfg<LP>;
-    using K = SqCfg<LP>;
+    using K = Cfg32<LP>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u32 *lds = reinterpret_cast<u32 *>(smem_raw);
     Tw32 *ltw = reinterpret_cast<Tw32 *>(smem_raw + K::TILE_BYTES);
@@ -543,7 +508,7 @@ template <bool LOOSE>
 __global__ __launch_bounds__(256) void sq2_block_mul_kernel(SmallQArgs a, u32 la) {
     constexpr int LP = kSqBlockLog;
     using C = ContigCfg<LP>;
-    using K = SqCfg<LP>;
+    using K = Cfg32<LP>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u32 *la_tile = reinterpret_cast<u32 *>(smem_raw), *lb_tile = reinterpret_cast<u32 *>(smem_raw + K::TILE_BYTES);
     Tw32 *ltw = reinterpret_cast<Tw32 *>(smem_raw + 2 * K::TILE_BYTES), *ltw_inv = ltw + C::LTW_N;
@@ -596,11 +561,11 @@ __global__ __launch_bounds__(256) void sq2_block_mul_kernel(SmallQArgs a, u32 la
         round_fwd32_tw<C::R0, 0, LOOSE>(va, t, q, q2);
         round_fwd32_tw<C::R0, 0, LOOSE>(vb, t, q, q2);
         load_tw32<4>(t, C::in_lds(1) ? ltw : a.tw_fwd, sq_block_t0<LP, 1>(la, blk, tf >> C::a_of(1)));
-        sq_exchange2<LP, C::A0, C::a_of(1), true>(va, vb, la_tile, lb_tile, 0u, tf);
+        exchange32x2<LP, C::A0, C::a_of(1), true>(va, vb, la_tile, lb_tile, 0u, tf);
         round_fwd32_tw<4, 0, LOOSE>(va, t, q, q2);
         round_fwd32_tw<4, 0, LOOSE>(vb, t, q, q2);
         load_tw32<4>(t, C::in_lds(2) ? ltw : a.tw_fwd, sq_block_t0<LP, 2>(la, blk, tf >> C::a_of(2)));
-        sq_exchange2<LP, C::a_of(1), C::a_of(2), false>(va, vb, la_tile, lb_tile, 0u, tf);
+        exchange32x2<LP, C::a_of(1), C::a_of(2), false>(va, vb, la_tile, lb_tile, 0u, tf);
         round_fwd32_tw<4, 0, LOOSE>(va, t, q, q2);
         round_fwd32_tw<4, 0, LOOSE>(vb, t, q, q2);
     } else {
@@ -623,7 +588,7 @@ __global__ __launch_bounds__(256) void sq2_block_mul_kernel(SmallQArgs a, u32 la
         store_evals(a.c_evals, va, lb_tile);
     } else {
 #pragma unroll
-        for (int k = 0; k < 16; k++) va[k] = sq_mont(barrett2p_32(va[k], q, a.bq), barrett2p_32(vb[k], q, a.bq), q, a.qinv_neg);
+        for (int k = 0; k < 16; k++) va[k] = mont32(barrett2p_32(va[k], q, a.bq), barrett2p_32(vb[k], q, a.bq), q, a.qinv_neg);
     }
     load_tw32<4>(t, C::in_lds(2) ? ltw_inv : a.tw_inv, sq_block_t0<LP, 2>(la, blk, tf >> C::a_of(2)));
     round_inv32_tw<4>(va, t, q, q2);
@@ -647,33 +612,22 @@ size_t smallq_scratch_bytes(unsigned log_n, uint64_t rows) { return log_n > 14 ?
 
 template <typename K>
 static hipError_t sq_launch(K kernel, const char *name, int lp, size_t lds, unsigned units, const SmallQArgs &a, hipStream_t st) {
-    if (a.rows == 0) return hipSuccess;
-    const u64 grid = (a.rows + units - 1) / units;
-    if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-    if (hipError_t e = allow_big_lds((const void *)kernel, lds)) return e;
-    KernelTimer kt(name, lp, st);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds, st, a);
-    return hipGetLastError();
+    return launch_kernel(kernel, name, lp, {(a.rows + units - 1) / units}, 256, lds, st, a);
 }
 // KERNEL<LP>: an alias template with the butterfly form already chosen (the _l / _h variables below)
 #define FHE_SQ_SWITCH(KERNEL, NAME, TILES, TWS)                                                                                         \
     switch (log_n) {                                                                                                                    \
-        case 8: return sq_launch(KERNEL<8>, NAME, 8, TILES * SqCfg<8>::TILE_BYTES + TWS * SqCfg<8>::TW_BYTES, ContigCfg<8>::W, a, st);      \
-        case 9: return sq_launch(KERNEL<9>, NAME, 9, TILES * SqCfg<9>::TILE_BYTES + TWS * SqCfg<9>::TW_BYTES, ContigCfg<9>::W, a, st);      \
-        case 10: return sq_launch(KERNEL<10>, NAME, 10, TILES * SqCfg<10>::TILE_BYTES + TWS * SqCfg<10>::TW_BYTES, ContigCfg<10>::W, a, st); \
-        case 11: return sq_launch(KERNEL<11>, NAME, 11, TILES * SqCfg<11>::TILE_BYTES + TWS * SqCfg<11>::TW_BYTES, ContigCfg<11>::W, a, st); \
-        case 12: return sq_launch(KERNEL<12>, NAME, 12, TILES * SqCfg<12>::TILE_BYTES + TWS * SqCfg<12>::TW_BYTES, ContigCfg<12>::W, a, st); \
+        case 8: return sq_launch(KERNEL<8>, NAME, 8, TILES * Cfg32<8>::TILE_BYTES + TWS * Cfg32<8>::TW_BYTES, ContigCfg<8>::W, a, st);      \
+        case 9: return sq_launch(KERNEL<9>, NAME, 9, TILES * Cfg32<9>::TILE_BYTES + TWS * Cfg32<9>::TW_BYTES, ContigCfg<9>::W, a, st);      \
+        case 10: return sq_launch(KERNEL<10>, NAME, 10, TILES * Cfg32<10>::TILE_BYTES + TWS * Cfg32<10>::TW_BYTES, ContigCfg<10>::W, a, st); \
+        case 11: return sq_launch(KERNEL<11>, NAME, 11, TILES * Cfg32<11>::TILE_BYTES + TWS * Cfg32<11>::TW_BYTES, ContigCfg<11>::W, a, st); \
+        case 12: return sq_launch(KERNEL<12>, NAME, 12, TILES * Cfg32<12>::TILE_BYTES + TWS * Cfg32<12>::TW_BYTES, ContigCfg<12>::W, a, st); \
     }                                                                                                                                   \
     return hipErrorNotSupported;
 
 template <typename K>
 static hipError_t sq_big_launch(K kernel, const char *name, int lp, size_t lds, unsigned th, const SmallQArgs &a, hipStream_t st) {
-    if (a.rows == 0) return hipSuccess;
-    if (a.rows > 0x7fffffffull) return hipErrorInvalidValue;
-    if (hipError_t e = allow_big_lds((const void *)kernel, lds)) return e;
-    KernelTimer kt(name, lp, st);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)a.rows), dim3(th), lds, st, a);
-    return hipGetLastError();
+    return launch_kernel(kernel, name, lp, {a.rows}, th, lds, st, a);
 }
 #define FHE_SQ_BIG(KERNEL, NAME, TWS)                                                                                             \
     if (log_n == 13) return sq_big_launch(KERNEL<13>, NAME, 13, Big32<13>::TILE_BYTES + TWS * Big32<13>::TW_BYTES, Big32<13>::TH, a, st); \
@@ -686,17 +640,9 @@ static hipError_t sq2_launch(KS strided, KB block, bool forward, int log_n, cons
     if (!a.mid) return hipErrorInvalidValue;
     const u64 gs = a.rows * ((1u << kSqBlockLog) / 256), gb = a.rows << la;
     if (gs > 0x7fffffffull || gb > 0x7fffffffull) return hipErrorInvalidValue;
-    constexpr size_t lds = SqCfg<kSqBlockLog>::TILE_BYTES + SqCfg<kSqBlockLog>::TW_BYTES;
-    auto run_strided = [&]() {
-        KernelTimer kt(forward ? "sq2_strided_fwd" : "sq2_strided_inv", log_n, st);
-        hipLaunchKernelGGL(strided, dim3((unsigned)gs), dim3(256), 0, st, a);
-        return hipGetLastError();
-    };
-    auto run_block = [&]() {
-        KernelTimer kt(forward ? "sq2_block_fwd" : "sq2_block_inv", log_n, st);
-        hipLaunchKernelGGL(block, dim3((unsigned)gb), dim3(256), lds, st, a, la);
-        return hipGetLastError();
-    };
+    constexpr size_t lds = Cfg32<kSqBlockLog>::TILE_BYTES + Cfg32<kSqBlockLog>::TW_BYTES;
+    auto run_strided = [&]() { return launch_kernel(strided, forward ? "sq2_strided_fwd" : "sq2_strided_inv", log_n, {gs}, 256, 0, st, a); };
+    auto run_block = [&]() { return launch_kernel(block, forward ? "sq2_block_fwd" : "sq2_block_inv", log_n, {gb}, 256, lds, st, a, la); };
     if (forward) { if (hipError_t e = run_strided()) return e; return run_block(); }
     if (hipError_t e = run_block()) return e;
     return run_strided();
@@ -741,7 +687,7 @@ static hipError_t sq2_mul_launch(KF sfwd, KI sinv, KM smid, int log_n, const Sma
     if (!a.mid || !a.mid_b) return hipErrorInvalidValue;
     const u64 gs = a.rows * ((1u << kSqBlockLog) / 256), gb = a.rows << la;
     if (gs > 0x7fffffffull || gb > 0x7fffffffull) return hipErrorInvalidValue;
-    constexpr size_t lds = 2 * SqCfg<kSqBlockLog>::TILE_BYTES + 2 * SqCfg<kSqBlockLog>::TW_BYTES;
+    constexpr size_t lds = 2 * Cfg32<kSqBlockLog>::TILE_BYTES + 2 * Cfg32<kSqBlockLog>::TW_BYTES;
     SmallQArgs fa = a, fb = a, inv = a;
     fb.a = a.b; fb.mid = a.mid_b;                               // strided forward of b into its own intermediate
     if (!a.c_evals) inv.ninv = a.ninv_mont;                     // the Montgomery product's 2^-32 leaves with n^-1
@@ -751,14 +697,8 @@ static hipError_t sq2_mul_launch(KF sfwd, KI sinv, KM smid, int log_n, const Sma
         if (!(a.flags & 2u)) hipLaunchKernelGGL(sfwd, dim3((unsigned)gs), dim3(256), 0, st, fb);
     }
     if (hipError_t e = hipGetLastError()) return e;
-    {
-        KernelTimer kt("sq2_block_mul", log_n, st);
-        hipLaunchKernelGGL(smid, dim3((unsigned)gb), dim3(256), lds, st, a, la);
-    }
-    if (hipError_t e = hipGetLastError()) return e;
-    KernelTimer kt("sq2_strided_inv", log_n, st);
-    hipLaunchKernelGGL(sinv, dim3((unsigned)gs), dim3(256), 0, st, inv);
-    return hipGetLastError();
+    if (hipError_t e = launch_kernel(smid, "sq2_block_mul", log_n, {gb}, 256, lds, st, a, la)) return e;
+    return launch_kernel(sinv, "sq2_strided_inv", log_n, {gs}, 256, 0, st, inv);
 }
 template <bool LOOSE>
 static hipError_t launch_sq_rq_mul_t(const SmallQArgs &a, int log_n, hipStream_t st) {

@@ -24,6 +24,7 @@
 #include "digit_mac.hpp"
 #include "digit32.hpp"
 #include "bfv32.hpp"
+#include "host_dispatch.hpp"
 #include "ntt_rounds.hpp"
 #include "zq_device.hpp"
 #include "mac_kernel.hpp"
@@ -440,24 +441,12 @@ static hipError_t z_inverse_mdr(const ZCtx &z, u64 *r, u64 *out, u64 rows, u64 q
     fhe::PassArgs a{};
     a.tw = dp.tw_inv; a.mod = dp.mod; a.ninv = dp.ninv; a.s_ninv = dp.s_ninv; a.log_n = dp.log_n; a.in = r; a.batch = rows;
     const int LA = L - fhe::contig_bits(L);
-    fhe::KernelTimer kt_("zr_inv_strided_mdr", LA, st);
-#define MDR_PASS(LA_, CW_)                                                                                              \
-    {                                                                                                                   \
-        using C = fhe::StridedCfg<LA_, CW_>;                                                                            \
-        const u64 grid = ((1ull << (L - LA_)) / CW_) * rows;                                                            \
-        if (grid > 0x7fffffffull) return hipErrorInvalidValue;                                                          \
-        if ((e = fhe::allow_big_lds((const void *)fhe::zr_inv_strided_mdr_kernel<LA_, CW_>, C::LDS_BYTES)) != hipSuccess) return e; \
-        hipLaunchKernelGGL((fhe::zr_inv_strided_mdr_kernel<LA_, CW_>), dim3((unsigned)grid), dim3(C::TH), C::LDS_BYTES, st, a, out, q, \
-                           (double)num, (double)den);                                                                   \
-    }
-    switch (LA) {
-        case 6: MDR_PASS(6, 128) break;
-        case 7: MDR_PASS(7, 64) break;
-        case 8: MDR_PASS(8, 32) break;
-        default: return hipErrorNotSupported;
-    }
-#undef MDR_PASS
-    return hipGetLastError();
+    return fhe::dispatch_int<6, 8>(LA, hipErrorNotSupported, [&](auto la) {
+        constexpr int CW = la() == 6 ? 128 : la() == 7 ? 64 : 32;
+        using C = fhe::StridedCfg<la(), CW>;
+        return fhe::launch_kernel(fhe::zr_inv_strided_mdr_kernel<la(), CW>, "zr_inv_strided_mdr", la, {((1ull << (L - la)) / CW) * rows}, C::TH, C::LDS_BYTES,
+                                  st, a, out, q, (double)num, (double)den);
+    });
 }
 
 static unsigned bits_of(u64 x) { unsigned b = 0; while (x) { b++; x >>= 1; } return b; }

@@ -105,6 +105,16 @@ def test_host_table_arithmetic_against_its_definitions(pkg):
     assert "all host table tests passed" in r.stdout
 
 
+def test_size_dispatch_reaches_every_value_once(pkg):
+    """csrc/host_dispatch.hpp, the launchers' one size switch: over [4, 13], [8, 12] and [13, 14] every value reaches the
+    callable exactly once with that compile-time value; Lo - 1, Hi + 1, 0 and a negative value return on_miss without a call
+    (fhe-study_amd/host/test_dispatch.cpp; needs neither the library nor a GPU)"""
+    exe = _build(pkg, "test_dispatch")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "all dispatch tests passed" in r.stdout
+
+
 def test_c_abi_without_a_device_or_with_one(pkg):
     """every path of include/fhe_ntt.h that needs no device — plan construction and cache (16 threads), the reference's
     argument checks in the reference's order, shard arithmetic, switches — and the compute entry points, which must return

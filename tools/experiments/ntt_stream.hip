@@ -30,6 +30,7 @@
 // SGPRs across tiles, and the launch has no per-tile ramp or tail.
 // The two register sets take turns (the loop body is written twice) so that no tile is ever copied between them.
 // Same arithmetic, same rounds (ntt_rounds.hpp), same words as ntt_fwd_strided_kernel / ntt_fwd_contig_kernel.
+#include "../../fhe-study_amd/csrc/launch.hpp"
 #include "../../fhe-study_amd/csrc/ntt_rounds.hpp"
 
 #include <cstdlib>

@@ -260,7 +260,7 @@ static hipError_t launch_fwd_strided_dma(const PassArgs &a, hipStream_t st) {
     KernelTimer kt("ntt_fwd_strided_dma", 8, st);
     hipLaunchKernelGGL((ntt_fwd_strided_dma_kernel<8, 16, WIDE>), dim3((unsigned)grid), dim3(C::TH),
                        C::LDS_BYTES, st, a);
-    return post_launch();
+    return hipGetLastError();
 }
 
 template <bool FINAL, bool WIDE>
@@ -278,7 +278,7 @@ static hipError_t launch_fwd_contig_dma(const PassArgs &a, hipStream_t st) {
     KernelTimer kt(FINAL ? "ntt_fwd_contig_dma_final" : "ntt_fwd_contig_dma", 8, st);
     hipLaunchKernelGGL((ntt_fwd_contig_dma_kernel<8, FINAL, WIDE>), dim3((unsigned)grid), dim3(C::TH),
                        C::LDS_BYTES, st, a);
-    return post_launch();
+    return hipGetLastError();
 }
 
 
