@@ -95,10 +95,13 @@ EXPORTS = [
     "fhe_ckks_rns_diag_sum_dev", "fhe_ckks_rns_diag_workspace_bytes",
     # CKKS on the RNS chain: fused sums of ciphertexts by public scalars (ckks_eval.hip)
     "fhe_ckks_rns_lincomb_dev",
+    # CKKS on the RNS chain: inner products, a sum of ct x ct pairs with one relinearisation (ckks_eval.hip)
+    "fhe_ckks_rns_dot_dev",
 ]
 FHE_CKKS_GALOIS_MAX_COUNT = 256              # include/fhe_ntt.h: the most Galois elements of one fhe_ckks_rns_galois_dev call
 FHE_CKKS_DIAG_MAX_OUTPUTS = 64               # include/fhe_ntt.h: the most outputs of one fhe_ckks_rns_diag_sum_dev call
 FHE_CKKS_LINCOMB_MAX_COUNT, FHE_CKKS_LINCOMB_MAX_OUTPUTS = 64, 16    # include/fhe_ntt.h: the most inputs and outputs of one fhe_ckks_rns_lincomb_dev call
+FHE_CKKS_DOT_MAX_COUNT = 64                  # include/fhe_ntt.h: the most pairs of one fhe_ckks_rns_dot_dev call
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
 GATES = {"AND": 0, "NAND": 1, "OR": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -326,6 +329,7 @@ def load_library():
     L.fhe_ckks_rns_diag_workspace_bytes.argtypes = [_u64, _uint, _sz, _uint, _uint]
     L.fhe_ckks_rns_diag_workspace_bytes.restype = _sz
     L.fhe_ckks_rns_lincomb_dev.argtypes = [_pp, _uint, _pp, _uint, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _uint, _vp, _sz, _vp]
+    L.fhe_ckks_rns_dot_dev.argtypes = [_pp, _uint, _vp, _vp, _uint, _pp, _pp, _uint, ctypes.POINTER(_u64), _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -887,6 +891,17 @@ def ckks_rns_lincomb_dev(plans, d_cts, w, k, outputs, d_out, batch, stream=None,
     ks = None if k is None else (_u64 * max(len(k), 1))(*k)
     _check(load_library().fhe_ckks_rns_lincomb_dev(None if plans is None else _plan_array(plans), len(plans) if limbs is None else limbs, cts, len(d_cts) if count is None else count, ws, ks,
                                                    outputs, d_out, batch, stream))
+
+
+def ckks_rns_dot_dev(plans, special, d_rlk, key_limbs, d_as, d_bs, w, d_out, batch, stream=None, limbs=None, count=None):
+    """fhe_ckks_rns_dot_dev: relinearize(sum_r w_r tensor(a_r, b_r)) -> [limbs][2][batch][n], one key switch whatever
+    the number of pairs; d_as and d_bs lists of device pointers (None is passed as NULL, as is a None list), w the canonical
+    residues [count][limbs] as a flat sequence of integers (None: every weight is 1)"""
+    a = None if d_as is None else (_vp * max(len(d_as), 1))(*d_as)
+    b = None if d_bs is None else (_vp * max(len(d_bs), 1))(*d_bs)
+    ws = None if w is None else (_u64 * max(len(w), 1))(*w)
+    _check(load_library().fhe_ckks_rns_dot_dev(None if plans is None else _plan_array(plans), len(plans) if limbs is None else limbs, _handle(special), d_rlk, key_limbs,
+                                               a, b, len(d_as) if count is None else count, ws, d_out, batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

@@ -582,6 +582,48 @@ def lincomb(cts, coeffs, consts=None, scale=None, level=None):
     return [RnsCiphertext(param, out[o], level, S[o]) for o in range(outputs)]
 
 
+def dot_weights(scales, coeffs=None, scale=None):
+    """the scale rule of `dot` -> (S, w): pair r of scale scales[r] takes the integer w[r] = round(coeffs[r] S / scales[r]) (the
+    float64 product, then the quotient, then Python's round: lincomb's rule), S = `scale`, or the largest pair scale where that
+    is None; coeffs real [count], None: ones.  w is None where every weight is 1: the kernel then multiplies by nothing."""
+    count = len(scales)
+    a = _real(np.ones(count) if coeffs is None else coeffs, "a coefficient")
+    if a.ndim != 1 or a.shape[0] != count:
+        raise ValueError("dot: coeffs must be [len(xs)]")
+    S = float(max(scales) if scale is None else scale)
+    if not (np.isfinite(S) and S > 0):
+        raise ValueError("dot: the target scale must be positive and finite")
+    w = [round(float(a[r]) * S / scales[r]) for r in range(count)]
+    return S, None if all(x == 1 for x in w) else w
+
+
+def dot(xs, ys, rlk, coeffs=None, scale=None, level=None):
+    """-> sum_r coeffs[r] xs[r] ys[r] from fhe_ckks_rns_dot_dev: the tensors of all pairs are summed on the device
+    and relinearised ONCE, so the call costs one key switch and one relinearisation noise term whatever len(xs) is.  xs, ys
+    equal-length lists of RnsCiphertext of one RnsParam and batch; dot([x], [x], rlk) is the square.  The level is the minimum
+    over all operands (or `level`, not above it); an operand at a higher level is read as it is.  Pair r has scale s_r =
+    xs[r].scale ys[r].scale and takes the weight of dot_weights, reduced per limb.  The result carries the target scale S and is
+    NOT rescaled, like mul."""
+    xs, ys = list(xs), list(ys)
+    if not xs or len(xs) != len(ys):
+        raise ValueError("dot: xs and ys must be non-empty lists of one length")
+    param, batch = xs[0].param, xs[0].batch
+    if any(ct.param != param or ct.batch != batch for ct in xs + ys):
+        raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "dot: operands differ in RnsParam or batch")
+    if rlk.param != param:
+        raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "dot: the relinearisation key is not of the operands' chain")
+    top = min(ct.level for ct in xs + ys)
+    level = top if level is None else int(level)
+    if not 0 <= level <= top:
+        raise ValueError(f"dot: level {level} is not in [0, {top}]")
+    S, w = dot_weights([x.scale * y.scale for x, y in zip(xs, ys)], coeffs, scale)
+    torch = _torch()
+    out = torch.empty((level + 1, 2, batch, param.n), dtype=torch.int64, device="cuda")
+    binding.ckks_rns_dot_dev(param.plans(level), param.special_plan(), rlk.d_rlk.data_ptr(), len(param.moduli), [ct.d.data_ptr() for ct in xs],
+                             [ct.d.data_ptr() for ct in ys], None if w is None else [x % q for x in w for q in param.moduli[:level + 1]], out.data_ptr(), batch)
+    return RnsCiphertext(param, out, level, S)
+
+
 def chebyshev_fit(f, degree, interval=(-1, 1)):
     """the Chebyshev coefficients c_0 .. c_degree of the interpolant of f at the degree + 1 Chebyshev nodes of `interval`:
     f(x) ~ sum_i c_i T_i((2x - a - b)/(b - a))"""

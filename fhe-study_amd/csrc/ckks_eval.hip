@@ -16,6 +16,9 @@
 //              coefficient-wise lift), and pi_g is folded into the key sums' and the divide-and-round's reads
 //   diag sum    out_o = sum_r m_{o,r} (.) sigma_{g_r}(ct) for plaintexts known modulo P as well: the key sums of all
 //              elements are weighted and added in the basis Q P by one fused kernel, and each output takes one division by P
+//   lincomb     out_o = sum_r w[o][r] ct_r + (k[o], 0) per limb, the inputs read once for up to four outputs
+//   dot         relin(sum_r w_r tensor(a_r, b_r)): the tensors of all pairs summed by one fused kernel into the
+//              slot ct x ct stages its tensor in, then relin as it is: one key switch whatever the number of pairs
 //
 // All kernels are grid-stride and element-wise on fhe_ew_grid, bounds-checked against their element count, plain C++ with
 // vector stores and no scratch.  The transforms are fhe_ntt_forward_dev / fhe_ntt_inverse_dev on the workspace (slot 12),
@@ -283,6 +286,69 @@ __global__ __launch_bounds__(256) void ckks_rns_lincomb_kernel(u64 *__restrict__
         }
 #pragma unroll
         for (u32 o = 0; o < NOUT; o++) out[o * out_os + i] = wide ? u[o].fold63(m) : u[o].fold(m);
+    }
+}
+
+// ---- inner products: the summed tensor of ct x ct pairs, relinearised once -------------------------------------------
+constexpr u32 kDotGroup = 16;      // pairs of one launch, passed by value; the registers do not depend on it (§29)
+
+// The pairs of one launch for one limb.  Indexed by the loop counter, which is uniform: scalar loads from the kernel-argument
+// segment, as LinGroup.
+struct DotGroup {
+    const u64 *a[kDotGroup], *b[kDotGroup];   // pair r's operands, this limb: two components `cs` words apart each
+    u64 w[kDotGroup];                         // w_r of this limb, canonical; not read unless WEIGHTED
+    u64 cs;                                   // every operand is a ciphertext of the call's batch: one component stride
+    u32 count;
+};
+
+// One limb of the summed tensor of the pairs of `grp`, over `count` words a component; out is three components o_cs words apart,
+// the layout ckks_rns_tensor_kernel writes, canonical:
+//   d0[e] (+)= sum_r w_r a_r0[e] b_r0[e],  d1[e] (+)= sum_r w_r (a_r0[e] b_r1[e] + a_r1[e] b_r0[e]),  d2[e] (+)= sum_r w_r a_r1[e] b_r1[e]
+// Every operand word is read once.  a_r and b_r may be the same pointer (a square) and a pointer may repeat across pairs: the
+// operands are only read, and `out` (the workspace's tensor slot) is none of them.  WEIGHTED = false: w_r = 1, no multiplication.
+// CARRY: the three sums start from the canonical words a former group left in `out`; otherwise from zero.
+// Overflow.  Operands are canonical, so a product of two of them is below q^2.  The weight is folded into a_r first: w a_r0 and
+// w a_r1 are reduced to canonical words (bfv_mulmod) before they meet b, since w a b < q^3 has no room in 128 bits; a term is
+// then below q^2 whether weighted or not.  d0 and d2 take one term a pair, d1 takes two, so d1 sets the period and all three
+// fold with it.  Between two folds an accumulator holds a canonical carry-over (zero, the last fold, or the word CARRY read:
+// below q) and the terms of T pairs, at most (q - 1) + 2 T (q - 1)^2:
+//   q < 2^62:         a term is below 2^124; T = kMacChunk / 2 = 4 pairs are eight terms, below 2^127 + 2^62 (MacAcc::fold)
+//   2^62 <= q < 2^63: a term is below 2^126; T = kMacChunk63 / 2 = 1 pair is two terms, below 2^127 + 2^63 (MacAcc::fold63)
+// (2 T <= 15 and 2 T <= 3 are what 128 bits allow: 7 pairs and 1; 4 keeps to kMacChunk's eight terms.)  So the accumulators
+// fold before pair r > 0 of the group where r is a multiple of T, and once more before they are stored; any count holds: 64
+// pairs are four groups, each folded to canonical words before it is stored.
+template <bool WEIGHTED, bool CARRY>
+__global__ __launch_bounds__(256) void ckks_rns_tensorsum_kernel(u64 *__restrict__ out, u64 o_cs, u64 count, DotGroup grp, Mod m) {
+    const u64 stride = (u64)gridDim.x * 256;
+    const bool wide = (m.q >> 62) != 0;
+    const u32 pairs = (wide ? kMacChunk63 : kMacChunk) / 2;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        MacAcc d0, d1, d2;
+        if (CARRY) {
+            d0.v = out[i];
+            d1.v = out[o_cs + i];
+            d2.v = out[2 * o_cs + i];
+        }
+        for (u32 r = 0; r < grp.count; r++) {
+            if (r && r % pairs == 0) {
+                if (wide) d0.fold63(m), d1.fold63(m), d2.fold63(m);
+                else d0.fold(m), d1.fold(m), d2.fold(m);
+            }
+            const u64 *a = grp.a[r], *b = grp.b[r];
+            u64 a0 = a[i], a1 = a[grp.cs + i];
+            const u64 b0 = b[i], b1 = b[grp.cs + i];
+            if (WEIGHTED) {
+                a0 = bfv_mulmod(grp.w[r], a0, m);
+                a1 = bfv_mulmod(grp.w[r], a1, m);
+            }
+            d0.mac(a0, b0);
+            d1.mac(a0, b1);
+            d1.mac(a1, b0);
+            d2.mac(a1, b1);
+        }
+        out[i] = wide ? d0.fold63(m) : d0.fold(m);
+        out[o_cs + i] = wide ? d1.fold63(m) : d1.fold(m);
+        out[2 * o_cs + i] = wide ? d2.fold63(m) : d2.fold(m);
     }
 }
 
@@ -961,4 +1027,66 @@ extern "C" int fhe_ckks_rns_lincomb_dev(const fhe_ntt_plan *const *plans, unsign
         }
     }
     return FHE_OK;
+}
+
+// ---- inner products: the summed tensor of ct x ct pairs, relinearised once -------------------------------------------
+namespace {
+
+// rows r0 .. r0 + cr of the `count` pairs -> their summed tensor in Dt [k][3][cr][n]: per limb, groups of kDotGroup pairs, every
+// group after the first carried; w [count][k] or NULL (every weight 1)
+int tensorsum_rows(const Chain &c, const void *const *d_as, const void *const *d_bs, unsigned count, const uint64_t *w, u64 batch, u64 r0, u64 *Dt, u64 cr,
+                   hipStream_t st) {
+    const u64 n = c.n, slab = cr * n;
+    for (unsigned i = 0; i < c.k; i++) {
+        for (unsigned p0 = 0; p0 < count; p0 += fhe::kDotGroup) {
+            fhe::DotGroup grp{};
+            grp.count = std::min<unsigned>(fhe::kDotGroup, count - p0);
+            grp.cs = batch * n;
+            for (unsigned r = 0; r < grp.count; r++) {
+                grp.a[r] = (const u64 *)d_as[p0 + r] + ((u64)i * 2 * batch + r0) * n;
+                grp.b[r] = (const u64 *)d_bs[p0 + r] + ((u64)i * 2 * batch + r0) * n;
+                grp.w[r] = w ? w[(u64)(p0 + r) * c.k + i] : 1;
+            }
+            const bool carry = p0 > 0;
+            auto kernel = w ? (carry ? fhe::ckks_rns_tensorsum_kernel<true, true> : fhe::ckks_rns_tensorsum_kernel<true, false>)
+                            : (carry ? fhe::ckks_rns_tensorsum_kernel<false, true> : fhe::ckks_rns_tensorsum_kernel<false, false>);
+            const int rc = launch("ckks_rns_tensorsum", (int)c.L, st, kernel, fhe_ew_grid(slab), 256, Dt + (u64)i * 3 * slab, slab, slab, grp, c.p[i]->mod);
+            if (rc != FHE_OK) return rc;
+        }
+    }
+    return FHE_OK;
+}
+
+}  // namespace
+
+extern "C" int fhe_ckks_rns_dot_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *d_rlk, unsigned key_limbs,
+                                    const void *const *d_as, const void *const *d_bs, unsigned count, const uint64_t *w, void *d_out, size_t batch,
+                                    void *hip_stream) {
+    const char *who = "fhe_ckks_rns_dot_dev";
+    Chain c;
+    int rc = check_chain(plans, limbs, special, true, &c, who);
+    if (rc != FHE_OK) return rc;
+    if ((rc = check_key_limbs(c, key_limbs, who)) != FHE_OK) return rc;
+    if (count < 1 || count > FHE_CKKS_DOT_MAX_COUNT) return fhe_fail(FHE_E_INVALID, "%s: count=%u must be in [1, %d]", who, count, FHE_CKKS_DOT_MAX_COUNT);
+    if (!d_as || !d_bs) return fhe_fail(FHE_E_NULL, "%s: NULL host array", who);
+    for (unsigned r = 0; w && r < count; r++)
+        for (unsigned i = 0; i < c.k; i++)
+            if (w[(u64)r * c.k + i] >= c.p[i]->q) return fhe_fail(FHE_E_INVALID, "%s: weight [%u][%u] is not below its modulus", who, r, i);
+    if (batch == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, 3ull * c.k * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_rlk || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_rlk) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 ct_bytes = 2ull * c.k * batch * n * 8, rlk_bytes = (u64)key_limbs * (key_limbs + 1) * 2 * n * 8;
+    if (overlaps_any(d_out, ct_bytes, {{d_rlk, rlk_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key", who);
+    for (unsigned r = 0; r < count; r++) {
+        if (!d_as[r] || !d_bs[r]) return fhe_fail(FHE_E_NULL, "%s: an operand of pair %u is NULL", who, r);
+        if (misaligned8(d_as[r]) || misaligned8(d_bs[r])) return fhe_fail(FHE_E_INVALID, "%s: the operands of pair %u must be 8-byte aligned", who, r);
+        if (overlaps_any(d_out, ct_bytes, {{d_as[r], ct_bytes}, {d_bs[r], ct_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an operand of pair %u", who, r);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    return switch_call(c, batch, words_per_row(c), st, [&](u64 r0, u64 cr, u64 *Dt, const u64 *pinv) {   // Dt: the chunk's summed tensor, then relin_rows' buffers
+        const int rc = tensorsum_rows(c, d_as, d_bs, count, w, batch, r0, Dt, cr, st);
+        return rc != FHE_OK ? rc : relin_rows(c, (const u64 *)d_rlk, key_limbs, pinv, Dt, cr, 0, (u64 *)d_out, batch, r0, cr, Dt + 3ull * c.k * cr * n, st);
+    });
 }

@@ -727,6 +727,30 @@ int fhe_ckks_rns_lincomb_dev(const fhe_ntt_plan *const *plans, unsigned limbs, c
                              const uint64_t *w, const uint64_t *k, unsigned outputs, void *d_out, size_t batch,
                              void *hip_stream);
 
+/* ---- CKKS on the RNS chain: inner products, a sum of ct x ct pairs with one relinearisation (ckks_eval.hip) ----
+ *   fhe_ckks_rns_dot_dev          d_out [limbs][2][batch][n] = relinearize(sum_{r < count} w_r tensor(a_r, b_r)): per limb i
+ *            d0 = sum_r w[r][i] a_r0 b_r0, d1 = sum_r w[r][i] (a_r0 b_r1 + a_r1 b_r0), d2 = sum_r w[r][i] a_r1 b_r1 mod q_i, then
+ *            the steps of fhe_ckks_rns_relinearize_dev on (d0, d1, d2).  A key switch is linear in d2, so the call takes ONE
+ *            key switch whatever `count` is, and one relinearisation noise term.  The words are those of
+ *            fhe_ckks_rns_relinearize_dev applied to the exact sum modulo q_i of the weighted tensors: every sum is exact, so
+ *            the order of accumulation does not matter.  d_as and d_bs are HOST arrays of `count` device pointers to
+ *            ciphertexts [>= limbs][2][batch][n] (a ciphertext at a higher level is read as it is, as for
+ *            fhe_ckks_rns_lincomb_dev); a_r and b_r may be the same pointer (a square) and a pointer may repeat across pairs.
+ *            w [count][limbs] is a HOST array of canonical residues, consumed before the call returns; NULL: every weight is
+ *            1.  d_rlk and key_limbs as for fhe_ckks_rns_mul_dev: one key serves every level.  The level is `limbs - 1`; the
+ *            result is not rescaled, and what the weights do to the scale is the caller's bookkeeping.
+ * The library workspace is that of fhe_ckks_rns_mul_dev at the same (n, limbs, batch): the summed tensor lies where that call
+ * stages its tensor, so fhe_ckks_rns_workspace_bytes answers for this call too and there is no size query of its own.
+ * FHE_E_NULL for a NULL plan (the special prime's included), key, host array, entry of either array or output;
+ * FHE_E_PARAM_MISMATCH for plans whose n differ; FHE_E_INVALID for the chain conditions of the §22 block, key_limbs < limbs or
+ * > 8, count not in [1, FHE_CKKS_DOT_MAX_COUNT], a weight that is not below its q_i, a misaligned buffer, an output that overlaps
+ * an operand or the key, and the batch-size limit of fhe_ckks_rns_mul_dev.  Everything is checked before any device call and
+ * nothing is written on rejection; batch = 0 is a no-op. */
+#define FHE_CKKS_DOT_MAX_COUNT 64
+int fhe_ckks_rns_dot_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *d_rlk,
+                         unsigned key_limbs, const void *const *d_as, const void *const *d_bs, unsigned count,
+                         const uint64_t *w, void *d_out, size_t batch, void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
