@@ -97,6 +97,8 @@ EXPORTS = [
     "fhe_ckks_rns_lincomb_dev",
     # CKKS on the RNS chain: inner products, a sum of ct x ct pairs with one relinearisation (ckks_eval.hip)
     "fhe_ckks_rns_dot_dev",
+    # CKKS on the RNS chain: baby-step giant-step linear transforms with hoisted giant steps (ckks_eval.hip)
+    "fhe_ckks_rns_bsgs_dev", "fhe_ckks_rns_bsgs_workspace_bytes",
 ]
 FHE_CKKS_GALOIS_MAX_COUNT = 256              # include/fhe_ntt.h: the most Galois elements of one fhe_ckks_rns_galois_dev call
 FHE_CKKS_DIAG_MAX_OUTPUTS = 64               # include/fhe_ntt.h: the most outputs of one fhe_ckks_rns_diag_sum_dev call
@@ -328,6 +330,9 @@ def load_library():
     L.fhe_ckks_rns_diag_sum_dev.argtypes = [_pp, _uint, _vp, _pp, ctypes.POINTER(_u64), _uint, _uint, _vp, _uint, _vp, _vp, _sz, _vp]
     L.fhe_ckks_rns_diag_workspace_bytes.argtypes = [_u64, _uint, _sz, _uint, _uint]
     L.fhe_ckks_rns_diag_workspace_bytes.restype = _sz
+    L.fhe_ckks_rns_bsgs_dev.argtypes = [_pp, _uint, _vp, _pp, ctypes.POINTER(_u64), _uint, _pp, ctypes.POINTER(_u64), _uint, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_rns_bsgs_workspace_bytes.argtypes = [_u64, _uint, _sz, _uint, _uint]
+    L.fhe_ckks_rns_bsgs_workspace_bytes.restype = _sz
     L.fhe_ckks_rns_lincomb_dev.argtypes = [_pp, _uint, _pp, _uint, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _uint, _vp, _sz, _vp]
     L.fhe_ckks_rns_dot_dev.argtypes = [_pp, _uint, _vp, _vp, _uint, _pp, _pp, _uint, ctypes.POINTER(_u64), _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
@@ -880,6 +885,24 @@ def ckks_rns_diag_sum_dev(plans, special, d_gks, gs, key_limbs, d_pts, outputs, 
 
 def ckks_rns_diag_workspace_bytes(n, limbs, batch, count, outputs):
     return int(load_library().fhe_ckks_rns_diag_workspace_bytes(n, limbs, batch, count, outputs))
+
+
+def ckks_rns_bsgs_dev(plans, special, d_baby_gks, baby_gs, d_giant_gks, giant_gs, key_limbs, d_pts, d_in, d_out, batch, stream=None, limbs=None, babies=None,
+                      giants=None):
+    """fhe_ckks_rns_bsgs_dev: [limbs][2][batch][n] -> [limbs][2][batch][n], sum_a sigma_{giant_gs[a]}(sum_b m_{a,b} (.)
+    sigma_{baby_gs[b]}(in)) with d_pts [giants][babies][limbs + 1][n] and the giant steps' rotations hoisted; each key list holds
+    device pointers, None (NULL) where the element is 1"""
+    def arrays(d_gks, gs):
+        return (None if d_gks is None else (_vp * max(len(d_gks), 1))(*d_gks)), (None if gs is None else (_u64 * max(len(gs), 1))(*gs))
+    bk, bg = arrays(d_baby_gks, baby_gs)
+    gk, gg = arrays(d_giant_gks, giant_gs)
+    _check(load_library().fhe_ckks_rns_bsgs_dev(_plan_array(plans), len(plans) if limbs is None else limbs, _handle(special), bk, bg,
+                                                len(baby_gs) if babies is None else babies, gk, gg, len(giant_gs) if giants is None else giants, key_limbs, d_pts,
+                                                d_in, d_out, batch, stream))
+
+
+def ckks_rns_bsgs_workspace_bytes(n, limbs, batch, babies, giants):
+    return int(load_library().fhe_ckks_rns_bsgs_workspace_bytes(n, limbs, batch, babies, giants))
 
 
 def ckks_rns_lincomb_dev(plans, d_cts, w, k, outputs, d_out, batch, stream=None, limbs=None, count=None):

@@ -484,6 +484,33 @@ class RnsCiphertext:
             acc = part if acc is None else acc + part
         return acc
 
+    def linear_transform_hoisted(self, lt, keys):
+        """M w for a LinearTransform from one call (fhe_ckks_rns_bsgs_dev): the inner sums stay in the basis Q P,
+        a giant step divides only its second component by P before its key switch, and one modulus-down finishes the sum.
+        keys as for linear_transform: step -> RnsGaloisKey for every step of lt.required_steps(), a missing one raises
+        KeyError(step).  Level unchanged; the scale multiplies; the caller rescales.  The words differ from linear_transform's
+        by its roundings; both are within their noise bounds of the product."""
+        missing = [st for st in lt.required_steps() if st not in keys]
+        if missing:
+            raise KeyError(missing[0])
+        torch = _torch()
+        pts, n = lt.pts, self.param.n
+        baby = [keys[i] if i else None for i in lt.baby]
+        giant = [keys[lt.n1 * j] if j else None for j in lt.giant]
+        giant_gs = [galois_element(n, lt.n1 * j) for j in lt.giant]
+        if pts.param != self.param or any(gk is not None and gk.param != self.param for gk in baby + giant):
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the plaintexts or a Galois key are not of this ciphertext's chain")
+        if pts.level != self.level:
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, f"the plaintexts are at level {pts.level}, the ciphertext at {self.level}")
+        for g, gk in zip(pts.gs + giant_gs, baby + giant):
+            if g != 1 and gk.g != g:
+                raise ValueError(f"linear_transform_hoisted: a key is of g={gk.g}, its step's element is {g}")
+        out = torch.empty_like(self.d)
+        binding.ckks_rns_bsgs_dev(self.param.plans(self.level), self.param.special_plan(), [None if gk is None else gk.d_gk.data_ptr() for gk in baby], pts.gs,
+                                  [None if gk is None else gk.d_gk.data_ptr() for gk in giant], giant_gs, len(self.param.moduli), pts.d_pts.data_ptr(),
+                                  self.d.data_ptr(), out.data_ptr(), self.batch)
+        return RnsCiphertext(self.param, out, self.level, self.scale * pts.scale)
+
     def _plain(self, m):
         """signed rows (n,) or (batch, n) -> evals [level + 1][batch][n]"""
         torch = _torch()

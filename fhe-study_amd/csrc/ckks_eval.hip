@@ -16,6 +16,9 @@
 //              coefficient-wise lift), and pi_g is folded into the key sums' and the divide-and-round's reads
 //   diag sum    out_o = sum_r m_{o,r} (.) sigma_{g_r}(ct) for plaintexts known modulo P as well: the key sums of all
 //              elements are weighted and added in the basis Q P by one fused kernel, and each output takes one division by P
+//   bsgs        out = sum_a sigma_{h_a}(sum_b m_{a,b} (.) sigma_{g_b}(ct)): the inner sums stay in the basis Q P; a giant
+//              step divides only its second component by P, switches it against gk_{h_a} in Q P and adds the permuted first
+//              component as it is; one division by P of the sum over the giant steps finishes
 //   lincomb     out_o = sum_r w[o][r] ct_r + (k[o], 0) per limb, the inputs read once for up to four outputs
 //   dot         relin(sum_r w_r tensor(a_r, b_r)): the tensors of all pairs summed by one fused kernel into the
 //              slot ct x ct stages its tensor in, then relin as it is: one key switch whatever the number of pairs
@@ -241,8 +244,48 @@ __global__ __launch_bounds__(256) void ckks_rns_diagmac_kernel(const u64 *__rest
     }
 }
 
+// ---- plaintext linear transforms: the hoisted giant steps -----------------------------------------------------------
+// One target limb i of a giant step h of the baby-step giant-step sum, in the extended basis, over `count` words a component
+// (rows of n = 2^L).  u is U_{a,i}, the inner sum of the giant step as ckks_rns_diagmac_kernel left it (canonical, its two
+// components u_cs words apart); v is V_i, the sum over the giant steps (components v_cs apart).
+//   SWITCH:  v[0][e] (+)= u[0][pi_h(e)] + sum_j D_j[pi_h(e)] key[j][0][x],  v[1][e] (+)= sum_j D_j[pi_h(e)] key[j][1][x],  x = e mod n
+//            D the digits of w_a, the second component of U_a divided by P: `dig`, `own`, `own_j`, `key` are key_sum's.  The first
+//            component of U_a is not divided: it is permuted and added as it is, so u's second component is not read.
+//   otherwise (h = 1, the identity): v[c][e] (+)= u[c][e] for both components; no digit or key is read.
+// CARRY: v holds the canonical words of the former giant steps and is added to; otherwise it is written (the call's first step).
+// Overflow.  Every word read is canonical.  The identity adds two words below q < 2^63 in 64 bits (add63).  SWITCH: on entry
+// the accumulators hold u[0][pi_h(e)] + v[0][e] < 2q, and v[1][e] < q: each is below q^2 (q >= 5), so each stands for the one
+// term that key_sum allows on entry (held = 1).  q < 2^62: that and k <= 8 terms below 2^124 are below 9 2^124 < 2^128, folded
+// once at the end.  2^62 <= q < 2^63: key_sum folds before every digit of odd index, so the accumulators hold the entry words
+// (below 2^64) and digit 0's term, or a canonical carry-over below 2^63 and two terms below 2^126: less than 2^127 + 2^64.
+template <bool SWITCH, bool CARRY>
+__global__ __launch_bounds__(256) void ckks_rns_giantmac_kernel(const u64 *__restrict__ dig, u64 dig_stride, const u64 *__restrict__ own, u32 own_j,
+                                                                const u64 *__restrict__ key, u64 key_stride, const u64 *__restrict__ u, u64 u_cs,
+                                                                u64 *__restrict__ v, u64 v_cs, u32 k, u32 L, u64 count, u32 g, Mod m) {
+    const u64 stride = (u64)gridDim.x * 256, n = 1ull << L;
+    const bool wide = (m.q >> 62) != 0;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        if (!SWITCH) {
+            const u64 u0 = u[i], u1 = u[u_cs + i];
+            v[i] = CARRY ? add63(v[i], u0, m) : u0;
+            v[v_cs + i] = CARRY ? add63(v[v_cs + i], u1, m) : u1;
+        } else {
+            const u64 x = i & (n - 1), s = i - x + galois_index((u32)x, g, L);
+            MacAcc a0, a1;
+            a0.v = u[s];
+            if (CARRY) {
+                a0.v += v[i];
+                a1.v = v[v_cs + i];
+            }
+            key_sum(a0, a1, 1, dig, dig_stride, own, own_j, key, key_stride, n, x, s, k, wide, m);
+            v[i] = wide ? a0.fold63(m) : a0.fold(m);
+            v[v_cs + i] = wide ? a1.fold63(m) : a1.fold(m);
+        }
+    }
+}
+
 // ---- polynomial evaluation: fused sums by public scalars ------------------------------------------------------------
-constexpr u32 kLinGroup = 16;      // inputs of one launch, passed by value
+constexpr u32 kLinGroup = 16;     // inputs of one launch, passed by value
 constexpr u32 kLinOutputs = 4;     // outputs whose accumulators one launch keeps in registers: 8 waves a SIMD still (§27)
 
 // The inputs of one launch for one limb.  Indexed by the loop counter, which is uniform: scalar loads from the kernel-argument
@@ -610,17 +653,21 @@ int check_switch_keys(const void *const *d_gks, const uint64_t *gs, unsigned cou
     return FHE_OK;
 }
 
-// The frame of a key-switch call: chunks of chunk_rows ciphertexts, `words` words of workspace a ciphertext (none: the call
-// only needs a device), the inverses of P, and body(r0, cr, W, pinv) per chunk
+// The frame of a key-switch call: chunks of chunk_rows ciphertexts, `words` words of workspace a ciphertext in `slot` (none:
+// the call only needs a device), the inverses of P, and body(r0, cr, W, pinv) per chunk
 template <class Body>
-int switch_call(const Chain &c, u64 batch, u64 words, hipStream_t st, Body body) {
+int switch_call_in(int slot, const Chain &c, u64 batch, u64 words, hipStream_t st, Body body) {
     const u64 cb = chunk_rows(c, batch);
     void *w = nullptr;
     int rc, dev;
-    if ((rc = words ? fhe_workspace_get(kCkksEvalSlot, (size_t)(words * cb * 8), st, &w) : fhe_current_device(&dev)) != FHE_OK) return rc;
+    if ((rc = words ? fhe_workspace_get(slot, (size_t)(words * cb * 8), st, &w) : fhe_current_device(&dev)) != FHE_OK) return rc;
     u64 pinv[fhe::kRnsMaxLimbs];
     for (unsigned i = 0; i < c.k; i++) pinv[i] = fhe::host::inv_mod(c.p[i]->q, c.p[c.k]->q);
     return for_chunks(batch, cb, [&](u64 r0, u64 cr) { return body(r0, cr, (u64 *)w, pinv); });
+}
+template <class Body>
+int switch_call(const Chain &c, u64 batch, u64 words, hipStream_t st, Body body) {
+    return switch_call_in(kCkksEvalSlot, c, batch, words, st, body);
 }
 
 }  // namespace
@@ -886,6 +933,34 @@ int diagmac_launch(unsigned nout, bool carry, int L, hipStream_t st, unsigned gr
     return fhe_fail(FHE_E_INVALID, "ckks_rns_diagmac: %u outputs in one launch", nout);
 }
 
+// The diagmac launches of outputs o0 .. o0 + nout of a diagonal sum over the rows of `ct`, in groups of kDiagGroup elements.
+// `extended`: the sums U' of §24 in the basis Q P, over the k + 1 targets, into the sets 0 .. nout - 1 of b's T (the digits are
+// read only for an element other than 1).  Otherwise the finished sums over the k chain limbs, into the rows out0 of output o0,
+// the outputs o_words apart.
+int diagmac_rows(const Chain &c, const u64 *const *gks, const uint64_t *gs, unsigned count, unsigned key_limbs, const u64 *pts, unsigned o0, unsigned nout,
+                 bool extended, const SwitchBufs &b, LimbRows<const u64> ct, LimbRows<u64> out0, u64 o_words, hipStream_t st) {
+    const u64 n = c.n, slab = b.slab, pt_os = (u64)count * (c.k + 1) * n;
+    const unsigned k = c.k;
+    for (unsigned i = 0; i < (extended ? k + 1 : k); i++) {
+        for (unsigned e0 = 0; e0 < count; e0 += fhe::kDiagGroup) {
+            fhe::DiagGroup grp{};
+            grp.count = std::min<unsigned>(fhe::kDiagGroup, count - e0);
+            for (unsigned r = 0; r < grp.count; r++) {
+                grp.g[r] = (u32)gs[e0 + r];
+                grp.key[r] = grp.g[r] == 1 ? nullptr : gks[e0 + r] + (u64)(i < k ? i : key_limbs) * 2 * n;
+                grp.pt[r] = pts + (((u64)o0 * count + e0 + r) * (k + 1) + i) * n;
+            }
+            u64 *dst = extended ? b.T + 2ull * i * slab : out0.of(i);
+            const u64 pmod = !extended ? 1 : i < k ? c.p[k]->q % c.p[i]->q : 0;
+            const int rc = diagmac_launch(nout, e0 > 0, (int)c.L, st, fhe_ew_grid(slab), extended ? b.D_of(i) : nullptr, slab, i < k ? ct.of(i) : nullptr, ct.cs, i,
+                                          (u64)(key_limbs + 1) * 2 * n, pt_os, dst, extended ? slab : ct.cs, extended ? b.set : o_words, k, c.L, slab, pmod, grp,
+                                          c.p[i]->mod);
+            if (rc != FHE_OK) return rc;
+        }
+    }
+    return FHE_OK;
+}
+
 // §24: rows r0 .. r0 + cr of in [k][2][batch][n] -> the same rows of out [outputs][k][2][batch][n], out_o = sum_r m_{o,r} (.)
 // sigma_{g_r}(in).  `switched` (some g != 1): the digits of c1 once; per launch of up to kDiagOutputs outputs, U over the k + 1
 // targets in groups of kDiagGroup elements; per output one modulus-down of U.  Otherwise the sums land in `out` and W is not used.
@@ -894,30 +969,14 @@ int diag_rows(const Chain &c, const u64 *const *gks, const uint64_t *gs, unsigne
     const u64 n = c.n, slab = cr * n;
     const unsigned k = c.k;
     const SwitchBufs b(W, k, std::min<unsigned>(outputs, fhe::kDiagOutputs), slab);   // set o of T is the U of a launch's output o
-    const u64 o_words = 2ull * k * batch * n, pt_os = (u64)count * (k + 1) * n;
+    const u64 o_words = 2ull * k * batch * n;
     const LimbRows<const u64> ct{in + r0 * n, 2 * batch * n, batch * n};
     auto out_rows = [&](unsigned o) { return LimbRows<u64>{out + o * o_words + r0 * n, ct.ls, ct.cs}; };
     int rc;
     if (switched && (rc = digit_rows(c, [&](unsigned limb) { return ct.of(limb) + ct.cs; }, b, cr, st)) != FHE_OK) return rc;
     for (unsigned o0 = 0; o0 < outputs; o0 += fhe::kDiagOutputs) {
         const unsigned nout = std::min<unsigned>(fhe::kDiagOutputs, outputs - o0);
-        for (unsigned i = 0; i < (switched ? k + 1 : k); i++) {
-            for (unsigned e0 = 0; e0 < count; e0 += fhe::kDiagGroup) {
-                fhe::DiagGroup grp{};
-                grp.count = std::min<unsigned>(fhe::kDiagGroup, count - e0);
-                for (unsigned r = 0; r < grp.count; r++) {
-                    grp.g[r] = (u32)gs[e0 + r];
-                    grp.key[r] = grp.g[r] == 1 ? nullptr : gks[e0 + r] + (u64)(i < k ? i : key_limbs) * 2 * n;
-                    grp.pt[r] = pts + (((u64)o0 * count + e0 + r) * (k + 1) + i) * n;
-                }
-                u64 *dst = switched ? b.T + 2ull * i * slab : out_rows(o0).of(i);
-                const u64 pmod = !switched ? 1 : i < k ? c.p[k]->q % c.p[i]->q : 0;
-                if ((rc = diagmac_launch(nout, e0 > 0, (int)c.L, st, fhe_ew_grid(slab), switched ? b.D_of(i) : nullptr, slab, i < k ? ct.of(i) : nullptr, ct.cs, i,
-                                         (u64)(key_limbs + 1) * 2 * n, pt_os, dst, switched ? slab : ct.cs, switched ? b.set : o_words, k, c.L, slab, pmod, grp,
-                                         c.p[i]->mod)) != FHE_OK)
-                    return rc;
-            }
-        }
+        if ((rc = diagmac_rows(c, gks, gs, count, key_limbs, pts, o0, nout, switched, b, ct, out_rows(o0), o_words, st)) != FHE_OK) return rc;
         for (unsigned o = 0; switched && o < nout; o++)
             if ((rc = special_down(c, b, o, {}, out_rows(o0 + o), pinv, 0u, st)) != FHE_OK) return rc;
     }
@@ -955,6 +1014,120 @@ extern "C" int fhe_ckks_rns_diag_sum_dev(const fhe_ntt_plan *const *plans, unsig
     hipStream_t st = (hipStream_t)hip_stream;
     return switch_call(c, batch, switched ? diag_words_per_row(c, outputs) : 0, st, [&](u64 r0, u64 cr, u64 *W, const u64 *pinv) {
         return diag_rows(c, (const u64 *const *)d_gks, gs, count, key_limbs, (const u64 *)d_pts, outputs, switched, pinv, (const u64 *)d_in, (u64 *)d_out, batch, r0, cr, W, st);
+    });
+}
+
+// ---- plaintext linear transforms: the hoisted giant steps -----------------------------------------------------------
+namespace {
+
+constexpr int kCkksBsgsSlot = 13;   // fhe_workspace_get slot of fhe_ckks_rns_bsgs_dev (12 is the other entry points')
+
+// The modulus-down by P of ONE component, the special prime's side of moddown_rows over one slab: X holds the component's
+// residues modulo P in coefficients; they are lifted to the k chain limbs and transformed in E (k slabs), and
+// out_i = (x_i - E_i) pinv[i] mod q_i.  The divide-and-round kernel takes two components: the slab goes to it as two halves.
+int moddown_one(const Chain &c, const u64 *X, u64 *E, u64 slab, LimbRows<const u64> x, LimbRows<u64> out, const u64 *pinv, hipStream_t st) {
+    int rc;
+    fhe::LiftArgs a{};
+    for (unsigned i = 0; i < c.k; i++) lift_target(&a, c.p[i], (u64)i * slab);
+    if ((rc = lift_launch(false, X, E, slab, c.p[c.k]->q, a, c.L, st)) != FHE_OK) return rc;
+    for (unsigned i = 0; i < c.k; i++)
+        if ((rc = fhe_ntt_forward_dev(c.p[i], E + a.off[i], E + a.off[i], slab >> c.L, st)) != FHE_OK) return rc;
+    const u64 half = slab / 2;                                       // n >= 2 divides the slab
+    for (unsigned i = 0; i < c.k; i++)
+        if ((rc = launch("ckks_rns_divround", (int)c.L, st, fhe::ckks_rns_divround_kernel<false>, fhe_ew_grid(slab), 256, x.of(i), half, (const u64 *)E + a.off[i], half,
+                         (const u64 *)nullptr, (u64)0, out.of(i), half, half, pinv[i], c.p[i]->mod, 0u, c.L)) != FHE_OK)
+            return rc;
+    return FHE_OK;
+}
+
+// words of workspace per ciphertext of a chunk: the key switch of the ciphertext with kDiagOutputs sets U and the set V, and
+// the digits of one giant step (its C and D) with w_a in the place of its E
+u64 bsgs_words_per_row(const Chain &c) { return (SwitchBufs::words(c.k, fhe::kDiagOutputs + 1) + SwitchBufs::words(c.k, 0) - c.k) * c.n; }
+
+// §30: rows r0 .. r0 + cr of in [k][2][batch][n] -> the same rows of out [k][2][batch][n], some element other than 1.  The
+// digits of c1 once (where a baby step has a key); per pair of giant steps their inner sums U in the basis Q P; per giant step
+// with a key the division by P of U's second component alone, its digits, and one accumulate launch per target into V (the
+// identity: the accumulate alone); one modulus-down of V.
+int bsgs_rows(const Chain &c, const u64 *const *bks, const uint64_t *bgs, unsigned babies, bool baby_switched, const u64 *const *gks, const uint64_t *ggs,
+              unsigned giants, unsigned key_limbs, const u64 *pts, const u64 *pinv, const u64 *in, u64 *out, u64 batch, u64 r0, u64 cr, u64 *W, hipStream_t st) {
+    const u64 n = c.n, slab = cr * n, key_stride = (u64)(key_limbs + 1) * 2 * n;
+    const unsigned k = c.k, vset = fhe::kDiagOutputs;
+    const SwitchBufs b(W, k, vset + 1, slab);                        // sets 0 .. vset - 1: the U of a launch's giant steps; set vset: V
+    const SwitchBufs gb(b.E + 2ull * k * slab, k, 0, slab);          // the digits of w_a: they leave the ciphertext's in place
+    u64 *w = gb.E;                                                   // w_a [k] slabs of evals, limb i's own digit
+    const LimbRows<const u64> ct{in + r0 * n, 2 * batch * n, batch * n};
+    int rc;
+    if (baby_switched && (rc = digit_rows(c, [&](unsigned limb) { return ct.of(limb) + ct.cs; }, b, cr, st)) != FHE_OK) return rc;
+    for (unsigned a0 = 0; a0 < giants; a0 += fhe::kDiagOutputs) {
+        const unsigned nout = std::min<unsigned>(fhe::kDiagOutputs, giants - a0);
+        if ((rc = diagmac_rows(c, bks, bgs, babies, key_limbs, pts, a0, nout, true, b, ct, {}, 0, st)) != FHE_OK) return rc;
+        for (unsigned o = 0; o < nout; o++) {
+            const unsigned a = a0 + o;
+            const u32 h = (u32)ggs[a];
+            if (h != 1) {
+                u64 *up1 = b.TP(o) + slab;                           // U_{a,P,1}: in coefficients, in place; nothing else reads it
+                if ((rc = fhe_ntt_inverse_dev(c.p[k], up1, up1, cr, st)) != FHE_OK) return rc;
+                if ((rc = moddown_one(c, up1, b.E, slab, {b.T_of(o) + slab, 2 * slab, slab}, {w, slab, slab}, pinv, st)) != FHE_OK) return rc;
+                if ((rc = digit_rows(c, [&](unsigned limb) { return (const u64 *)w + limb * slab; }, gb, cr, st)) != FHE_OK) return rc;
+            }
+            for (unsigned i = 0; i <= k; i++) {
+                const bool carry = a > 0;
+                auto kernel = h != 1 ? (carry ? fhe::ckks_rns_giantmac_kernel<true, true> : fhe::ckks_rns_giantmac_kernel<true, false>)
+                                     : (carry ? fhe::ckks_rns_giantmac_kernel<false, true> : fhe::ckks_rns_giantmac_kernel<false, false>);
+                const u64 *col = h != 1 ? gks[a] + (u64)(i < k ? i : key_limbs) * 2 * n : nullptr;
+                if ((rc = launch("ckks_rns_giantmac", (int)c.L, st, kernel, fhe_ew_grid(slab), 256, (const u64 *)gb.D_of(i), slab, i < k ? (const u64 *)w + i * slab : nullptr, i,
+                                 col, key_stride, (const u64 *)b.T_of(o) + 2ull * i * slab, slab, b.T_of(vset) + 2ull * i * slab, slab, k, c.L, slab, h, c.p[i]->mod)) != FHE_OK)
+                    return rc;
+            }
+        }
+    }
+    return special_down(c, b, vset, {}, {out + r0 * n, ct.ls, ct.cs}, pinv, 0u, st);
+}
+
+bool bsgs_counts_ok(unsigned babies, unsigned giants) {
+    return babies >= 1 && babies <= FHE_CKKS_GALOIS_MAX_COUNT && giants >= 1 && giants <= FHE_CKKS_DIAG_MAX_OUTPUTS;
+}
+
+}  // namespace
+
+extern "C" size_t fhe_ckks_rns_bsgs_workspace_bytes(uint64_t n, unsigned limbs, size_t batch, unsigned babies, unsigned giants) {
+    Chain c;
+    if (!chain_of(n, limbs, batch, &c) || !bsgs_counts_ok(babies, giants)) return 0;
+    return (size_t)(bsgs_words_per_row(c) * chunk_rows(c, batch) * 8);
+}
+
+extern "C" int fhe_ckks_rns_bsgs_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *const *d_baby_gks,
+                                     const uint64_t *baby_gs, unsigned babies, const void *const *d_giant_gks, const uint64_t *giant_gs, unsigned giants,
+                                     unsigned key_limbs, const void *d_pts, const void *d_in, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_rns_bsgs_dev";
+    Chain c;
+    int rc = check_chain(plans, limbs, special, true, &c, who);
+    if (rc != FHE_OK) return rc;
+    if ((rc = check_key_limbs(c, key_limbs, who)) != FHE_OK) return rc;
+    if (babies < 1 || babies > FHE_CKKS_GALOIS_MAX_COUNT) return fhe_fail(FHE_E_INVALID, "%s: babies=%u must be in [1, %d]", who, babies, FHE_CKKS_GALOIS_MAX_COUNT);
+    if (giants < 1 || giants > FHE_CKKS_DIAG_MAX_OUTPUTS) return fhe_fail(FHE_E_INVALID, "%s: giants=%u must be in [1, %d]", who, giants, FHE_CKKS_DIAG_MAX_OUTPUTS);
+    if (batch == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, 2ull * c.k * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!baby_gs || !giant_gs || !d_pts || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_pts) || misaligned8(d_in) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 ct_bytes = 2ull * c.k * batch * n * 8;
+    bool baby_switched = false, giant_switched = false;
+    if ((rc = check_switch_keys(d_baby_gks, baby_gs, babies, true, n, key_limbs, d_out, ct_bytes, &baby_switched, "fhe_ckks_rns_bsgs_dev, baby steps")) != FHE_OK) return rc;
+    if ((rc = check_switch_keys(d_giant_gks, giant_gs, giants, true, n, key_limbs, d_out, ct_bytes, &giant_switched, "fhe_ckks_rns_bsgs_dev, giant steps")) != FHE_OK) return rc;
+    if (overlaps_any(d_out, ct_bytes, {{d_in, ct_bytes}, {d_pts, (u64)giants * babies * (c.k + 1) * n * 8}}))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the ciphertexts or the plaintexts", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!baby_switched && !giant_switched) {
+        // every element the identity: the plain sum over all giants x babies products, as a diagonal sum of one output
+        const std::vector<uint64_t> ones((size_t)giants * babies, 1);
+        return switch_call_in(kCkksBsgsSlot, c, batch, 0, st, [&](u64 r0, u64 cr, u64 *W, const u64 *pinv) {
+            return diag_rows(c, nullptr, ones.data(), giants * babies, key_limbs, (const u64 *)d_pts, 1, false, pinv, (const u64 *)d_in, (u64 *)d_out, batch, r0, cr, W, st);
+        });
+    }
+    return switch_call_in(kCkksBsgsSlot, c, batch, bsgs_words_per_row(c), st, [&](u64 r0, u64 cr, u64 *W, const u64 *pinv) {
+        return bsgs_rows(c, (const u64 *const *)d_baby_gks, baby_gs, babies, baby_switched, (const u64 *const *)d_giant_gks, giant_gs, giants, key_limbs,
+                         (const u64 *)d_pts, pinv, (const u64 *)d_in, (u64 *)d_out, batch, r0, cr, W, st);
     });
 }
 

@@ -708,6 +708,32 @@ int fhe_ckks_rns_diag_sum_dev(const fhe_ntt_plan *const *plans, unsigned limbs, 
                               void *hip_stream);
 size_t fhe_ckks_rns_diag_workspace_bytes(uint64_t n, unsigned limbs, size_t batch, unsigned count, unsigned outputs);
 
+/* ---- CKKS on the RNS chain: baby-step giant-step linear transforms with hoisted giant steps (ckks_eval.hip) ----
+ *   fhe_ckks_rns_bsgs_dev         d_out [limbs][2][batch][n] = sum_{a < giants} sigma_{giant_gs[a]}(sum_{b < babies} m_{a,b} (.)
+ *            sigma_{baby_gs[b]}(d_in)) for d_in [limbs][2][batch][n] and the plaintexts d_pts [giants][babies][limbs + 1][n], the
+ *            layout and contract of fhe_ckks_rns_diag_sum_dev's with `giants` for its outputs.  With i over {0 .. limbs - 1, P}:
+ *            (1) U_{a,i,c}: the key sums of the baby steps weighted by the plaintexts, plus (P mod q_i) times the addends
+ *                pi_{g_b}(c0) in component 0 and c1 (for g_b = 1) in component 1; the digits of c1 are made once per chunk.
+ *            (2) V = 0 in the basis Q P.  For h_a = 1: V += U_a.  Otherwise w_a = (U_{a,i,1} - lift(U_{a,P,1})) P^-1 mod q_i, the
+ *                modulus-down of component 1 of U_a alone; D^(a) the digits of w_a; S_{a,i,c}[x] = sum_j D^(a)_{j,i}[pi_{h_a}(x)]
+ *                gk_{h_a}[j][i][c][x]; V_{i,0} += S_{a,i,0} + U_{a,i,0}[pi_{h_a}(x)], V_{i,1} += S_{a,i,1}, on every i, P included.
+ *            (3) d_out = the modulus-down by P of both components of V.
+ *            Every word is canonical modulo its limb's prime, so the result does not depend on the order or grouping of the
+ *            giant steps.  One division by P of one component per giant step with a key and one of both components per call,
+ *            where the composition of fhe_ckks_rns_diag_sum_dev and fhe_ckks_rns_galois_dev takes two of both per giant step.
+ *            An element 1 is the identity in either role: it takes no key and its entry is not read.  Where every element is
+ *            1 no digit, transform or modulus-down runs.  Level unchanged; the scale is the ciphertext's times the plaintexts'.
+ *   fhe_ckks_rns_bsgs_workspace_bytes  the library workspace that call takes at most; 0 for a shape it refuses
+ * d_baby_gks, baby_gs, d_giant_gks and giant_gs are HOST arrays.  The conditions are those of fhe_ckks_rns_diag_sum_dev for
+ * both lists, and: FHE_E_INVALID for babies outside [1, FHE_CKKS_GALOIS_MAX_COUNT] or giants outside [1,
+ * FHE_CKKS_DIAG_MAX_OUTPUTS]; FHE_E_NULL for a NULL key of an element other than 1, baby or giant; FHE_E_INVALID for an output
+ * that overlaps the input, a key or the plaintexts.  Nothing is written on rejection; batch = 0 is a no-op. */
+int fhe_ckks_rns_bsgs_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special,
+                          const void *const *d_baby_gks, const uint64_t *baby_gs, unsigned babies,
+                          const void *const *d_giant_gks, const uint64_t *giant_gs, unsigned giants, unsigned key_limbs,
+                          const void *d_pts, const void *d_in, void *d_out, size_t batch, void *hip_stream);
+size_t fhe_ckks_rns_bsgs_workspace_bytes(uint64_t n, unsigned limbs, size_t batch, unsigned babies, unsigned giants);
+
 /* ---- CKKS on the RNS chain: fused sums of ciphertexts by public scalars (ckks_eval.hip) ----
  *   fhe_ckks_rns_lincomb_dev      d_out [outputs][limbs][2][batch][n]: per limb i, component c and word e
  *            out_o[c][e] = (sum_{r < count} w[o][r][i] ct_r[c][e] + [c = 0] k[o][i]) mod q_i.
