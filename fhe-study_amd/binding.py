@@ -99,6 +99,8 @@ EXPORTS = [
     "fhe_ckks_rns_dot_dev",
     # CKKS on the RNS chain: baby-step giant-step linear transforms with hoisted giant steps (ckks_eval.hip)
     "fhe_ckks_rns_bsgs_dev", "fhe_ckks_rns_bsgs_workspace_bytes",
+    # CKKS: the encoder up to n = 2^16, a two-pass transform above 2^13 (ckks_client.hip)
+    "fhe_ckks_embed_twiddles", "fhe_ckks_embed_encode_dev", "fhe_ckks_embed_decode_dev", "fhe_ckks_embed_workspace_bytes",
 ]
 FHE_CKKS_GALOIS_MAX_COUNT = 256              # include/fhe_ntt.h: the most Galois elements of one fhe_ckks_rns_galois_dev call
 FHE_CKKS_DIAG_MAX_OUTPUTS = 64               # include/fhe_ntt.h: the most outputs of one fhe_ckks_rns_diag_sum_dev call
@@ -309,6 +311,11 @@ def load_library():
     L.fhe_ckks_twiddles.argtypes = [_u64, _vp]
     L.fhe_ckks_encode_dev.argtypes = [_u64, _f64, _vp, _vp, _sz, _vp, _sz, _vp]
     L.fhe_ckks_decode_dev.argtypes = [_u64, _f64, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_embed_twiddles.argtypes = [_u64, _vp]
+    L.fhe_ckks_embed_encode_dev.argtypes = [_u64, _f64, _vp, _vp, _sz, _vp, _sz, _vp]
+    L.fhe_ckks_embed_decode_dev.argtypes = [_u64, _f64, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_embed_workspace_bytes.argtypes = [_u64, _sz]
+    L.fhe_ckks_embed_workspace_bytes.restype = _sz
     L.fhe_ckks_secret_key_dev.argtypes = [_vp, ctypes.c_char_p, _u64, _vp, _vp]
     L.fhe_ckks_public_key_dev.argtypes = [_vp, ctypes.c_char_p, _u64, _vp, _vp, _uint, _vp, _vp]
     L.fhe_ckks_encrypt_dev.argtypes = [_vp, ctypes.c_char_p, _u64, _vp, _vp, _sz, _vp, _uint, _vp, _sz, _vp]
@@ -782,6 +789,28 @@ def ckks_encode_dev(n, delta, d_tw, d_z, z_stride, d_out, batch, stream=None):
 def ckks_decode_dev(n, delta, d_tw, d_p, d_out, batch, stream=None):
     """d_p [batch][n] int64 -> d_out [batch][n/2] complex"""
     _check(load_library().fhe_ckks_decode_dev(n, delta, d_tw, d_p, d_out, batch, stream))
+
+
+def ckks_embed_twiddles(n):
+    """ckks_twiddles for n <= 2^16: the table of the ckks_embed_* calls"""
+    out = np.empty(n, dtype=np.complex128)
+    _check(load_library().fhe_ckks_embed_twiddles(n, out.ctypes.data_as(_vp)))
+    return out
+
+
+def ckks_embed_encode_dev(n, delta, d_tw, d_z, z_stride, d_out, batch, stream=None):
+    """ckks_encode_dev for n <= 2^16: two passes through the library workspace above 2^13"""
+    _check(load_library().fhe_ckks_embed_encode_dev(n, delta, d_tw, d_z, z_stride, d_out, batch, stream))
+
+
+def ckks_embed_decode_dev(n, delta, d_tw, d_p, d_out, batch, stream=None):
+    """ckks_decode_dev for n <= 2^16"""
+    _check(load_library().fhe_ckks_embed_decode_dev(n, delta, d_tw, d_p, d_out, batch, stream))
+
+
+def ckks_embed_workspace_bytes(n, batch):
+    """the library workspace of one ckks_embed_* call; 0 for n <= 2^13 and for a refused shape"""
+    return int(load_library().fhe_ckks_embed_workspace_bytes(n, batch))
 
 
 def ckks_secret_key_dev(plan, seed, key_row, d_s, stream=None):

@@ -33,17 +33,22 @@ class Param:
 
 
 class Encoder:
-    """encoder.rs: slot i < n/2 of a polynomial is its value at exp(i pi (2i+1) / n).  Holds fhe_ckks_twiddles(n) on the device."""
+    """encoder.rs: slot i < n/2 of a polynomial is its value at exp(i pi (2i+1) / n).  Holds fhe_ckks_twiddles(n) on the device.
+    n <= 2^13 runs the one-pass entry points as before; 2^14 <= n <= 2^16 the two-pass ones (fhe_ckks_embed_*)."""
 
     def __init__(self, n, delta):
         self.n, self.delta = int(n), float(delta)
-        self.d_tw = _torch().from_numpy(binding.ckks_twiddles(self.n).view(np.float64)).cuda()
+        big = self.n > 1 << 13
+        twiddles = binding.ckks_embed_twiddles if big else binding.ckks_twiddles
+        self._encode_dev = binding.ckks_embed_encode_dev if big else binding.ckks_encode_dev
+        self._decode_dev = binding.ckks_embed_decode_dev if big else binding.ckks_decode_dev
+        self.d_tw = _torch().from_numpy(twiddles(self.n).view(np.float64)).cuda()
 
     def encode_dev(self, d_z, batch, z_stride=None):
         """device complex128 [batch][n/2] -> device int64 [batch][n]"""
         torch = _torch()
         out = torch.empty((batch, self.n), dtype=torch.int64, device="cuda")
-        binding.ckks_encode_dev(self.n, self.delta, self.d_tw.data_ptr(), d_z.data_ptr(), self.n // 2 if z_stride is None else z_stride, out.data_ptr(), batch)
+        self._encode_dev(self.n, self.delta, self.d_tw.data_ptr(), d_z.data_ptr(), self.n // 2 if z_stride is None else z_stride, out.data_ptr(), batch)
         return out
 
     def encode(self, z):
@@ -56,7 +61,7 @@ class Encoder:
     def decode_dev(self, d_p, batch, scale=None):
         torch = _torch()
         out = torch.empty((batch, self.n // 2, 2), dtype=torch.float64, device="cuda")
-        binding.ckks_decode_dev(self.n, self.delta if scale is None else float(scale), self.d_tw.data_ptr(), d_p.data_ptr(), out.data_ptr(), batch)
+        self._decode_dev(self.n, self.delta if scale is None else float(scale), self.d_tw.data_ptr(), d_p.data_ptr(), out.data_ptr(), batch)
         return out
 
     def decode(self, p, scale=None):

@@ -29,6 +29,11 @@
 // into bits 2 and 3: the bank bits of the three patterns are (b3, b4, b5, b6 ^ b3) -> 16 values, (b0, b1, b2, b6) -> 16
 // values, and the identity: conflict-free in every round for M >= 128 (smaller rings pack several polynomials into a
 // group and may meet 2-way conflicts; they are not the sizes that matter).
+//
+// N = 2^14 .. 2^16 (fhe_ckks_embed_*): M = N/2 points do not fit a workgroup's LDS; the transform runs as
+// two passes of ckks_fft sub-transforms, M = M1 M2, through [batch][M] complex values of workspace slot 11, with the same
+// table (the sub-transforms read it with a stride, the factor between the passes is w^(4 j2 k1)), the same load-side work
+// in front of pass 1 and the same store-side work behind pass 2.  The kernels and their tile are further down.
 #include <cmath>
 
 #include "bfv_client_kernels.hpp"
@@ -125,8 +130,10 @@ struct CkksShape {
 __device__ __forceinline__ u32 swz(u32 a) { return a ^ (((a >> 4) & 3u) | (((a >> 6) & 1u) * 12u)); }
 
 // One polynomial: X_k = sum_j x_j exp(S 2 pi i jk / M), x_j = in(j), X_k to out(k, .); thread t of the polynomial's TP.
-// Every thread of the workgroup calls it (the rounds meet at barriers).
-template <int LM, int S, class In, class Out>
+// Every thread of the workgroup calls it (the rounds meet at barriers).  TS: the table is that of a ring 2^TS times as
+// large (entry k of this transform's own table is entry k << TS of it); LS: the stride in doubles of the points in sre and
+// sim.  Both are constants of the instantiation: at the defaults the indices are what they were before the two-pass kernels.
+template <int LM, int S, int TS = 0, int LS = 1, class In, class Out>
 __device__ __forceinline__ void ckks_fft(double *sre, double *sim, u32 t, const double *__restrict__ tw, In in, Out out) {
     using Sh = CkksShape<LM>;
     constexpr int E = Sh::E, TP = Sh::TP, NR8 = Sh::NR8, LR = Sh::LR;
@@ -147,10 +154,10 @@ __device__ __forceinline__ void ckks_fft(double *sre, double *sim, u32 t, const 
             } else {
                 __syncthreads();
 #pragma unroll
-                for (int r = 0; r < 8; r++) v[r] = {sre[swz(t + r * TP)], sim[swz(t + r * TP)]};
+                for (int r = 0; r < 8; r++) v[r] = {sre[swz(t + r * TP) * LS], sim[swz(t + r * TP) * LS]};
                 cplx tws[3];
 #pragma unroll
-                for (int s = 0; s < 3; s++) tws[s] = tw_at<S>(tw, k << (LM + 1 - s - LNS));
+                for (int s = 0; s < 3; s++) tws[s] = tw_at<S>(tw, k << (LM + 1 - s - LNS + TS));
                 bfly<3, S, false>(v, tws);
             }
             if (rd == NR8 - 1 && LR == 0) {
@@ -161,7 +168,7 @@ __device__ __forceinline__ void ckks_fft(double *sre, double *sim, u32 t, const 
                 const u32 j0 = ((t >> LNS) << (LNS + 3)) + k;
 #pragma unroll
                 for (int p = 0; p < 8; p++) {
-                    const u32 a = swz(j0 + (brev(p, 3) << LNS));
+                    const u32 a = swz(j0 + (brev(p, 3) << LNS)) * LS;
                     sre[a] = v[p].re; sim[a] = v[p].im;
                 }
             }
@@ -174,9 +181,9 @@ __device__ __forceinline__ void ckks_fft(double *sre, double *sim, u32 t, const 
                 const u32 j = t + u * TP;
                 cplx x[R], tws[LR];
 #pragma unroll
-                for (int r = 0; r < R; r++) x[r] = {sre[swz(j + (r << LNS))], sim[swz(j + (r << LNS))]};
+                for (int r = 0; r < R; r++) x[r] = {sre[swz(j + (r << LNS)) * LS], sim[swz(j + (r << LNS)) * LS]};
 #pragma unroll
-                for (int s = 0; s < LR; s++) tws[s] = tw_at<S>(tw, j << (LR + 1 - s));
+                for (int s = 0; s < LR; s++) tws[s] = tw_at<S>(tw, j << (LR + 1 - s + TS));
                 bfly<LR, S, false>(x, tws);
 #pragma unroll
                 for (int p = 0; p < R; p++) out(j + (brev(p, LR) << LNS), x[p]);
@@ -243,6 +250,125 @@ __global__ __launch_bounds__(CkksShape<LM>::BT) void ckks_encode_kernel(const do
     ckks_fft<LM, -1>(lds + pl * 2 * M, lds + pl * 2 * M + M, t, tw, in, out);
 }
 
+// ---- 2^14 <= N <= 2^16: the same transform in two passes --------------------------------------------------
+// M = 2^LB = M1 M2 points, j = j1 M2 + j2, k = k1 + M1 k2:
+//   X_k = sum_j2 [ exp(S 2 pi i j2 k1 / M) sum_j1 x_(j1 M2 + j2) exp(S 2 pi i j1 k1 / M1) ] exp(S 2 pi i j2 k2 / M2)
+// Pass 1: the M2 transforms of length M1 over j1 (stride M2), the one-pass kernels' load-side work in front, the factor
+// exp(S 2 pi i j2 k1 / M) = w^(S 4 j2 k1) behind (4 j2 k1 < 2N; w^(e + N) = -w^e), Y [k1][j2] to the workspace.  Pass 2: the
+// M1 transforms of length M2 over the rows k1 of Y, the store-side work behind.  A workgroup takes C = 16 adjacent columns
+// j2 (pass 1) or rows k1 (pass 2), so that the strided side of either pass moves runs of 16 words: 128 bytes of signed
+// words, 256 of the workspace.
+//   pass 1   thread = (t, column c), c the fast index: a wave's loads and stores run along j2.  The points of the 16
+//            columns interleave in LDS (point a of column c at 16 a + c, two planes of 16 M1 doubles): a 32-lane read
+//            covers 16 columns x 2 points = 32 banks, a 16-lane write 16 columns = 16 banks
+//   pass 2   thread = (row c, t), t the fast index: a wave reads runs of TP complex values (>= 256 bytes) of a row; rows
+//            sit 2 M2 + 16 doubles apart (two rows of a 32-lane read meet different banks).  The outputs X_(k1 + M1 k2)
+//            of a thread run along k2, M1 words apart: they cross LDS once more (row c at c (M2 + 2), so that a read of
+//            16 rows x 2 points meets 32 banks) and leave along k1.
+template <int LB>
+struct EmbedShape {
+    static constexpr int L1 = LB == 13 ? 6 : 7, L2 = LB - L1, C = 16;
+    static constexpr u32 M = 1u << LB, M1 = 1u << L1, M2 = 1u << L2;
+    static constexpr int TP1 = CkksShape<L1>::TP, TP2 = CkksShape<L2>::TP, BT1 = C * TP1, BT2 = C * TP2;
+    static constexpr int LDS1 = 2 * C * M1;                                            // doubles
+    static constexpr int ROW2 = 2 * M2 + 16, TROW2 = M2 + 2, LDS2 = C * ROW2;          // LDS2 >= 2 C TROW2
+    static_assert(M1 % C == 0 && M2 % C == 0 && CkksShape<L1>::E == 8 && CkksShape<L2>::E == 8 && LDS2 >= 2 * C * TROW2, "tile");
+};
+
+// the load side of a polynomial: decode's fold and twist of the signed words, encode's Delta and Hermitian order
+template <u32 M, bool DEC>
+__device__ __forceinline__ cplx embed_load(const double *__restrict__ tw, const void *__restrict__ src, u32 j, double delta) {
+    if constexpr (DEC) {
+        const long long *pp = (const long long *)src;
+        return cmul(cplx{(double)pp[j], (double)pp[j + M]}, tw_at<1>(tw, j));
+    } else {
+        const double *zz = (const double *)src;
+        const bool lo = 2 * j < M;
+        const u32 slot = lo ? 2 * j : 2 * M - 1 - 2 * j;
+        const double re = delta * zz[2 * slot], im = delta * zz[2 * slot + 1];
+        return {re, lo ? im : -im};
+    }
+}
+// the store side: decode's slot order, conjugate and division; encode's untwist, 1/M, rounding and conversion
+template <u32 M, bool DEC>
+__device__ __forceinline__ void embed_store(const double *__restrict__ tw, void *__restrict__ dst, u32 k, cplx X, double delta) {
+    if constexpr (DEC) {
+        double *zz = (double *)dst;
+        const bool lo = 2 * k < M;
+        const u32 slot = lo ? 2 * k : 2 * M - 1 - 2 * k;
+        zz[2 * slot] = X.re / delta;
+        zz[2 * slot + 1] = (lo ? X.im : -X.im) / delta;
+    } else {
+        long long *oo = (long long *)dst;
+        constexpr double inv_m = 1.0 / (double)M;
+        const cplx c = cmul(X, tw_at<-1>(tw, k));
+        oo[k] = f64_as_i64(round(c.re * inv_m));
+        oo[k + M] = f64_as_i64(round(c.im * inv_m));
+    }
+}
+
+// src: the chunk's polynomials ([rows][N] signed words, DEC) or slot rows (row r at 2 r src_stride doubles); ws [rows][M]
+// complex.  Grid: rows x M2 / C workgroups, all of them whole.
+template <int LB, bool DEC>
+__global__ __launch_bounds__(EmbedShape<LB>::BT1) void ckks_embed_pass1_kernel(const double *__restrict__ tw, const void *__restrict__ src, u64 src_stride,
+                                                                               double2 *__restrict__ ws, double delta) {
+    using Sh = EmbedShape<LB>;
+    constexpr u32 M = Sh::M, M2 = Sh::M2, N = 2 * M, C = Sh::C;
+    constexpr int S = DEC ? 1 : -1;
+    __shared__ double lds[Sh::LDS1];
+    const u32 c = threadIdx.x % C, t = threadIdx.x / C;
+    const u64 row = blockIdx.x / (M2 / C);
+    const u32 j2 = (blockIdx.x % (M2 / C)) * C + c;
+    const void *sp = DEC ? (const void *)((const long long *)src + row * N) : (const void *)((const double *)src + row * src_stride * 2);
+    double2 *wp = ws + row * M;
+    auto in = [&](u32 j1) -> cplx { return embed_load<M, DEC>(tw, sp, j1 * M2 + j2, delta); };
+    auto out = [&](u32 k1, cplx Y) {
+        const u32 e = 4 * j2 * k1;
+        const bool neg = e >= N;
+        const cplx T = tw_at<S>(tw, neg ? e - N : e);
+        const cplx y = cmul(Y, neg ? cplx{-T.re, -T.im} : T);
+        wp[k1 * M2 + j2] = make_double2(y.re, y.im);
+    };
+    ckks_fft<Sh::L1, S, LB - Sh::L1, C>(lds + c, lds + C * Sh::M1 + c, t, tw, in, out);
+}
+
+// dst: the chunk's slot rows ([rows][M] complex, DEC) or polynomials ([rows][N] signed words).  Grid: rows x M1 / C.
+template <int LB, bool DEC>
+__global__ __launch_bounds__(EmbedShape<LB>::BT2) void ckks_embed_pass2_kernel(const double *__restrict__ tw, const double2 *__restrict__ ws,
+                                                                               void *__restrict__ dst, double delta) {
+    using Sh = EmbedShape<LB>;
+    constexpr u32 M = Sh::M, M1 = Sh::M1, M2 = Sh::M2, N = 2 * M, C = Sh::C, TP = Sh::TP2, P = Sh::TROW2;
+    constexpr int S = DEC ? 1 : -1;
+    __shared__ double lds[Sh::LDS2];
+    const u32 c = threadIdx.x / TP, t = threadIdx.x % TP;
+    const u64 row = blockIdx.x / (M1 / C);
+    const u32 k1_0 = (blockIdx.x % (M1 / C)) * C;
+    const double2 *wp = ws + row * M + (u64)(k1_0 + c) * M2;
+    void *dp = DEC ? (void *)((double *)dst + row * N) : (void *)((long long *)dst + row * N);
+    cplx xs[8];
+    u32 ks[8];
+    int cnt = 0;
+    auto in = [&](u32 j2) -> cplx {
+        const double2 v = wp[j2];
+        return {v.x, v.y};
+    };
+    auto out = [&](u32 k2, cplx X) { ks[cnt] = k2; xs[cnt] = X; cnt++; };
+    ckks_fft<Sh::L2, S, LB - Sh::L2>(lds + c * Sh::ROW2, lds + c * Sh::ROW2 + M2, t, tw, in, out);
+    __syncthreads();
+    double *tre = lds, *tim = lds + C * P;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        tre[c * P + ks[i]] = xs[i].re;
+        tim[c * P + ks[i]] = xs[i].im;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const u32 e = threadIdx.x + i * Sh::BT2, cc = e % C, k2 = e / C;             // e < 8 BT2 = C M2
+        embed_store<M, DEC>(tw, dp, k1_0 + cc + M1 * k2, cplx{tre[cc * P + k2], tim[cc * P + k2]}, delta);
+    }
+}
+
 // out = c0 + P mod q, centred as ring_n.rs:113-127: d - q where d > floor(q / 2), a signed word
 __global__ __launch_bounds__(256) void ckks_decrypt_epilogue_kernel(const u64 *__restrict__ c0, const u64 *__restrict__ P, u64 *__restrict__ out, u64 count,
                                                                     Mod m) {
@@ -259,10 +385,16 @@ __global__ __launch_bounds__(256) void ckks_decrypt_epilogue_kernel(const u64 *_
 namespace {
 
 constexpr u64 kCkksMaxN = 1ull << 13;           // M = N/2 = 2^12 complex points fill 64 KiB of LDS
+constexpr u64 kCkksEmbedMaxN = 1ull << 16;      // the two-pass kernels: M = 2^13 .. 2^15
 
-int check_encoder(uint64_t n, double delta, const char *who) {
-    if (n < 2 || (n & (n - 1)) != 0 || n > kCkksMaxN)
-        return fhe_fail(FHE_E_INVALID, "%s: n=%llu must be a power of two in [2, 2^13]", who, (unsigned long long)n);
+int check_encoder_n(uint64_t n, u64 max_n, const char *who) {
+    if (n < 2 || (n & (n - 1)) != 0 || n > max_n)
+        return fhe_fail(FHE_E_INVALID, "%s: n=%llu must be a power of two in [2, 2^%u]", who, (unsigned long long)n, log2_of(max_n));
+    return FHE_OK;
+}
+int check_encoder(uint64_t n, double delta, u64 max_n, const char *who) {
+    int rc = check_encoder_n(n, max_n, who);
+    if (rc != FHE_OK) return rc;
     if (!(delta > 0.0) || !std::isfinite(delta)) return fhe_fail(FHE_E_INVALID, "%s: the scale must be finite and positive", who);
     return FHE_OK;
 }
@@ -285,11 +417,44 @@ int launch_encode(const double *tw, const double *z, u64 z_stride, long long *o,
         default: return CALL(12);                                                                                   \
     }
 
-}  // namespace
+// the polynomials of one pass over the workspace: the chunk of the other CKKS calls (2^21 words; 16 MiB of complex values)
+u64 embed_chunk(uint64_t n, u64 batch) { return std::min<u64>(batch, std::max<u64>(1, kChunkWords >> log2_of(n))); }
 
-extern "C" int fhe_ckks_twiddles(uint64_t n, double *out) {
-    const char *who = "fhe_ckks_twiddles";
-    if (n < 2 || (n & (n - 1)) != 0 || n > kCkksMaxN) return fhe_fail(FHE_E_INVALID, "%s: n=%llu must be a power of two in [2, 2^13]", who, (unsigned long long)n);
+// the two passes over `rows` polynomials of a chunk (rows n / 16 <= 2^17 workgroups a pass)
+template <int LB, bool DEC>
+int launch_embed(const double *tw, const void *src, u64 src_stride, double2 *ws, void *dst, double delta, u64 rows, hipStream_t st) {
+    using Sh = fhe::EmbedShape<LB>;
+    int rc = launch(DEC ? "ckks_embed_decode_pass1" : "ckks_embed_encode_pass1", LB + 1, st, fhe::ckks_embed_pass1_kernel<LB, DEC>,
+                    (unsigned)(rows * (Sh::M2 / Sh::C)), Sh::BT1, tw, src, src_stride, ws, delta);
+    if (rc != FHE_OK) return rc;
+    return launch(DEC ? "ckks_embed_decode_pass2" : "ckks_embed_encode_pass2", LB + 1, st, fhe::ckks_embed_pass2_kernel<LB, DEC>,
+                  (unsigned)(rows * (Sh::M1 / Sh::C)), Sh::BT2, tw, ws, dst, delta);
+}
+// 2^14 <= n <= 2^16: chunk by chunk through workspace slot 11 (nothing else of CKKS's is live during an encoder call)
+template <bool DEC>
+int embed_two_pass(uint64_t n, double delta, const double *tw, const void *src, u64 src_stride, void *dst, u64 batch, hipStream_t st) {
+    const u64 chunk = embed_chunk(n, batch);
+    void *w = nullptr;
+    int rc = fhe_workspace_get(fhe::Ckks::slot, chunk * n * 8, st, &w);
+    if (rc != FHE_OK) return rc;
+    for (u64 r0 = 0; r0 < batch; r0 += chunk) {
+        const u64 rows = std::min<u64>(chunk, batch - r0);
+        const void *s = DEC ? (const void *)((const long long *)src + r0 * n) : (const void *)((const double *)src + r0 * src_stride * 2);
+        void *d = (void *)((u64 *)dst + r0 * n);                    // n words a row either way: signed words, or n / 2 complex values
+        switch (log2_of(n)) {
+            case 14: rc = launch_embed<13, DEC>(tw, s, src_stride, (double2 *)w, d, delta, rows, st); break;
+            case 15: rc = launch_embed<14, DEC>(tw, s, src_stride, (double2 *)w, d, delta, rows, st); break;
+            default: rc = launch_embed<15, DEC>(tw, s, src_stride, (double2 *)w, d, delta, rows, st); break;
+        }
+        if (rc != FHE_OK) return rc;
+    }
+    return FHE_OK;
+}
+
+// the table of fhe_ckks_twiddles and fhe_ckks_embed_twiddles
+int ckks_twiddles(uint64_t n, u64 max_n, double *out, const char *who) {
+    int rc = check_encoder_n(n, max_n, who);
+    if (rc != FHE_OK) return rc;
     if (!out) return fhe_fail(FHE_E_NULL, "%s: NULL table", who);
     const long double pi = 3.141592653589793238462643383279502884L;
     for (uint64_t k = 0; k < n; k++) {
@@ -309,9 +474,10 @@ extern "C" int fhe_ckks_twiddles(uint64_t n, double *out) {
     return FHE_OK;
 }
 
-extern "C" int fhe_ckks_encode_dev(uint64_t n, double delta, const void *d_tw, const void *d_z, size_t z_stride, void *d_out, size_t batch, void *hip_stream) {
-    const char *who = "fhe_ckks_encode_dev";
-    int rc = check_encoder(n, delta, who);
+// fhe_ckks_encode_dev and fhe_ckks_embed_encode_dev: the checks in the ABI's order, the one-pass kernels up to 2^13
+int ckks_encode(const char *who, u64 max_n, uint64_t n, double delta, const void *d_tw, const void *d_z, size_t z_stride, void *d_out, size_t batch,
+                void *hip_stream) {
+    int rc = check_encoder(n, delta, max_n, who);
     if (rc != FHE_OK) return rc;
     if (z_stride != 0 && z_stride < n / 2) return fhe_fail(FHE_E_INVALID, "%s: z_stride must be 0 (one vector) or at least n / 2", who);
     if (batch == 0) return FHE_OK;
@@ -324,14 +490,14 @@ extern "C" int fhe_ckks_encode_dev(uint64_t n, double delta, const void *d_tw, c
     int dev;
     if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
+    if (n > kCkksMaxN) return embed_two_pass<false>(n, delta, (const double *)d_tw, d_z, (u64)z_stride, d_out, (u64)batch, st);
 #define CKKS_ENC(LM) launch_encode<LM>((const double *)d_tw, (const double *)d_z, (u64)z_stride, (long long *)d_out, delta, (u64)batch, st)
     CKKS_BY_SIZE(log2_of(n) - 1, CKKS_ENC)
 #undef CKKS_ENC
 }
 
-extern "C" int fhe_ckks_decode_dev(uint64_t n, double delta, const void *d_tw, const void *d_p, void *d_out, size_t batch, void *hip_stream) {
-    const char *who = "fhe_ckks_decode_dev";
-    int rc = check_encoder(n, delta, who);
+int ckks_decode(const char *who, u64 max_n, uint64_t n, double delta, const void *d_tw, const void *d_p, void *d_out, size_t batch, void *hip_stream) {
+    int rc = check_encoder(n, delta, max_n, who);
     if (rc != FHE_OK) return rc;
     if (batch == 0) return FHE_OK;
     if (!mul_fits((u64)batch, n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
@@ -342,9 +508,37 @@ extern "C" int fhe_ckks_decode_dev(uint64_t n, double delta, const void *d_tw, c
     int dev;
     if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
+    if (n > kCkksMaxN) return embed_two_pass<true>(n, delta, (const double *)d_tw, d_p, 0, d_out, (u64)batch, st);
 #define CKKS_DEC(LM) launch_decode<LM>((const double *)d_tw, (const long long *)d_p, (double *)d_out, delta, (u64)batch, st)
     CKKS_BY_SIZE(log2_of(n) - 1, CKKS_DEC)
 #undef CKKS_DEC
+}
+
+}  // namespace
+
+extern "C" int fhe_ckks_twiddles(uint64_t n, double *out) { return ckks_twiddles(n, kCkksMaxN, out, "fhe_ckks_twiddles"); }
+extern "C" int fhe_ckks_embed_twiddles(uint64_t n, double *out) { return ckks_twiddles(n, kCkksEmbedMaxN, out, "fhe_ckks_embed_twiddles"); }
+
+extern "C" int fhe_ckks_encode_dev(uint64_t n, double delta, const void *d_tw, const void *d_z, size_t z_stride, void *d_out, size_t batch, void *hip_stream) {
+    return ckks_encode("fhe_ckks_encode_dev", kCkksMaxN, n, delta, d_tw, d_z, z_stride, d_out, batch, hip_stream);
+}
+extern "C" int fhe_ckks_embed_encode_dev(uint64_t n, double delta, const void *d_tw, const void *d_z, size_t z_stride, void *d_out, size_t batch,
+                                         void *hip_stream) {
+    return ckks_encode("fhe_ckks_embed_encode_dev", kCkksEmbedMaxN, n, delta, d_tw, d_z, z_stride, d_out, batch, hip_stream);
+}
+
+extern "C" int fhe_ckks_decode_dev(uint64_t n, double delta, const void *d_tw, const void *d_p, void *d_out, size_t batch, void *hip_stream) {
+    return ckks_decode("fhe_ckks_decode_dev", kCkksMaxN, n, delta, d_tw, d_p, d_out, batch, hip_stream);
+}
+extern "C" int fhe_ckks_embed_decode_dev(uint64_t n, double delta, const void *d_tw, const void *d_p, void *d_out, size_t batch, void *hip_stream) {
+    return ckks_decode("fhe_ckks_embed_decode_dev", kCkksEmbedMaxN, n, delta, d_tw, d_p, d_out, batch, hip_stream);
+}
+
+// the workspace of one fhe_ckks_embed_encode_dev / _decode_dev call: the chunk's [M] complex rows; 0 where no workspace is
+// taken (n <= 2^13, batch = 0) and for a shape the calls refuse
+extern "C" size_t fhe_ckks_embed_workspace_bytes(uint64_t n, size_t batch) {
+    if (n < 2 || (n & (n - 1)) != 0 || n > kCkksEmbedMaxN || n <= kCkksMaxN || batch == 0 || !mul_fits((u64)batch, n, kWordLimit)) return 0;
+    return (size_t)(embed_chunk(n, (u64)batch) * n * 8);
 }
 
 extern "C" int fhe_ckks_secret_key_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t key_row, void *d_s, void *hip_stream) {

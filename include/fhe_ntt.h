@@ -623,6 +623,25 @@ int fhe_ckks_encrypt_dev(const fhe_ntt_plan *plan, const uint8_t *seed, uint64_t
 int fhe_ckks_decrypt_dev(const fhe_ntt_plan *plan, const void *d_s_evals, const void *d_ct, void *d_out, size_t batch,
                          void *hip_stream);
 
+/* ---- CKKS: the encoder up to n = 2^16 (ckks_client.hip) ----
+ * The three encoder entry points above with the ring-size bound 2 <= n <= 2^16; arguments, layouts, alignment, overlap
+ * rules, error codes and the order of the checks are theirs, and nothing is written on a rejection.
+ *   fhe_ckks_embed_twiddles     HOST only: the table of fhe_ckks_twiddles (the same entries where both accept n)
+ *   fhe_ckks_embed_encode_dev   n <= 2^13: the kernel of fhe_ckks_encode_dev, the same words.  2^14 <= n <= 2^16: the
+ *            transform of M = n/2 points as two passes, M = M1 M2 (2^6 2^7, 2^7 2^7, 2^7 2^8), through [batch][M] complex
+ *            values of library workspace, `chunk` polynomials at a time; the roundings differ from a one-pass transform's
+ *            in the last bits, the error bound of §21 holds.
+ *   fhe_ckks_embed_decode_dev   the same for fhe_ckks_decode_dev
+ *   fhe_ckks_embed_workspace_bytes  the library workspace one such call takes: 8 n min(batch, max(1, 2^21 / n)) bytes for
+ *            2^14 <= n <= 2^16 and batch > 0; 0 for n <= 2^13, for batch = 0 and for a shape the calls refuse
+ * fhe_ckks_twiddles, fhe_ckks_encode_dev and fhe_ckks_decode_dev keep their bound n <= 2^13. */
+int fhe_ckks_embed_twiddles(uint64_t n, double *out);
+int fhe_ckks_embed_encode_dev(uint64_t n, double delta, const void *d_tw, const void *d_z, size_t z_stride, void *d_out,
+                              size_t batch, void *hip_stream);
+int fhe_ckks_embed_decode_dev(uint64_t n, double delta, const void *d_tw, const void *d_p, void *d_out, size_t batch,
+                              void *hip_stream);
+size_t fhe_ckks_embed_workspace_bytes(uint64_t n, size_t batch);
+
 /* ---- CKKS on an RNS modulus chain: ct x ct, relinearisation, rescaling (ckks_eval.hip) ----
  * A chain is `limbs` plans (1 <= limbs <= 8) of distinct primes q_0 .. and the same n, passed as a HOST array `plans`; the
  * entry points that switch keys also take the plan of one special prime P >= max q_i, distinct from all of them.  A
