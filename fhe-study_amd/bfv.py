@@ -188,3 +188,355 @@ class ClientKey(ClientKeyBase):
         out = torch.empty((batch, ring.n), dtype=torch.int64, device="cuda")
         binding.bfv_decrypt_dev(_plan(ring), self.param.t, self.d_s_evals.data_ptr(), d_ct.data_ptr(), out.data_ptr(), batch)
         return Rq(self.param.pt(), _from_dev(out).reshape(shape))
+
+
+# ---- BFV on an RNS modulus chain: exact ct x ct, batching, slot rotations (bfv_rns.hip) -------------------------------
+def _ckks():
+    """ckks.py, whose key builders and Galois key switch the chain uses unchanged; imported on first use"""
+    from . import ckks
+    return ckks
+
+
+def _is_prime(x):
+    """deterministic Miller-Rabin for x < 2^64 (the first twelve primes as bases)"""
+    if x < 2:
+        return False
+    small = (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37)
+    for p in small:
+        if x % p == 0:
+            return x == p
+    d, r = x - 1, 0
+    while d % 2 == 0:
+        d, r = d // 2, r + 1
+    for a in small:
+        y = pow(a, d, x)
+        if y in (1, x - 1):
+            continue
+        for _ in range(r - 1):
+            y = y * y % x
+            if y == x - 1:
+                break
+        else:
+            return False
+    return True
+
+
+@dataclass(frozen=True)
+class RnsParam:
+    """n, the chain primes q_0 .. q_{k-1} (1 <= k <= 4, Q their product), the auxiliary base b_0 .. b_k (B its product), the
+    special prime P >= max q_i of the switching keys and the plaintext modulus t.  Every prime is distinct, NTT-friendly for n
+    (1 modulo 2n) and below 2^62; admission: B > t n Q + 1.  Every ciphertext lives at all k limbs."""
+    n: int
+    moduli: tuple
+    aux: tuple
+    special: int
+    t: int
+
+    def __post_init__(self):
+        for name in ("moduli", "aux"):
+            object.__setattr__(self, name, tuple(int(q) for q in getattr(self, name)))
+        for name in ("n", "special", "t"):
+            object.__setattr__(self, name, int(getattr(self, name)))
+        n, k = self.n, len(self.moduli)
+        if n < 2 or n & (n - 1) or n > 1 << 19:
+            raise ValueError("RnsParam: n must be a power of two in [2, 2^19]")
+        if not 1 <= k <= 4:
+            raise ValueError("RnsParam: the chain has 1 to 4 primes")
+        if len(self.aux) != k + 1:
+            raise ValueError(f"RnsParam: the auxiliary base of a chain of {k} primes has {k + 1}")
+        every = self.moduli + self.aux + (self.special,)
+        if len(set(every)) != len(every):
+            raise ValueError("RnsParam: the primes of the chain, the auxiliary base and the special prime must be distinct")
+        for p in every:
+            if p >= 1 << 62 or p % (2 * n) != 1 or not _is_prime(p):
+                raise ValueError(f"RnsParam: {p} is not a prime below 2^62 that is 1 modulo 2n")
+        if self.special < max(self.moduli):
+            raise ValueError("RnsParam: the special prime must not be below a chain prime")
+        if self.t < 2:
+            raise ValueError("RnsParam: t must be at least 2")
+        if not self.B > self.t * n * self.Q + 1:
+            raise ValueError("RnsParam: the auxiliary base must exceed t n Q + 1")
+
+    @property
+    def Q(self):
+        out = 1
+        for q in self.moduli:
+            out *= q
+        return out
+
+    @property
+    def B(self):
+        out = 1
+        for b in self.aux:
+            out *= b
+        return out
+
+    @property
+    def max_level(self):
+        return len(self.moduli) - 1
+
+    def plans(self, level=None):
+        """the plans of the chain (`level` is accepted for the CKKS key builders and must name every limb)"""
+        if level is not None and level != self.max_level:
+            raise ValueError("RnsParam: a BFV ciphertext lives at every limb")
+        return [_plan(RingParam(q, self.n)) for q in self.moduli]
+
+    def aux_plans(self):
+        return [_plan(RingParam(b, self.n)) for b in self.aux]
+
+    def special_plan(self):
+        return _plan(RingParam(self.special, self.n))
+
+
+class BatchEncoder:
+    """t prime, t = 1 (mod 2n): the n slots of a plaintext as a 2 x n/2 matrix.  Slot (r, c) is the value of the polynomial at
+    psi^e, e = 5^c mod 2n for r = 0 and 2n - 5^c for r = 1, which the engine's forward transform modulo t leaves at index
+    brv((e - 1) / 2): encode and decode are that transform's inverse / forward composed with this index map.  sigma_g with
+    g = 5^step rotates both rows left by `step`; g = 2n - 1 swaps the rows."""
+
+    def __init__(self, n, t):
+        n, t = int(n), int(t)
+        if n < 2 or n & (n - 1):
+            raise ValueError("BatchEncoder: n must be a power of two, at least 2")
+        if t % (2 * n) != 1 or not _is_prime(t):
+            raise ValueError("BatchEncoder: t must be a prime that is 1 modulo 2n")
+        self.n, self.t = n, t
+        self.index = slot_index(n)
+
+    def _plan(self):
+        return _plan(RingParam(self.t, self.n))
+
+    def encode(self, slots):
+        """[..][2][n/2] values modulo t -> coefficients [..][n] in [0, t)"""
+        s = np.mod(np.asarray(slots, dtype=np.int64), self.t).astype(np.uint64)
+        lead = s.shape[:-2]
+        ev = np.zeros(lead + (self.n,), dtype=np.uint64)
+        ev[..., self.index.reshape(-1)] = s.reshape(lead + (self.n,))
+        return self._plan().inverse(ev.reshape(-1, self.n)).reshape(lead + (self.n,))
+
+    def decode(self, m):
+        """coefficients [..][n] modulo t -> slots [..][2][n/2]"""
+        m = np.ascontiguousarray(m, dtype=np.uint64)
+        ev = self._plan().forward(m.reshape(-1, self.n)).reshape(m.shape)
+        return ev[..., self.index.reshape(-1)].reshape(m.shape[:-1] + (2, self.n // 2))
+
+
+def slot_index(n):
+    """-> int64 [2][n/2]: the index of slot (r, c) in the engine's order, brv(((+-5^c mod 2n) - 1) / 2) over log2 n bits"""
+    L = n.bit_length() - 1
+    idx = np.empty((2, max(n // 2, 1)), dtype=np.int64)
+    for c in range(max(n // 2, 1)):
+        e = pow(5, c, 2 * n)
+        for r, ee in enumerate((e, 2 * n - e)):
+            idx[r, c] = int(format((ee - 1) // 2, f"0{L}b")[::-1], 2)
+    return idx
+
+
+class RnsCiphertext:
+    """A device tensor [k][2][batch][n] of evals over every limb of an RnsParam"""
+
+    def __init__(self, param, d):
+        self.param, self.d = param, d
+
+    @property
+    def batch(self):
+        return self.d.shape[2]
+
+    def _check(self, rhs):
+        if rhs.param != self.param or rhs.batch != self.batch:
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "operands differ in RnsParam or batch")
+
+    def _rows(self, rhs, fn):
+        self._check(rhs)
+        out = _torch().empty_like(self.d)
+        for i, plan in enumerate(self.param.plans()):
+            binding._check(fn(plan.handle, self.d[i].data_ptr(), rhs.d[i].data_ptr(), out[i].data_ptr(), 2 * self.batch, None))
+        return RnsCiphertext(self.param, out)
+
+    def __add__(self, rhs):
+        return self._rows(rhs, binding.load_library().fhe_rq_add_dev)
+
+    def __sub__(self, rhs):
+        return self._rows(rhs, binding.load_library().fhe_rq_sub_dev)
+
+    def __neg__(self):
+        out = _torch().empty_like(self.d)
+        for i, plan in enumerate(self.param.plans()):
+            binding._check(binding.load_library().fhe_rq_neg_dev(plan.handle, self.d[i].data_ptr(), out[i].data_ptr(), 2 * self.batch, None))
+        return RnsCiphertext(self.param, out)
+
+    def mul(self, rhs, rlk):
+        """ct x ct: the scale-invariant tensor and its relinearisation (fhe_bfv_rns_mul_dev)"""
+        self._check(rhs)
+        p = self.param
+        if rlk.param != p:
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the relinearisation key is not of this ciphertext's chain")
+        out = _torch().empty_like(self.d)
+        binding.bfv_rns_mul_dev(p.plans(), p.aux_plans(), p.special_plan(), p.t, rlk.d_rlk.data_ptr(), self.d.data_ptr(), rhs.d.data_ptr(), out.data_ptr(), self.batch)
+        return RnsCiphertext(p, out)
+
+    def _rows_of(self, m):
+        return np.array(np.broadcast_to(np.asarray(m, dtype=np.int64), (self.batch, self.param.n)))   # a writable copy
+
+    def add_plain(self, m):
+        """c0 + floor(Q / t) m for a plaintext m in [0, t)^n, (n,) or (batch, n)"""
+        torch = _torch()
+        p, n = self.param, self.param.n
+        d_m = torch.from_numpy(np.mod(self._rows_of(m), p.t)).cuda()
+        dm = torch.empty((len(p.moduli), self.batch, n), dtype=torch.int64, device="cuda")
+        ev = torch.empty_like(dm)
+        binding.bfv_rns_scale_msg_dev(p.plans(), p.t, d_m.data_ptr(), dm.data_ptr(), self.batch)
+        out = self.d.clone()
+        for i, plan in enumerate(p.plans()):
+            binding.ckks_rns_from_i64_dev([plan], dm[i].data_ptr(), ev[i].data_ptr(), self.batch)
+            binding._check(binding.load_library().fhe_rq_add_dev(plan.handle, self.d[i, 0].data_ptr(), ev[i].data_ptr(), out[i, 0].data_ptr(), self.batch, None))
+        return RnsCiphertext(p, out)
+
+    def mul_plain(self, m):
+        """both components times the plaintext m in [0, t)^n, lifted centred into every limb (fhe_ckks_rns_from_i64_dev)"""
+        torch = _torch()
+        p = self.param
+        rows = np.mod(self._rows_of(m), p.t)
+        rows = np.where(rows > p.t // 2, rows - p.t, rows)
+        pt = torch.empty((len(p.moduli), self.batch, p.n), dtype=torch.int64, device="cuda")
+        binding.ckks_rns_from_i64_dev(p.plans(), torch.from_numpy(np.ascontiguousarray(rows)).cuda().data_ptr(), pt.data_ptr(), self.batch)
+        out = torch.empty_like(self.d)
+        for i, plan in enumerate(p.plans()):
+            for c in range(2):
+                plan.pointwise_mul_dev(self.d[i, c].data_ptr(), pt[i].data_ptr(), out[i, c].data_ptr(), self.batch)
+        return RnsCiphertext(p, out)
+
+    def rotate_many(self, gks):
+        """sigma_g of this ciphertext for every key of `gks` from one call (fhe_ckks_rns_galois_dev): one digit decomposition"""
+        torch = _torch()
+        gks, p = list(gks), self.param
+        if any(gk.param != p for gk in gks):
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "a Galois key is not of this ciphertext's chain")
+        out = torch.empty((len(gks),) + tuple(self.d.shape), dtype=torch.int64, device="cuda")
+        binding.ckks_rns_galois_dev(p.plans(), p.special_plan(), [gk.d_gk.data_ptr() for gk in gks], [gk.g for gk in gks], len(p.moduli), self.d.data_ptr(),
+                                    out.data_ptr(), self.batch)
+        return [RnsCiphertext(p, out[r]) for r in range(len(gks))]
+
+    def rotate(self, gk):
+        """both rows of the slot matrix moved left by the key's step; a key that is no rotation key is refused"""
+        if not gk.is_rotation:
+            raise ValueError(f"rotate: g={gk.g} is no power of 5 modulo 2n")
+        return self.rotate_many([gk])[0]
+
+    def swap_rows(self, gk):
+        """the two rows of the slot matrix exchanged; a key of another element is refused"""
+        if gk.g != 2 * self.param.n - 1:
+            raise ValueError(f"swap_rows: g={gk.g} is not 2n - 1")
+        return self.rotate_many([gk])[0]
+
+
+class RnsClientKey(ClientKeyBase):
+    """The BFV secret under every prime of an RnsParam, on ClientKeyBase with the row plan of ckks.RnsClientKey:
+        [0, 2^56)                    fresh encryptions
+        1 2^56 + slot                public_key(slot)
+        2 2^56 + 64 slot + j         digit j of relin_key(slot)
+        3 2^56 + 64 slot + j         digit j of galois_key(g, slot)
+    public_key, relin_key, galois_key and rotation_key go through the key builders of ckks.RnsClientKey, and the keys are the
+    same objects (ckks.RnsPublicKey, ckks.RnsRelinKey, ckks.RnsGaloisKey).  row_swap_key is the key of g = 2n - 1."""
+
+    RLK_BASE, GK_BASE = 2 << 56, 3 << 56
+
+    def __init__(self, seed, param, d_s, d_s_evals, sigma):
+        super().__init__(seed, sigma)
+        self.param, self.d_s, self.d_s_evals = param, d_s, d_s_evals
+
+    @classmethod
+    def generate(cls, seed, param, sigma=3.2):
+        torch = _torch()
+        plans = param.plans() + [param.special_plan()]
+        d_s = torch.empty((len(plans), param.n), dtype=torch.int64, device="cuda")
+        d_e = torch.empty_like(d_s)
+        for i, plan in enumerate(plans):
+            binding.ckks_secret_key_dev(plan, seed, 0, d_s[i].data_ptr())
+            plan.forward_dev(d_s[i].data_ptr(), d_e[i].data_ptr(), 1)
+        torch.cuda.synchronize()
+        return cls(seed, param, d_s, d_e, sigma)
+
+    def public_key(self, slot=0):
+        return _ckks().RnsClientKey.public_key(self, slot)
+
+    def relin_key(self, slot=0):
+        return _ckks().RnsClientKey.relin_key(self, slot)
+
+    def galois_key(self, g, slot):
+        return _ckks().RnsClientKey.galois_key(self, g, slot)
+
+    def rotation_key(self, step, slot):
+        """the key of g = 5^step mod 2n (ckks.galois_element): both rows of the slot matrix move left by `step`"""
+        return self.galois_key(_ckks().galois_element(self.param.n, step), slot)
+
+    def row_swap_key(self, slot):
+        return self.galois_key(2 * self.param.n - 1, slot)
+
+    def encrypt(self, pk, m):
+        """m in [0, t)^n, (n,) or (batch, n) -> RnsCiphertext: floor(Q / t) m per limb (fhe_bfv_rns_scale_msg_dev), then
+        fhe_ckks_encrypt_dev per limb on the same fresh rows"""
+        torch = _torch()
+        p, n = self.param, self.param.n
+        msg = np.mod(np.ascontiguousarray(m, dtype=np.int64).reshape(-1, n), p.t)
+        batch = msg.shape[0]
+        plans = p.plans()
+        d_m = torch.from_numpy(msg).cuda()
+        dm = torch.empty((len(plans), batch, n), dtype=torch.int64, device="cuda")
+        binding.bfv_rns_scale_msg_dev(plans, p.t, d_m.data_ptr(), dm.data_ptr(), batch)
+        out = torch.empty((len(plans), 2, batch, n), dtype=torch.int64, device="cuda")
+
+        def limbs(row):
+            for i, plan in enumerate(plans):
+                binding.ckks_encrypt_dev(plan, self.seed, row, pk.d_evals[i].data_ptr(), dm[i].data_ptr(), n, self._cdt_ptr(), self._m, out[i].data_ptr(), batch)
+                plan.forward_dev(out[i].data_ptr(), out[i].data_ptr(), 2 * batch)
+
+        self._on_fresh_rows(batch, limbs)
+        return RnsCiphertext(p, out)
+
+    def _own(self, ct):
+        if ct.param != self.param:
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the ciphertext is not in this key's chain")
+
+    def decrypt(self, ct):
+        """-> m [batch][n] in [0, t): floor((t v + floor(Q / 2)) / Q) mod t of the phase v (fhe_bfv_rns_decrypt_dev)"""
+        torch = _torch()
+        self._own(ct)
+        p = self.param
+        out = torch.empty((ct.batch, p.n), dtype=torch.int64, device="cuda")
+        binding.bfv_rns_decrypt_dev(p.plans(), p.aux[0], p.t, self.d_s_evals.data_ptr(), ct.d.data_ptr(), out.data_ptr(), ct.batch)
+        return out.cpu().numpy().view(np.uint64)
+
+    def phase(self, ct):
+        """the phase v = c0 + c1 s centred in Q, as Python integers [batch][n]: per limb on the device, the CRT on the host"""
+        torch = _torch()
+        self._own(ct)
+        p = self.param
+        v = torch.empty((len(p.moduli), ct.batch, p.n), dtype=torch.int64, device="cuda")
+        w = torch.empty_like(v)
+        L = binding.load_library()
+        for i, plan in enumerate(p.plans()):
+            for r in range(ct.batch):
+                plan.pointwise_mul_dev(ct.d[i, 1, r].data_ptr(), self.d_s_evals[i].data_ptr(), v[i, r].data_ptr(), 1)
+            binding._check(L.fhe_rq_add_dev(plan.handle, v[i].data_ptr(), ct.d[i, 0].data_ptr(), w[i].data_ptr(), ct.batch, None))
+            plan.inverse_dev(w[i].data_ptr(), w[i].data_ptr(), ct.batch)
+        res = w.cpu().numpy().view(np.uint64).astype(object)
+        Q = p.Q
+        x = np.zeros(res.shape[1:], dtype=object)
+        for i, q in enumerate(p.moduli):
+            x = x + res[i] * ((Q // q) * pow(Q // q, -1, q))
+        x = x % Q
+        return np.where(x > Q // 2, x - Q, x)
+
+    def noise_budget(self, ct):
+        """the bits of log2(Q / (2 |t v - Q m|_inf)) - 1, m the rounded quotient t v / Q: what is left before decryption fails;
+        computed on the host in Python integers from the phase"""
+        p = self.param
+        Q, t = p.Q, p.t
+        worst = 0
+        for v in self.phase(ct).reshape(-1):
+            v = int(v)
+            worst = max(worst, abs(t * v - Q * ((t * v + Q // 2) // Q)))
+        if worst == 0:
+            return Q.bit_length() - 1
+        return max((Q // (2 * worst)).bit_length() - 1, 0) - 1

@@ -14,8 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FHE_NTT_LIB") or os.path.join(_HERE, "libfhe_ntt.so")  # env: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip", "tfhe_client.hip", "bfv_client.hip", "ckks_client.hip", "ckks_eval.hip"]
-HEADERS = ["ntt_kernels.hpp", "ntt_rounds.hpp", "ntt_persist.hpp", "persist_sched.hpp", "digit_mac.hpp", "digit32.hpp", "bfv32.hpp", "smallq.hpp", "ntt32_rounds.hpp", "ntt32_big.hpp", "zq_device.hpp", "capi_internal.hpp", "host_tables.hpp", "host_dispatch.hpp", "launch.hpp", "mac_kernel.hpp", "chacha_stream.hpp", "bfv_client_kernels.hpp", "ntt_kernels.hip",
+SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip", "tfhe_client.hip", "bfv_client.hip", "ckks_client.hip", "ckks_eval.hip", "bfv_rns.hip"]
+HEADERS = ["ntt_kernels.hpp", "ntt_rounds.hpp", "ntt_persist.hpp", "persist_sched.hpp", "digit_mac.hpp", "digit32.hpp", "bfv32.hpp", "smallq.hpp", "ntt32_rounds.hpp", "ntt32_big.hpp", "zq_device.hpp", "capi_internal.hpp", "host_tables.hpp", "host_dispatch.hpp", "launch.hpp", "mac_kernel.hpp", "chacha_stream.hpp", "bfv_client_kernels.hpp", "rns_tables.hpp", "ntt_kernels.hip",
            os.path.join("..", "..", "include", "fhe_ntt.h"), os.path.join("..", "..", "include", "fhe_ntt_experimental.h")]
 OBJ_DIR = os.path.join(_HERE, "build")
 # -ffp-contract=off: zring.hip restates the reference's f64 scale-and-round (one IEEE rounding
@@ -101,6 +101,8 @@ EXPORTS = [
     "fhe_ckks_rns_bsgs_dev", "fhe_ckks_rns_bsgs_workspace_bytes",
     # CKKS: the encoder up to n = 2^16, a two-pass transform above 2^13 (ckks_client.hip)
     "fhe_ckks_embed_twiddles", "fhe_ckks_embed_encode_dev", "fhe_ckks_embed_decode_dev", "fhe_ckks_embed_workspace_bytes",
+    # BFV on an RNS modulus chain: exact basis extension, ct x ct, message scaling, decryption (bfv_rns.hip)
+    "fhe_rns_extend_dev", "fhe_bfv_rns_tensor_dev", "fhe_bfv_rns_mul_dev", "fhe_bfv_rns_workspace_bytes", "fhe_bfv_rns_scale_msg_dev", "fhe_bfv_rns_decrypt_dev",
 ]
 FHE_CKKS_GALOIS_MAX_COUNT = 256              # include/fhe_ntt.h: the most Galois elements of one fhe_ckks_rns_galois_dev call
 FHE_CKKS_DIAG_MAX_OUTPUTS = 64               # include/fhe_ntt.h: the most outputs of one fhe_ckks_rns_diag_sum_dev call
@@ -342,6 +344,13 @@ def load_library():
     L.fhe_ckks_rns_bsgs_workspace_bytes.restype = _sz
     L.fhe_ckks_rns_lincomb_dev.argtypes = [_pp, _uint, _pp, _uint, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _uint, _vp, _sz, _vp]
     L.fhe_ckks_rns_dot_dev.argtypes = [_pp, _uint, _vp, _vp, _uint, _pp, _pp, _uint, ctypes.POINTER(_u64), _vp, _sz, _vp]
+    L.fhe_rns_extend_dev.argtypes = [ctypes.POINTER(_u64), _uint, ctypes.POINTER(_u64), _uint, _int, _vp, _vp, _sz, _vp]
+    L.fhe_bfv_rns_tensor_dev.argtypes = [_pp, _uint, _pp, _u64, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_bfv_rns_mul_dev.argtypes = [_pp, _uint, _pp, _vp, _u64, _vp, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_bfv_rns_workspace_bytes.argtypes = [_u64, _uint, _sz]
+    L.fhe_bfv_rns_workspace_bytes.restype = _sz
+    L.fhe_bfv_rns_scale_msg_dev.argtypes = [_pp, _uint, _u64, _vp, _vp, _sz, _vp]
+    L.fhe_bfv_rns_decrypt_dev.argtypes = [_pp, _uint, _u64, _u64, _vp, _vp, _vp, _sz, _vp]
     L.fhe_glwe_ksk_prepared_words.argtypes = [_vp, _uint, _uint, _uint]
     L.fhe_glwe_ksk_prepared_words.restype = _sz
     L.fhe_glwe_ksk_prepare_dev.argtypes = [_vp, _uint, _uint, _uint, _vp, _vp, _vp]
@@ -954,6 +963,43 @@ def ckks_rns_dot_dev(plans, special, d_rlk, key_limbs, d_as, d_bs, w, d_out, bat
     ws = None if w is None else (_u64 * max(len(w), 1))(*w)
     _check(load_library().fhe_ckks_rns_dot_dev(None if plans is None else _plan_array(plans), len(plans) if limbs is None else limbs, _handle(special), d_rlk, key_limbs,
                                                a, b, len(d_as) if count is None else count, ws, d_out, batch, stream))
+
+
+# ---- BFV on an RNS modulus chain (bfv_rns.hip) ---------------------------------------------------------------------
+def rns_extend_dev(src_mods, dst_mods, centred, d_in, d_out, count, stream=None, src=None, dst=None):
+    """fhe_rns_extend_dev: residues [src][count] modulo src_mods -> [dst][count] modulo dst_mods of the same integer, taken in
+    [0, M) or, centred, in (-M/2, M/2]; the moduli are sequences of integers (None is passed as NULL)"""
+    sm = None if src_mods is None else (_u64 * max(len(src_mods), 1))(*src_mods)
+    dm = None if dst_mods is None else (_u64 * max(len(dst_mods), 1))(*dst_mods)
+    _check(load_library().fhe_rns_extend_dev(sm, len(src_mods) if src is None else src, dm, len(dst_mods) if dst is None else dst, int(bool(centred)), d_in, d_out,
+                                             count, stream))
+
+
+def bfv_rns_tensor_dev(plans, aux, t, d_a, d_b, d_out, batch, stream=None, limbs=None):
+    """fhe_bfv_rns_tensor_dev: [limbs][2][batch][n] x 2 -> the scaled tensor [limbs][3][batch][n]; aux the limbs + 1 auxiliary plans"""
+    _check(load_library().fhe_bfv_rns_tensor_dev(None if plans is None else _plan_array(plans), len(plans) if limbs is None else limbs,
+                                                 None if aux is None else _plan_array(aux), t, d_a, d_b, d_out, batch, stream))
+
+
+def bfv_rns_mul_dev(plans, aux, special, t, d_rlk, d_a, d_b, d_out, batch, stream=None, limbs=None):
+    """fhe_bfv_rns_mul_dev: the scaled tensor and its relinearisation against d_rlk [limbs][limbs + 1][2][n] in one call"""
+    _check(load_library().fhe_bfv_rns_mul_dev(None if plans is None else _plan_array(plans), len(plans) if limbs is None else limbs,
+                                              None if aux is None else _plan_array(aux), _handle(special), t, d_rlk, d_a, d_b, d_out, batch, stream))
+
+
+def bfv_rns_workspace_bytes(n, limbs, batch):
+    return int(load_library().fhe_bfv_rns_workspace_bytes(n, limbs, batch))
+
+
+def bfv_rns_scale_msg_dev(plans, t, d_msg, d_out, batch, stream=None, limbs=None):
+    """fhe_bfv_rns_scale_msg_dev: m [batch][n] in [0, t) -> floor(Q / t) m mod q_i, centred signed words [limbs][batch][n]"""
+    _check(load_library().fhe_bfv_rns_scale_msg_dev(None if plans is None else _plan_array(plans), len(plans) if limbs is None else limbs, t, d_msg, d_out, batch, stream))
+
+
+def bfv_rns_decrypt_dev(plans, aux0, t, d_s_evals, d_ct, d_out, batch, stream=None, limbs=None):
+    """fhe_bfv_rns_decrypt_dev: [limbs][2][batch][n] evals -> m [batch][n] modulo t; aux0 one auxiliary prime above 2 t + 2"""
+    _check(load_library().fhe_bfv_rns_decrypt_dev(None if plans is None else _plan_array(plans), len(plans) if limbs is None else limbs, aux0, t, d_s_evals, d_ct, d_out,
+                                                  batch, stream))
 
 
 def shard_gather_dev(total_rows, row_words, src_devices, d_src_shards, dst_device, d_dst, stream=None):

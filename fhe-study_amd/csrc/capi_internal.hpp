@@ -73,6 +73,12 @@ namespace fhe { struct Ext32Args; }
 int fhe_ext32_tables(uint64_t n, fhe::Ext32Args *a);   // fills the per-prime fields for the current device
 // zring.hip: `keys` TGGSWs [key][(k+1)][l][(k+1)][n] -> keys * fhe_tggsw_prepared_words, in one or two launches (unvalidated)
 int fhe_tggsw_prepare_keys(uint64_t n, unsigned k, unsigned l, uint64_t keys, const void *d_tggsw, void *d_prepared, hipStream_t st);
+// ckks_eval.hip, for bfv_rns.hip: one limb of the eval-domain tensor (three components o_cs words apart, `count`
+// words each), and the relinearisation of a chunk's tensor d [limbs][3][cr][n] into rows r0 .. of out [limbs][2][batch][n]
+int fhe_rns_tensor_limb(const fhe_ntt_plan *p, const fhe::u64 *a, fhe::u64 a_cs, const fhe::u64 *b, fhe::u64 b_cs, fhe::u64 *out, fhe::u64 o_cs, fhe::u64 count,
+                        hipStream_t st);
+int fhe_rns_relin_rows(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const fhe::u64 *rlk, const fhe::u64 *d, fhe::u64 cr,
+                       fhe::u64 *out, fhe::u64 batch, fhe::u64 r0, hipStream_t st);
 namespace fhe { struct SmallQArgs; }
 // fills the modulus-dependent fields when the plan has a 32-bit form on this device (smallq.hip) and FHE_EXT32 is on
 bool fhe_smallq_args(const fhe_ntt_plan *plan, const fhe::DevicePlan &dp, fhe::SmallQArgs *a);

@@ -811,6 +811,25 @@ extern "C" int fhe_ckks_rns_relinearize_dev(const fhe_ntt_plan *const *plans, un
     });
 }
 
+// ---- what bfv_rns.hip runs of this unit (capi_internal.hpp): a kernel is launched from the unit that defines it ----
+// one limb of the tensor, ckks_rns_tensor_kernel as tensor_rows launches it
+int fhe_rns_tensor_limb(const fhe_ntt_plan *p, const u64 *a, u64 a_cs, const u64 *b, u64 b_cs, u64 *out, u64 o_cs, u64 count, hipStream_t st) {
+    return launch("ckks_rns_tensor", (int)p->log_n, st, fhe::ckks_rns_tensor_kernel, fhe_ew_grid(count), 256, a, a_cs, b, b_cs, out, o_cs, count, p->mod);
+}
+// relin_rows on a chunk's tensor d [limbs][3][cr][n] that the caller keeps: -> rows r0 .. r0 + cr of out [limbs][2][batch][n],
+// against a key of `limbs` digits; the key switch's buffers come from this unit's workspace slot
+int fhe_rns_relin_rows(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const u64 *rlk, const u64 *d, u64 cr, u64 *out, u64 batch,
+                       u64 r0, hipStream_t st) {
+    Chain c;
+    int rc = check_chain(plans, limbs, special, true, &c, "fhe_rns_relin_rows");
+    if (rc != FHE_OK) return rc;
+    void *w = nullptr;
+    if ((rc = fhe_workspace_get(kCkksEvalSlot, (size_t)(galois_words_per_row(c) * cr * 8), st, &w)) != FHE_OK) return rc;
+    u64 pinv[fhe::kRnsMaxLimbs];
+    for (unsigned i = 0; i < c.k; i++) pinv[i] = fhe::host::inv_mod(c.p[i]->q, c.p[c.k]->q);
+    return relin_rows(c, rlk, limbs, pinv, d, cr, 0, out, batch, r0, cr, (u64 *)w, st);
+}
+
 extern "C" int fhe_ckks_rns_mul_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *d_rlk, unsigned key_limbs,
                                     const void *d_a, const void *d_b, void *d_out, size_t batch, void *hip_stream) {
     const char *who = "fhe_ckks_rns_mul_dev";

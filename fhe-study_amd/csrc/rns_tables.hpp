@@ -1,0 +1,151 @@
+// rns_tables.hpp — the host tables of the exact basis extension (bfv_rns.hip): Garner's inverses, the
+// mixed-radix digits of floor(M / 2), the weights of the Horner sums, and the small multi-word integers they are made with.
+// Plain C++17, no HIP: host/test_rns_tables.cpp checks each of these against its definition without the library.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "host_tables.hpp"
+
+namespace fhe {
+
+constexpr unsigned kExtMax = 9;            // the most source or target moduli of one extension
+constexpr unsigned long long kExtModLimit = 1ull << 62;
+
+// What the extension kernel needs of the source moduli m_0 .. m_{s-1} (M their product) and the targets p_0 .. p_{t-1}, by
+// value: indexed by unrolled constants only.  A pair {w, wp} is w and floor(w 2^64 / modulus), the Shoup companion.
+//   digits   x = a_0 + a_1 m_0 + a_2 m_0 m_1 + ..., 0 <= a_i < m_i; a_i = (..((x_i - a_0) inv[0][i] - a_1) inv[1][i] ..) mod m_i
+//   half     the digits of floor(M / 2): x > floor(M / 2) exactly when its digits are greater, compared from the top
+//   W[j][t]  m_0 .. m_{j-1} mod p_t, so x = sum_j a_j W[j][t] mod p_t; pM[t] = M mod p_t, subtracted for a centred x above half
+template <unsigned S, unsigned T>
+struct ExtArgs {
+    unsigned long long mq[S], monep[S];              // m_i, floor(2^64 / m_i)
+    unsigned long long inv[S][S], invp[S][S];        // [j][i], j < i: m_j^-1 mod m_i and its companion
+    unsigned long long half[S];
+    unsigned long long pq[T], ponep[T], pr64[T], pr64p[T], pM[T];   // p_t, floor(2^64 / p_t), 2^64 mod p_t and its companion, M mod p_t
+    unsigned long long W[S][T];
+    uint32_t s, t;
+};
+
+namespace host {
+
+// a non-negative integer in 64-bit words, least significant first, no leading zero word
+struct Big {
+    std::vector<u64> w;
+    Big() = default;
+    explicit Big(u64 x) { if (x) w.push_back(x); }
+    void trim() { while (!w.empty() && w.back() == 0) w.pop_back(); }
+    void mul(u64 x) {
+        u64 carry = 0;
+        for (u64 &d : w) {
+            const u128 p = (u128)d * x + carry;
+            d = (u64)p;
+            carry = (u64)(p >> 64);
+        }
+        if (carry) w.push_back(carry);
+        trim();
+    }
+    void add(u64 x) {
+        for (size_t i = 0; x && i < w.size(); i++) {
+            const u64 s = w[i] + x;
+            x = s < x ? 1 : 0;
+            w[i] = s;
+        }
+        if (x) w.push_back(x);
+    }
+    // this = floor(this / x), returns the remainder; x != 0
+    u64 divmod(u64 x) {
+        u64 rem = 0;
+        for (size_t i = w.size(); i-- > 0;) {
+            const u128 cur = ((u128)rem << 64) | w[i];
+            w[i] = (u64)(cur / x);
+            rem = (u64)(cur % x);
+        }
+        trim();
+        return rem;
+    }
+    u64 mod(u64 x) const {
+        u64 rem = 0;
+        for (size_t i = w.size(); i-- > 0;) rem = (u64)((((u128)rem << 64) | w[i]) % x);
+        return rem;
+    }
+    // -1, 0, 1
+    int cmp(const Big &o) const {
+        if (w.size() != o.w.size()) return w.size() < o.w.size() ? -1 : 1;
+        for (size_t i = w.size(); i-- > 0;)
+            if (w[i] != o.w[i]) return w[i] < o.w[i] ? -1 : 1;
+        return 0;
+    }
+};
+
+inline Big big_product(const u64 *m, unsigned count) {
+    Big p(1);
+    for (unsigned i = 0; i < count; i++) p.mul(m[i]);
+    return p;
+}
+
+// x^-1 mod m by the extended Euclidean algorithm, for any m >= 2; false where gcd(x, m) != 1
+inline bool inv_mod_any(u64 x, u64 m, u64 *out) {
+    typedef __int128 i128;
+    i128 r0 = (i128)m, r1 = (i128)(x % m), t0 = 0, t1 = 1;
+    while (r1 != 0) {
+        const i128 qt = r0 / r1, r2 = r0 - qt * r1, t2 = t0 - qt * t1;
+        r0 = r1; r1 = r2; t0 = t1; t1 = t2;
+    }
+    if (r0 != 1) return false;
+    *out = (u64)(t0 < 0 ? t0 + (i128)m : t0);
+    return true;
+}
+
+// the moduli of one side of an extension: 1 .. max of them, each odd, at least 3 and below 2^62, pairwise coprime
+inline bool ext_moduli_ok(const u64 *m, unsigned count, unsigned max) {
+    if (count < 1 || count > max) return false;
+    for (unsigned i = 0; i < count; i++) {
+        if (m[i] < 3 || (m[i] & 1) == 0 || m[i] >= kExtModLimit) return false;
+        for (unsigned j = 0; j < i; j++) {
+            u64 inv;
+            if (m[j] == m[i] || !inv_mod_any(m[j] % m[i], m[i], &inv)) return false;
+        }
+    }
+    return true;
+}
+
+// the tables of the extension from src[0 .. s) to dst[0 .. t); false where a side is not ext_moduli_ok (nothing usable is
+// left in *e).  The targets need not be coprime to the sources.
+template <unsigned S, unsigned T>
+bool ext_tables(const u64 *src, unsigned s, const u64 *dst, unsigned t, ExtArgs<S, T> *e) {
+    *e = ExtArgs<S, T>{};
+    if (!ext_moduli_ok(src, s, S) || t < 1 || t > T) return false;
+    for (unsigned i = 0; i < t; i++)
+        if (dst[i] < 3 || (dst[i] & 1) == 0 || dst[i] >= kExtModLimit) return false;
+    e->s = s;
+    e->t = t;
+    for (unsigned i = 0; i < s; i++) {
+        e->mq[i] = src[i];
+        e->monep[i] = (u64)((((u128)1) << 64) / src[i]);
+        for (unsigned j = 0; j < i; j++) {
+            if (!inv_mod_any(src[j] % src[i], src[i], &e->inv[j][i])) return false;
+            e->invp[j][i] = shoup(e->inv[j][i], src[i]);
+        }
+    }
+    Big h = big_product(src, s);
+    h.divmod(2);                                                     // floor(M / 2)
+    for (unsigned i = 0; i < s; i++) e->half[i] = h.divmod(src[i]);   // its mixed-radix digits, least significant first
+    for (unsigned k = 0; k < t; k++) {
+        const u64 p = dst[k];
+        e->pq[k] = p;
+        e->ponep[k] = (u64)((((u128)1) << 64) / p);
+        e->pr64[k] = (u64)((((u128)1) << 64) % p);
+        e->pr64p[k] = shoup(e->pr64[k], p);
+        u64 w = 1 % p;
+        for (unsigned j = 0; j < s; j++) {
+            e->W[j][k] = w;
+            w = mulmod(w, src[j] % p, p);
+        }
+        e->pM[k] = w;
+    }
+    return true;
+}
+
+}  // namespace host
+}  // namespace fhe

@@ -796,6 +796,45 @@ int fhe_ckks_rns_dot_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const
                          unsigned key_limbs, const void *const *d_as, const void *const *d_bs, unsigned count,
                          const uint64_t *w, void *d_out, size_t batch, void *hip_stream);
 
+/* ---- BFV on an RNS modulus chain: exact ct x ct, message scaling, decryption (bfv_rns.hip) ----
+ * The chain is q_0 .. q_{k-1}, 1 <= k <= 4, Q their product; the auxiliary base b_0 .. b_k, B its product; the special prime P
+ * of the key switch; the plaintext modulus t >= 2.  Every prime is distinct, below 2^62 and has a plan of the same n.  A
+ * ciphertext is [k][2][batch][n] evals over all k limbs (the layout of the CKKS block of §22; BFV has no levels), and public
+ * keys, relinearisation keys and Galois keys are those of fhe_ckks_public_key_dev, fhe_ckks_rns_relin_key_dev and
+ * fhe_ckks_rns_galois_key_dev with limbs = k; slot rotations are fhe_ckks_rns_galois_dev unchanged.
+ *   fhe_rns_extend_dev            d_in [src][count], the canonical residues of an integer x modulo src_mods[0 .. src) (M their
+ *            product) -> d_out [dst][count], its residues modulo dst_mods[0 .. dst), exactly: x is taken in [0, M), or with
+ *            `centred` != 0 in (-M / 2, M / 2].  The moduli are HOST arrays; each is odd, at least 3 and below 2^62, no modulus
+ *            repeats within a side, the source moduli are pairwise coprime, and a side has 1 to 9 of them.
+ *   fhe_bfv_rns_tensor_dev        d_out [k][3][batch][n] evals: for every coefficient of every component
+ *            floor((t d + floor(Q / 2)) / Q) mod q_i, d the negacyclic tensor over the integers (d0 = a0 b0, d1 = a0 b1 + a1 b0,
+ *            d2 = a1 b1) of the operands' coefficients centred in Q: round-to-nearest of t d / Q, Q being odd.  Admission:
+ *            B > t n Q + 1.  d_out is 16-byte aligned.
+ *   fhe_bfv_rns_mul_dev           that, kept in the library workspace, then the steps of fhe_ckks_rns_relinearize_dev against
+ *            d_rlk [k][k + 1][2][n] -> d_out [k][2][batch][n]
+ *   fhe_bfv_rns_workspace_bytes   the library workspace of fhe_bfv_rns_mul_dev in bytes, or 0 for a shape the calls refuse
+ *   fhe_bfv_rns_scale_msg_dev     d_msg [batch][n], words in [0, t) -> d_out [k][batch][n]: floor(Q / t) m mod q_i as centred
+ *            signed words, the message fhe_ckks_encrypt_dev takes under limb i (on the same fresh rows for every limb)
+ *   fhe_bfv_rns_decrypt_dev       d_ct [k][2][batch][n] evals, d_s_evals [k][n] -> d_out [batch][n]:
+ *            floor((t v + floor(Q / 2)) / Q) mod t for the phase v = c0 + c1 s centred in Q; aux0 is one auxiliary prime,
+ *            odd, above 2 t + 2, below 2^62 and coprime to Q (t < 2^60)
+ * FHE_E_NULL for a NULL plan, modulus array or buffer; FHE_E_PARAM_MISMATCH for plans whose n differ; FHE_E_INVALID for k not
+ * in [1, 4] (more than 9 moduli on a side of fhe_rns_extend_dev), a repeated, even or too large modulus, a base that misses
+ * the admission, t < 2, a misaligned buffer, an output that overlaps an input, and a batch whose words pass 2^60.  Everything is
+ * checked before any device call and nothing is written on rejection; batch = 0 (count = 0) is a no-op. */
+int fhe_rns_extend_dev(const uint64_t *src_mods, unsigned src, const uint64_t *dst_mods, unsigned dst, int centred,
+                       const void *d_in, void *d_out, size_t count, void *hip_stream);
+int fhe_bfv_rns_tensor_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *aux, uint64_t t,
+                           const void *d_a, const void *d_b, void *d_out, size_t batch, void *hip_stream);
+int fhe_bfv_rns_mul_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *aux,
+                        const fhe_ntt_plan *special, uint64_t t, const void *d_rlk, const void *d_a, const void *d_b,
+                        void *d_out, size_t batch, void *hip_stream);
+size_t fhe_bfv_rns_workspace_bytes(uint64_t n, unsigned limbs, size_t batch);
+int fhe_bfv_rns_scale_msg_dev(const fhe_ntt_plan *const *plans, unsigned limbs, uint64_t t, const void *d_msg, void *d_out,
+                              size_t batch, void *hip_stream);
+int fhe_bfv_rns_decrypt_dev(const fhe_ntt_plan *const *plans, unsigned limbs, uint64_t aux0, uint64_t t,
+                            const void *d_s_evals, const void *d_ct, void *d_out, size_t batch, void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
