@@ -275,6 +275,11 @@ class RnsParam:
     def max_level(self):
         return len(self.moduli) - 1
 
+    @property
+    def max_dot_weight(self):
+        """the largest W = sum_r |w_r| that `dot` admits: B > t n Q W + 1, so floor((B - 2) / (t n Q)); at least 1"""
+        return (self.B - 2) // (self.t * self.n * self.Q)
+
     def plans(self, level=None):
         """the plans of the chain (`level` is accepted for the CKKS key builders and must name every limb)"""
         if level is not None and level != self.max_level:
@@ -429,6 +434,224 @@ class RnsCiphertext:
             raise ValueError(f"swap_rows: g={gk.g} is not 2n - 1")
         return self.rotate_many([gk])[0]
 
+    def square(self, rlk):
+        """self x self: dot([self], [self], rlk)"""
+        return dot([self], [self], rlk)
+
+    def mul_const(self, c):
+        """both components times the integer c, taken centred modulo t: lincomb([self], [c])"""
+        return lincomb([self], [int(c)])[0]
+
+    def diag_sum(self, pts, gks):
+        """-> [sum_r m_{o,r} (.) sigma_{g_r}(self) for each output o] from one call (fhe_ckks_rns_diag_sum_dev): one digit
+        decomposition for all elements and outputs.  pts is what encode_diagonals returns; gks[r] is the key of pts.gs[r], not
+        read and possibly None where pts.gs[r] = 1."""
+        torch = _torch()
+        gks, p = list(gks), self.param
+        if pts.param != p or any(gk is not None and gk.param != p for gk in gks):
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the plaintexts or a Galois key are not of this ciphertext's chain")
+        if len(gks) != len(pts.gs):
+            raise ValueError(f"diag_sum: {len(gks)} keys for {len(pts.gs)} elements")
+        for r, (g, gk) in enumerate(zip(pts.gs, gks)):
+            if g != 1 and gk is None:
+                raise ValueError(f"diag_sum: element {r} (g={g}) has no key")
+            if g != 1 and gk.g != g:
+                raise ValueError(f"diag_sum: key {r} is of g={gk.g}, the plaintexts' element is {g}")
+        out = torch.empty((pts.outputs,) + tuple(self.d.shape), dtype=torch.int64, device="cuda")
+        binding.ckks_rns_diag_sum_dev(p.plans(), p.special_plan(), [None if g == 1 else gk.d_gk.data_ptr() for g, gk in zip(pts.gs, gks)], pts.gs, len(p.moduli),
+                                      pts.d_pts.data_ptr(), pts.outputs, self.d.data_ptr(), out.data_ptr(), self.batch)
+        return [RnsCiphertext(p, out[o]) for o in range(pts.outputs)]
+
+    def linear_transform(self, lt, keys):
+        """out[r] = M[r] in[r] mod t on the two slot rows for a LinearTransform, from one call (fhe_ckks_rns_bsgs_dev): the giant
+        steps' rotations hoisted, one modulus-down.  keys: step -> Galois key for every step of lt.required_steps(); a missing
+        one raises KeyError(step)."""
+        missing = [st for st in lt.required_steps() if st not in keys]
+        if missing:
+            raise KeyError(missing[0])
+        torch = _torch()
+        pts, p = lt.pts, self.param
+        baby = [keys[i] if i else None for i in lt.baby]
+        giant = [keys[lt.n1 * j] if j else None for j in lt.giant]
+        giant_gs = [_ckks().galois_element(p.n, lt.n1 * j) for j in lt.giant]
+        if pts.param != p or any(gk is not None and gk.param != p for gk in baby + giant):
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the plaintexts or a Galois key are not of this ciphertext's chain")
+        for g, gk in zip(pts.gs + giant_gs, baby + giant):
+            if g != 1 and gk.g != g:
+                raise ValueError(f"linear_transform: a key is of g={gk.g}, its step's element is {g}")
+        out = torch.empty_like(self.d)
+        binding.ckks_rns_bsgs_dev(p.plans(), p.special_plan(), [None if gk is None else gk.d_gk.data_ptr() for gk in baby], pts.gs,
+                                  [None if gk is None else gk.d_gk.data_ptr() for gk in giant], giant_gs, len(p.moduli), pts.d_pts.data_ptr(), self.d.data_ptr(),
+                                  out.data_ptr(), self.batch)
+        return RnsCiphertext(p, out)
+
+
+# ---- inner products, scalar sums and linear transforms over Z_t (DESIGN.md §34) --------------------------------------------------------
+def centred(x, t):
+    """the Python integer x modulo t, in (-t / 2, t / 2]"""
+    x = int(x) % t
+    return x - t if x > t // 2 else x
+
+
+def dot_weights(param, count, weights=None):
+    """the weights of `dot` -> (w, W): Python integers centred modulo t, W the sum of their absolute values; w is None where
+    `weights` is None or every weight is 1 (the kernel then multiplies by nothing).  ValueError for a weight that is zero modulo
+    t, and where B <= t n Q W + 1: W is past what the auxiliary base admits (RnsParam.max_dot_weight)."""
+    if weights is None:
+        w = None
+    else:
+        w = [centred(x, param.t) for x in weights]
+        if len(w) != count:
+            raise ValueError("dot: weights must be [len(xs)]")
+        if any(x == 0 for x in w):
+            raise ValueError("dot: a weight is zero modulo t; leave the pair out")
+        if any(abs(x) >> 61 for x in w):
+            raise ValueError("dot: a weight is not below 2^61 in absolute value")
+    W = count if w is None else sum(abs(x) for x in w)
+    if W > param.max_dot_weight:
+        raise ValueError(f"dot: the sum of the absolute weights W = {W} is past the auxiliary base: B > t n Q W + 1 admits at most W = {param.max_dot_weight}")
+    return (None if w is None or all(x == 1 for x in w) else w), W
+
+
+def dot(xs, ys, rlk, weights=None):
+    """-> sum_r weights[r] xs[r] ys[r] from fhe_bfv_rns_dot_dev: the integer tensors of all pairs are summed before
+    the ONE division by Q and relinearised ONCE, so the call rounds once and adds one relinearisation noise term whatever
+    len(xs) is.  xs, ys equal-length lists of RnsCiphertext of one RnsParam and batch; dot([x], [x], rlk) is the square.
+    weights are Python integers, taken centred modulo t; None: ones."""
+    xs, ys = list(xs), list(ys)
+    if not xs or len(xs) != len(ys):
+        raise ValueError("dot: xs and ys must be non-empty lists of one length")
+    param, batch = xs[0].param, xs[0].batch
+    if any(ct.param != param or ct.batch != batch for ct in xs + ys):
+        raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "dot: operands differ in RnsParam or batch")
+    if rlk.param != param:
+        raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "dot: the relinearisation key is not of the operands' chain")
+    w, _ = dot_weights(param, len(xs), weights)
+    out = _torch().empty_like(xs[0].d)
+    binding.bfv_rns_dot_dev(param.plans(), param.aux_plans(), param.special_plan(), param.t, rlk.d_rlk.data_ptr(), [ct.d.data_ptr() for ct in xs],
+                            [ct.d.data_ptr() for ct in ys], w, out.data_ptr(), batch)
+    return RnsCiphertext(param, out)
+
+
+def lincomb_residues(param, weights, consts=None):
+    """what `lincomb` hands fhe_ckks_rns_lincomb_dev -> (w, k): weights [outputs][count] Python integers, centred modulo t, as
+    canonical residues [outputs][count][limbs] in a flat list; consts [outputs] (or None -> None) as floor(Q / t) c mod q_i, c
+    centred modulo t, [outputs][limbs] in a flat list"""
+    delta = param.Q // param.t
+    w = [centred(x, param.t) % q for row in weights for x in row for q in param.moduli]
+    k = None if consts is None else [delta * centred(c, param.t) % q for c in consts for q in param.moduli]
+    return w, k
+
+
+def lincomb(cts, weights, consts=None):
+    """-> [sum_r weights[o][r] cts[r] + consts[o] for each output o] from fhe_ckks_rns_lincomb_dev: every input is read once for
+    up to four outputs and nothing is transformed.  weights Python integers [outputs][count] (1-D: one output), taken centred
+    modulo t and reduced per limb; consts integers [outputs] or None.  A constant c is added as floor(Q / t) c mod q_i to
+    component 0, which is the encoding of the CONSTANT POLYNOMIAL c only: under the batch encoder that is c in every slot, and
+    no other plaintext can be added this way (use add_plain).  The noise grows by the sum of the absolute weights."""
+    cts = list(cts)
+    if not cts:
+        raise ValueError("lincomb: no input")
+    weights = list(weights)
+    if not weights:
+        raise ValueError("lincomb: no weight")
+    rows = [list(r) for r in weights] if hasattr(weights[0], "__len__") else [weights]
+    if any(len(r) != len(cts) for r in rows):
+        raise ValueError("lincomb: weights must be [outputs][len(cts)]")
+    outputs = len(rows)
+    consts = None if consts is None else list(np.asarray(consts, dtype=object).reshape(-1))
+    if consts is not None and len(consts) != outputs:
+        raise ValueError("lincomb: consts must be [outputs]")
+    param, batch = cts[0].param, cts[0].batch
+    if any(ct.param != param or ct.batch != batch for ct in cts):
+        raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "lincomb: operands differ in RnsParam or batch")
+    k = len(param.moduli)
+    out = _torch().empty((outputs, k, 2, batch, param.n), dtype=_torch().int64, device="cuda")
+    cap = binding.FHE_CKKS_LINCOMB_MAX_OUTPUTS
+    for o0 in range(0, outputs, cap):
+        o1 = min(outputs, o0 + cap)
+        w, kk = lincomb_residues(param, rows[o0:o1], None if consts is None else consts[o0:o1])
+        binding.ckks_rns_lincomb_dev(param.plans(), [ct.d.data_ptr() for ct in cts], w, kk, o1 - o0, out[o0].data_ptr(), batch)
+    return [RnsCiphertext(param, out[o]) for o in range(outputs)]
+
+
+def encode_diagonals(param, encoder, rows, steps):
+    """rows [outputs][count][2][n/2] (or [count][2][n/2]: one output) slot values modulo t; column r multiplies the ciphertext
+    rotated by steps[r].  BatchEncoder.encode, centred modulo t, then fhe_ckks_rns_from_i64_dev over the chain's plans and once
+    more over the special prime's plan -> ckks.RnsPlaintextSet with d_pts [outputs][count][k + 1][n], what
+    fhe_ckks_rns_diag_sum_dev and fhe_ckks_rns_bsgs_dev take"""
+    torch = _torch()
+    n, t, k = param.n, param.t, len(param.moduli)
+    if encoder.n != n or encoder.t != t:
+        raise ValueError("encode_diagonals: the encoder is not of this RnsParam's n and t")
+    rows = np.asarray(rows, dtype=np.int64)
+    if rows.ndim == 3:
+        rows = rows[None]
+    steps = [int(st) for st in steps]
+    if rows.ndim != 4 or rows.shape[0] < 1 or rows.shape[1:] != (len(steps), 2, max(n // 2, 1)):
+        raise ValueError("encode_diagonals: rows must be [outputs][len(steps)][2][n/2]")
+    outputs, count = rows.shape[:2]
+    coef = encoder.encode(rows.reshape(outputs * count, 2, max(n // 2, 1))).astype(np.int64)
+    coef = np.where(coef > t // 2, coef - t, coef)
+    d_rows = torch.from_numpy(np.ascontiguousarray(coef)).cuda()
+    d_pts = torch.empty((outputs * count, k + 1, n), dtype=torch.int64, device="cuda")
+    for plans, lo in ((param.plans(), 0), ([param.special_plan()], k)):
+        ev = torch.empty((len(plans), outputs * count, n), dtype=torch.int64, device="cuda")
+        binding.ckks_rns_from_i64_dev(plans, d_rows.data_ptr(), ev.data_ptr(), outputs * count)
+        d_pts[:, lo:lo + len(plans)] = ev.permute(1, 0, 2)
+    ck = _ckks()
+    return ck.RnsPlaintextSet(param, k - 1, d_pts.reshape(outputs, count, k + 1, n), 1.0, [ck.galois_element(n, st) for st in steps])
+
+
+def bsgs_diagonals(M, t, n1=None):
+    """The baby-step giant-step form of out[r] = M[r] in[r] mod t on the two slot rows (N = n/2 columns): M integers [2][N][N],
+    or [N][N] for both rows.  Diagonal d is diag_d[r][c] = M[r][c][(c + d) mod N]; a diagonal that is zero modulo t in both rows
+    is dropped; d = n1 a + b.  -> (n1, baby, giant, rows): the sorted baby steps b and giant steps a that occur, and rows
+    int64 [len(giant)][len(baby)][2][N] in [0, t) with rows[a][b] = roll(diag_{n1 giant[a] + baby[b]}, +n1 giant[a]) along the
+    columns (zero where that diagonal is dropped), the giant step's plaintext pre-rotated as ckks.bsgs_diagonals does, so that
+        M x = sum_a roll(sum_b rows[a][b] * roll(x, -baby[b]), -n1 giant[a])   (mod t, rolls along the columns).
+    n1 defaults to the ceiling of the square root of the number of diagonals kept."""
+    M = np.asarray(M)
+    if M.ndim == 2:
+        M = np.stack([M, M])
+    if M.ndim != 3 or M.shape[0] != 2 or M.shape[1] != M.shape[2] or M.shape[1] < 1:
+        raise ValueError("bsgs_diagonals: M must be [2][N][N] or [N][N]")
+    M = np.mod(M.astype(object), int(t)).astype(np.int64)
+    N = M.shape[1]
+    c = np.arange(N)
+    diag = {d: M[:, c, (c + d) % N] for d in range(N)}
+    kept = [d for d in range(N) if np.any(diag[d] != 0)] or [0]
+    if n1 is None:
+        n1 = int(np.ceil(np.sqrt(len(kept))))
+    n1 = int(n1)
+    if not 1 <= n1 <= N:
+        raise ValueError(f"bsgs_diagonals: n1={n1} must be in [1, {N}]")
+    baby, giant = sorted({d % n1 for d in kept}), sorted({d // n1 for d in kept})
+    rows = np.zeros((len(giant), len(baby), 2, N), dtype=np.int64)
+    for d in kept:
+        rows[giant.index(d // n1), baby.index(d % n1)] = np.roll(diag[d], n1 * (d // n1), axis=1)
+    return n1, baby, giant, rows
+
+
+class LinearTransform:
+    """out[r] = M[r] in[r] mod t on the two slot rows, encoded for RnsCiphertext.linear_transform: one plaintext set whose
+    outputs are the giant steps and whose columns the baby steps of bsgs_diagonals"""
+
+    def __init__(self, param, n1, baby, giant, pts):
+        self.param, self.n1, self.baby, self.giant, self.pts = param, n1, list(baby), list(giant), pts
+
+    @classmethod
+    def from_matrices(cls, param, encoder, M, n1=None):
+        N = max(param.n // 2, 1)
+        if np.asarray(M).shape not in ((2, N, N), (N, N)):
+            raise ValueError(f"LinearTransform: M must be [2][{N}][{N}] or [{N}][{N}]")
+        n1, baby, giant, rows = bsgs_diagonals(M, param.t, n1)
+        return cls(param, n1, baby, giant, encode_diagonals(param, encoder, rows, baby))
+
+    def required_steps(self):
+        """the rotation steps whose keys linear_transform needs: the non-zero baby steps and n1 times the non-zero giant steps"""
+        return sorted({i for i in self.baby if i} | {self.n1 * j for j in self.giant if j})
+
 
 class RnsClientKey(ClientKeyBase):
     """The BFV secret under every prime of an RnsParam, on ClientKeyBase with the row plan of ckks.RnsClientKey:
@@ -472,6 +695,10 @@ class RnsClientKey(ClientKeyBase):
 
     def row_swap_key(self, slot):
         return self.galois_key(2 * self.param.n - 1, slot)
+
+    def encode_diagonals(self, rows, steps):
+        """the plaintext set of RnsCiphertext.diag_sum: encode_diagonals with the batch encoder of this key's n and t"""
+        return encode_diagonals(self.param, BatchEncoder(self.param.n, self.param.t), rows, steps)
 
     def encrypt(self, pk, m):
         """m in [0, t)^n, (n,) or (batch, n) -> RnsCiphertext: floor(Q / t) m per limb (fhe_bfv_rns_scale_msg_dev), then

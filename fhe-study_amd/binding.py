@@ -103,11 +103,14 @@ EXPORTS = [
     "fhe_ckks_embed_twiddles", "fhe_ckks_embed_encode_dev", "fhe_ckks_embed_decode_dev", "fhe_ckks_embed_workspace_bytes",
     # BFV on an RNS modulus chain: exact basis extension, ct x ct, message scaling, decryption (bfv_rns.hip)
     "fhe_rns_extend_dev", "fhe_bfv_rns_tensor_dev", "fhe_bfv_rns_mul_dev", "fhe_bfv_rns_workspace_bytes", "fhe_bfv_rns_scale_msg_dev", "fhe_bfv_rns_decrypt_dev",
+    # BFV on the chain: inner products, one rounding and one relinearisation (bfv_rns.hip)
+    "fhe_bfv_rns_dot_dev",
 ]
 FHE_CKKS_GALOIS_MAX_COUNT = 256              # include/fhe_ntt.h: the most Galois elements of one fhe_ckks_rns_galois_dev call
 FHE_CKKS_DIAG_MAX_OUTPUTS = 64               # include/fhe_ntt.h: the most outputs of one fhe_ckks_rns_diag_sum_dev call
 FHE_CKKS_LINCOMB_MAX_COUNT, FHE_CKKS_LINCOMB_MAX_OUTPUTS = 64, 16    # include/fhe_ntt.h: the most inputs and outputs of one fhe_ckks_rns_lincomb_dev call
 FHE_CKKS_DOT_MAX_COUNT = 64                  # include/fhe_ntt.h: the most pairs of one fhe_ckks_rns_dot_dev call
+FHE_BFV_DOT_MAX_COUNT = 64                   # include/fhe_ntt.h: the most pairs of one fhe_bfv_rns_dot_dev call
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
 GATES = {"AND": 0, "NAND": 1, "OR": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -347,6 +350,7 @@ def load_library():
     L.fhe_rns_extend_dev.argtypes = [ctypes.POINTER(_u64), _uint, ctypes.POINTER(_u64), _uint, _int, _vp, _vp, _sz, _vp]
     L.fhe_bfv_rns_tensor_dev.argtypes = [_pp, _uint, _pp, _u64, _vp, _vp, _vp, _sz, _vp]
     L.fhe_bfv_rns_mul_dev.argtypes = [_pp, _uint, _pp, _vp, _u64, _vp, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_bfv_rns_dot_dev.argtypes = [_pp, _uint, _pp, _vp, _u64, _vp, _pp, _pp, _uint, ctypes.POINTER(ctypes.c_int64), _vp, _sz, _vp]
     L.fhe_bfv_rns_workspace_bytes.argtypes = [_u64, _uint, _sz]
     L.fhe_bfv_rns_workspace_bytes.restype = _sz
     L.fhe_bfv_rns_scale_msg_dev.argtypes = [_pp, _uint, _u64, _vp, _vp, _sz, _vp]
@@ -985,6 +989,18 @@ def bfv_rns_mul_dev(plans, aux, special, t, d_rlk, d_a, d_b, d_out, batch, strea
     """fhe_bfv_rns_mul_dev: the scaled tensor and its relinearisation against d_rlk [limbs][limbs + 1][2][n] in one call"""
     _check(load_library().fhe_bfv_rns_mul_dev(None if plans is None else _plan_array(plans), len(plans) if limbs is None else limbs,
                                               None if aux is None else _plan_array(aux), _handle(special), t, d_rlk, d_a, d_b, d_out, batch, stream))
+
+
+def bfv_rns_dot_dev(plans, aux, special, t, d_rlk, d_as, d_bs, w, d_out, batch, stream=None, limbs=None, count=None):
+    """fhe_bfv_rns_dot_dev: relinearize(round(t sum_r w_r tensor(a_r, b_r) / Q)) -> [limbs][2][batch][n], one rounding
+    and one key switch whatever the number of pairs; d_as and d_bs lists of device pointers (None is passed as NULL, as is a
+    None list), w the signed weights [count] as a sequence of integers (None: every weight is 1)"""
+    a = None if d_as is None else (_vp * max(len(d_as), 1))(*d_as)
+    b = None if d_bs is None else (_vp * max(len(d_bs), 1))(*d_bs)
+    ws = None if w is None else (ctypes.c_int64 * max(len(w), 1))(*w)
+    _check(load_library().fhe_bfv_rns_dot_dev(None if plans is None else _plan_array(plans), len(plans) if limbs is None else limbs,
+                                              None if aux is None else _plan_array(aux), _handle(special), t, d_rlk, a, b, len(d_as) if count is None else count, ws,
+                                              d_out, batch, stream))
 
 
 def bfv_rns_workspace_bytes(n, limbs, batch):

@@ -14,6 +14,9 @@
 //              (3) u = t d + floor(Q / 2) in every limb, r = u mod Q extended (not centred) to B, y_j = (u_j - r_j) Q^-1 mod b_j:
 //                  the quotient exactly;  (4) y extended centred from B to Q; forward transforms -> [k][3][batch][n]
 //              (3) and (4) are one kernel, in place on the tensor's Q limbs; relinearisation is ckks_eval.hip's
+//   dot        sum_r w_r d^(r) over pairs before the one division by Q: step (1) per pair, then ONE launch of
+//              bfv_rns_tensorsum_kernel adds the pair's weighted tensor into all 2k + 1 limbs; steps (2, inverse) .. (4) and the
+//              relinearisation once.  Admission B > t n Q W + 1, W the sum of the absolute weights
 //   decrypt    v = c0 + c1 s per limb, centred in Q; m = floor((t v + floor(Q / 2)) / Q) mod t by (3) with b_0 alone (b_0 > 2 t + 2)
 //
 // All kernels are grid-stride and element-wise on fhe_ew_grid, bounds-checked against their element count, plain C++ with
@@ -186,6 +189,60 @@ __global__ __launch_bounds__(256) void bfv_rns_scale_msg_kernel(const u64 *__res
     }
 }
 
+// ---- inner products: the weighted sum of the pairs' tensors before the one division by Q ------------------------
+constexpr u32 kBfvAllLimbs = kBfvMaxLimbs + kBfvMaxAux;
+
+// one limb of Q u B for one pair: its modulus, the weight's canonical residue (not read unless WEIGHTED) and the pair's operands,
+// two components `cs` words apart each: the caller's ciphertexts for a limb of Q, the extended operands X for a limb of B
+struct TensorSumLimb {
+    Mod m;
+    u64 w;
+    const u64 *a, *b;
+    u64 cs;
+};
+// Indexed by blockIdx.y, which is uniform: scalar loads from the kernel-argument segment, as DotGroup of ckks_eval.hip.
+struct TensorSumArgs {
+    TensorSumLimb l[kBfvAllLimbs];
+};
+
+// One pair into all 2k + 1 limbs of the summed tensor D [2k + 1][3][count] in ONE launch: blockIdx.y is the limb, `count` the words
+// of a component, and per limb
+//   d0[e] (+)= w a0[e] b0[e],  d1[e] (+)= w (a0[e] b1[e] + a1[e] b0[e]),  d2[e] (+)= w a1[e] b1[e]
+// CARRY: the sums start from the canonical words the pairs before left in D; otherwise from zero.  WEIGHTED = false: w = 1.
+// Overflow: every prime is below 2^62 (check_bfv_chain), so only MacAcc's narrow fold applies.  The weight is folded into a0 and
+// a1 first (ckks_rns_tensorsum_kernel), so a term is a product of two canonical words, below 2^124; an accumulator holds a
+// canonical carry-over and at most two terms: below 2^62 + 2^125.  Operands are only read; D is none of them (the workspace).
+template <bool WEIGHTED, bool CARRY>
+__global__ __launch_bounds__(256) void bfv_rns_tensorsum_kernel(u64 *__restrict__ D, u64 count, TensorSumArgs args) {
+    const TensorSumLimb &l = args.l[blockIdx.y];
+    const Mod m = l.m;
+    const u64 *__restrict__ a = l.a, *__restrict__ b = l.b;
+    const u64 cs = l.cs, w = l.w;
+    u64 *__restrict__ out = D + 3ull * blockIdx.y * count;
+    const u64 stride = (u64)gridDim.x * 256;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        MacAcc d0, d1, d2;
+        if (CARRY) {
+            d0.v = out[i];
+            d1.v = out[count + i];
+            d2.v = out[2 * count + i];
+        }
+        u64 a0 = a[i], a1 = a[cs + i];
+        const u64 b0 = b[i], b1 = b[cs + i];
+        if (WEIGHTED) {
+            a0 = mul_mod_var(w, a0, m);
+            a1 = mul_mod_var(w, a1, m);
+        }
+        d0.mac(a0, b0);
+        d1.mac(a0, b1);
+        d1.mac(a1, b0);
+        d2.mac(a1, b1);
+        out[i] = d0.fold(m);
+        out[count + i] = d1.fold(m);
+        out[2 * count + i] = d2.fold(m);
+    }
+}
+
 }  // namespace fhe
 
 // ---- host side -----------------------------------------------------------------------------------------------------
@@ -236,11 +293,7 @@ int check_bfv_chain(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_
     for (unsigned i = 0; i < limbs; i++) c->qm[i] = plans[i]->q;
     if (aux) {
         for (unsigned j = 0; j <= limbs; j++) c->bm[j] = aux[j]->q;
-        fhe::host::Big lhs = fhe::host::big_product(c->bm, limbs + 1), rhs = fhe::host::big_product(c->qm, limbs);
-        rhs.mul(t);
-        rhs.mul(c->n);
-        rhs.add(1);
-        if (lhs.cmp(rhs) <= 0) return fhe_fail(FHE_E_INVALID, "%s: the auxiliary base must exceed t n Q + 1", who);
+        if (!fhe::host::bfv_admits(c->bm, limbs + 1, c->qm, limbs, t, c->n, 1)) return fhe_fail(FHE_E_INVALID, "%s: the auxiliary base must exceed t n Q + 1", who);
     }
     return FHE_OK;
 }
@@ -297,15 +350,17 @@ int inverse_into(const fhe_ntt_plan *p, const u64 *src, u64 *dst, u64 polys, hip
     return rc != FHE_OK ? rc : fhe_ntt_inverse_dev(p, src, dst, polys, st);
 }
 
-// Rows r0 .. r0 + cr of a, b [k][2][batch][n] -> the scaled tensor of the chunk as evals in the Q limbs of D = W + 4 (2k + 1) slab
-// words, [k][3][cr][n]; slab = cr n.  W: X [2k + 1][4][slab] (the operands' coefficients, a0 a1 b0 b1 per limb; the limbs of B
-// then transformed), D [2k + 1][3][slab].
-int scaled_tensor_rows(const BfvChain &c, const fhe::ScaleArgs &s, const u64 *a, const u64 *b, u64 batch, u64 r0, u64 cr, u64 *W, hipStream_t st) {
-    const unsigned k = c.k, all = 2 * k + 1;
+// The workspace rows of a chunk of cr ciphertexts, slab = cr n words: X [2k + 1][4][slab] (the operands' coefficients, a0 a1 b0 b1
+// per limb; the limbs of B then transformed), D = W + 4 (2k + 1) slab words, [2k + 1][3][slab] (the tensor).
+//
+// Step (1) for rows r0 .. r0 + cr of a, b [k][2][batch][n]: their coefficients per limb of Q, the centred extension to B and the
+// forward transforms there -> the evals modulo b_j in the limbs k .. 2k of X
+int extend_operand_rows(const BfvChain &c, const fhe::ScaleArgs &s, const u64 *a, const u64 *b, u64 batch, u64 r0, u64 cr, u64 *W, hipStream_t st) {
+    const unsigned k = c.k;
     const u64 n = c.n, slab = cr * n;
-    u64 *X = W, *D = W + 4ull * all * slab;
+    u64 *X = W;
     int rc;
-    for (unsigned i = 0; i < k; i++) {                               // (1) coefficients of the operands, limb by limb
+    for (unsigned i = 0; i < k; i++) {                               // coefficients of the operands, limb by limb
         const u64 *op[2] = {a + ((u64)i * 2 * batch + r0) * n, b + ((u64)i * 2 * batch + r0) * n};
         for (unsigned o = 0; o < 2; o++) {
             u64 *dst = X + ((u64)i * 4 + 2 * o) * slab;
@@ -322,14 +377,16 @@ int scaled_tensor_rows(const BfvChain &c, const fhe::ScaleArgs &s, const u64 *a,
         u64 *xb = X + 4ull * (k + j) * slab;
         if ((rc = fhe_ntt_forward_dev(c.b[j], xb, xb, 4 * cr, st)) != FHE_OK) return rc;
     }
-    for (unsigned i = 0; i < k; i++)                                 // (2) the tensor per limb: modulo Q from the operands' own evals
-        if ((rc = fhe_rns_tensor_limb(c.q[i], a + ((u64)i * 2 * batch + r0) * n, batch * n, b + ((u64)i * 2 * batch + r0) * n, batch * n, D + 3ull * i * slab, slab, slab,
-                                      st)) != FHE_OK)
-            return rc;
-    for (unsigned j = 0; j <= k; j++) {
-        const u64 *xb = X + 4ull * (k + j) * slab;
-        if ((rc = fhe_rns_tensor_limb(c.b[j], xb, slab, xb + 2 * slab, slab, D + 3ull * (k + j) * slab, slab, slab, st)) != FHE_OK) return rc;
-    }
+    return FHE_OK;
+}
+
+// Steps (2, the inverse transforms), (3) and (4) on the chunk's tensor D, evals in all 2k + 1 limbs -> the scaled tensor as evals
+// in the Q limbs of D, [k][3][cr][n]
+int scale_tensor_rows(const BfvChain &c, const fhe::ScaleArgs &s, u64 cr, u64 *W, hipStream_t st) {
+    const unsigned k = c.k, all = 2 * k + 1;
+    const u64 slab = cr * c.n;
+    u64 *D = W + 4ull * all * slab;
+    int rc;
     for (unsigned l = 0; l < all; l++) {
         u64 *dl = D + 3ull * l * slab;
         if ((rc = fhe_ntt_inverse_dev(l < k ? c.q[l] : c.b[l - k], dl, dl, 3 * cr, st)) != FHE_OK) return rc;
@@ -340,6 +397,60 @@ int scaled_tensor_rows(const BfvChain &c, const fhe::ScaleArgs &s, const u64 *a,
         if ((rc = fhe_ntt_forward_dev(c.q[i], dl, dl, 3 * cr, st)) != FHE_OK) return rc;
     }
     return FHE_OK;
+}
+
+// Rows r0 .. r0 + cr of a, b [k][2][batch][n] -> the scaled tensor of the chunk as evals in the Q limbs of D, [k][3][cr][n]
+int scaled_tensor_rows(const BfvChain &c, const fhe::ScaleArgs &s, const u64 *a, const u64 *b, u64 batch, u64 r0, u64 cr, u64 *W, hipStream_t st) {
+    const unsigned k = c.k, all = 2 * k + 1;
+    const u64 n = c.n, slab = cr * n;
+    u64 *X = W, *D = W + 4ull * all * slab;
+    int rc;
+    if ((rc = extend_operand_rows(c, s, a, b, batch, r0, cr, W, st)) != FHE_OK) return rc;
+    for (unsigned i = 0; i < k; i++)                                 // (2) the tensor per limb: modulo Q from the operands' own evals
+        if ((rc = fhe_rns_tensor_limb(c.q[i], a + ((u64)i * 2 * batch + r0) * n, batch * n, b + ((u64)i * 2 * batch + r0) * n, batch * n, D + 3ull * i * slab, slab, slab,
+                                      st)) != FHE_OK)
+            return rc;
+    for (unsigned j = 0; j <= k; j++) {
+        const u64 *xb = X + 4ull * (k + j) * slab;
+        if ((rc = fhe_rns_tensor_limb(c.b[j], xb, slab, xb + 2 * slab, slab, D + 3ull * (k + j) * slab, slab, slab, st)) != FHE_OK) return rc;
+    }
+    return scale_tensor_rows(c, s, cr, W, st);
+}
+
+// The weighted sum of the tensors of `count` pairs over rows r0 .. r0 + cr, scaled once -> as scaled_tensor_rows.  Per pair step
+// (1) into X, then ONE launch adds its tensor into all 2k + 1 limbs of D; wres [count][2k + 1] the weights' canonical residues
+// (Q's primes, then B's), NULL where every weight is 1.
+int scaled_tensorsum_rows(const BfvChain &c, const fhe::ScaleArgs &s, const void *const *d_as, const void *const *d_bs, unsigned count, const u64 *wres, u64 batch,
+                          u64 r0, u64 cr, u64 *W, hipStream_t st) {
+    const unsigned k = c.k, all = 2 * k + 1;
+    const u64 n = c.n, slab = cr * n;
+    u64 *X = W, *D = W + 4ull * all * slab;
+    for (unsigned r = 0; r < count; r++) {
+        const u64 *a = (const u64 *)d_as[r], *b = (const u64 *)d_bs[r];
+        int rc = extend_operand_rows(c, s, a, b, batch, r0, cr, W, st);
+        if (rc != FHE_OK) return rc;
+        fhe::TensorSumArgs args{};
+        for (unsigned l = 0; l < all; l++) {
+            fhe::TensorSumLimb &t = args.l[l];
+            t.m = (l < k ? c.q[l] : c.b[l - k])->mod;
+            t.w = wres ? wres[(u64)r * all + l] : 1;
+            if (l < k) {
+                t.a = a + ((u64)l * 2 * batch + r0) * n;
+                t.b = b + ((u64)l * 2 * batch + r0) * n;
+                t.cs = batch * n;
+            } else {
+                t.a = X + 4ull * l * slab;
+                t.b = t.a + 2 * slab;
+                t.cs = slab;
+            }
+        }
+        const bool carry = r > 0;
+        auto kernel = wres ? (carry ? fhe::bfv_rns_tensorsum_kernel<true, true> : fhe::bfv_rns_tensorsum_kernel<true, false>)
+                           : (carry ? fhe::bfv_rns_tensorsum_kernel<false, true> : fhe::bfv_rns_tensorsum_kernel<false, false>);
+        const hipError_t e = fhe::launch_grid(kernel, "bfv_rns_tensorsum", (int)c.L, dim3(fhe_ew_grid(slab), all), 256, 0, st, D, slab, args);
+        if (e != hipSuccess) return fhe_hip_fail(e, "bfv_rns_tensorsum_kernel");
+    }
+    return scale_tensor_rows(c, s, cr, W, st);
 }
 
 int check_product_args(const BfvChain &c, const void *d_rlk, const void *d_a, const void *d_b, void *d_out, unsigned out_comps, size_t batch, const char *who) {
@@ -440,6 +551,65 @@ extern "C" int fhe_bfv_rns_mul_dev(const fhe_ntt_plan *const *plans, unsigned li
         const u64 cr = std::min<u64>(cb, batch - r0);
         if ((rc = scaled_tensor_rows(c, s, (const u64 *)d_a, (const u64 *)d_b, batch, r0, cr, (u64 *)w, st)) != FHE_OK) return rc;
         const u64 *D = (const u64 *)w + 4ull * (2 * c.k + 1) * cr * n;   // the chunk's tensor stays in the workspace
+        if ((rc = fhe_rns_relin_rows(plans, limbs, special, (const u64 *)d_rlk, D, cr, (u64 *)d_out, batch, r0, st)) != FHE_OK) return rc;
+    }
+    return FHE_OK;
+}
+
+extern "C" int fhe_bfv_rns_dot_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *aux, const fhe_ntt_plan *special, uint64_t t,
+                                   const void *d_rlk, const void *const *d_as, const void *const *d_bs, unsigned count, const int64_t *w, void *d_out, size_t batch,
+                                   void *hip_stream) {
+    const char *who = "fhe_bfv_rns_dot_dev";
+    if (!aux) return fhe_fail(FHE_E_NULL, "%s: aux is NULL", who);
+    if (!special) return fhe_fail(FHE_E_NULL, "%s: the special prime's plan is NULL", who);
+    BfvChain c;
+    int rc = check_bfv_chain(plans, limbs, aux, special, t, &c, who);
+    if (rc != FHE_OK) return rc;
+    for (unsigned i = 0; i < c.k; i++)
+        if (special->q < c.qm[i]) return fhe_fail(FHE_E_INVALID, "%s: the special prime must not be below a chain prime", who);
+    if (count < 1 || count > FHE_BFV_DOT_MAX_COUNT) return fhe_fail(FHE_E_INVALID, "%s: count=%u must be in [1, %d]", who, count, FHE_BFV_DOT_MAX_COUNT);
+    if (!d_as || !d_bs) return fhe_fail(FHE_E_NULL, "%s: NULL host array", who);
+    const unsigned all = 2 * c.k + 1;
+    fhe::u128 W = count;                                             // the sum of the absolute weights
+    std::vector<u64> wres;                                           // [count][2k + 1] canonical residues, empty where w is NULL
+    if (w) {
+        W = 0;
+        wres.resize((size_t)count * all);
+        for (unsigned r = 0; r < count; r++) {
+            const u64 mag = w[r] < 0 ? 0 - (u64)w[r] : (u64)w[r];
+            if (mag == 0) return fhe_fail(FHE_E_INVALID, "%s: weight %u is zero", who, r);
+            if (mag >= (1ull << 61)) return fhe_fail(FHE_E_INVALID, "%s: weight %u is not below 2^61 in absolute value", who, r);
+            W += mag;
+            for (unsigned l = 0; l < all; l++) {
+                const u64 p = l < c.k ? c.qm[l] : c.bm[l - c.k], res = mag % p;
+                wres[(size_t)r * all + l] = (w[r] < 0 && res) ? p - res : res;
+            }
+        }
+    }
+    if (!fhe::host::bfv_admits(c.bm, c.k + 1, c.qm, c.k, t, c.n, W))
+        return fhe_fail(FHE_E_INVALID, "%s: the auxiliary base must exceed t n Q W + 1, W the sum of the absolute weights", who);
+    fhe::ScaleArgs s;
+    if ((rc = scale_args(c, &s, who)) != FHE_OK) return rc;
+    if (batch == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, 3ull * c.k * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_rlk || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_rlk) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 ct_bytes = 2ull * c.k * batch * n * 8, rlk_bytes = (u64)c.k * (c.k + 1) * 2 * n * 8;
+    if (overlaps_any(d_out, ct_bytes, {{d_rlk, rlk_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key", who);
+    for (unsigned r = 0; r < count; r++) {
+        if (!d_as[r] || !d_bs[r]) return fhe_fail(FHE_E_NULL, "%s: an operand of pair %u is NULL", who, r);
+        if (misaligned8(d_as[r]) || misaligned8(d_bs[r])) return fhe_fail(FHE_E_INVALID, "%s: the operands of pair %u must be 8-byte aligned", who, r);
+        if (overlaps_any(d_out, ct_bytes, {{d_as[r], ct_bytes}, {d_bs[r], ct_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an operand of pair %u", who, r);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    const u64 cb = bfv_chunk_rows(c.k, c.L, batch);
+    void *ws = nullptr;
+    if ((rc = fhe_workspace_get(kBfvRnsSlot, (size_t)(bfv_words_per_row(c.k, n) * cb * 8), st, &ws)) != FHE_OK) return rc;
+    for (u64 r0 = 0; r0 < batch; r0 += cb) {
+        const u64 cr = std::min<u64>(cb, batch - r0);
+        if ((rc = scaled_tensorsum_rows(c, s, d_as, d_bs, count, wres.empty() ? nullptr : wres.data(), batch, r0, cr, (u64 *)ws, st)) != FHE_OK) return rc;
+        const u64 *D = (const u64 *)ws + 4ull * (2 * c.k + 1) * cr * n;   // the chunk's summed tensor stays in the workspace
         if ((rc = fhe_rns_relin_rows(plans, limbs, special, (const u64 *)d_rlk, D, cr, (u64 *)d_out, batch, r0, st)) != FHE_OK) return rc;
     }
     return FHE_OK;

@@ -84,6 +84,33 @@ inline Big big_product(const u64 *m, unsigned count) {
     return p;
 }
 
+// a x for a 128-bit x: a lo + 2^64 (a hi), the second product added one word up
+inline Big big_mul128(const Big &a, u128 x) {
+    Big lo = a, hi = a;
+    lo.mul((u64)x);
+    hi.mul((u64)(x >> 64));
+    u64 carry = 0;
+    for (size_t i = 0; i < hi.w.size() || carry; i++) {
+        if (lo.w.size() <= i + 1) lo.w.resize(i + 2, 0);
+        const u128 s = (u128)lo.w[i + 1] + (i < hi.w.size() ? hi.w[i] : 0) + carry;
+        lo.w[i + 1] = (u64)s;
+        carry = (u64)(s >> 64);
+    }
+    lo.trim();
+    return lo;
+}
+
+// The admission of the BFV products: B > t n Q W + 1, B the product of aux[0 .. na), Q of mods[0 .. nq),
+// W the sum of the absolute weights of an inner product (1 for a single product; at most 64 (2^61 - 1), so 128 bits).  Exact.
+inline bool bfv_admits(const u64 *aux, unsigned na, const u64 *mods, unsigned nq, u64 t, u64 n, u128 W) {
+    Big rhs = big_product(mods, nq);
+    rhs.mul(t);
+    rhs.mul(n);
+    rhs = big_mul128(rhs, W);
+    rhs.add(1);
+    return big_product(aux, na).cmp(rhs) > 0;
+}
+
 // x^-1 mod m by the extended Euclidean algorithm, for any m >= 2; false where gcd(x, m) != 1
 inline bool inv_mod_any(u64 x, u64 m, u64 *out) {
     typedef __int128 i128;

@@ -835,6 +835,25 @@ int fhe_bfv_rns_scale_msg_dev(const fhe_ntt_plan *const *plans, unsigned limbs, 
 int fhe_bfv_rns_decrypt_dev(const fhe_ntt_plan *const *plans, unsigned limbs, uint64_t aux0, uint64_t t,
                             const void *d_s_evals, const void *d_ct, void *d_out, size_t batch, void *hip_stream);
 
+/* ---- BFV inner products on the chain: sum of ct x ct pairs, one rounding, one relinearisation (bfv_rns.hip) ----
+ *   fhe_bfv_rns_dot_dev   d_as, d_bs HOST arrays of `count` device pointers to ciphertexts [k][2][batch][n]; a_r = b_r is a
+ *            square and a pointer may repeat across pairs.  w a HOST array of `count` signed weights, each non-zero and below
+ *            2^61 in absolute value; NULL: every weight is 1.  For every coefficient of every component
+ *                D = sum_r w_r d^(r),   out = floor((t D + floor(Q / 2)) / Q) mod q_i,
+ *            d^(r) the negacyclic integer tensor (d0, d1, d2) of pair r's operands centred in Q as fhe_bfv_rns_tensor_dev takes
+ *            it; then the steps of fhe_ckks_rns_relinearize_dev against d_rlk [k][k + 1][2][n] -> d_out [k][2][batch][n].  ONE
+ *            rounding and ONE key switch whatever `count` is; one pair with w = NULL is fhe_bfv_rns_mul_dev word for word.
+ *            Admission: B > t n Q W + 1, W = sum_r |w_r| (|D| <= W n Q^2 / 2).  The library workspace is that of
+ *            fhe_bfv_rns_mul_dev: fhe_bfv_rns_workspace_bytes answers for this call too.
+ * The rejections are those of fhe_bfv_rns_mul_dev, and FHE_E_INVALID for count not in [1, FHE_BFV_DOT_MAX_COUNT], a zero weight, a
+ * weight of 2^61 or more in absolute value, a base that admits fhe_bfv_rns_mul_dev but not this W, and an output that overlaps
+ * an operand or the key; FHE_E_NULL for a NULL array or entry.  Everything is checked before any device call and nothing is
+ * written on rejection; batch = 0 is a no-op. */
+#define FHE_BFV_DOT_MAX_COUNT 64
+int fhe_bfv_rns_dot_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *aux,
+                        const fhe_ntt_plan *special, uint64_t t, const void *d_rlk, const void *const *d_as,
+                        const void *const *d_bs, unsigned count, const int64_t *w, void *d_out, size_t batch, void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
