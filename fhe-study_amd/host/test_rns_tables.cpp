@@ -1,9 +1,10 @@
 // test_rns_tables.cpp — csrc/rns_tables.hpp against its definitions, without the library or a GPU: the multi-word integers
 // against 128-bit arithmetic, Garner's inverses, the mixed-radix digits of floor(M / 2), the weights and M mod p of every
 // target, and the whole route (digits, comparison from the top, weighted sum) against x mod p for integers that fit 128 bits.
-// Also the program the sanitizers run on these builders (`make san`).
+// Also the program the sanitizers run on these builders (`make san`, or alone `make san_tables`).
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 #include "../csrc/rns_tables.hpp"
 
@@ -204,7 +205,70 @@ static void test_shapes_and_rejections() {
     CHECK(!(fhe::host::ext_tables<4, 5>(big, 5, small, 2, &narrow)));   // more sources than the shape holds
 }
 
+// sources and targets of mixed size in one base: 3, 5 and 7 beside primes of 20, 37 and 62 bits, small before
+// large and large before small.  The tables against their definitions at every size; the route against 128-bit arithmetic where
+// M fits, on the integers that differ from floor(M / 2) in one mixed-radix digit, with the digits below it all zero and all
+// m_j - 1, so that digit 0 alone points the wrong way.
+static void test_mixed_sizes() {
+    u64 p20[4], p37[4], p62[4];
+    primes_below(20, 4, p20);
+    primes_below(37, 4, p37);
+    primes_below(62, 4, p62);
+    const u64 up9[9] = {3, 5, 7, p20[0], p20[1], p37[0], p37[1], p62[0], p62[1]};
+    const u64 dst9[9] = {3, 5, 11, p20[2], p20[3], p37[2], p37[3], p62[2], p62[3]};
+    u64 down9[9], ddst9[9];
+    for (unsigned i = 0; i < 9; i++) down9[i] = up9[8 - i], ddst9[i] = dst9[8 - i];
+    check_tables<9, 9>(up9, 9, dst9, 9);
+    check_tables<9, 9>(down9, 9, ddst9, 9);
+    check_tables<9, 9>(up9, 9, dst9, 1);                             // the one target 3, a source as well
+    const u64 up5[5] = {3, 7, p20[0], p37[0], p62[0]}, down5[5] = {p62[0], p37[0], p20[0], 7, 3};
+    const u64 up3[3] = {5, p37[0], p62[0]}, down3[3] = {p62[0], p37[0], 5};
+    const u64 up2[2] = {7, p62[0]}, down2[2] = {p62[0], 7};
+    check_tables<4, 5>(up3, 3, dst9, 5);
+    check_tables<5, 4>(down5, 5, ddst9, 4);
+    check_tables<4, 1>(down2, 2, dst9, 1);
+    struct Case { const u64 *src; unsigned s; };
+    const Case cases[] = {{up5, 5}, {down5, 5}, {up3, 3}, {down3, 3}, {up2, 2}, {down2, 2}};   // M < 2^124
+    for (const Case &c : cases) {
+        for (const u64 *dst : {(const u64 *)dst9, (const u64 *)ddst9}) {
+            fhe::ExtArgs<9, 9> e;
+            CHECK((fhe::host::ext_tables<9, 9>(c.src, c.s, dst, 9, &e)));
+            u128 M = 1, w[9];
+            for (unsigned i = 0; i < c.s; i++) w[i] = M, M *= c.src[i];
+            std::vector<u128> xs = {0, 1, M - 1, M / 2, M / 2 + 1, M / 2 - 1};
+            for (unsigned i = 0; i < c.s; i++) {
+                for (int step = -1; step <= 1; step += 2) {
+                    if ((step < 0 && e.half[i] == 0) || (step > 0 && e.half[i] + 1 == c.src[i])) continue;
+                    for (int low = 0; low < 3; low++) {              // the digits below i: those of floor(M / 2), zero, m_j - 1
+                        u128 x = 0;
+                        for (unsigned j = 0; j < c.s; j++) {
+                            const u64 d = j > i ? e.half[j] : j == i ? e.half[i] + step : low == 0 ? e.half[j] : low == 1 ? 0 : c.src[j] - 1;
+                            x += w[j] * d;
+                        }
+                        xs.push_back(x);
+                    }
+                }
+                xs.push_back(w[i] * (c.src[i] - 1));                 // a single non-zero digit
+                xs.push_back(w[i]);
+            }
+            for (int it = 0; it < 500; it++) xs.push_back((((u128)rnd() << 64) | rnd()) % M);
+            for (const u128 x : xs) {
+                CHECK(x < M);
+                u64 res[9];
+                for (unsigned i = 0; i < c.s; i++) res[i] = (u64)(x % c.src[i]);
+                for (unsigned k = 0; k < 9; k++) {
+                    const u64 p = dst[k];
+                    CHECK(route(e, res, false, k) == (u64)(x % p));
+                    const u64 want = x > M / 2 ? (u64)((p - (u64)((M - x) % p)) % p) : (u64)(x % p);
+                    CHECK(route(e, res, true, k) == want);
+                }
+            }
+        }
+    }
+}
+
 int main() {
+    test_mixed_sizes();
     test_big();
     test_inverses();
     test_shapes_and_rejections();

@@ -250,3 +250,8 @@ def galois_coeffs(n, t, m, g):
 
 def chunk_rows(n, k, batch):
     return min(batch, max(1, (CHUNK_WORDS // n) // (7 * (2 * k + 1))))
+
+
+def decrypt_chunk_rows(n, k, batch):
+    """ciphertexts of a chunk of the decryption: k slabs of phase a ciphertext, 2^21 / (k n), at least one"""
+    return min(batch, max(1, (CHUNK_WORDS // n) // k))
