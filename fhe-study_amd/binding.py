@@ -14,8 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FHE_NTT_LIB") or os.path.join(_HERE, "libfhe_ntt.so")  # env: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip", "tfhe_client.hip", "bfv_client.hip", "ckks_client.hip", "ckks_eval.hip", "bfv_rns.hip"]
-HEADERS = ["ntt_kernels.hpp", "ntt_rounds.hpp", "ntt_persist.hpp", "persist_sched.hpp", "digit_mac.hpp", "digit32.hpp", "bfv32.hpp", "smallq.hpp", "ntt32_rounds.hpp", "ntt32_big.hpp", "zq_device.hpp", "capi_internal.hpp", "host_tables.hpp", "host_dispatch.hpp", "launch.hpp", "mac_kernel.hpp", "chacha_stream.hpp", "bfv_client_kernels.hpp", "rns_tables.hpp", "ntt_kernels.hip",
+SOURCES = ["capi.hip", "ntt_kernels.hip", "ntt_kernels_q62.hip", "ntt_persist.hip", "digit_mac.hip", "digit32.hip", "bfv32.hip", "smallq.hip", "generic63.hip", "zring.hip", "glue.hip", "tfhe_boot.hip", "tfhe_client.hip", "bfv_client.hip", "ckks_client.hip", "ckks_eval.hip", "bfv_rns.hip", "ckks_deep.hip"]
+HEADERS = ["ntt_kernels.hpp", "ntt_rounds.hpp", "ntt_persist.hpp", "persist_sched.hpp", "digit_mac.hpp", "digit32.hpp", "bfv32.hpp", "smallq.hpp", "ntt32_rounds.hpp", "ntt32_big.hpp", "zq_device.hpp", "capi_internal.hpp", "host_tables.hpp", "host_dispatch.hpp", "launch.hpp", "mac_kernel.hpp", "chacha_stream.hpp", "bfv_client_kernels.hpp", "rns_tables.hpp", "rns_ext_device.hpp", "ntt_kernels.hip",
            os.path.join("..", "..", "include", "fhe_ntt.h"), os.path.join("..", "..", "include", "fhe_ntt_experimental.h")]
 OBJ_DIR = os.path.join(_HERE, "build")
 # -ffp-contract=off: zring.hip restates the reference's f64 scale-and-round (one IEEE rounding
@@ -105,12 +105,16 @@ EXPORTS = [
     "fhe_rns_extend_dev", "fhe_bfv_rns_tensor_dev", "fhe_bfv_rns_mul_dev", "fhe_bfv_rns_workspace_bytes", "fhe_bfv_rns_scale_msg_dev", "fhe_bfv_rns_decrypt_dev",
     # BFV on the chain: inner products, one rounding and one relinearisation (bfv_rns.hip)
     "fhe_bfv_rns_dot_dev",
+    # CKKS on a deep RNS chain: grouped-digit key switching, up to 32 limbs (ckks_deep.hip)
+    "fhe_ckks_deep_relin_key_dev", "fhe_ckks_deep_galois_key_dev", "fhe_ckks_deep_relinearize_dev", "fhe_ckks_deep_mul_dev", "fhe_ckks_deep_galois_dev",
+    "fhe_ckks_deep_rescale_dev", "fhe_ckks_deep_workspace_bytes",
 ]
 FHE_CKKS_GALOIS_MAX_COUNT = 256              # include/fhe_ntt.h: the most Galois elements of one fhe_ckks_rns_galois_dev call
 FHE_CKKS_DIAG_MAX_OUTPUTS = 64               # include/fhe_ntt.h: the most outputs of one fhe_ckks_rns_diag_sum_dev call
 FHE_CKKS_LINCOMB_MAX_COUNT, FHE_CKKS_LINCOMB_MAX_OUTPUTS = 64, 16    # include/fhe_ntt.h: the most inputs and outputs of one fhe_ckks_rns_lincomb_dev call
 FHE_CKKS_DOT_MAX_COUNT = 64                  # include/fhe_ntt.h: the most pairs of one fhe_ckks_rns_dot_dev call
 FHE_BFV_DOT_MAX_COUNT = 64                   # include/fhe_ntt.h: the most pairs of one fhe_bfv_rns_dot_dev call
+FHE_CKKS_DEEP_MAX_LIMBS, FHE_CKKS_DEEP_MAX_SPECIALS = 32, 8    # include/fhe_ntt.h: the most chain and special primes of the fhe_ckks_deep_* calls
 
 # FHE_GATE_* (include/fhe_ntt.h): name -> op code of fhe_tfhe_gate_bootstrap_dev
 GATES = {"AND": 0, "NAND": 1, "OR": 2, "NOR": 3, "XOR": 4, "XNOR": 5, "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9}
@@ -346,6 +350,14 @@ def load_library():
     L.fhe_ckks_rns_bsgs_workspace_bytes.argtypes = [_u64, _uint, _sz, _uint, _uint]
     L.fhe_ckks_rns_bsgs_workspace_bytes.restype = _sz
     L.fhe_ckks_rns_lincomb_dev.argtypes = [_pp, _uint, _pp, _uint, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _uint, _vp, _sz, _vp]
+    L.fhe_ckks_deep_relin_key_dev.argtypes = [_pp, _uint, _pp, _uint, ctypes.c_char_p, _u64, _vp, _vp, _uint, _vp, _vp]
+    L.fhe_ckks_deep_galois_key_dev.argtypes = [_pp, _uint, _pp, _uint, ctypes.c_char_p, _u64, _u64, _vp, _vp, _uint, _vp, _vp]
+    L.fhe_ckks_deep_relinearize_dev.argtypes = [_pp, _uint, _pp, _uint, _vp, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_deep_mul_dev.argtypes = [_pp, _uint, _pp, _uint, _vp, _uint, _vp, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_deep_galois_dev.argtypes = [_pp, _uint, _pp, _uint, _pp, ctypes.POINTER(_u64), _uint, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_deep_rescale_dev.argtypes = [_pp, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_deep_workspace_bytes.argtypes = [_u64, _uint, _uint, _sz]
+    L.fhe_ckks_deep_workspace_bytes.restype = _sz
     L.fhe_ckks_rns_dot_dev.argtypes = [_pp, _uint, _vp, _vp, _uint, _pp, _pp, _uint, ctypes.POINTER(_u64), _vp, _sz, _vp]
     L.fhe_rns_extend_dev.argtypes = [ctypes.POINTER(_u64), _uint, ctypes.POINTER(_u64), _uint, _int, _vp, _vp, _sz, _vp]
     L.fhe_bfv_rns_tensor_dev.argtypes = [_pp, _uint, _pp, _u64, _vp, _vp, _vp, _sz, _vp]
@@ -945,6 +957,53 @@ def ckks_rns_bsgs_dev(plans, special, d_baby_gks, baby_gs, d_giant_gks, giant_gs
 
 def ckks_rns_bsgs_workspace_bytes(n, limbs, batch, babies, giants):
     return int(load_library().fhe_ckks_rns_bsgs_workspace_bytes(n, limbs, batch, babies, giants))
+
+
+def _plans_or_none(plans):
+    return None if plans is None else _plan_array(plans)
+
+
+def ckks_deep_relin_key_dev(plans, specials, seed, first_row, d_s, d_cdt, m, d_key, stream=None, limbs=None, alpha=None):
+    """fhe_ckks_deep_relin_key_dev: d_key [dnum][limbs + alpha][2][n] evals from d_s [limbs + alpha][n]"""
+    _check(load_library().fhe_ckks_deep_relin_key_dev(_plans_or_none(plans), len(plans) if limbs is None else limbs, _plans_or_none(specials),
+                                                      len(specials) if alpha is None else alpha, _seed(seed), first_row, d_s, d_cdt, m, d_key, stream))
+
+
+def ckks_deep_galois_key_dev(plans, specials, seed, first_row, g, d_s, d_cdt, m, d_key, stream=None, limbs=None, alpha=None):
+    """fhe_ckks_deep_galois_key_dev: the same key with the diagonal term on sigma_g(s)"""
+    _check(load_library().fhe_ckks_deep_galois_key_dev(_plans_or_none(plans), len(plans) if limbs is None else limbs, _plans_or_none(specials),
+                                                       len(specials) if alpha is None else alpha, _seed(seed), first_row, g, d_s, d_cdt, m, d_key, stream))
+
+
+def ckks_deep_relinearize_dev(plans, specials, d_key, key_limbs, d_d, d_out, batch, stream=None, limbs=None, alpha=None):
+    """fhe_ckks_deep_relinearize_dev: [limbs][3][batch][n] -> [limbs][2][batch][n]"""
+    _check(load_library().fhe_ckks_deep_relinearize_dev(_plans_or_none(plans), len(plans) if limbs is None else limbs, _plans_or_none(specials),
+                                                        len(specials) if alpha is None else alpha, d_key, key_limbs, d_d, d_out, batch, stream))
+
+
+def ckks_deep_mul_dev(plans, specials, d_key, key_limbs, d_a, d_b, d_out, batch, stream=None, limbs=None, alpha=None):
+    """fhe_ckks_deep_mul_dev: the tensor and its relinearisation in one call"""
+    _check(load_library().fhe_ckks_deep_mul_dev(_plans_or_none(plans), len(plans) if limbs is None else limbs, _plans_or_none(specials),
+                                                len(specials) if alpha is None else alpha, d_key, key_limbs, d_a, d_b, d_out, batch, stream))
+
+
+def ckks_deep_galois_dev(plans, specials, d_gks, gs, key_limbs, d_in, d_out, batch, stream=None, limbs=None, alpha=None, count=None):
+    """fhe_ckks_deep_galois_dev: [limbs][2][batch][n] -> [count][limbs][2][batch][n], one digit decomposition for all of gs;
+    d_gks a list of device key pointers (None is passed as NULL, as is a None list)"""
+    keys = None if d_gks is None else (_vp * max(len(d_gks), 1))(*d_gks)
+    els = None if gs is None else (_u64 * max(len(gs), 1))(*gs)
+    _check(load_library().fhe_ckks_deep_galois_dev(_plans_or_none(plans), len(plans) if limbs is None else limbs, _plans_or_none(specials),
+                                                   len(specials) if alpha is None else alpha, keys, els, len(gs) if count is None else count, key_limbs, d_in, d_out,
+                                                   batch, stream))
+
+
+def ckks_deep_rescale_dev(plans, d_in, d_out, batch, stream=None, limbs=None):
+    """fhe_ckks_deep_rescale_dev: [limbs][2][batch][n] -> [limbs - 1][2][batch][n]"""
+    _check(load_library().fhe_ckks_deep_rescale_dev(_plans_or_none(plans), len(plans) if limbs is None else limbs, d_in, d_out, batch, stream))
+
+
+def ckks_deep_workspace_bytes(n, limbs, alpha, batch):
+    return int(load_library().fhe_ckks_deep_workspace_bytes(n, limbs, alpha, batch))
 
 
 def ckks_rns_lincomb_dev(plans, d_cts, w, k, outputs, d_out, batch, stream=None, limbs=None, count=None):

@@ -200,6 +200,9 @@ class RnsParam:
     def special_plan(self):
         return _plan(RingParam(self.special, self.n))
 
+    def special_plans(self):
+        return [self.special_plan()]
+
 
 class RnsRelinKey:
     """rlk [j][i][2][n] evals on the device, j <= L, i in {0 .. L, P}"""
@@ -383,7 +386,7 @@ class RnsCiphertext:
         """dropping top limbs is truncation"""
         if not 0 <= level <= self.level:
             raise ValueError(f"at_level: level {level} is not in [0, {self.level}]")
-        return RnsCiphertext(self.param, self.d[:level + 1].contiguous(), level, self.scale)
+        return type(self)(self.param, self.d[:level + 1].contiguous(), level, self.scale)
 
     def _pair(self, rhs):
         if rhs.param != self.param or rhs.batch != self.batch:
@@ -398,7 +401,7 @@ class RnsCiphertext:
         out = _torch().empty_like(a.d)
         for i, plan in enumerate(self.param.plans(level)):
             binding._check(fn(plan.handle, a.d[i].data_ptr(), b.d[i].data_ptr(), out[i].data_ptr(), 2 * self.batch, None))
-        return RnsCiphertext(self.param, out, level, self.scale)
+        return type(self)(self.param, out, level, self.scale)
 
     def __add__(self, rhs):
         return self._rows(rhs, binding.load_library().fhe_rq_add_dev)
@@ -531,7 +534,7 @@ class RnsCiphertext:
         pt, out = self._plain(m), self.d.clone()
         for i, plan in enumerate(self.param.plans(self.level)):
             binding._check(binding.load_library().fhe_rq_add_dev(plan.handle, self.d[i, 0].data_ptr(), pt[i].data_ptr(), out[i, 0].data_ptr(), self.batch, None))
-        return RnsCiphertext(self.param, out, self.level, self.scale)
+        return type(self)(self.param, out, self.level, self.scale)
 
     def mul_plain(self, m, scale):
         """both components times an encoded plaintext of scale `scale`; the scale multiplies"""
@@ -539,7 +542,7 @@ class RnsCiphertext:
         for i, plan in enumerate(self.param.plans(self.level)):
             for c in range(2):
                 plan.pointwise_mul_dev(self.d[i, c].data_ptr(), pt[i].data_ptr(), out[i, c].data_ptr(), self.batch)
-        return RnsCiphertext(self.param, out, self.level, self.scale * float(scale))
+        return type(self)(self.param, out, self.level, self.scale * float(scale))
 
     # ---- polynomial evaluation ----
     def mul_const(self, c, scale=None):
@@ -861,13 +864,15 @@ class RnsClientKey(ClientKeyBase):
         self.param, self.delta, self.d_s, self.d_s_evals = param, float(delta), d_s, d_s_evals
         self.encoder = Encoder(param.n, delta)
 
+    _ciphertext = RnsCiphertext   # what encrypt returns
+
     def _all_plans(self):
-        return self.param.plans() + [self.param.special_plan()]
+        return self.param.plans() + self.param.special_plans()
 
     @classmethod
     def generate(cls, seed, param, delta, sigma=3.2):
         torch = _torch()
-        plans = param.plans() + [param.special_plan()]
+        plans = param.plans() + param.special_plans()
         d_s = torch.empty((len(plans), param.n), dtype=torch.int64, device="cuda")
         d_e = torch.empty_like(d_s)
         for i, plan in enumerate(plans):
@@ -935,7 +940,7 @@ class RnsClientKey(ClientKeyBase):
                 plan.forward_dev(out[i].data_ptr(), out[i].data_ptr(), 2 * batch)
 
         self._on_fresh_rows(batch, limbs)
-        return RnsCiphertext(self.param, out, self.param.max_level, self.delta if scale is None else scale)
+        return self._ciphertext(self.param, out, self.param.max_level, self.delta if scale is None else scale)
 
     def decrypt(self, ct):
         """limb 0 only: exact while |m + e| < q_0 / 2 -> int64 coefficients [batch][n]"""
@@ -954,3 +959,139 @@ class RnsClientKey(ClientKeyBase):
 
     def decrypt_and_decode(self, ct):
         return self.encoder.decode(self.decrypt(ct), ct.scale)
+
+
+# ---- the deep chain: grouped-digit key switching, up to 32 limbs (ckks_deep.hip) --------------------------------------
+@dataclass(frozen=True)
+class DeepParam:
+    """n, the chain primes q_0 .. q_{L-1} (1 <= L <= 32) and the special primes p_0 .. p_{alpha-1} (1 <= alpha <= 8) of the
+    switching keys, P their product: all distinct, 1 modulo 2n, below 2^62.  Digit group j holds limbs [j alpha, (j + 1) alpha);
+    P must not be below the product of a group's primes.  Level l = limbs 0 .. l."""
+    n: int
+    moduli: tuple
+    specials: tuple
+
+    def __post_init__(self):
+        object.__setattr__(self, "moduli", tuple(int(q) for q in self.moduli))
+        object.__setattr__(self, "specials", tuple(int(p) for p in self.specials))
+        if not 1 <= len(self.moduli) <= binding.FHE_CKKS_DEEP_MAX_LIMBS:
+            raise ValueError("DeepParam: the chain has 1 to 32 primes")
+        if not 1 <= len(self.specials) <= binding.FHE_CKKS_DEEP_MAX_SPECIALS:
+            raise ValueError("DeepParam: there are 1 to 8 special primes")
+        primes = self.moduli + self.specials
+        if len(set(primes)) != len(primes):
+            raise ValueError("DeepParam: the primes of the chain and the special primes must be distinct")
+        if any(p >= 1 << 62 for p in primes):
+            raise ValueError("DeepParam: every prime must be below 2^62")
+        if any(p % (2 * self.n) != 1 for p in primes):
+            raise ValueError("DeepParam: every prime must be 1 modulo 2n")
+        P, alpha = 1, len(self.specials)
+        for p in self.specials:
+            P *= p
+        for j in range(0, len(self.moduli), alpha):
+            Qj = 1
+            for q in self.moduli[j:j + alpha]:
+                Qj *= q
+            if P < Qj:
+                raise ValueError(f"DeepParam: the product of the special primes is below that of digit group {j // alpha}")
+
+    @property
+    def max_level(self):
+        return len(self.moduli) - 1
+
+    @property
+    def dnum(self):
+        return -(-len(self.moduli) // len(self.specials))
+
+    def plans(self, level=None):
+        """the plans of limbs 0 .. level (default: all)"""
+        k = len(self.moduli) if level is None else level + 1
+        return [_plan(RingParam(q, self.n)) for q in self.moduli[:k]]
+
+    def special_plans(self):
+        return [_plan(RingParam(p, self.n)) for p in self.specials]
+
+
+class DeepCiphertext(RnsCiphertext):
+    """RnsCiphertext on a DeepParam: +, -, at_level, add_plain and mul_plain are the base class's, per limb; the products, the
+    rescale and the Galois maps go through the fhe_ckks_deep_* entry points.  The fused sums, the linear transforms and the
+    Chebyshev plans are not carried to the deep chain yet."""
+
+    def mul(self, rhs, rlk):
+        """ct x ct and relinearisation (fhe_ckks_deep_mul_dev); the scale multiplies and the result is NOT rescaled"""
+        if rlk.param != self.param:
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the relinearisation key is not of this ciphertext's chain")
+        a, b, level = self._pair(rhs)
+        out = _torch().empty_like(a.d)
+        binding.ckks_deep_mul_dev(self.param.plans(level), self.param.special_plans(), rlk.d_rlk.data_ptr(), len(self.param.moduli), a.d.data_ptr(), b.d.data_ptr(),
+                                  out.data_ptr(), self.batch)
+        return DeepCiphertext(self.param, out, level, self.scale * rhs.scale)
+
+    def rescale(self):
+        if self.level == 0:
+            raise binding.FheError(binding.FHE_E_INVALID, "rescale: a ciphertext at level 0 cannot be rescaled")
+        torch = _torch()
+        out = torch.empty((self.level, 2, self.batch, self.param.n), dtype=torch.int64, device="cuda")
+        binding.ckks_deep_rescale_dev(self.param.plans(self.level), self.d.data_ptr(), out.data_ptr(), self.batch)
+        return DeepCiphertext(self.param, out, self.level - 1, self.scale / self.param.moduli[self.level])
+
+    def rotate_many(self, gks):
+        """sigma_g of this ciphertext for every key of `gks` from one call (fhe_ckks_deep_galois_dev)"""
+        torch = _torch()
+        gks = list(gks)
+        if any(gk.param != self.param for gk in gks):
+            raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "a Galois key is not of this ciphertext's chain")
+        out = torch.empty((len(gks),) + tuple(self.d.shape), dtype=torch.int64, device="cuda")
+        binding.ckks_deep_galois_dev(self.param.plans(self.level), self.param.special_plans(), [gk.d_gk.data_ptr() for gk in gks], [gk.g for gk in gks],
+                                     len(self.param.moduli), self.d.data_ptr(), out.data_ptr(), self.batch)
+        return [DeepCiphertext(self.param, out[r], self.level, self.scale) for r in range(len(gks))]
+
+    def _plain(self, m):
+        """signed rows -> evals [level + 1][batch][n]: fhe_ckks_rns_from_i64_dev is limb-independent, so in slices of 8 plans"""
+        torch = _torch()
+        n = self.param.n
+        rows = np.array(np.broadcast_to(np.asarray(m, dtype=np.int64), (self.batch, n)))
+        out = torch.empty((self.level + 1, self.batch, n), dtype=torch.int64, device="cuda")
+        d_rows = torch.from_numpy(rows).cuda()
+        plans = self.param.plans(self.level)
+        for i in range(0, len(plans), 8):
+            binding.ckks_rns_from_i64_dev(plans[i:i + 8], d_rows.data_ptr(), out[i:i + 8].data_ptr(), self.batch)
+        return out
+
+    def __neg__(self):
+        out = _torch().empty_like(self.d)
+        for i, plan in enumerate(self.param.plans(self.level)):
+            binding._check(binding.load_library().fhe_rq_neg_dev(plan.handle, self.d[i].data_ptr(), out[i].data_ptr(), 2 * self.batch, None))
+        return DeepCiphertext(self.param, out, self.level, self.scale)
+
+    def _not_yet(self, *args, **kwargs):
+        raise NotImplementedError("not carried to the deep chain yet (DESIGN.md §36)")
+
+    diag_sum = linear_transform = linear_transform_hoisted = mul_const = add_const = eval_chebyshev = _not_yet
+
+
+class DeepClientKey(RnsClientKey):
+    """RnsClientKey on a DeepParam, on the same row plan: a key slot's 64 rows cover dnum <= 32 digit groups.  The secret's rows
+    are the chain's, then the special primes'."""
+
+    _ciphertext = DeepCiphertext
+
+    def _switch_key(self, what, base, slot, build, *element):
+        torch = _torch()
+        row = self._take_slot(what, base, slot, rows=64)
+        L, alpha = len(self.param.moduli), len(self.param.specials)
+        key = torch.empty((self.param.dnum, L + alpha, 2, self.param.n), dtype=torch.int64, device="cuda")
+        build(self.param.plans(), self.param.special_plans(), self.seed, row, *element, self.d_s.data_ptr(), self._cdt_ptr(), self._m, key.data_ptr())
+        return key
+
+    def relin_key(self, slot=0):
+        return RnsRelinKey(self.param, self._switch_key("relin_key", self.RLK_BASE, slot, binding.ckks_deep_relin_key_dev))
+
+    def galois_key(self, g, slot):
+        g = int(g)
+        if g % 2 == 0 or not 0 < g < 2 * self.param.n:
+            raise ValueError(f"galois_key: g={g} must be odd and in [1, 2n)")
+        return RnsGaloisKey(self.param, g, self._switch_key("galois_key", self.GK_BASE, slot, binding.ckks_deep_galois_key_dev, g))
+
+    def encode_diagonals(self, rows, steps, level, scale):
+        raise NotImplementedError("not carried to the deep chain yet (DESIGN.md §36)")

@@ -24,6 +24,7 @@
 // the workspace (slot 13), one call per limb and direction over everything of that limb that is ready; a chunk is
 // 2^21 / (7 (2k + 1) n) ciphertexts, at least one: 4 (2k + 1) slabs of operands and 3 (2k + 1) of tensor a ciphertext.
 #include "bfv_client_kernels.hpp"
+#include "rns_ext_device.hpp"
 #include "rns_tables.hpp"
 
 using fhe::u32;
@@ -32,38 +33,6 @@ using fhe::u64;
 namespace fhe {
 
 constexpr u32 kBfvMaxLimbs = 4, kBfvMaxAux = kBfvMaxLimbs + 1;
-
-__device__ __forceinline__ u64 ext_csub(u64 x, u64 q) { return x >= q ? x - q : x; }
-// x w mod q for ANY 64-bit x and w < q < 2^63: x w - floor(x wp / 2^64) q lies in [0, 2q)
-__device__ __forceinline__ u64 ext_mul(u64 x, u64 w, u64 wp, u64 q) { return ext_csub(x * w - __umul64hi(x, wp) * q, q); }
-// x mod q for any 64-bit x, onep = floor(2^64 / q)
-__device__ __forceinline__ u64 ext_red(u64 x, u64 q, u64 onep) { return ext_csub(x - __umul64hi(x, onep) * q, q); }
-
-// Garner: the mixed-radix digits a of the integer in [0, M) whose canonical residues are x (x[i] for i >= s is not read into
-// a digit that is used).  s (s - 1) / 2 multiplications.  -> whether the integer is above floor(M / 2).
-template <u32 S, u32 T>
-__device__ __forceinline__ bool ext_digits(const u64 (&x)[S], u64 (&a)[S], const ExtArgs<S, T> &e) {
-#pragma unroll
-    for (u32 i = 0; i < S; i++) {
-        u64 v = x[i];
-        if (i < e.s) {
-            const u64 q = e.mq[i];
-#pragma unroll
-            for (u32 j = 0; j < i; j++) v = ext_mul(v + q - ext_red(a[j], q, e.monep[i]), e.inv[j][i], e.invp[j][i], q);   // v + q - r in (0, 2q)
-        }
-        a[i] = v;
-    }
-    bool gt = false, eq = true;
-#pragma unroll
-    for (u32 ii = 0; ii < S; ii++) {
-        const u32 i = S - 1 - ii;
-        if (i < e.s && eq && a[i] != e.half[i]) {
-            gt = a[i] > e.half[i];
-            eq = false;
-        }
-    }
-    return gt;
-}
 
 // the integer of digits a (less M where `neg`) modulo target t: sum_j a_j W[j][t], at most nine terms below 2^124, reduced once
 template <u32 S, u32 T>

@@ -1214,6 +1214,7 @@ extern "C" int fhe_ntt_shutdown(void) {
     }
     fhe_workspace_free_all();
     fhe_ext32_free_all();
+    fhe_deep_free_all();
     persist_free_all();
     std::lock_guard<std::mutex> lk(g_plans_lock);
     for (auto &kv : g_plans) {

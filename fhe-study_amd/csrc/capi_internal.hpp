@@ -69,6 +69,7 @@ fhe::u64 fhe_batch_tile_for(const fhe_ntt_plan *plan);
 int fhe_workspace_get(int slot, size_t bytes, hipStream_t st, void **out);
 void fhe_workspace_free_all();
 void fhe_ext32_free_all();   // zring.hip: tables of the two-small-prime (27-bit) products (digit32.hip)
+void fhe_deep_free_all();    // ckks_deep.hip: the extension tables of the deep CKKS chains
 namespace fhe { struct Ext32Args; }
 int fhe_ext32_tables(uint64_t n, fhe::Ext32Args *a);   // fills the per-prime fields for the current device
 // zring.hip: `keys` TGGSWs [key][(k+1)][l][(k+1)][n] -> keys * fhe_tggsw_prepared_words, in one or two launches (unvalidated)
@@ -79,6 +80,12 @@ int fhe_rns_tensor_limb(const fhe_ntt_plan *p, const fhe::u64 *a, fhe::u64 a_cs,
                         hipStream_t st);
 int fhe_rns_relin_rows(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const fhe::u64 *rlk, const fhe::u64 *d, fhe::u64 cr,
                        fhe::u64 *out, fhe::u64 batch, fhe::u64 r0, hipStream_t st);
+// ckks_eval.hip, for ckks_deep.hip: one limb of the divide-and-round out = (x - t) inv (+ add) over two components
+// of `count` words (g != 0: add's first component gathered at pi_g, for the first component only), and the diagonal term of one
+// switching-key row in evals, pk0 += c s^2 or, where galois, c sigma_g(s)
+int fhe_rns_divround_limb(const fhe_ntt_plan *p, const fhe::u64 *x, fhe::u64 x_cs, const fhe::u64 *t, fhe::u64 t_cs, const fhe::u64 *add, fhe::u64 add_cs, fhe::u64 *out,
+                          fhe::u64 out_cs, fhe::u64 count, fhe::u64 inv, fhe::u32 g, hipStream_t st);
+int fhe_rns_keyterm_limb(const fhe_ntt_plan *p, fhe::u64 *pk0, const fhe::u64 *s_evals, fhe::u64 c, fhe::u32 g, bool galois, hipStream_t st);
 namespace fhe { struct SmallQArgs; }
 // fills the modulus-dependent fields when the plan has a 32-bit form on this device (smallq.hip) and FHE_EXT32 is on
 bool fhe_smallq_args(const fhe_ntt_plan *plan, const fhe::DevicePlan &dp, fhe::SmallQArgs *a);

@@ -32,6 +32,7 @@
 // of every key switch and of the rescale (lift, forward and divide-and-round per remaining limb); SwitchBufs the layout and
 // the size of a key switch's workspace; switch_call the chunking, workspace and inverses of P of every key-switch entry point.
 #include "bfv_client_kernels.hpp"
+#include "rns_ext_device.hpp"
 
 using fhe::Mod;
 using fhe::u32;
@@ -68,14 +69,6 @@ __global__ __launch_bounds__(256) void ckks_rns_lift_kernel(const u64 *__restric
             }
         }
     }
-}
-
-// pi_g(x) of DESIGN.md §23: index x of the engine's order holds the value at psi^(2 brv_L(x) + 1), so sigma_g(a)^[x] = a^[pi_g(x)]
-// with pi_g(x) = brv_L((((2 brv_L(x) + 1) g mod 2n) - 1) / 2).  2n divides 2^32, so the 32-bit product may wrap; L >= 1, so
-// the shifts by 32 - L are defined.  pi_g maps an aligned block of 2^t indices onto an aligned block of 2^t indices.
-__device__ __forceinline__ u32 galois_index(u32 x, u32 g, u32 L) {
-    const u32 e = (2u * (__brev(x) >> (32u - L)) + 1u) * g;
-    return __brev((e & ((2u << L) - 1u)) >> 1) >> (32u - L);
 }
 
 // the bare automorphism on `count` words of rows of n = 2^L evals: out[r n + x] = in[r n + pi_g(x)]; count is a multiple of n
@@ -828,6 +821,19 @@ int fhe_rns_relin_rows(const fhe_ntt_plan *const *plans, unsigned limbs, const f
     u64 pinv[fhe::kRnsMaxLimbs];
     for (unsigned i = 0; i < c.k; i++) pinv[i] = fhe::host::inv_mod(c.p[i]->q, c.p[c.k]->q);
     return relin_rows(c, rlk, limbs, pinv, d, cr, 0, out, batch, r0, cr, (u64 *)w, st);
+}
+
+// ---- what ckks_deep.hip runs of this unit ----
+// one limb of a divide-and-round, ckks_rns_divround_kernel as moddown_rows launches it: g != 0 gathers add's first component
+int fhe_rns_divround_limb(const fhe_ntt_plan *p, const u64 *x, u64 x_cs, const u64 *t, u64 t_cs, const u64 *add, u64 add_cs, u64 *out, u64 out_cs, u64 count, u64 inv,
+                          u32 g, hipStream_t st) {
+    return launch(g ? "ckks_rns_divround_galois" : "ckks_rns_divround", (int)p->log_n, st, g ? fhe::ckks_rns_divround_kernel<true> : fhe::ckks_rns_divround_kernel<false>,
+                  fhe_ew_grid(2 * count), 256, x, x_cs, t, t_cs, add, add_cs, out, out_cs, count, inv, p->mod, g, p->log_n);
+}
+// the diagonal term of one key row, ckks_rns_keyterm_kernel as switch_key launches it: pk0 += c s^2, or c sigma_g(s) where galois
+int fhe_rns_keyterm_limb(const fhe_ntt_plan *p, u64 *pk0, const u64 *s_evals, u64 c, u32 g, bool galois, hipStream_t st) {
+    return launch(galois ? "ckks_rns_keyterm_galois" : "ckks_rns_keyterm", (int)p->log_n, st, galois ? fhe::ckks_rns_keyterm_kernel<true> : fhe::ckks_rns_keyterm_kernel<false>,
+                  fhe_ew_grid(p->n), 256, pk0, s_evals, c, g, p->log_n, p->mod);
 }
 
 extern "C" int fhe_ckks_rns_mul_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *special, const void *d_rlk, unsigned key_limbs,

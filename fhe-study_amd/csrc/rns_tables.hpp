@@ -175,4 +175,77 @@ bool ext_tables(const u64 *src, unsigned s, const u64 *dst, unsigned t, ExtArgs<
 }
 
 }  // namespace host
+
+// ---- the grouped-digit key switch of the deep CKKS chain (ckks_deep.hip) -------------------------------------
+constexpr unsigned kDeepMaxLimbs = 32, kDeepMaxSpecials = 8, kDeepMaxTargets = kDeepMaxLimbs + kDeepMaxSpecials;
+
+// The source side of one extension from a digit group (or from the special primes) of 1 .. 8 moduli: what Garner's digits and
+// the centring need, ExtArgs' fields of the same names.  By value, indexed by unrolled constants only.
+struct DeepSrc {
+    unsigned long long mq[kDeepMaxSpecials], monep[kDeepMaxSpecials];
+    unsigned long long inv[kDeepMaxSpecials][kDeepMaxSpecials], invp[kDeepMaxSpecials][kDeepMaxSpecials];
+    unsigned long long half[kDeepMaxSpecials];
+    uint32_t s;
+};
+// One target of that extension, an entry of a device table: p, floor(2^64 / p), 2^64 mod p and its companion, M mod p, the
+// place of the target's residues in the destination (in units the launch names) and the radix weights m_0 .. m_{j-1} mod p.
+struct DeepTarget {
+    unsigned long long q, onep, r64, r64p, pM, off;
+    unsigned long long W[kDeepMaxSpecials];
+};
+
+namespace host {
+
+// digit groups of `limbs` limbs in groups of alpha: group j holds limbs [j alpha, min((j + 1) alpha, limbs))
+inline unsigned deep_groups(unsigned limbs, unsigned alpha) { return (limbs + alpha - 1) / alpha; }
+
+// The admission of the grouped key switch: P >= Q_j for every digit group j of q[0 .. limbs), P the product of p[0 .. alpha),
+// Q_j that of the group's primes.  Exact: both sides are products of at most eight words.
+inline bool deep_admits(const u64 *q, unsigned limbs, const u64 *p, unsigned alpha) {
+    if (alpha < 1 || alpha > kDeepMaxSpecials) return false;
+    const Big P = big_product(p, alpha);
+    for (unsigned j0 = 0; j0 < limbs; j0 += alpha)
+        if (P.cmp(big_product(q + j0, limbs - j0 < alpha ? limbs - j0 : alpha)) < 0) return false;
+    return true;
+}
+
+// the tables of the centred extension from src[0 .. s), s <= 8, to dst[0 .. t), target k's residues at off[k]; false where a
+// side is not ext_moduli_ok's kind (nothing usable is left).  tab holds t entries.
+inline bool deep_ext_tables(const u64 *src, unsigned s, const u64 *dst, const u64 *off, unsigned t, DeepSrc *e, DeepTarget *tab) {
+    *e = DeepSrc{};
+    if (!ext_moduli_ok(src, s, kDeepMaxSpecials)) return false;
+    for (unsigned k = 0; k < t; k++)
+        if (dst[k] < 3 || (dst[k] & 1) == 0 || dst[k] >= kExtModLimit) return false;
+    e->s = s;
+    for (unsigned i = 0; i < s; i++) {
+        e->mq[i] = src[i];
+        e->monep[i] = (u64)((((u128)1) << 64) / src[i]);
+        for (unsigned j = 0; j < i; j++) {
+            if (!inv_mod_any(src[j] % src[i], src[i], &e->inv[j][i])) return false;
+            e->invp[j][i] = shoup(e->inv[j][i], src[i]);
+        }
+    }
+    Big h = big_product(src, s);
+    h.divmod(2);
+    for (unsigned i = 0; i < s; i++) e->half[i] = h.divmod(src[i]);
+    for (unsigned k = 0; k < t; k++) {
+        const u64 p = dst[k];
+        DeepTarget &d = tab[k];
+        d = DeepTarget{};
+        d.q = p;
+        d.onep = (u64)((((u128)1) << 64) / p);
+        d.r64 = (u64)((((u128)1) << 64) % p);
+        d.r64p = shoup(d.r64, p);
+        d.off = off[k];
+        u64 w = 1 % p;
+        for (unsigned j = 0; j < s; j++) {
+            d.W[j] = w;
+            w = mulmod(w, src[j] % p, p);
+        }
+        d.pM = w;
+    }
+    return true;
+}
+
+}  // namespace host
 }  // namespace fhe

@@ -854,6 +854,59 @@ int fhe_bfv_rns_dot_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const 
                         const fhe_ntt_plan *special, uint64_t t, const void *d_rlk, const void *const *d_as,
                         const void *const *d_bs, unsigned count, const int64_t *w, void *d_out, size_t batch, void *hip_stream);
 
+/* ---- CKKS on a deep RNS chain: grouped-digit key switching, up to 32 limbs (ckks_deep.hip) ----
+ * The block of §22 / §23 with the digits of the key switch grouped: `limbs` plans (1 <= limbs <= 32) of chain primes q_0 ..
+ * and `alpha` plans (1 <= alpha <= 8) of special primes p_0 .., P their product, as HOST arrays `plans` and `specials`; all
+ * primes distinct, below 2^62, of the same n.  Digit group j holds limbs [j alpha, min((j + 1) alpha, limbs)), Q_j is the
+ * product of its primes, dnum = ceil(limbs / alpha).  Admission: P >= Q_j for every j, compared exactly.  Ciphertexts, the
+ * tensor, alignment (8 bytes) and the overlap rules are §22's.  A group's integer x_j is the one with d's residues modulo the
+ * group's primes, centred in (-Q_j / 2, Q_j / 2].
+ *   fhe_ckks_deep_relin_key_dev   d_key [dnum][limbs + alpha][2][n] evals, column i < limbs modulo q_i, column limbs + m modulo
+ *            p_m: key[j][i] = (-a_ji s + e_j + [i in group j] (P mod q_i) s^2, a_ji) = fhe_ckks_public_key_dev on plan i with
+ *            row first_row + j, plus the diagonal term.  d_s [limbs + alpha][n], the special primes' rows last.  At alpha = 1
+ *            the words of fhe_ckks_rns_relin_key_dev.
+ *   fhe_ckks_deep_galois_key_dev  the same with sigma_g(s) for s^2
+ *   fhe_ckks_deep_relinearize_dev d_out [limbs][2][batch][n] from a tensor d_d [limbs][3][batch][n]: D_ji = x_j mod m_i for every
+ *            m_i of {q_0 .. q_{limbs-1}, p_0 .. p_{alpha-1}}, x_j of d2 (i in group j: d2's own limb); t_i = sum_j D_ji key[j][col(i)],
+ *            col(i) = i for a chain limb and key_limbs + m for p_m; y the centred integer of t modulo P;
+ *            r_i = (t_i - y) P^-1 mod q_i; out = (d0 + r0, d1 + r1).  d_key was made for key_limbs >= limbs limbs with the
+ *            same alpha: one key serves every level.
+ *   fhe_ckks_deep_mul_dev         the tensor of d_a and d_b and that, the tensor kept in the library workspace
+ *   fhe_ckks_deep_galois_dev      d_out [count][limbs][2][batch][n], fhe_ckks_rns_galois_dev's contract: (pi_g(c0) + r0, r1) per
+ *            element of the HOST arrays d_gks, gs; one digit decomposition per chunk whatever `count` is
+ *   fhe_ckks_deep_rescale_dev     d_out [limbs - 1][2][batch][n], fhe_ckks_rns_rescale_dev's formula for limbs up to 32
+ *   fhe_ckks_deep_workspace_bytes the most library workspace one of these calls takes; 0 for a shape they refuse.  With
+ *            ng = ceil(limbs / alpha) a key switch stages S = (limbs + alpha) ng + 7 limbs + 2 alpha slabs of n words a
+ *            ciphertext (the tensor 3 limbs, the limbs in coefficients, the lifted digits (limbs + alpha) ng - limbs, the key
+ *            sums 2 (limbs + alpha), the lifted t_P 2 limbs) over chunks of c = min(batch, max(1, floor(floor(2^21 / n) / S)))
+ *            ciphertexts, a rescale 2 limbs slabs over chunks of c' = min(batch, max(1, floor(floor(2^21 / n) / (2 limbs)))):
+ *            8 max(S n c, 2 limbs n c') bytes.  The extension tables of a chain (a few KB) are kept on the device apart from it.
+ * At alpha = 1 and limbs <= 8 every output equals the §22 / §23 entry point's word for word.  FHE_E_NULL for a NULL pointer (a
+ * plan or a key included); FHE_E_PARAM_MISMATCH for plans whose n differ; FHE_E_INVALID for limbs outside [1, 32], alpha
+ * outside [1, 8], a repeated prime, a prime of 2^62 or more, a missed admission, key_limbs < limbs or > 32, g even or >= 2n,
+ * count > FHE_CKKS_GALOIS_MAX_COUNT, a rescale at one limb, an output that overlaps an input or a key, and the table and
+ * row-range conditions of the BFV block.  Nothing is written on rejection; batch = 0 (or count = 0) is a no-op. */
+#define FHE_CKKS_DEEP_MAX_LIMBS 32
+#define FHE_CKKS_DEEP_MAX_SPECIALS 8
+int fhe_ckks_deep_relin_key_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *specials,
+                                unsigned alpha, const uint8_t *seed, uint64_t first_row, const void *d_s, const void *d_cdt,
+                                unsigned m, void *d_key, void *hip_stream);
+int fhe_ckks_deep_galois_key_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *specials,
+                                 unsigned alpha, const uint8_t *seed, uint64_t first_row, uint64_t g, const void *d_s,
+                                 const void *d_cdt, unsigned m, void *d_key, void *hip_stream);
+int fhe_ckks_deep_relinearize_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *specials,
+                                  unsigned alpha, const void *d_key, unsigned key_limbs, const void *d_d, void *d_out,
+                                  size_t batch, void *hip_stream);
+int fhe_ckks_deep_mul_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *specials,
+                          unsigned alpha, const void *d_key, unsigned key_limbs, const void *d_a, const void *d_b,
+                          void *d_out, size_t batch, void *hip_stream);
+int fhe_ckks_deep_galois_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *specials,
+                             unsigned alpha, const void *const *d_gks, const uint64_t *gs, unsigned count,
+                             unsigned key_limbs, const void *d_in, void *d_out, size_t batch, void *hip_stream);
+int fhe_ckks_deep_rescale_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *d_in, void *d_out, size_t batch,
+                              void *hip_stream);
+size_t fhe_ckks_deep_workspace_bytes(uint64_t n, unsigned limbs, unsigned alpha, size_t batch);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
