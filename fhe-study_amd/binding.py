@@ -108,6 +108,8 @@ EXPORTS = [
     # CKKS on a deep RNS chain: grouped-digit key switching, up to 32 limbs (ckks_deep.hip)
     "fhe_ckks_deep_relin_key_dev", "fhe_ckks_deep_galois_key_dev", "fhe_ckks_deep_relinearize_dev", "fhe_ckks_deep_mul_dev", "fhe_ckks_deep_galois_dev",
     "fhe_ckks_deep_rescale_dev", "fhe_ckks_deep_workspace_bytes",
+    # CKKS on a deep RNS chain: plaintext linear transforms, the double-hoisted diagonal sum (ckks_deep.hip)
+    "fhe_ckks_deep_diag_sum_dev", "fhe_ckks_deep_diag_workspace_bytes",
 ]
 FHE_CKKS_GALOIS_MAX_COUNT = 256              # include/fhe_ntt.h: the most Galois elements of one fhe_ckks_rns_galois_dev call
 FHE_CKKS_DIAG_MAX_OUTPUTS = 64               # include/fhe_ntt.h: the most outputs of one fhe_ckks_rns_diag_sum_dev call
@@ -358,6 +360,9 @@ def load_library():
     L.fhe_ckks_deep_rescale_dev.argtypes = [_pp, _uint, _vp, _vp, _sz, _vp]
     L.fhe_ckks_deep_workspace_bytes.argtypes = [_u64, _uint, _uint, _sz]
     L.fhe_ckks_deep_workspace_bytes.restype = _sz
+    L.fhe_ckks_deep_diag_sum_dev.argtypes = [_pp, _uint, _pp, _uint, _pp, ctypes.POINTER(_u64), _uint, _uint, _vp, _uint, _vp, _vp, _sz, _vp]
+    L.fhe_ckks_deep_diag_workspace_bytes.argtypes = [_u64, _uint, _uint, _sz, _uint, _uint]
+    L.fhe_ckks_deep_diag_workspace_bytes.restype = _sz
     L.fhe_ckks_rns_dot_dev.argtypes = [_pp, _uint, _vp, _vp, _uint, _pp, _pp, _uint, ctypes.POINTER(_u64), _vp, _sz, _vp]
     L.fhe_rns_extend_dev.argtypes = [ctypes.POINTER(_u64), _uint, ctypes.POINTER(_u64), _uint, _int, _vp, _vp, _sz, _vp]
     L.fhe_bfv_rns_tensor_dev.argtypes = [_pp, _uint, _pp, _u64, _vp, _vp, _vp, _sz, _vp]
@@ -1004,6 +1009,20 @@ def ckks_deep_rescale_dev(plans, d_in, d_out, batch, stream=None, limbs=None):
 
 def ckks_deep_workspace_bytes(n, limbs, alpha, batch):
     return int(load_library().fhe_ckks_deep_workspace_bytes(n, limbs, alpha, batch))
+
+
+def ckks_deep_diag_sum_dev(plans, specials, d_gks, gs, key_limbs, d_pts, outputs, d_in, d_out, batch, stream=None, limbs=None, alpha=None, count=None):
+    """fhe_ckks_deep_diag_sum_dev: [limbs][2][batch][n] -> [outputs][limbs][2][batch][n], out_o = sum_r m_{o,r} (.)
+    sigma_{gs[r]}(in) with d_pts [outputs][count][limbs + alpha][n]; d_gks a list of device key pointers, None (NULL) where gs[r] = 1"""
+    keys = None if d_gks is None else (_vp * max(len(d_gks), 1))(*d_gks)
+    els = None if gs is None else (_u64 * max(len(gs), 1))(*gs)
+    _check(load_library().fhe_ckks_deep_diag_sum_dev(_plans_or_none(plans), len(plans) if limbs is None else limbs, _plans_or_none(specials),
+                                                     len(specials) if alpha is None else alpha, keys, els, len(gs) if count is None else count, key_limbs, d_pts,
+                                                     outputs, d_in, d_out, batch, stream))
+
+
+def ckks_deep_diag_workspace_bytes(n, limbs, alpha, batch, count, outputs):
+    return int(load_library().fhe_ckks_deep_diag_workspace_bytes(n, limbs, alpha, batch, count, outputs))
 
 
 def ckks_rns_lincomb_dev(plans, d_cts, w, k, outputs, d_out, batch, stream=None, limbs=None, count=None):

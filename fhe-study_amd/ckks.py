@@ -279,13 +279,20 @@ class RnsPlaintextSet:
     """The plaintexts of one diagonal sum, d_pts [outputs][count][level + 2][n] canonical evals on the device (the chain limbs
     0 .. level, then the special prime), their scale, and the Galois element gs[r] that column r multiplies"""
 
+    _limbs_name = "level + 2"
+
+    @staticmethod
+    def _special_count(param):
+        return 1
+
     def __init__(self, param, level, d_pts, scale, gs):
         gs = [int(g) for g in gs]
         for g in gs:
             if g % 2 == 0 or not 0 < g < 2 * param.n:
-                raise ValueError(f"RnsPlaintextSet: g={g} must be odd and in [1, 2n)")
-        if d_pts is not None and (d_pts.dim() != 4 or d_pts.shape[1] != len(gs) or d_pts.shape[2] != level + 2 or d_pts.shape[3] != param.n):
-            raise ValueError("RnsPlaintextSet: d_pts is not [outputs][count][level + 2][n]")
+                raise ValueError(f"{type(self).__name__}: g={g} must be odd and in [1, 2n)")
+        limbs = level + 1 + self._special_count(param)
+        if d_pts is not None and (d_pts.dim() != 4 or d_pts.shape[1] != len(gs) or d_pts.shape[2] != limbs or d_pts.shape[3] != param.n):
+            raise ValueError(f"{type(self).__name__}: d_pts is not [outputs][count][{self._limbs_name}][n]")
         self.param, self.level, self.d_pts, self.scale, self.gs = param, int(level), d_pts, float(scale), gs
 
     @property
@@ -293,10 +300,22 @@ class RnsPlaintextSet:
         return self.d_pts.shape[0]
 
 
+class DeepPlaintextSet(RnsPlaintextSet):
+    """RnsPlaintextSet on a DeepParam: d_pts [outputs][count][level + 1 + alpha][n], the chain limbs 0 .. level, then the special
+    primes p_0 .. p_{alpha-1} in order"""
+
+    _limbs_name = "level + 1 + alpha"
+
+    @staticmethod
+    def _special_count(param):
+        return len(param.specials)
+
+
 def encode_diagonals(param, encoder, rows, steps, level, scale):
     """rows complex [outputs][count][n/2] (or [count][n/2]: one output), slots in the rotation order; column r multiplies the
     ciphertext rotated by steps[r].  from_rotation_order and Encoder.encode at `scale`, then fhe_ckks_rns_from_i64_dev over the
-    chain limbs 0 .. level and once more over the special prime -> RnsPlaintextSet"""
+    chain limbs 0 .. level and once more over the special prime -> RnsPlaintextSet.  Given a DeepParam: over the chain limbs and
+    the special primes in slices of at most 8 plans -> DeepPlaintextSet"""
     torch = _torch()
     n = param.n
     rows = np.asarray(rows, dtype=np.complex128)
@@ -310,12 +329,18 @@ def encode_diagonals(param, encoder, rows, steps, level, scale):
     outputs, count = rows.shape[:2]
     coef = encoder.encode(from_rotation_order(rows.reshape(outputs * count, n // 2)) * (float(scale) / encoder.delta))
     d_rows = torch.from_numpy(np.ascontiguousarray(coef)).cuda()
-    d_pts = torch.empty((outputs * count, level + 2, n), dtype=torch.int64, device="cuda")
-    for plans, lo in ((param.plans(level), 0), ([param.special_plan()], level + 1)):
+    if isinstance(param, DeepParam):
+        every = param.plans(level) + param.special_plans()
+        slices, kind = [(every[lo:lo + 8], lo) for lo in range(0, len(every), 8)], DeepPlaintextSet
+    else:
+        slices, kind = [(param.plans(level), 0), ([param.special_plan()], level + 1)], RnsPlaintextSet
+    limbs = sum(len(plans) for plans, _ in slices)
+    d_pts = torch.empty((outputs * count, limbs, n), dtype=torch.int64, device="cuda")
+    for plans, lo in slices:
         ev = torch.empty((len(plans), outputs * count, n), dtype=torch.int64, device="cuda")
         binding.ckks_rns_from_i64_dev(plans, d_rows.data_ptr(), ev.data_ptr(), outputs * count)
         d_pts[:, lo:lo + len(plans)] = ev.permute(1, 0, 2)
-    return RnsPlaintextSet(param, level, d_pts.reshape(outputs, count, level + 2, n), scale, [galois_element(n, st) for st in steps])
+    return kind(param, level, d_pts.reshape(outputs, count, limbs, n), scale, [galois_element(n, st) for st in steps])
 
 
 def bsgs_diagonals(M, n1=None):
@@ -461,6 +486,14 @@ class RnsCiphertext:
         decomposition for all elements and outputs, one division by P an output.  gks[r] is the key of pts.gs[r]; where
         pts.gs[r] = 1 it is not read and may be None.  Level unchanged; the scale multiplies; the caller rescales."""
         torch = _torch()
+        key_ptrs = self._diag_keys(pts, gks)
+        out = torch.empty((pts.outputs,) + tuple(self.d.shape), dtype=torch.int64, device="cuda")
+        binding.ckks_rns_diag_sum_dev(self.param.plans(self.level), self.param.special_plan(), key_ptrs, pts.gs, len(self.param.moduli),
+                                      pts.d_pts.data_ptr(), pts.outputs, self.d.data_ptr(), out.data_ptr(), self.batch)
+        return [RnsCiphertext(self.param, out[o], self.level, self.scale * pts.scale) for o in range(pts.outputs)]
+
+    def _diag_keys(self, pts, gks):
+        """diag_sum's argument checks -> the device pointer of every element's key, None where the element is 1"""
         gks = list(gks)
         if pts.param != self.param or any(gk is not None and gk.param != self.param for gk in gks):
             raise binding.FheError(binding.FHE_E_PARAM_MISMATCH, "the plaintexts or a Galois key are not of this ciphertext's chain")
@@ -473,11 +506,7 @@ class RnsCiphertext:
                 raise ValueError(f"diag_sum: element {r} (g={g}) has no key")
             if g != 1 and gk.g != g:
                 raise ValueError(f"diag_sum: key {r} is of g={gk.g}, the plaintexts' element is {g}")
-        out = torch.empty((pts.outputs,) + tuple(self.d.shape), dtype=torch.int64, device="cuda")
-        binding.ckks_rns_diag_sum_dev(self.param.plans(self.level), self.param.special_plan(),
-                                      [None if g == 1 else gk.d_gk.data_ptr() for g, gk in zip(pts.gs, gks)], pts.gs, len(self.param.moduli),
-                                      pts.d_pts.data_ptr(), pts.outputs, self.d.data_ptr(), out.data_ptr(), self.batch)
-        return [RnsCiphertext(self.param, out[o], self.level, self.scale * pts.scale) for o in range(pts.outputs)]
+        return [None if g == 1 else gk.d_gk.data_ptr() for g, gk in zip(pts.gs, gks)]
 
     def linear_transform(self, lt, keys):
         """M w for a LinearTransform: one diag_sum whose outputs are the giant steps' inner sums, then rotate by n1 j and add
@@ -1014,8 +1043,9 @@ class DeepParam:
 
 class DeepCiphertext(RnsCiphertext):
     """RnsCiphertext on a DeepParam: +, -, at_level, add_plain and mul_plain are the base class's, per limb; the products, the
-    rescale and the Galois maps go through the fhe_ckks_deep_* entry points.  The fused sums, the linear transforms and the
-    Chebyshev plans are not carried to the deep chain yet."""
+    rescale, the Galois maps and the diagonal sums go through the fhe_ckks_deep_* entry points; linear_transform is the base
+    class's composition over them.  The fused scalar sums, the inner products, the hoisted giant steps and the Chebyshev plans
+    are not carried to the deep chain yet."""
 
     def mul(self, rhs, rlk):
         """ct x ct and relinearisation (fhe_ckks_deep_mul_dev); the scale multiplies and the result is NOT rescaled"""
@@ -1064,10 +1094,21 @@ class DeepCiphertext(RnsCiphertext):
             binding._check(binding.load_library().fhe_rq_neg_dev(plan.handle, self.d[i].data_ptr(), out[i].data_ptr(), 2 * self.batch, None))
         return DeepCiphertext(self.param, out, self.level, self.scale)
 
+    def diag_sum(self, pts, gks):
+        """RnsCiphertext.diag_sum from one fhe_ckks_deep_diag_sum_dev call: pts a DeepPlaintextSet"""
+        torch = _torch()
+        if not isinstance(pts, DeepPlaintextSet):
+            raise ValueError("diag_sum: the plaintexts of a deep chain are a DeepPlaintextSet")
+        key_ptrs = self._diag_keys(pts, gks)
+        out = torch.empty((pts.outputs,) + tuple(self.d.shape), dtype=torch.int64, device="cuda")
+        binding.ckks_deep_diag_sum_dev(self.param.plans(self.level), self.param.special_plans(), key_ptrs, pts.gs, len(self.param.moduli), pts.d_pts.data_ptr(),
+                                       pts.outputs, self.d.data_ptr(), out.data_ptr(), self.batch)
+        return [DeepCiphertext(self.param, out[o], self.level, self.scale * pts.scale) for o in range(pts.outputs)]
+
     def _not_yet(self, *args, **kwargs):
         raise NotImplementedError("not carried to the deep chain yet (DESIGN.md §36)")
 
-    diag_sum = linear_transform = linear_transform_hoisted = mul_const = add_const = eval_chebyshev = _not_yet
+    linear_transform_hoisted = mul_const = add_const = eval_chebyshev = _not_yet
 
 
 class DeepClientKey(RnsClientKey):
@@ -1093,5 +1134,3 @@ class DeepClientKey(RnsClientKey):
             raise ValueError(f"galois_key: g={g} must be odd and in [1, 2n)")
         return RnsGaloisKey(self.param, g, self._switch_key("galois_key", self.GK_BASE, slot, binding.ckks_deep_galois_key_dev, g))
 
-    def encode_diagonals(self, rows, steps, level, scale):
-        raise NotImplementedError("not carried to the deep chain yet (DESIGN.md §36)")

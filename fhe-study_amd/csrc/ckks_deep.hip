@@ -12,8 +12,10 @@
 //              D_ji = x_j mod m_i for every m_i of {q_0 .. q_{l-1}, p_0 .. p_{alpha-1}} (i in G_j: d's own limb, never lifted);
 //              t_i = sum_j D_ji (.) key[j][col(i)]; y the centred integer of t modulo P; r_i = (t_i - y) P^-1 mod q_i
 //   rescale    c'_i = (c_i - lift(c_top)) q_top^-1 mod q_i, §22's, for l up to 32
+//   diag sum   out_o = sum_r m_{o,r} (.) sigma_{g_r}(ct) (§37): the digits of c1 once, the key sums of all elements weighted and
+//              added in the basis Q P with the addends as (P mod q_i) ct, one modulus-down by P an output
 //
-// Both kernels are grid-stride and element-wise on fhe_ew_grid, bounds-checked against their element count, plain C++ with
+// The kernels are grid-stride and element-wise on fhe_ew_grid, bounds-checked against their element count, plain C++ with
 // vector stores and no scratch.  The tensor, the divide-and-round and the key's diagonal term are ckks_eval.hip's kernels,
 // launched from that unit (capi_internal.hpp); the transforms are fhe_ntt_forward_dev / fhe_ntt_inverse_dev on the workspace
 // (slot 14), one call per limb and direction over everything of that limb that is ready.
@@ -89,6 +91,97 @@ __global__ __launch_bounds__(256) void ckks_deep_keymac_kernel(const u64 *__rest
     }
 }
 
+// ---- plaintext linear transforms on the deep chain: the double-hoisted diagonal sum ----------------------------
+constexpr u32 kDeepDiagGroup = 16;    // elements of one launch, passed by value
+constexpr u32 kDeepDiagOutputs = 2;   // outputs whose accumulators one launch keeps in registers: no scratch, 8 waves a SIMD (§37)
+
+// The elements of one launch for one target.  Indexed by the loop counter, which is uniform: the reads are scalar loads from
+// the kernel-argument segment, not scratch.
+struct DeepDiagGroup {
+    const u64 *key[kDeepDiagGroup];   // element r's key rows of this target's column: digit j at + j key_stride, [2][n]; not read where g = 1
+    const u64 *pt[kDeepDiagGroup];    // m_{o, r, i} [n] of the launch's first output; output o at + o pt_os
+    u32 g[kDeepDiagGroup];
+    u32 count;
+};
+
+// One target i of {q_0 .. q_{l-1}, p_0 .. p_{alpha-1}} of out_o = sum_r m_{o,r} (.) sigma_{g_r}(ct) in the extended basis, the
+// grouped-digit form of ckks_rns_diagmac_kernel (§24): NOUT outputs and the elements of `grp`, over `count` words a component
+// (rows of n = 2^L):
+//   u_o[c][e] (+)= sum_r m_{o,r,i}[x] (t^(r)_c[e] + pmod ct_c[pi_{g_r}(e)] [c = 0 or g_r = 1]),  x = e mod n
+//   t^(r)_c[e]   = sum_{j < k} D_j[pi_{g_r}(e)] key_r[j][c][x]                                    (zero for g_r = 1)
+// D_j are ckks_deep_keymac_kernel's digits: `ct`'s second component for j = own_j, dig[(j - (j > own_j)) dig_stride + .]
+// otherwise.  `ct` is limb i's two components, ct_cs words apart, and NULL for a special prime, where the addend vanishes, no
+// digit is the target's own (own_j = k) and the identity is skipped.  With pmod = P mod q_i the addend rides through the
+// division by P: (u + P a - E) P^-1 = (u - E) P^-1 + a.  With pmod = 1 and no element but the identity, u is the finished sum
+// and `out` the output ciphertext.
+// CARRY: u starts from the canonical words a former group of 16 left in `out`; otherwise from zero.
+// Overflow.  Every modulus is below 2^62 (the deep chain refuses others, so there is no 2^62 <= q < 2^63 branch) and the operands
+// are canonical, so a term is below 2^124.  Inner key sum: the accumulators hold the addend's one term, then take one term a
+// digit and fold before every digit j > 0 where j is a multiple of kMacChunk = 8.  The first run is the addend and eight terms,
+// 9 2^124 < 2^128; a later one a canonical carry-over below 2^62 and at most eight terms, less than 2^127 + 2^62 (MacAcc::fold).
+// 32 digits are four runs.  Outer sum: u_o takes one term m t < 2^124 an element and folds before element r > 0 of the group
+// where r is a multiple of 8: a carry-over below 2^62 (the last fold or the word CARRY read, both canonical) and at most eight
+// terms.  An element that is skipped adds no term.  So any count holds: 256 elements are 16 groups, each folded to canonical
+// words before it is stored.
+template <u32 NOUT, bool CARRY>
+__global__ __launch_bounds__(256) void ckks_deep_diagmac_kernel(const u64 *__restrict__ dig, u64 dig_stride, const u64 *__restrict__ ct, u64 ct_cs, u32 own_j,
+                                                                u64 key_stride, u64 pt_os, u64 *__restrict__ out, u64 out_cs, u64 out_os, u32 k, u32 L, u64 count,
+                                                                u64 pmod, DeepDiagGroup grp, Mod m) {
+    const u64 stride = (u64)gridDim.x * 256, n = 1ull << L;
+    const u64 *__restrict__ own = ct ? ct + ct_cs : nullptr;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        const u64 x = i & (n - 1);
+        MacAcc u[NOUT][2];
+        if (CARRY) {
+#pragma unroll
+            for (u32 o = 0; o < NOUT; o++) {
+                u[o][0].v = out[o * out_os + i];
+                u[o][1].v = out[o * out_os + out_cs + i];
+            }
+        }
+        for (u32 r = 0; r < grp.count; r++) {
+            if (r && r % kMacChunk == 0) {
+#pragma unroll
+                for (u32 o = 0; o < NOUT; o++) u[o][0].fold(m), u[o][1].fold(m);
+            }
+            const u32 g = grp.g[r];
+            if (g == 1 && !ct) continue;                             // the identity contributes nothing modulo a special prime
+            const u64 s = i - x + galois_index((u32)x, g, L);
+            MacAcc a0, a1;
+            if (ct) {
+                a0.mac(ct[s], pmod);
+                if (g == 1) a1.mac(ct[ct_cs + s], pmod);
+            }
+            if (g != 1) {
+                const u64 *__restrict__ key = grp.key[r];
+                for (u32 j = 0; j < k; j++) {
+                    if (j && j % kMacChunk == 0) {
+                        a0.fold(m);
+                        a1.fold(m);
+                    }
+                    const u64 d = j == own_j ? own[s] : dig[(u64)(j - (j > own_j ? 1u : 0u)) * dig_stride + s];
+                    const u64 *__restrict__ kp = key + (u64)j * key_stride + x;
+                    a0.mac(d, kp[0]);
+                    a1.mac(d, kp[n]);
+                }
+            }
+            const u64 t0 = a0.fold(m), t1 = a1.fold(m);
+            const u64 *__restrict__ pr = grp.pt[r] + x;
+#pragma unroll
+            for (u32 o = 0; o < NOUT; o++) {
+                const u64 w = pr[o * pt_os];
+                u[o][0].mac(w, t0);
+                u[o][1].mac(w, t1);
+            }
+        }
+#pragma unroll
+        for (u32 o = 0; o < NOUT; o++) {
+            out[o * out_os + i] = u[o][0].fold(m);
+            out[o * out_os + out_cs + i] = u[o][1].fold(m);
+        }
+    }
+}
+
 }  // namespace fhe
 
 // ---- host side -----------------------------------------------------------------------------------------------------
@@ -108,7 +201,8 @@ struct Deep {
 
 // slabs (cr n words) of one ciphertext of a chunk: the tensor 3k, C k, D (k + alpha) ng - k, T 2 (k + alpha), E 2k
 u64 deep_slabs(unsigned k, unsigned alpha) { return (u64)(k + alpha) * fhe::host::deep_groups(k, alpha) + 7ull * k + 2ull * alpha; }
-u64 deep_chunk(u64 n, unsigned k, unsigned alpha, u64 batch) { return std::min<u64>(batch, std::max<u64>(1, (kChunkWords / n) / deep_slabs(k, alpha))); }
+u64 slab_chunk(u64 n, u64 slabs, u64 batch) { return std::min<u64>(batch, std::max<u64>(1, (kChunkWords / n) / slabs)); }
+u64 deep_chunk(u64 n, unsigned k, unsigned alpha, u64 batch) { return slab_chunk(n, deep_slabs(k, alpha), batch); }
 u64 rescale_chunk(u64 n, unsigned k, u64 batch) { return std::min<u64>(batch, std::max<u64>(1, (kChunkWords / n) / (2ull * k))); }
 
 // plans[0 .. limbs) and, where the entry point takes them, specials[0 .. alpha): FHE_E_NULL, then the counts, the ring, the
@@ -246,6 +340,7 @@ struct DeepBufs {
     u64 slab;
     DeepBufs(u64 *W, const Deep &c, u64 slab_)
         : Dt(W), C(Dt + 3ull * c.k * slab_), D(C + (u64)c.k * slab_), T(D + ((u64)(c.k + c.alpha) * c.ng - c.k) * slab_), E(T + 2ull * (c.k + c.alpha) * slab_), slab(slab_) {}
+    DeepBufs(u64 *C_, u64 *D_, u64 *T_, u64 *E_, u64 slab_) : Dt(nullptr), C(C_), D(D_), T(T_), E(E_), slab(slab_) {}   // a diagonal sum: no tensor, T one of its sets
 };
 
 // `polys` rows of evals, which the ABI aligns to 8 bytes, as coefficients in the workspace rows dst
@@ -328,16 +423,16 @@ int relin_rows(const Deep &c, const DeepTables &t, const u64 *rlk, unsigned key_
     return special_down(c, t, b, {d + d_r0 * n, 3 * d_rows * n, d_rows * n}, {out + o_r0 * n, 2 * o_rows * n, o_rows * n}, pinv, 0u, st);
 }
 
-// The frame of a key-switch call: the chain's tables, the workspace, the inverses of P, and body(r0, cr, tables, bufs, pinv) over
-// the batch in chunks
+// The frame of a key-switch call: the chain's tables, the workspace of `slabs` slabs a ciphertext, the inverses of P, and
+// body(r0, cr, tables, W, pinv) over the batch in chunks
 template <class Body>
-int switch_call(const Deep &c, u64 batch, hipStream_t st, const char *who, Body body) {
+int switch_call(const Deep &c, u64 batch, u64 slabs, hipStream_t st, const char *who, Body body) {
     const DeepTables *t = nullptr;
     int rc = tables_get(c, false, &t, [&](DeepTables *b) { return switch_tables(c, b, who); });
     if (rc != FHE_OK) return rc;
-    const u64 cb = deep_chunk(c.n, c.k, c.alpha, batch);
+    const u64 cb = slab_chunk(c.n, slabs, batch);
     void *w = nullptr;
-    if ((rc = fhe_workspace_get(kCkksDeepSlot, (size_t)(deep_slabs(c.k, c.alpha) * cb * c.n * 8), st, &w)) != FHE_OK) return rc;
+    if ((rc = fhe_workspace_get(kCkksDeepSlot, (size_t)(slabs * cb * c.n * 8), st, &w)) != FHE_OK) return rc;
     u64 pinv[fhe::kDeepMaxLimbs];
     for (unsigned i = 0; i < c.k; i++) {
         const u64 q = c.p[i]->q;
@@ -347,7 +442,7 @@ int switch_call(const Deep &c, u64 batch, hipStream_t st, const char *who, Body 
     }
     for (u64 r0 = 0; r0 < batch; r0 += cb) {
         const u64 cr = std::min<u64>(cb, batch - r0);
-        if ((rc = body(r0, cr, *t, DeepBufs((u64 *)w, c, cr * c.n), pinv)) != FHE_OK) return rc;
+        if ((rc = body(r0, cr, *t, (u64 *)w, pinv)) != FHE_OK) return rc;
     }
     return FHE_OK;
 }
@@ -438,8 +533,8 @@ extern "C" int fhe_ckks_deep_relinearize_dev(const fhe_ntt_plan *const *plans, u
     if (overlaps_any(d_out, 2ull * c.k * batch * n * 8, {{d_d, 3ull * c.k * batch * n * 8}, {d_key, key_words(key_limbs, alpha, n) * 8}}))
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the tensor or the key", who);
     hipStream_t st = (hipStream_t)hip_stream;
-    return switch_call(c, batch, st, who, [&](u64 r0, u64 cr, const DeepTables &t, const DeepBufs &b, const u64 *pinv) {
-        return relin_rows(c, t, (const u64 *)d_key, key_limbs, pinv, (const u64 *)d_d, batch, r0, (u64 *)d_out, batch, r0, b, cr, st);
+    return switch_call(c, batch, deep_slabs(c.k, c.alpha), st, who, [&](u64 r0, u64 cr, const DeepTables &t, u64 *W, const u64 *pinv) {
+        return relin_rows(c, t, (const u64 *)d_key, key_limbs, pinv, (const u64 *)d_d, batch, r0, (u64 *)d_out, batch, r0, DeepBufs(W, c, cr * n), cr, st);
     });
 }
 
@@ -460,8 +555,9 @@ extern "C" int fhe_ckks_deep_mul_dev(const fhe_ntt_plan *const *plans, unsigned 
         return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an operand or the key", who);
     hipStream_t st = (hipStream_t)hip_stream;
     const u64 *a = (const u64 *)d_a, *bb = (const u64 *)d_b;
-    return switch_call(c, batch, st, who, [&](u64 r0, u64 cr, const DeepTables &t, const DeepBufs &b, const u64 *pinv) {
+    return switch_call(c, batch, deep_slabs(c.k, c.alpha), st, who, [&](u64 r0, u64 cr, const DeepTables &t, u64 *W, const u64 *pinv) {
         const u64 slab = cr * n;
+        const DeepBufs b(W, c, slab);
         for (unsigned i = 0; i < c.k; i++) {
             const int rc = fhe_rns_tensor_limb(c.p[i], a + ((u64)i * 2 * batch + r0) * n, batch * n, bb + ((u64)i * 2 * batch + r0) * n, batch * n, b.Dt + (u64)i * 3 * slab,
                                                slab, slab, st);
@@ -495,7 +591,8 @@ extern "C" int fhe_ckks_deep_galois_dev(const fhe_ntt_plan *const *plans, unsign
     hipStream_t st = (hipStream_t)hip_stream;
     // the digits are those of the unpermuted c1, made once a chunk; every g then takes its key sums with the digits read at pi_g,
     // the divide-and-round by P, and pi_g(c0) gathered in that last kernel (§23)
-    return switch_call(c, batch, st, who, [&](u64 r0, u64 cr, const DeepTables &t, const DeepBufs &b, const u64 *pinv) {
+    return switch_call(c, batch, deep_slabs(c.k, c.alpha), st, who, [&](u64 r0, u64 cr, const DeepTables &t, u64 *W, const u64 *pinv) {
+        const DeepBufs b(W, c, cr * n);
         const LimbRows<const u64> ct{(const u64 *)d_in + r0 * n, 2 * batch * n, batch * n};
         auto c1 = [&](unsigned limb) { return ct.of(limb) + ct.cs; };
         int rc;
@@ -504,6 +601,132 @@ extern "C" int fhe_ckks_deep_galois_dev(const fhe_ntt_plan *const *plans, unsign
             const u32 g = (u32)gs[r];
             if ((rc = keymac_rows(c, (const u64 *)d_gks[r], key_limbs, c1, b, g, st)) != FHE_OK) return rc;
             if ((rc = special_down(c, t, b, ct, {(u64 *)d_out + r * 2ull * c.k * batch * n + r0 * n, ct.ls, ct.cs}, pinv, g, st)) != FHE_OK) return rc;
+        }
+        return FHE_OK;
+    });
+}
+
+// ---- plaintext linear transforms: the double-hoisted diagonal sum ---------------------------------------------------
+namespace {
+
+// slabs of one ciphertext of a chunk of a diagonal sum: C k, D (k + alpha) ng - k, min(outputs, kDeepDiagOutputs) sets U of
+// 2 (k + alpha), E 2k
+u64 diag_slabs(unsigned k, unsigned alpha, unsigned outputs) {
+    return (u64)(k + alpha) * fhe::host::deep_groups(k, alpha) + 2ull * (k + alpha) * std::min<unsigned>(outputs, fhe::kDeepDiagOutputs) + 2ull * k;
+}
+
+template <class... A>
+int deep_diagmac_launch(unsigned nout, bool carry, int L, hipStream_t st, unsigned grid, A... a) {
+    const char *lab = "ckks_deep_diagmac";
+#define FHE_DEEP_DIAG_CASE(N) \
+    case N: return carry ? launch(lab, L, st, fhe::ckks_deep_diagmac_kernel<N, true>, grid, 256, a...) : launch(lab, L, st, fhe::ckks_deep_diagmac_kernel<N, false>, grid, 256, a...)
+    switch (nout) {
+        FHE_DEEP_DIAG_CASE(1);
+        FHE_DEEP_DIAG_CASE(2);
+    }
+#undef FHE_DEEP_DIAG_CASE
+    static_assert(fhe::kDeepDiagOutputs == 2, "one case per accumulator count");
+    return fhe_fail(FHE_E_INVALID, "ckks_deep_diagmac: %u outputs in one launch", nout);
+}
+
+// The diagmac launches of outputs o0 .. o0 + nout of a diagonal sum over `slab` words a component of `ct`, in groups of
+// kDeepDiagGroup elements.  U != NULL: the sums of §37 in the basis Q P, over the k + alpha targets, into the sets 0 .. nout - 1 at
+// U (D the lifted digits).  Otherwise (no element but 1) the finished sums over the k chain limbs, into the rows out0 of output
+// o0, the outputs o_words apart.
+int deep_diagmac_rows(const Deep &c, const u64 *const *gks, const uint64_t *gs, unsigned count, unsigned key_limbs, const u64 *pts, unsigned o0, unsigned nout,
+                      const u64 *D, u64 *U, u64 slab, LimbRows<const u64> ct, LimbRows<u64> out0, u64 o_words, hipStream_t st) {
+    const unsigned k = c.k, all = k + c.alpha;
+    const u64 n = c.n, pt_os = (u64)count * all * n, set = 2ull * all * slab;
+    for (unsigned i = 0; i < (U ? all : k); i++) {
+        u64 pmod = 1;
+        if (U && i < k)
+            for (unsigned m = 0; m < c.alpha; m++) pmod = fhe::host::mulmod(pmod, c.p[k + m]->q % c.p[i]->q, c.p[i]->q);
+        for (unsigned e0 = 0; e0 < count; e0 += fhe::kDeepDiagGroup) {
+            fhe::DeepDiagGroup grp{};
+            grp.count = std::min<unsigned>(fhe::kDeepDiagGroup, count - e0);
+            for (unsigned r = 0; r < grp.count; r++) {
+                grp.g[r] = (u32)gs[e0 + r];
+                grp.key[r] = grp.g[r] == 1 ? nullptr : gks[e0 + r] + (u64)(i < k ? i : key_limbs + (i - k)) * 2 * n;
+                grp.pt[r] = pts + (((u64)o0 * count + e0 + r) * all + i) * n;
+            }
+            const int rc = deep_diagmac_launch(nout, e0 > 0, (int)c.L, st, fhe_ew_grid(slab), U ? D + c.D_off(i) * slab : nullptr, slab, i < k ? ct.of(i) : nullptr, ct.cs,
+                                               c.group_of(i), (u64)(key_limbs + c.alpha) * 2 * n, pt_os, U ? U + 2ull * i * slab : out0.of(i), U ? slab : out0.cs,
+                                               U ? set : o_words, c.ng, c.L, slab, i < k ? pmod : 0ull, grp, c.p[i]->mod);
+            if (rc != FHE_OK) return rc;
+        }
+    }
+    return FHE_OK;
+}
+
+}  // namespace
+
+extern "C" size_t fhe_ckks_deep_diag_workspace_bytes(uint64_t n, unsigned limbs, unsigned alpha, size_t batch, unsigned count, unsigned outputs) {
+    if (!shape_of(n, limbs, alpha, batch) || count == 0 || count > FHE_CKKS_GALOIS_MAX_COUNT || outputs == 0 || outputs > FHE_CKKS_DIAG_MAX_OUTPUTS) return 0;
+    const u64 slabs = diag_slabs(limbs, alpha, outputs);
+    return (size_t)(slabs * n * slab_chunk(n, slabs, batch) * 8);
+}
+
+extern "C" int fhe_ckks_deep_diag_sum_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *specials, unsigned alpha, const void *const *d_gks,
+                                          const uint64_t *gs, unsigned count, unsigned key_limbs, const void *d_pts, unsigned outputs, const void *d_in, void *d_out,
+                                          size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_deep_diag_sum_dev";
+    Deep c;
+    int rc = check_deep(plans, limbs, specials, alpha, true, &c, who);
+    if (rc != FHE_OK) return rc;
+    if ((rc = check_key_limbs(c, key_limbs, who)) != FHE_OK) return rc;
+    if (count > FHE_CKKS_GALOIS_MAX_COUNT) return fhe_fail(FHE_E_INVALID, "%s: count=%u passes %d", who, count, FHE_CKKS_GALOIS_MAX_COUNT);
+    if (outputs < 1 || outputs > FHE_CKKS_DIAG_MAX_OUTPUTS) return fhe_fail(FHE_E_INVALID, "%s: outputs=%u must be in [1, %d]", who, outputs, FHE_CKKS_DIAG_MAX_OUTPUTS);
+    if (batch == 0 || count == 0) return FHE_OK;
+    const u64 n = c.n;
+    const unsigned k = c.k;
+    if (!mul_fits((u64)batch, 2ull * k * n * outputs, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!gs || !d_pts || !d_in || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_pts) || misaligned8(d_in) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 ct_bytes = 2ull * k * batch * n * 8, out_bytes = ct_bytes * outputs, gk_bytes = key_words(key_limbs, alpha, n) * 8;
+    bool switched = false;
+    for (unsigned r = 0; r < count; r++) {                           // g = 1 takes no key: the element is looked at before its key
+        if ((rc = check_galois_element(gs[r], n, (int)r, who)) != FHE_OK) return rc;
+        if (gs[r] == 1) continue;
+        switched = true;
+        if (!d_gks || !d_gks[r]) return fhe_fail(FHE_E_NULL, "%s: key %u is NULL", who, r);
+        if (misaligned8(d_gks[r])) return fhe_fail(FHE_E_INVALID, "%s: key %u must be 8-byte aligned", who, r);
+        if (overlaps_any(d_out, out_bytes, {{d_gks[r], gk_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps key %u", who, r);
+    }
+    if (overlaps_any(d_out, out_bytes, {{d_in, ct_bytes}, {d_pts, (u64)outputs * count * (k + alpha) * n * 8}}))
+        return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the ciphertexts or the plaintexts", who);
+    hipStream_t st = (hipStream_t)hip_stream;
+    const u64 *const *gks = (const u64 *const *)d_gks;
+    const u64 *pts = (const u64 *)d_pts;
+    const u64 o_words = 2ull * k * batch * n;
+    if (!switched) {
+        // no element but the identity: the sums are finished modulo the chain primes, element-wise over the whole batch; no
+        // digit, no transform, no modulus-down and no workspace
+        int dev;                                                     // not used: the call is here to refuse, as the workspace would, where there is no device
+        if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
+        for (unsigned o0 = 0; o0 < outputs; o0 += fhe::kDeepDiagOutputs) {
+            const unsigned nout = std::min<unsigned>(fhe::kDeepDiagOutputs, outputs - o0);
+            if ((rc = deep_diagmac_rows(c, gks, gs, count, key_limbs, pts, o0, nout, nullptr, nullptr, batch * n, {(const u64 *)d_in, 2 * batch * n, batch * n},
+                                        {(u64 *)d_out + o0 * o_words, 2 * batch * n, batch * n}, o_words, st)) != FHE_OK)
+                return rc;
+        }
+        return FHE_OK;
+    }
+    // the digits are those of the unpermuted c1, made once a chunk; per launch of up to kDeepDiagOutputs outputs, U over the
+    // k + alpha targets; per output one modulus-down of its U, with no addend: it rode through as (P mod q_i) ct
+    const unsigned sets = std::min<unsigned>(outputs, fhe::kDeepDiagOutputs);
+    return switch_call(c, batch, diag_slabs(k, alpha, outputs), st, who, [&](u64 r0, u64 cr, const DeepTables &t, u64 *W, const u64 *pinv) {
+        const u64 slab = cr * n, set = 2ull * (k + alpha) * slab;
+        u64 *C = W, *D = C + (u64)k * slab, *U = D + ((u64)(k + alpha) * c.ng - k) * slab, *E = U + sets * set;
+        const LimbRows<const u64> ct{(const u64 *)d_in + r0 * n, 2 * batch * n, batch * n};
+        auto c1 = [&](unsigned limb) { return ct.of(limb) + ct.cs; };
+        int rc;
+        if ((rc = digit_rows(c, t, c1, DeepBufs(C, D, U, E, slab), cr, st)) != FHE_OK) return rc;
+        for (unsigned o0 = 0; o0 < outputs; o0 += fhe::kDeepDiagOutputs) {
+            const unsigned nout = std::min<unsigned>(fhe::kDeepDiagOutputs, outputs - o0);
+            if ((rc = deep_diagmac_rows(c, gks, gs, count, key_limbs, pts, o0, nout, D, U, slab, ct, {}, 0, st)) != FHE_OK) return rc;
+            for (unsigned o = 0; o < nout; o++)
+                if ((rc = special_down(c, t, DeepBufs(C, D, U + o * set, E, slab), {}, {(u64 *)d_out + (o0 + o) * o_words + r0 * n, ct.ls, ct.cs}, pinv, 0u, st)) != FHE_OK)
+                    return rc;
         }
         return FHE_OK;
     });

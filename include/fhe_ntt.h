@@ -907,6 +907,35 @@ int fhe_ckks_deep_rescale_dev(const fhe_ntt_plan *const *plans, unsigned limbs, 
                               void *hip_stream);
 size_t fhe_ckks_deep_workspace_bytes(uint64_t n, unsigned limbs, unsigned alpha, size_t batch);
 
+/* ---- CKKS on a deep RNS chain: plaintext linear transforms, the double-hoisted diagonal sum (ckks_deep.hip) ----
+ * fhe_ckks_rns_diag_sum_dev (§24) on the chain of the block above, with its plans, specials, alpha, key layout and key_limbs.
+ *   fhe_ckks_deep_diag_sum_dev    d_out [outputs][limbs][2][batch][n]: out_o = sum_{r < count} m_{o,r} (.) sigma_{gs[r]}(d_in) for
+ *            d_in [limbs][2][batch][n] and the plaintexts d_pts [outputs][count][limbs + alpha][n], canonical evals under the
+ *            chain primes and then under the special primes p_0 .. p_{alpha-1} in order, shared by the batch (at alpha = 1
+ *            §24's layout).  The grouped digits of c1 are made once per chunk; the key sums of all elements are weighted and
+ *            added in the basis Q P, the addends riding along as (P mod q_i) ct, and each output takes ONE division by P.
+ *            An element gs[r] = 1 is the identity: it takes no key, d_gks[r] is not read and may be NULL (d_gks itself may be
+ *            NULL where every element is 1; then no digit is made, nothing is transformed and no modulus-down runs).  Elements
+ *            may repeat.  Level is unchanged; the scale is the ciphertext's times the plaintexts'.  At alpha = 1 and limbs <= 8
+ *            the output equals fhe_ckks_rns_diag_sum_dev's word for word.
+ *   fhe_ckks_deep_diag_workspace_bytes  the library workspace that call takes at most; 0 for a shape it refuses.  With
+ *            ng = ceil(limbs / alpha) and s = min(outputs, 2), the outputs one launch accumulates, the call stages
+ *            S = limbs + ((limbs + alpha) ng - limbs) + 2 (limbs + alpha) s + 2 limbs slabs of n words a ciphertext (the limbs in
+ *            coefficients, the lifted digits, s sets U of the sums in the basis Q P, the lifted t_P) over chunks of
+ *            c = min(batch, max(1, floor(floor(2^21 / n) / S))) ciphertexts: 8 S n c bytes.  `count` does not enter: the
+ *            elements are added in registers.
+ * d_gks and gs are HOST arrays.  The conditions are the block's above, and: FHE_E_INVALID for count > FHE_CKKS_GALOIS_MAX_COUNT,
+ * outputs = 0 or > FHE_CKKS_DIAG_MAX_OUTPUTS, g even or >= 2n, a misaligned buffer or key, a batch too large, and an output that
+ * overlaps the input, a key or the plaintexts; FHE_E_NULL for a NULL key of an element other than 1.  A plaintext word must be
+ * below its modulus: the caller's contract, not checked on the device.  Nothing is written on rejection; batch = 0 or
+ * count = 0 is a no-op (count = 0 writes nothing, not zeros). */
+int fhe_ckks_deep_diag_sum_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *specials,
+                               unsigned alpha, const void *const *d_gks, const uint64_t *gs, unsigned count,
+                               unsigned key_limbs, const void *d_pts, unsigned outputs, const void *d_in, void *d_out,
+                               size_t batch, void *hip_stream);
+size_t fhe_ckks_deep_diag_workspace_bytes(uint64_t n, unsigned limbs, unsigned alpha, size_t batch, unsigned count,
+                                          unsigned outputs);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
