@@ -2,7 +2,9 @@
 // deep_ext_tables), without the library or a GPU.  The admission is held against a comparison by successive
 // divisions, which shares nothing with the products deep_admits compares; the tables against their definitions, and the
 // kernel's route (Garner's digits, the centring compare, one 128-bit sum per target) against the CRT definition on multiword
-// integers, at the edges 0, 1, floor(M / 2), floor(M / 2) + 1, M - 1 and at random.  Also the program the sanitizers run on this
+// integers, at the edges 0, 1, floor(M / 2), floor(M / 2) + 1, M - 1 and at random; on the bases of §38's sweep (every prime just
+// below 2^62; 30-bit beside 37, 61 and 62-bit primes in both orders) the source tables against their definitions, the device's word
+// formulas against the digits, and the compare decided at every digit position.  Also the program the sanitizers run on this
 // arithmetic (`make san_deep`).
 #include <cstdio>
 #include <cstdlib>
@@ -203,10 +205,119 @@ static void test_extension() {
     CHECK(fhe::host::deep_ext_tables(mid.data(), 2, mid.data() + 2, off, 0, &e, tab));   // no target: a group that is the whole chain
 }
 
+// ---- the bases of the sweep ----------------------------------------------------------------------------------------
+// the device's word arithmetic (csrc/rns_ext_device.hpp), restated with 128-bit products
+static u64 hi64(u64 a, u64 b) { return (u64)(((u128)a * b) >> 64); }
+static u64 csub(u64 x, u64 q) { return x >= q ? x - q : x; }
+static u64 dev_mul(u64 x, u64 w, u64 wp, u64 q) { return csub(x * w - hi64(x, wp) * q, q); }
+static u64 dev_red(u64 x, u64 q, u64 onep) { return csub(x - hi64(x, onep) * q, q); }
+
+// the source tables against their definitions, and Garner's digits by the device's formulas (ext_red of an earlier digit modulo a
+// later source, ext_mul by the Shoup pair) against the digits the integer was made from
+static void check_sources(const std::vector<u64> &src, const std::vector<u64> &dst, const u64 *digits_of_x) {
+    const unsigned s = (unsigned)src.size(), t = (unsigned)dst.size();
+    fhe::DeepSrc e;
+    std::vector<fhe::DeepTarget> tab(t);
+    std::vector<u64> off(t, 0);
+    CHECK(fhe::host::deep_ext_tables(src.data(), s, dst.data(), off.data(), t, &e, tab.data()));
+    Big half = fhe::host::big_product(src.data(), s);
+    half.divmod(2);
+    CHECK(from_digits(src.data(), s, e.half).cmp(half) == 0);
+    for (unsigned i = 0; i < s; i++) {
+        CHECK(e.mq[i] == src[i] && e.monep[i] == (u64)((((u128)1) << 64) / src[i]) && e.half[i] < src[i]);
+        for (unsigned j = 0; j < i; j++) {
+            CHECK(e.inv[j][i] < src[i] && (u64)((u128)e.inv[j][i] * (src[j] % src[i]) % src[i]) == 1);
+            CHECK(e.invp[j][i] == (u64)((((u128)e.inv[j][i]) << 64) / src[i]));
+        }
+    }
+    for (unsigned k = 0; k < t; k++) CHECK(tab[k].r64p == (u64)((((u128)tab[k].r64) << 64) / dst[k]));
+    const Big X = from_digits(src.data(), s, digits_of_x);
+    u64 a[8];
+    for (unsigned i = 0; i < s; i++) {
+        const u64 q = src[i];
+        u64 v = X.mod(q);
+        for (unsigned j = 0; j < i; j++) v = dev_mul(v + q - dev_red(a[j], q, e.monep[i]), e.inv[j][i], e.invp[j][i], q);
+        a[i] = v;
+        CHECK(a[i] == digits_of_x[i]);
+    }
+    // one target's sum by the device's reduction: the low word by ext_red, the high word times 2^64 mod p by ext_mul
+    for (unsigned k = 0; k < t; k++) {
+        const fhe::DeepTarget &d = tab[k];
+        u128 acc = 0;
+        for (unsigned j = 0; j < s; j++) acc += (u128)a[j] * d.W[j];
+        const u64 v = csub(dev_red((u64)acc, d.q, d.onep) + dev_mul((u64)(acc >> 64), d.r64, d.r64p, d.q), d.q);
+        CHECK(v == X.mod(d.q));
+    }
+}
+
+// for every digit position i: the digits of floor(M / 2) above i, one more or one less at i, and below i those of floor(M / 2), all
+// zero, or all m_j - 1: the compare is decided at every depth, with the low digits pointing the other way
+static void check_depths(const std::vector<u64> &src, const std::vector<u64> &dst) {
+    const unsigned s = (unsigned)src.size();
+    fhe::DeepSrc e;
+    std::vector<fhe::DeepTarget> tab(dst.size());
+    std::vector<u64> off(dst.size(), 0);
+    CHECK(fhe::host::deep_ext_tables(src.data(), s, dst.data(), off.data(), (unsigned)dst.size(), &e, tab.data()));
+    u64 top[8];
+    for (unsigned i = 0; i < s; i++) top[i] = src[i] - 1;
+    check_sources(src, dst, top);
+    check_sources(src, dst, e.half);
+    for (unsigned i = 0; i < s; i++)
+        for (int step = -1; step <= 1; step += 2) {
+            if ((step < 0 && e.half[i] == 0) || (step > 0 && e.half[i] + 1 >= src[i])) continue;
+            for (int low = 0; low < 3; low++) {
+                u64 a[8];
+                for (unsigned j = 0; j < s; j++) a[j] = j > i ? e.half[j] : j == i ? e.half[i] + (u64)step : low == 0 ? e.half[j] : low == 1 ? 0 : src[j] - 1;
+                check_word(src, dst, a);
+                check_sources(src, dst, a);
+            }
+        }
+}
+
+static void test_sweep_bases() {
+    for (u64 step : {16ull, 128ull}) {                               // the primes of n = 8 and n = 64
+        // A1: every prime just below 2^62; the first alpha are the special primes, the next L the chain
+        const unsigned shapes[4][3] = {{32, 1, 32}, {17, 8, 17}, {9, 3, 7}, {5, 2, 4}};
+        for (const auto &sh : shapes) {
+            const unsigned L = sh[0], alpha = sh[1], l = sh[2];
+            const std::vector<u64> ps = primes_below(62, step, alpha + L);
+            const u64 *sp = ps.data(), *q = ps.data() + alpha;
+            CHECK(fhe::host::deep_admits(q, L, sp, alpha) && fhe::host::deep_admits(q, l, sp, alpha));
+            for (unsigned j0 = 0; j0 < l; j0 += alpha) {
+                const unsigned s = l - j0 < alpha ? l - j0 : alpha;
+                std::vector<u64> src(q + j0, q + j0 + s), dst(sp, sp + alpha);
+                for (unsigned i = 0; i < l && dst.size() < 12; i++)
+                    if (i < j0 || i >= j0 + s) dst.push_back(q[i]);
+                check_depths(src, dst);
+            }
+            check_depths(std::vector<u64>(sp, sp + alpha), std::vector<u64>(q, q + (l < 8 ? l : 8)));   // the modulus-down
+        }
+        // A3: a 30-bit prime beside 37, 61 and 62-bit ones, small before large and large before small
+        const std::vector<u64> p30 = primes_below(30, step, 4), p37 = primes_below(37, step, 4), p61 = primes_below(61, step, 4), p62 = primes_below(62, step, 12);
+        for (unsigned alpha : {2u, 4u, 8u})
+            for (int down = 0; down < 2; down++) {
+                std::vector<u64> grp;
+                for (unsigned i = 0; i < alpha; i++) grp.push_back(i % 4 == 0 ? p30[i / 4] : i % 4 == 1 ? p62[8 + i / 4] : i % 4 == 2 ? p37[i / 4] : p61[i / 4]);
+                if (down) grp = std::vector<u64>(grp.rbegin(), grp.rend());
+                std::vector<u64> dst(p62.begin(), p62.begin() + alpha);
+                dst.push_back(p30[2]);
+                dst.push_back(p37[2]);
+                dst.push_back(p61[2]);
+                CHECK(fhe::host::deep_admits(grp.data(), alpha, p62.data(), alpha));
+                check_depths(grp, dst);
+                if (alpha == 2) {                                    // the other neighbours of the 30-bit prime at alpha = 2
+                    check_depths(down ? std::vector<u64>{p61[0], p30[1]} : std::vector<u64>{p30[1], p61[0]}, dst);
+                    check_depths(down ? std::vector<u64>{p37[0], p30[3]} : std::vector<u64>{p30[3], p37[0]}, dst);
+                }
+            }
+    }
+}
+
 int main() {
     test_groups();
     test_admission();
     test_extension();
+    test_sweep_bases();
     if (failures) {
         printf("%d FAILURES\n", failures);
         return 1;

@@ -47,7 +47,11 @@ def diag_sum(mods, specials, gks, gs, pts, ct):
     targets = list(mods) + list(specials)
     if switched:
         Dg = D.digits(mods, specials, ct[:, 1])
-        ts = {r: key_sums(mods, specials, gks[r], gs[r], Dg) for r in switched}
+        once = {}                                                    # a key object that recurs with its element: its sums once
+        for r in switched:
+            if (id(gks[r]), gs[r]) not in once:
+                once[id(gks[r]), gs[r]] = key_sums(mods, specials, gks[r], gs[r], Dg)
+        ts = {r: once[id(gks[r]), gs[r]] for r in switched}
     out = []
     for o in range(outputs):
         if switched:
