@@ -110,6 +110,8 @@ EXPORTS = [
     "fhe_ckks_deep_rescale_dev", "fhe_ckks_deep_workspace_bytes",
     # CKKS on a deep RNS chain: plaintext linear transforms, the double-hoisted diagonal sum (ckks_deep.hip)
     "fhe_ckks_deep_diag_sum_dev", "fhe_ckks_deep_diag_workspace_bytes",
+    # CKKS on a deep RNS chain: scalar sums and inner products over a slice of limbs a launch (ckks_deep.hip)
+    "fhe_ckks_deep_lincomb_dev", "fhe_ckks_deep_dot_dev",
 ]
 FHE_CKKS_GALOIS_MAX_COUNT = 256              # include/fhe_ntt.h: the most Galois elements of one fhe_ckks_rns_galois_dev call
 FHE_CKKS_DIAG_MAX_OUTPUTS = 64               # include/fhe_ntt.h: the most outputs of one fhe_ckks_rns_diag_sum_dev call
@@ -363,6 +365,8 @@ def load_library():
     L.fhe_ckks_deep_diag_sum_dev.argtypes = [_pp, _uint, _pp, _uint, _pp, ctypes.POINTER(_u64), _uint, _uint, _vp, _uint, _vp, _vp, _sz, _vp]
     L.fhe_ckks_deep_diag_workspace_bytes.argtypes = [_u64, _uint, _uint, _sz, _uint, _uint]
     L.fhe_ckks_deep_diag_workspace_bytes.restype = _sz
+    L.fhe_ckks_deep_lincomb_dev.argtypes = [_pp, _uint, _pp, _uint, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _uint, _vp, _sz, _vp]
+    L.fhe_ckks_deep_dot_dev.argtypes = [_pp, _uint, _pp, _uint, _vp, _uint, _pp, _pp, _uint, ctypes.POINTER(_u64), _vp, _sz, _vp]
     L.fhe_ckks_rns_dot_dev.argtypes = [_pp, _uint, _vp, _vp, _uint, _pp, _pp, _uint, ctypes.POINTER(_u64), _vp, _sz, _vp]
     L.fhe_rns_extend_dev.argtypes = [ctypes.POINTER(_u64), _uint, ctypes.POINTER(_u64), _uint, _int, _vp, _vp, _sz, _vp]
     L.fhe_bfv_rns_tensor_dev.argtypes = [_pp, _uint, _pp, _u64, _vp, _vp, _vp, _sz, _vp]
@@ -1023,6 +1027,27 @@ def ckks_deep_diag_sum_dev(plans, specials, d_gks, gs, key_limbs, d_pts, outputs
 
 def ckks_deep_diag_workspace_bytes(n, limbs, alpha, batch, count, outputs):
     return int(load_library().fhe_ckks_deep_diag_workspace_bytes(n, limbs, alpha, batch, count, outputs))
+
+
+def ckks_deep_lincomb_dev(plans, d_cts, w, k, outputs, d_out, batch, stream=None, limbs=None, count=None):
+    """fhe_ckks_deep_lincomb_dev: ckks_rns_lincomb_dev's arguments on a chain of up to 32 limbs, a slice of 8 limbs
+    a launch"""
+    cts = None if d_cts is None else (_vp * max(len(d_cts), 1))(*d_cts)
+    ws = None if w is None else (_u64 * max(len(w), 1))(*w)
+    ks = None if k is None else (_u64 * max(len(k), 1))(*k)
+    _check(load_library().fhe_ckks_deep_lincomb_dev(_plans_or_none(plans), len(plans) if limbs is None else limbs, cts, len(d_cts) if count is None else count, ws, ks,
+                                                    outputs, d_out, batch, stream))
+
+
+def ckks_deep_dot_dev(plans, specials, d_key, key_limbs, d_as, d_bs, w, d_out, batch, stream=None, limbs=None, alpha=None, count=None):
+    """fhe_ckks_deep_dot_dev: relinearize(sum_r w_r tensor(a_r, b_r)) -> [limbs][2][batch][n] with the grouped-digit
+    key switch, one whatever the number of pairs; the lists and w as for ckks_rns_dot_dev"""
+    a = None if d_as is None else (_vp * max(len(d_as), 1))(*d_as)
+    b = None if d_bs is None else (_vp * max(len(d_bs), 1))(*d_bs)
+    ws = None if w is None else (_u64 * max(len(w), 1))(*w)
+    _check(load_library().fhe_ckks_deep_dot_dev(_plans_or_none(plans), len(plans) if limbs is None else limbs, _plans_or_none(specials),
+                                                len(specials) if alpha is None else alpha, d_key, key_limbs, a, b, len(d_as) if count is None else count, ws, d_out,
+                                                batch, stream))
 
 
 def ckks_rns_lincomb_dev(plans, d_cts, w, k, outputs, d_out, batch, stream=None, limbs=None, count=None):

@@ -590,8 +590,7 @@ class RnsCiphertext:
         """sum_i coeffs[i] T_i(y) of every slot x, y = (2x - a - b)/(b - a): a ChebyshevPlan, or Chebyshev coefficients from which
         one is built.  Consumes plan.levels levels; the result has this ciphertext's scale (up to float rounding).  A
         ciphertext with fewer levels is refused before anything runs."""
-        plan = plan_or_coeffs if isinstance(plan_or_coeffs, ChebyshevPlan) else ChebyshevPlan.build(plan_or_coeffs, interval)
-        return plan.run(self, rlk)
+        return eval_chebyshev(self, plan_or_coeffs, rlk, interval)
 
 
 def _real(x, what):
@@ -604,8 +603,9 @@ def _real(x, what):
 
 
 def lincomb(cts, coeffs, consts=None, scale=None, level=None):
-    """-> [sum_r coeffs[o][r] cts[r] + consts[o] for each output o] from fhe_ckks_rns_lincomb_dev: every input is read once for
-    up to four outputs, nothing is transformed and no level is used.  coeffs real [outputs][count] (1-D: one output), consts
+    """-> [sum_r coeffs[o][r] cts[r] + consts[o] for each output o] from fhe_ckks_rns_lincomb_dev, or from
+    fhe_ckks_deep_lincomb_dev where the operands are DeepCiphertexts, which then the outputs are too: every input
+    is read once for up to four outputs, nothing is transformed and no level is used.  coeffs real [outputs][count] (1-D: one output), consts
     real [outputs] or None.  The level is the minimum over the inputs (or `level`, not above it: dropping limbs is truncation).
     scale is the target scale S of every output (or one per output, [outputs]): input r takes the integer weight round(coeffs[o][r] S / cts[r].scale), reduced
     per limb, and the constant is round(consts[o] S).  scale=None: S is the largest input scale, so an input at that scale takes
@@ -639,11 +639,13 @@ def lincomb(cts, coeffs, consts=None, scale=None, level=None):
     torch = _torch()
     out = torch.empty((outputs, level + 1, 2, batch, param.n), dtype=torch.int64, device="cuda")
     cap = binding.FHE_CKKS_LINCOMB_MAX_OUTPUTS
+    deep = isinstance(param, DeepParam)
+    call = binding.ckks_deep_lincomb_dev if deep else binding.ckks_rns_lincomb_dev
     for o0 in range(0, outputs, cap):
         o1 = min(outputs, o0 + cap)
-        binding.ckks_rns_lincomb_dev(param.plans(level), [ct.d.data_ptr() for ct in cts], [x % q for row in w[o0:o1] for x in row for q in mods],
-                                     None if kk is None else [x % q for x in kk[o0:o1] for q in mods], o1 - o0, out[o0].data_ptr(), batch)
-    return [RnsCiphertext(param, out[o], level, S[o]) for o in range(outputs)]
+        call(param.plans(level), [ct.d.data_ptr() for ct in cts], [x % q for row in w[o0:o1] for x in row for q in mods],
+             None if kk is None else [x % q for x in kk[o0:o1] for q in mods], o1 - o0, out[o0].data_ptr(), batch)
+    return [(DeepCiphertext if deep else RnsCiphertext)(param, out[o], level, S[o]) for o in range(outputs)]
 
 
 def dot_weights(scales, coeffs=None, scale=None):
@@ -662,7 +664,8 @@ def dot_weights(scales, coeffs=None, scale=None):
 
 
 def dot(xs, ys, rlk, coeffs=None, scale=None, level=None):
-    """-> sum_r coeffs[r] xs[r] ys[r] from fhe_ckks_rns_dot_dev: the tensors of all pairs are summed on the device
+    """-> sum_r coeffs[r] xs[r] ys[r] from fhe_ckks_rns_dot_dev, or from fhe_ckks_deep_dot_dev (§39) where the
+    operands are DeepCiphertexts, which then the result is too: the tensors of all pairs are summed on the device
     and relinearised ONCE, so the call costs one key switch and one relinearisation noise term whatever len(xs) is.  xs, ys
     equal-length lists of RnsCiphertext of one RnsParam and batch; dot([x], [x], rlk) is the square.  The level is the minimum
     over all operands (or `level`, not above it); an operand at a higher level is read as it is.  Pair r has scale s_r =
@@ -683,9 +686,15 @@ def dot(xs, ys, rlk, coeffs=None, scale=None, level=None):
     S, w = dot_weights([x.scale * y.scale for x, y in zip(xs, ys)], coeffs, scale)
     torch = _torch()
     out = torch.empty((level + 1, 2, batch, param.n), dtype=torch.int64, device="cuda")
-    binding.ckks_rns_dot_dev(param.plans(level), param.special_plan(), rlk.d_rlk.data_ptr(), len(param.moduli), [ct.d.data_ptr() for ct in xs],
-                             [ct.d.data_ptr() for ct in ys], None if w is None else [x % q for x in w for q in param.moduli[:level + 1]], out.data_ptr(), batch)
-    return RnsCiphertext(param, out, level, S)
+    deep = isinstance(param, DeepParam)
+    ws = None if w is None else [x % q for x in w for q in param.moduli[:level + 1]]
+    if deep:
+        binding.ckks_deep_dot_dev(param.plans(level), param.special_plans(), rlk.d_rlk.data_ptr(), len(param.moduli), [ct.d.data_ptr() for ct in xs],
+                                  [ct.d.data_ptr() for ct in ys], ws, out.data_ptr(), batch)
+    else:
+        binding.ckks_rns_dot_dev(param.plans(level), param.special_plan(), rlk.d_rlk.data_ptr(), len(param.moduli), [ct.d.data_ptr() for ct in xs],
+                                 [ct.d.data_ptr() for ct in ys], ws, out.data_ptr(), batch)
+    return (DeepCiphertext if deep else RnsCiphertext)(param, out, level, S)
 
 
 def chebyshev_fit(f, degree, interval=(-1, 1)):
@@ -877,6 +886,15 @@ class ChebyshevPlan:
         return w[self.result]
 
 
+def eval_chebyshev(ct, plan_or_coeffs, rlk, interval=(-1, 1)):
+    """sum_i coeffs[i] T_i(y) of every slot x of `ct`, y = (2x - a - b)/(b - a): a ChebyshevPlan, or Chebyshev coefficients from
+    which one is built.  `ct` an RnsCiphertext or a DeepCiphertext; the result is of its class.  Consumes
+    plan.levels levels; the result has the ciphertext's scale (up to float rounding).  A ciphertext with fewer levels is refused
+    before anything runs."""
+    plan = plan_or_coeffs if isinstance(plan_or_coeffs, ChebyshevPlan) else ChebyshevPlan.build(plan_or_coeffs, interval)
+    return plan.run(ct, rlk)
+
+
 class RnsClientKey(ClientKeyBase):
     """The CKKS secret under every prime of an RnsParam: the same ternary row (KEY row 0) as residues and evals per limb, the
     special prime's last.  Rows of a seed, as ClientKey and disjoint from its rows:
@@ -1044,8 +1062,10 @@ class DeepParam:
 class DeepCiphertext(RnsCiphertext):
     """RnsCiphertext on a DeepParam: +, -, at_level, add_plain and mul_plain are the base class's, per limb; the products, the
     rescale, the Galois maps and the diagonal sums go through the fhe_ckks_deep_* entry points; linear_transform is the base
-    class's composition over them.  The fused scalar sums, the inner products, the hoisted giant steps and the Chebyshev plans
-    are not carried to the deep chain yet."""
+    class's composition over them.  The fused scalar sums, the inner products and the Chebyshev plans are reached through the
+    module's lincomb, dot and eval_chebyshev, which dispatch on the operands' param and return DeepCiphertexts (DESIGN.md §39);
+    the methods mul_const, add_const and eval_chebyshev keep raising NotImplementedError, as the tests of §36 and §37 assert,
+    and so does linear_transform_hoisted, which is not carried to the deep chain yet."""
 
     def mul(self, rhs, rlk):
         """ct x ct and relinearisation (fhe_ckks_deep_mul_dev); the scale multiplies and the result is NOT rescaled"""

@@ -182,6 +182,108 @@ __global__ __launch_bounds__(256) void ckks_deep_diagmac_kernel(const u64 *__res
     }
 }
 
+// ---- polynomial evaluation on the deep chain: scalar sums and summed tensors over a slice of limbs a launch ----
+// The per-limb kernels of ckks_eval.hip (§27, §29) launch once a limb; at 24 to 32 limbs and the small batches of the deep chain
+// that is 24 to 32 launches of a few megabytes.  Here blockIdx.y is the limb within a slice of up to kDeepPolyLimbs = 8, and the
+// slice's moduli, weights and constants pass by value, as bfv_rns_tensorsum_kernel's: they are indexed by blockIdx.y and by the
+// loop counter, both uniform over the wave, so they are scalar loads from the kernel-argument segment.  Every modulus is below
+// 2^62 (check_deep), so only MacAcc's narrow fold applies: there is no 2^62 <= q < 2^63 branch.
+struct DeepLinArgs {
+    Mod m[kDeepPolyLimbs];              // the slice's moduli
+    DeepLinWords s;                     // w[l][o][r], k[l][o], canonical; k is not used where CARRY
+    const u64 *ct[kDeepLinInputs];      // input r at the slice's first limb; limb l at + l limb_words
+    u32 count;                          // inputs of this launch, 1 .. kDeepLinInputs
+};
+struct DeepDotArgs {
+    Mod m[kDeepPolyLimbs];
+    DeepDotWords s;                     // w[l][r], canonical; not read unless WEIGHTED
+    const u64 *a[kDeepDotPairs], *b[kDeepDotPairs];   // pair r's operands at the slice's first limb and the chunk's first row; limb l at + l ls
+    u32 count;                          // pairs of this launch, 1 .. kDeepDotPairs
+};
+// the kernel-argument segment that §36 keeps its by-value tables within; the scalars beside the struct are at most 64 bytes
+static_assert(sizeof(DeepLinArgs) + 64 <= 4096 && sizeof(DeepDotArgs) + 64 <= 4096, "the slice's arguments pass by value within 4 KiB");
+
+// Limb blockIdx.y of the slice of out_o = sum_r w[o][r] ct_r + (k[o], 0), ckks_rns_lincomb_kernel's semantics (§27) for NOUT
+// outputs and the inputs of `a`: over the limb_words = 2 half words of a limb, component 0 first,
+//   out[o out_os + l limb_words + e] (+)= sum_r w[l][o][r] ct_r[l limb_words + e] + [e < half] k[l][o].
+// Every input has the layout [limb][2][batch][n], so a limb's words are limb_words apart in the inputs and in every output.
+// CARRY: the sum starts from the canonical words a former group of inputs left in `out`; otherwise from the constant.
+// Launches of one call: ceil(limbs / 8) ceil(outputs / 4) ceil(count / 8) (rns_tables.hpp: deep_lincomb_launches).
+// Overflow.  Operands are canonical and every modulus is below 2^62, so a term is below 2^124.  The accumulator starts from a
+// canonical word (the constant or the carried word) and folds before input r > 0 where r is a multiple of kMacChunk = 8: between
+// two folds it holds a canonical carry-over below 2^62 and at most eight terms, less than 2^127 + 2^62 (MacAcc::fold).  A launch
+// of kDeepLinInputs = 8 inputs is one such run, folded to canonical words before it is stored, so any count holds.
+template <u32 NOUT, bool CARRY>
+__global__ __launch_bounds__(256) void ckks_deep_lincomb_kernel(u64 *__restrict__ out, u64 out_os, u64 limb_words, u64 half, DeepLinArgs a) {
+    const u32 l = blockIdx.y;
+    const Mod m = a.m[l];
+    const u64 base = (u64)l * limb_words, stride = (u64)gridDim.x * 256;
+    u64 kk[NOUT];
+#pragma unroll
+    for (u32 o = 0; o < NOUT; o++) kk[o] = a.s.k[l][o];
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < limb_words; i += stride) {
+        MacAcc u[NOUT];
+#pragma unroll
+        for (u32 o = 0; o < NOUT; o++) u[o].v = CARRY ? out[o * out_os + base + i] : (i < half ? kk[o] : 0ull);
+        for (u32 r = 0; r < a.count; r++) {
+            if (r && r % kMacChunk == 0) {
+#pragma unroll
+                for (u32 o = 0; o < NOUT; o++) u[o].fold(m);
+            }
+            const u64 x = a.ct[r][base + i];
+#pragma unroll
+            for (u32 o = 0; o < NOUT; o++) u[o].mac(a.s.w[l][o][r], x);
+        }
+#pragma unroll
+        for (u32 o = 0; o < NOUT; o++) out[o * out_os + base + i] = u[o].fold(m);
+    }
+}
+
+// Limb blockIdx.y of the slice of the summed tensor of the pairs of `a`, ckks_rns_tensorsum_kernel's semantics (§29), over
+// `count` words a component; out is the slice's first limb of the chunk's tensor [limbs][3][count], canonical:
+//   d0[e] (+)= sum_r w_r a_r0[e] b_r0[e],  d1[e] (+)= sum_r w_r (a_r0[e] b_r1[e] + a_r1[e] b_r0[e]),  d2[e] (+)= sum_r w_r a_r1[e] b_r1[e]
+// An operand's limbs are ls words apart and its two components cs.  a_r and b_r may be the same pointer (a square) and a pointer
+// may repeat across pairs: the operands are only read, and `out` (the workspace's tensor slot) is none of them.  WEIGHTED = false:
+// w_r = 1, no multiplication.  CARRY: the sums start from the canonical words a former group left in `out`; otherwise from zero.
+// Launches of one chunk: ceil(limbs / 8) ceil(count / 16) (rns_tables.hpp: deep_tensorsum_launches).
+// Overflow.  The weight is folded into a_r first (w a_r0 and w a_r1 reduced to canonical words before they meet b: w a b < q^3 has
+// no room in 128 bits), so a term is below 2^124 whether weighted or not.  d0 and d2 take one term a pair, d1 two, so d1 sets
+// the period: all three fold before pair r > 0 where r is a multiple of kMacChunk / 2 = 4, and between two folds hold a canonical
+// carry-over below 2^62 and at most eight terms, less than 2^127 + 2^62.  16 pairs are four runs; any count holds.
+template <bool WEIGHTED, bool CARRY>
+__global__ __launch_bounds__(256) void ckks_deep_tensorsum_kernel(u64 *__restrict__ out, u64 count, u64 ls, u64 cs, DeepDotArgs a) {
+    const u32 l = blockIdx.y;
+    const Mod m = a.m[l];
+    const u64 in = (u64)l * ls, stride = (u64)gridDim.x * 256;
+    out += 3ull * l * count;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+        MacAcc d0, d1, d2;
+        if (CARRY) {
+            d0.v = out[i];
+            d1.v = out[count + i];
+            d2.v = out[2 * count + i];
+        }
+        for (u32 r = 0; r < a.count; r++) {
+            if (r && r % (kMacChunk / 2) == 0) d0.fold(m), d1.fold(m), d2.fold(m);
+            const u64 *pa = a.a[r] + in, *pb = a.b[r] + in;
+            u64 a0 = pa[i], a1 = pa[cs + i];
+            const u64 b0 = pb[i], b1 = pb[cs + i];
+            if (WEIGHTED) {
+                const u64 w = a.s.w[l][r];
+                a0 = mul_mod_var(w, a0, m);
+                a1 = mul_mod_var(w, a1, m);
+            }
+            d0.mac(a0, b0);
+            d1.mac(a0, b1);
+            d1.mac(a1, b0);
+            d2.mac(a1, b1);
+        }
+        out[i] = d0.fold(m);
+        out[count + i] = d1.fold(m);
+        out[2 * count + i] = d2.fold(m);
+    }
+}
+
 }  // namespace fhe
 
 // ---- host side -----------------------------------------------------------------------------------------------------
@@ -768,4 +870,126 @@ extern "C" int fhe_ckks_deep_rescale_dev(const fhe_ntt_plan *const *plans, unsig
             return rc;
     }
     return FHE_OK;
+}
+
+// ---- polynomial evaluation: scalar sums and inner products ---------------------------------------------------------
+namespace {
+
+template <class... A>
+int deep_lincomb_launch(unsigned nout, bool carry, int L, hipStream_t st, dim3 grid, const A &...a) {
+    const char *lab = "ckks_deep_lincomb";
+    hipError_t e = hipErrorInvalidValue;
+#define FHE_DEEP_LIN_CASE(N) \
+    case N: e = carry ? fhe::launch_grid(fhe::ckks_deep_lincomb_kernel<N, true>, lab, L, grid, 256, 0, st, a...) : fhe::launch_grid(fhe::ckks_deep_lincomb_kernel<N, false>, lab, L, grid, 256, 0, st, a...); break
+    switch (nout) {
+        FHE_DEEP_LIN_CASE(1);
+        FHE_DEEP_LIN_CASE(2);
+        FHE_DEEP_LIN_CASE(3);
+        FHE_DEEP_LIN_CASE(4);
+        default: return fhe_fail(FHE_E_INVALID, "ckks_deep_lincomb: %u outputs in one launch", nout);
+    }
+#undef FHE_DEEP_LIN_CASE
+    static_assert(fhe::kDeepLinOutputs == 4, "one case per accumulator count");
+    return e == hipSuccess ? FHE_OK : fhe_hip_fail(e, "ckks_deep_lincomb_kernel");
+}
+
+// rows r0 .. r0 + cr of the `count` pairs -> their summed tensor in Dt [k][3][cr][n]: per slice of limbs, groups of kDeepDotPairs
+// pairs, every group after the first carried; w [count][k] or NULL (every weight 1)
+int deep_tensorsum_rows(const Deep &c, const void *const *d_as, const void *const *d_bs, unsigned count, const uint64_t *w, u64 batch, u64 r0, u64 *Dt, u64 cr,
+                        hipStream_t st) {
+    const u64 n = c.n, slab = cr * n;
+    return fhe::host::deep_tensorsum_each(c.k, count, [&](unsigned i0, unsigned nl, unsigned p0, unsigned np) {
+        fhe::DeepDotArgs a{};
+        for (unsigned l = 0; l < nl; l++) a.m[l] = c.p[i0 + l]->mod;
+        fhe::host::deep_tensorsum_words((const u64 *)w, c.k, i0, nl, p0, np, &a.s);
+        for (unsigned r = 0; r < np; r++) {
+            a.a[r] = (const u64 *)d_as[p0 + r] + ((u64)i0 * 2 * batch + r0) * n;
+            a.b[r] = (const u64 *)d_bs[p0 + r] + ((u64)i0 * 2 * batch + r0) * n;
+        }
+        a.count = np;
+        const bool carry = p0 > 0;
+        auto kernel = w ? (carry ? fhe::ckks_deep_tensorsum_kernel<true, true> : fhe::ckks_deep_tensorsum_kernel<true, false>)
+                        : (carry ? fhe::ckks_deep_tensorsum_kernel<false, true> : fhe::ckks_deep_tensorsum_kernel<false, false>);
+        const hipError_t e = fhe::launch_grid(kernel, "ckks_deep_tensorsum", (int)c.L, dim3(fhe_ew_grid(slab), nl), 256, 0, st, Dt + (u64)i0 * 3 * slab, slab, 2 * batch * n,
+                                              batch * n, a);
+        return e == hipSuccess ? (int)FHE_OK : fhe_hip_fail(e, "ckks_deep_tensorsum_kernel");
+    });
+}
+
+}  // namespace
+
+extern "C" int fhe_ckks_deep_lincomb_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *const *d_cts, unsigned count, const uint64_t *w,
+                                         const uint64_t *k, unsigned outputs, void *d_out, size_t batch, void *hip_stream) {
+    const char *who = "fhe_ckks_deep_lincomb_dev";
+    Deep c;
+    int rc = check_deep(plans, limbs, nullptr, 0, false, &c, who);
+    if (rc != FHE_OK) return rc;
+    if (count < 1 || count > FHE_CKKS_LINCOMB_MAX_COUNT) return fhe_fail(FHE_E_INVALID, "%s: count=%u must be in [1, %d]", who, count, FHE_CKKS_LINCOMB_MAX_COUNT);
+    if (outputs < 1 || outputs > FHE_CKKS_LINCOMB_MAX_OUTPUTS)
+        return fhe_fail(FHE_E_INVALID, "%s: outputs=%u must be in [1, %d]", who, outputs, FHE_CKKS_LINCOMB_MAX_OUTPUTS);
+    if (!d_cts || !w) return fhe_fail(FHE_E_NULL, "%s: NULL host array", who);
+    for (unsigned o = 0; o < outputs; o++)
+        for (unsigned i = 0; i < c.k; i++) {
+            for (unsigned r = 0; r < count; r++)
+                if (w[((u64)o * count + r) * c.k + i] >= c.p[i]->q) return fhe_fail(FHE_E_INVALID, "%s: weight [%u][%u][%u] is not below its modulus", who, o, r, i);
+            if (k && k[(u64)o * c.k + i] >= c.p[i]->q) return fhe_fail(FHE_E_INVALID, "%s: constant [%u][%u] is not below its modulus", who, o, i);
+        }
+    if (batch == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, 2ull * c.k * n * outputs, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 limb_words = 2ull * batch * n, ct_bytes = c.k * limb_words * 8;
+    for (unsigned r = 0; r < count; r++) {
+        if (!d_cts[r]) return fhe_fail(FHE_E_NULL, "%s: input %u is NULL", who, r);
+        if (misaligned8(d_cts[r])) return fhe_fail(FHE_E_INVALID, "%s: input %u must be 8-byte aligned", who, r);
+        if (overlaps_any(d_out, ct_bytes * outputs, {{d_cts[r], ct_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps input %u", who, r);
+    }
+    int dev;                                                         // not used: the call is here to refuse, as a workspace would, where there is no device
+    if ((rc = fhe_current_device(&dev)) != FHE_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    // no workspace and no chunk: the sum is element-wise over the whole batch
+    return fhe::host::deep_lincomb_each(c.k, outputs, count, [&](unsigned o0, unsigned no, unsigned i0, unsigned nl, unsigned r0, unsigned nr) {
+        fhe::DeepLinArgs a{};
+        for (unsigned l = 0; l < nl; l++) a.m[l] = c.p[i0 + l]->mod;
+        fhe::host::deep_lincomb_words((const u64 *)w, (const u64 *)k, c.k, count, o0, no, i0, nl, r0, nr, &a.s);
+        for (unsigned r = 0; r < nr; r++) a.ct[r] = (const u64 *)d_cts[r0 + r] + (u64)i0 * limb_words;
+        a.count = nr;
+        return deep_lincomb_launch(no, r0 > 0, (int)c.L, st, dim3(fhe_ew_grid(limb_words), nl), (u64 *)d_out + ((u64)o0 * c.k + i0) * limb_words, c.k * limb_words,
+                                   limb_words, limb_words / 2, a);
+    });
+}
+
+extern "C" int fhe_ckks_deep_dot_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *specials, unsigned alpha, const void *d_key,
+                                     unsigned key_limbs, const void *const *d_as, const void *const *d_bs, unsigned count, const uint64_t *w, void *d_out, size_t batch,
+                                     void *hip_stream) {
+    const char *who = "fhe_ckks_deep_dot_dev";
+    Deep c;
+    int rc = check_deep(plans, limbs, specials, alpha, true, &c, who);
+    if (rc != FHE_OK) return rc;
+    if ((rc = check_key_limbs(c, key_limbs, who)) != FHE_OK) return rc;
+    if (count < 1 || count > FHE_CKKS_DOT_MAX_COUNT) return fhe_fail(FHE_E_INVALID, "%s: count=%u must be in [1, %d]", who, count, FHE_CKKS_DOT_MAX_COUNT);
+    if (!d_as || !d_bs) return fhe_fail(FHE_E_NULL, "%s: NULL host array", who);
+    for (unsigned r = 0; w && r < count; r++)
+        for (unsigned i = 0; i < c.k; i++)
+            if (w[(u64)r * c.k + i] >= c.p[i]->q) return fhe_fail(FHE_E_INVALID, "%s: weight [%u][%u] is not below its modulus", who, r, i);
+    if (batch == 0) return FHE_OK;
+    const u64 n = c.n;
+    if (!mul_fits((u64)batch, 3ull * c.k * n, kWordLimit)) return fhe_fail(FHE_E_INVALID, "%s: batch too large", who);
+    if (!d_key || !d_out) return fhe_fail(FHE_E_NULL, "%s: NULL buffer", who);
+    if (misaligned8(d_key) || misaligned8(d_out)) return fhe_fail(FHE_E_INVALID, "%s: buffers must be 8-byte aligned", who);
+    const u64 ct_bytes = 2ull * c.k * batch * n * 8;
+    if (overlaps_any(d_out, ct_bytes, {{d_key, key_words(key_limbs, alpha, n) * 8}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps the key", who);
+    for (unsigned r = 0; r < count; r++) {
+        if (!d_as[r] || !d_bs[r]) return fhe_fail(FHE_E_NULL, "%s: an operand of pair %u is NULL", who, r);
+        if (misaligned8(d_as[r]) || misaligned8(d_bs[r])) return fhe_fail(FHE_E_INVALID, "%s: the operands of pair %u must be 8-byte aligned", who, r);
+        if (overlaps_any(d_out, ct_bytes, {{d_as[r], ct_bytes}, {d_bs[r], ct_bytes}})) return fhe_fail(FHE_E_INVALID, "%s: d_out overlaps an operand of pair %u", who, r);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    // mul's chunk and workspace: the chunk's summed tensor where fhe_ckks_deep_mul_dev stages its tensor, then ONE relinearisation
+    return switch_call(c, batch, deep_slabs(c.k, c.alpha), st, who, [&](u64 r0, u64 cr, const DeepTables &t, u64 *W, const u64 *pinv) {
+        const DeepBufs b(W, c, cr * n);
+        const int rc = deep_tensorsum_rows(c, d_as, d_bs, count, w, batch, r0, b.Dt, cr, st);
+        return rc != FHE_OK ? rc : relin_rows(c, t, (const u64 *)d_key, key_limbs, pinv, b.Dt, cr, 0, (u64 *)d_out, batch, r0, b, cr, st);
+    });
 }

@@ -248,4 +248,75 @@ inline bool deep_ext_tables(const u64 *src, unsigned s, const u64 *dst, const u6
 }
 
 }  // namespace host
+
+// ---- scalar sums and inner products on the deep chain (ckks_deep.hip) ----------------------------------------
+// One launch covers a slice of up to kDeepPolyLimbs limbs (blockIdx.y); a scalar sum up to kDeepLinInputs inputs into up to
+// kDeepLinOutputs outputs, a summed tensor up to kDeepDotPairs pairs.  The slice's weights and constants pass by value.
+constexpr unsigned kDeepPolyLimbs = 8, kDeepLinInputs = 8, kDeepLinOutputs = 4, kDeepDotPairs = 16;
+
+// the scalars of one scalar-sum launch: w[l][o][r] of slice limb l, launch output o and launch input r; k[l][o]
+struct DeepLinWords {
+    unsigned long long w[kDeepPolyLimbs][kDeepLinOutputs][kDeepLinInputs];
+    unsigned long long k[kDeepPolyLimbs][kDeepLinOutputs];
+};
+// the weights of one summed-tensor launch: w[l][r] of slice limb l and launch pair r
+struct DeepDotWords {
+    unsigned long long w[kDeepPolyLimbs][kDeepDotPairs];
+};
+
+namespace host {
+
+// launches of a scalar sum: ceil(limbs / 8) ceil(outputs / 4) ceil(count / 8)
+inline u64 deep_lincomb_launches(unsigned limbs, unsigned outputs, unsigned count) {
+    return (u64)((limbs + kDeepPolyLimbs - 1) / kDeepPolyLimbs) * ((outputs + kDeepLinOutputs - 1) / kDeepLinOutputs) * ((count + kDeepLinInputs - 1) / kDeepLinInputs);
+}
+// launches of the summed tensor of one chunk of a dot: ceil(limbs / 8) ceil(count / 16)
+inline u64 deep_tensorsum_launches(unsigned limbs, unsigned count) {
+    return (u64)((limbs + kDeepPolyLimbs - 1) / kDeepPolyLimbs) * ((count + kDeepDotPairs - 1) / kDeepDotPairs);
+}
+
+// The launches of a scalar sum in the order they are issued: f(o0, no, i0, nl, r0, nr) covers outputs [o0, o0 + no), limbs
+// [i0, i0 + nl) and inputs [r0, r0 + nr); the groups of inputs of one (outputs, limbs) block follow each other, so every one
+// after the first (r0 > 0) carries the words the former left.  Stops at and returns the first non-zero result.
+template <class F>
+inline int deep_lincomb_each(unsigned limbs, unsigned outputs, unsigned count, F f) {
+    for (unsigned o0 = 0; o0 < outputs; o0 += kDeepLinOutputs)
+        for (unsigned i0 = 0; i0 < limbs; i0 += kDeepPolyLimbs)
+            for (unsigned r0 = 0; r0 < count; r0 += kDeepLinInputs) {
+                const unsigned no = outputs - o0 < kDeepLinOutputs ? outputs - o0 : kDeepLinOutputs, nl = limbs - i0 < kDeepPolyLimbs ? limbs - i0 : kDeepPolyLimbs,
+                               nr = count - r0 < kDeepLinInputs ? count - r0 : kDeepLinInputs;
+                if (const int rc = f(o0, no, i0, nl, r0, nr)) return rc;
+            }
+    return 0;
+}
+// The same for the summed tensor: f(i0, nl, p0, np), pairs [p0, p0 + np); p0 > 0 carries.
+template <class F>
+inline int deep_tensorsum_each(unsigned limbs, unsigned count, F f) {
+    for (unsigned i0 = 0; i0 < limbs; i0 += kDeepPolyLimbs)
+        for (unsigned p0 = 0; p0 < count; p0 += kDeepDotPairs) {
+            const unsigned nl = limbs - i0 < kDeepPolyLimbs ? limbs - i0 : kDeepPolyLimbs, np = count - p0 < kDeepDotPairs ? count - p0 : kDeepDotPairs;
+            if (const int rc = f(i0, nl, p0, np)) return rc;
+        }
+    return 0;
+}
+
+// the scalars of that launch from the call's arrays: w [outputs][count][limbs], k [outputs][limbs] or NULL (zeros).  What the
+// launch does not cover stays zero.
+inline void deep_lincomb_words(const u64 *w, const u64 *k, unsigned limbs, unsigned count, unsigned o0, unsigned no, unsigned i0, unsigned nl, unsigned r0, unsigned nr,
+                               DeepLinWords *out) {
+    *out = DeepLinWords{};
+    for (unsigned l = 0; l < nl; l++)
+        for (unsigned o = 0; o < no; o++) {
+            for (unsigned r = 0; r < nr; r++) out->w[l][o][r] = w[((u64)(o0 + o) * count + r0 + r) * limbs + i0 + l];
+            out->k[l][o] = k ? k[(u64)(o0 + o) * limbs + i0 + l] : 0;
+        }
+}
+// w [count][limbs] or NULL (ones)
+inline void deep_tensorsum_words(const u64 *w, unsigned limbs, unsigned i0, unsigned nl, unsigned p0, unsigned np, DeepDotWords *out) {
+    *out = DeepDotWords{};
+    for (unsigned l = 0; l < nl; l++)
+        for (unsigned r = 0; r < np; r++) out->w[l][r] = w ? w[(u64)(p0 + r) * limbs + i0 + l] : 1;
+}
+
+}  // namespace host
 }  // namespace fhe

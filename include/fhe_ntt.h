@@ -936,6 +936,38 @@ int fhe_ckks_deep_diag_sum_dev(const fhe_ntt_plan *const *plans, unsigned limbs,
 size_t fhe_ckks_deep_diag_workspace_bytes(uint64_t n, unsigned limbs, unsigned alpha, size_t batch, unsigned count,
                                           unsigned outputs);
 
+/* ---- CKKS on a deep RNS chain: scalar sums and inner products (ckks_deep.hip) ----
+ * fhe_ckks_rns_lincomb_dev (§27) and fhe_ckks_rns_dot_dev (§29) on the chain of the §36 block, for limbs up to 32: what a
+ * Chebyshev plan is made of.  The definitions, the HOST arrays, FHE_CKKS_LINCOMB_MAX_COUNT, FHE_CKKS_LINCOMB_MAX_OUTPUTS and
+ * FHE_CKKS_DOT_MAX_COUNT are those two blocks'; one launch covers a slice of up to 8 limbs.
+ *   fhe_ckks_deep_lincomb_dev     d_out [outputs][limbs][2][batch][n]: out_o[c][e] = (sum_{r < count} w[o][r][i] ct_r[c][e] +
+ *            [c = 0] k[o][i]) mod q_i per limb i.  d_cts `count` device pointers to ciphertexts [>= limbs][2][batch][n], a
+ *            pointer may repeat; w [outputs][count][limbs] and k [outputs][limbs] (NULL: no constant) canonical residues,
+ *            consumed before the call returns: they travel in the kernel arguments, never through a copy from host memory.
+ *            Takes no special primes, no workspace and no chunk: ceil(limbs / 8) ceil(outputs / 4) ceil(count / 8) launches
+ *            over the whole batch.  The operation is limb-independent, so the words are those of fhe_ckks_rns_lincomb_dev on
+ *            slices of at most 8 plans of the same buffers.
+ *   fhe_ckks_deep_dot_dev         d_out [limbs][2][batch][n] = relinearize(sum_{r < count} w_r tensor(a_r, b_r)), the relinearisation
+ *            fhe_ckks_deep_relinearize_dev's: ONE key switch and one switch error whatever `count` is.  d_as, d_bs `count`
+ *            device pointers each, a_r = b_r (a square) and repeated pointers allowed; w [count][limbs] canonical residues or
+ *            NULL (every weight 1); d_key, key_limbs, specials and alpha as for fhe_ckks_deep_mul_dev.  The workspace and the
+ *            chunk are those of fhe_ckks_deep_mul_dev (the summed tensor lies where that call stages its tensor), so
+ *            fhe_ckks_deep_workspace_bytes answers for this call too; a chunk takes ceil(limbs / 8) ceil(count / 16) launches
+ *            for the summed tensor and then those of the relinearisation.  With count = 1 and w = NULL the words of
+ *            fhe_ckks_deep_mul_dev; at alpha = 1 and limbs <= 8 those of fhe_ckks_rns_dot_dev.
+ * FHE_E_NULL for a NULL plan, key, host array, entry of an array or output; FHE_E_PARAM_MISMATCH for plans whose n differ;
+ * FHE_E_INVALID for the chain conditions of the §36 block (the dot: with the admission and key_limbs < limbs or > 32), count or
+ * outputs outside their ranges, a weight or constant that is not below its q_i, a misaligned buffer, an output that overlaps an
+ * input, an operand or the key, and a batch too large.  Everything is checked before any device call and nothing is written on
+ * rejection; batch = 0 is a no-op after the host checks. */
+int fhe_ckks_deep_lincomb_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const void *const *d_cts, unsigned count,
+                              const uint64_t *w, const uint64_t *k, unsigned outputs, void *d_out, size_t batch,
+                              void *hip_stream);
+int fhe_ckks_deep_dot_dev(const fhe_ntt_plan *const *plans, unsigned limbs, const fhe_ntt_plan *const *specials,
+                          unsigned alpha, const void *d_key, unsigned key_limbs, const void *const *d_as,
+                          const void *const *d_bs, unsigned count, const uint64_t *w, void *d_out, size_t batch,
+                          void *hip_stream);
+
 /* ---- rows N3 / N4: batch surfaces and element-wise glue, device-resident ----
  * Sums of products are accumulated in the NTT domain and transformed back once; arithmetic
  * mod q is exact, so the words equal the reference's sum of canonical products.
